@@ -20,8 +20,14 @@ the chains' statistics only.
 ``--chains`` (default 16) chains per step through nmgp_sep_batch_eval (the chains' B x D blocks form one batch of the blocked
 Cholesky); ``--workload subjects`` is config 4 (independent subjects, one multi-subject batch per GPU).
 
+A plain run (no ``--full``) does only what the headline needs: set-up, ``--warmup`` steps, exactly ``--steps`` timed steps, the
+outputs of the last timed step written as .npy files when ``--dump-outputs DIR`` is given, and the result line (``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, the run's configuration and the reduction of the chains'
+statistics).  No stage timers run in it.  Everything else below -- the per-kernel and roofline figures, the value+gradient and
+sampler side measurements, the CPU baseline -- is measured with ``--full`` only.
+
 One JSON line is printed by rank 0 (contract in the task statement).  Flat scalars come first so that a truncated record still
-shows them (value_grad_evals_per_s, hmc_samples_per_s, roofline_frac_end_to_end, ...), then these objects:
+shows them (value_grad_evals_per_s, hmc_samples_per_s, roofline_frac_end_to_end, ...), then these objects (``--full``):
   roofline      -- the dominant kernel (k_syrk_lower, the FP64-MFMA trailing update of the blocked Cholesky): algorithmic
                    flop of its launches divided by their summed HIP-event durations on the launching stream.
   grad          -- the MCMC-relevant rate: value+gradient evaluations / second at the same chain count (HMC spends 20
@@ -61,6 +67,28 @@ TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic.json")
 
 
 SCHEDULE_NEUTRAL_ENV = ("NMGP_ROUND", "NMGP_BENCH_SELF_LAUNCHED", "NMGP_POISON")
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: at most this much in all (larger arrays: a fixed, seeded sample of rows)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float64.  When they would exceed DUMP_LIMIT_BYTES together, the
+    largest ones are cut to a fixed sample of rows (numpy seed 0, sorted) and the chosen row indices go into <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    total = sum(v.nbytes for v in arrays.values())
+    for name in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        v = arrays[name]
+        if total <= DUMP_LIMIT_BYTES or v.ndim == 0 or v.shape[0] < 2:
+            break
+        row = v.nbytes // v.shape[0]
+        keep = max(1, min(v.shape[0] - 1, (v.nbytes - (total - DUMP_LIMIT_BYTES)) // (row + 8)))
+        rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=keep, replace=False))
+        arrays[name] = v[rows]
+        arrays[name + "_rows"] = rows.astype(np.float64)
+        total += arrays[name].nbytes + arrays[name + "_rows"].nbytes - v.nbytes
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return sorted(arrays)
 
 
 def measured_traffic(N, M, chains, want_grad=False, workload="chain"):
@@ -504,7 +532,7 @@ def run_chains(a, rank, world, be):
     allp = chain_parameters(sim, d, B)
     ev = be.chains(d, allp, hv, a.groups)
     want_grad = bool(a.grad)
-    prof = getattr(ev, "ctx", None)          # stage timers exist on the HIP backend only
+    prof = getattr(ev, "ctx", None) if a.full else None          # stage timers: HIP backend, --full only
     if prof is not None:
         prof.profile_enable(True)   # on from the warm-up on: the HIP events are created on first use, outside the timed region
     for _ in range(a.warmup):
@@ -513,6 +541,7 @@ def run_chains(a, rank, world, be):
         prof.profile_reset()
     elapsed, out, status = timed_steps(be, ev, world, a.steps, want_grad)
     rank_seconds = timed_steps.rank_seconds
+    last_grads = ev.grads
     stage = prof.profile_read() if prof is not None else {}
     kprof = None
     if prof is not None:
@@ -528,7 +557,7 @@ def run_chains(a, rank, world, be):
         prof.profile_enable(False)
     # the MCMC-relevant rate: value + gradient at the same chain count (skipped when the headline itself is --grad)
     grad_rec = None
-    if not want_grad and a.grad_steps > 0:
+    if a.full and not want_grad and a.grad_steps > 0:
         for _ in range(max(1, min(a.warmup, 1))):
             ev.step(True)
         if prof is not None:
@@ -591,12 +620,13 @@ def run_chains(a, rank, world, be):
             rec["grad"] = grad_rec
         if hmc_rec is not None:
             rec["hmc"] = hmc_rec
-        elif world > 1 and a.hmc_samples > 0:
+        elif a.full and world > 1 and a.hmc_samples > 0:
             rec["hmc_note"] = "not measured on multi-GPU lines (--hmc-all-ranks turns it on): the N = 1 line carries the sampler object"
         rec["distributed"] = dist_report(be, world, rank_seconds, a.steps)
-        if not a.no_cpu_baseline:
-            # every line carries its CPU figure: rank 0 times the oracle AFTER the timed region (the other ranks wait at the final
-            # barrier), with fewer evaluations when N > 1 so that a multi-GPU run is not held up
+        rec["outputs"] = {"out": out, "status": status, "grad": last_grads if want_grad else None}
+        if a.full and not a.no_cpu_baseline:
+            # every --full line carries its CPU figure: rank 0 times the oracle AFTER the timed region (the other ranks wait at the
+            # final barrier), with fewer evaluations when N > 1 so that a multi-GPU run is not held up
             ce, cg = (a.cpu_evals, a.cpu_grad_evals) if world == 1 else (min(a.cpu_evals, 3), min(a.cpu_grad_evals, 1))
             rec["cpu_baseline"] = cpu_baseline(d, allp[0], hyper, ce, want_grad, cg)
         # flat scalars first: a truncated record still shows them
@@ -683,7 +713,7 @@ def run_subjects(a, rank, world, be):
     pars = np.stack([sim.perturb(d["pars_true"], 0.05, 0.7 + 0.37 * k) for d in subs for k in range(K)])
     ev = be.subjects(subs, pars, hv, K) if K > 1 else be.subjects(subs, pars, hv)
     want_grad = bool(a.grad)
-    prof = getattr(ev, "ctx", None)
+    prof = getattr(ev, "ctx", None) if a.full else None          # stage timers: HIP backend, --full only
     if prof is not None:
         prof.profile_enable(True)
     for _ in range(a.warmup):
@@ -692,6 +722,7 @@ def run_subjects(a, rank, world, be):
         prof.profile_reset()
     elapsed, outs, status = timed_steps(be, ev, world, a.steps, want_grad)
     rank_seconds = timed_steps.rank_seconds
+    last_grads = ev.grads
     stage = prof.profile_read() if prof is not None else {}
     if prof is not None:
         prof.profile_enable(False)
@@ -706,7 +737,6 @@ def run_subjects(a, rank, world, be):
         fact_tf = (len(mine) * K * (2.0 if want_grad else 1.0) * float(n) ** 3 / 3.0) / chol_s / 1e12 if chol_s > 0 else 0.0
         total = a.steps * n_subj * K
         value = total / elapsed
-        traffic, traffic_note, traffic_scope = measured_traffic(N, M, len(mine) * K, want_grad, "subjects")
         e2e = value * float(n) ** 3 / (1.0 if want_grad else 3.0) / 1e12 / world / FP64_MATRIX_PEAK_TFLOPS
         rec = {
             "metric": "log-posterior evals/sec (%d subjects, N=%d, D=%d nonseparable GP)" % (n_subj, N, M),
@@ -724,21 +754,24 @@ def run_subjects(a, rank, world, be):
                                                                        "value+gradient" if want_grad else "value", M, N),
                        "chains_per_subject": K,
                        "subjects_total": n_subj, "subjects_ok": int(stats[0]), "subjects_failed": int(stats[1]),
-                       "sum_neglog": float(stats[3]), "subject_table_rows": int(table.shape[0]), "stage_ms": stage_ms},
-            "roofline": {"kernel": "blocked FP64 Cholesky stage of rank 0's multi-subject batch (k_syrk_lower + panel "
-                                   "kernels%s): subjects * n^3/3 flop%s over the HIP-event stage time" % (
-                                       ", with the L^-T rows" if want_grad else "", " x 2" if want_grad else ""),
-                         "bound": "mfma", "achieved": fact_tf, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": fact_tf / FP64_MATRIX_PEAK_TFLOPS, "traffic": traffic, "traffic_note": traffic_note,
-                         "traffic_scope": traffic_scope},
-            "distributed": dist_report(be, world, rank_seconds, a.steps)}
+                       "sum_neglog": float(stats[3]), "subject_table_rows": int(table.shape[0]), "stage_ms": stage_ms}}
+        if a.full:
+            traffic, traffic_note, traffic_scope = measured_traffic(N, M, len(mine) * K, want_grad, "subjects")
+            rec["roofline"] = {"kernel": "blocked FP64 Cholesky stage of rank 0's multi-subject batch (k_syrk_lower + panel "
+                                         "kernels%s): subjects * n^3/3 flop%s over the HIP-event stage time" % (
+                                             ", with the L^-T rows" if want_grad else "", " x 2" if want_grad else ""),
+                               "bound": "mfma", "achieved": fact_tf, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": fact_tf / FP64_MATRIX_PEAK_TFLOPS, "traffic": traffic, "traffic_note": traffic_note,
+                               "traffic_scope": traffic_scope}
+        rec["distributed"] = dist_report(be, world, rank_seconds, a.steps)
+        rec["outputs"] = {"out": outs, "status": status, "grad": last_grads if want_grad else None}
         if world == 1 and a.all_subjects > len(mine) and prof is not None:
             # the other end of config 4's scaling curve on the same box: ALL subjects of the 8-GPU job as one batch on this GPU
             rec["all_subjects_on_one_gpu"] = subjects_side_rate(a, be, a.all_subjects, hv, K, want_grad)
             rec["all_subjects_on_one_gpu"]["note"] = (
                 "config 4 scales STRONGLY: %d subjects on one GPU run at this rate; %d GPUs x the per-GPU share's rate above is the "
                 "most the sharded job can reach" % (a.all_subjects, max(1, a.all_subjects // max(len(mine), 1))))
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             ce = a.cpu_evals if world == 1 else min(a.cpu_evals, 3)
             rec["cpu_baseline"] = cpu_baseline(subs[0], pars[0], hyper, ce, want_grad, 0)
             rec["cpu_evals_per_s"] = rec["cpu_baseline"]["value"]
@@ -783,7 +816,7 @@ def run_separable(a, rank, world, be):
     pars = np.stack([sim.perturb(d["pars_true"], 0.05, 0.4 + 0.1 * k) for k in range(B)])
     ev = be.separable(d, pars, hv)
     want_grad = bool(a.grad)
-    prof = getattr(ev, "ctx", None)
+    prof = getattr(ev, "ctx", None) if a.full else None          # stage timers: HIP backend, --full only
     if prof is not None:
         prof.profile_enable(True)
     for _ in range(a.warmup):
@@ -792,6 +825,7 @@ def run_separable(a, rank, world, be):
         prof.profile_reset()
     elapsed, out, status = timed_steps(be, ev, world, a.steps, want_grad)
     rank_seconds = timed_steps.rank_seconds
+    last_grads = ev.grads
     stage = prof.profile_read() if prof is not None else {}
     kprof = None
     if prof is not None:
@@ -803,7 +837,7 @@ def run_separable(a, rank, world, be):
         kprof = prof.profile_read_work()
         prof.profile_enable(False)
     grad_rec = None
-    if not want_grad and a.grad_steps > 0:
+    if a.full and not want_grad and a.grad_steps > 0:
         ev.step(True)
         if prof is not None:
             prof.profile_enable(True)
@@ -854,7 +888,7 @@ def run_separable(a, rank, world, be):
         rec = {
             "metric": "log-posterior evals/sec (N=%d, D=%d separable GP)" % (N, M),
             "value": value, "unit": "evals/s", "n_gpus": world,
-            "roofline_frac_end_to_end": e2e, "roofline_frac_kernel": rl["frac"],
+            "roofline_frac_end_to_end": e2e, "roofline_frac_kernel": rl["frac"] if a.full else None,
             "value_grad_evals_per_s": value if want_grad else (grad_rec["value"] if grad_rec else None),
             "value_grad_roofline_frac_end_to_end": e2e if want_grad else (grad_rec["roofline"]["frac"] if grad_rec else None),
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True,
@@ -866,12 +900,14 @@ def run_separable(a, rank, world, be):
                                                                    (", gradients [B, P] of every chain" if want_grad else ""),
                        "host_writes_per_step": "parameter vectors [B, 2N+T+1]",
                        "neglog_rank0_chain0": float(out[0][0]), "chains_total": B * world, "chains_ok": int(stats[0]),
-                       "chains_failed": int(stats[1]), "sum_neglog_all_chains": float(stats[3]), "stage_ms": stage_ms},
-            "roofline": rl}
+                       "chains_failed": int(stats[1]), "sum_neglog_all_chains": float(stats[3]), "stage_ms": stage_ms}}
+        if a.full:
+            rec["roofline"] = rl
         if grad_rec is not None:
             rec["grad"] = grad_rec
         rec["distributed"] = dist_report(be, world, rank_seconds, a.steps)
-        if not a.no_cpu_baseline:
+        rec["outputs"] = {"out": out, "status": status, "grad": last_grads if want_grad else None}
+        if a.full and not a.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline_separable(d, pars[0], hyper, 2 if world == 1 else 1, want_grad or grad_rec is not None)
             rec["cpu_evals_per_s"] = rec["cpu_baseline"]["value"]
     ev.close()
@@ -974,8 +1010,14 @@ def self_launch(argv, n, script=None, out=None, timeout=None):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=12)
+    ap.add_argument("--steps", type=int, default=12, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: stage and k_syrk_lower timers (roofline), the value+gradient "
+                         "(`grad`) and sampler (`hmc`) side measurements, the HBM / dgemm ceilings, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's out, status and, with --grad, "
+                         "grad; with N > 1 ranks also the reduced table of every chain) as DIR/<name>.npy in float64")
     ap.add_argument("--N", type=int, default=None, help="locations (default 2048; workload separable: 4096)")
     ap.add_argument("--M", type=int, default=None, help="outputs D (default 3; workload separable: 5)")
     ap.add_argument("--grad", action="store_true", help="time value+gradient evaluations as the headline")
@@ -1028,6 +1070,8 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-grad-evals", type=int, default=2,
                     help="timed value+gradient evaluations of the CPU oracle (cpu_baseline.grad, next to the `grad` object)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     sep = a.workload == "separable"
     if a.N is None:
         a.N = 4096 if sep else 2048
@@ -1070,6 +1114,12 @@ def main(argv=None, backend=None):
         extra = rec.pop("config_extra", None)
         if extra:
             rec["config"].update(extra)
+        outputs = rec.pop("outputs")
+        if a.dump_outputs:
+            if world > 1:
+                outputs["table"] = table          # [global id, ok, evals, NegLog, loglik, lp_l, lp_uL, lp_s2] of every chain
+            rec["dumped_outputs"] = dump_outputs(a.dump_outputs, outputs)
+        rec["full"] = bool(a.full)
         if a.rehearse_on_one_gpu:
             rec["rehearsal"] = True
             rec["rehearsal_note"] = ("ranks share GPU(s) (rank r -> GPU r mod visible) and talk gloo: a functional rehearsal of the "

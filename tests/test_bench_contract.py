@@ -28,7 +28,7 @@ def test_cpu_baseline_helper_runs_on_cpu():
 @pytest.mark.parametrize("extra", [["--chains", "3"], ["--chains", "1", "--grad"],
                                    ["--workload", "subjects", "--subjects-per-gpu", "3"]])
 def test_bench_prints_one_valid_json_line(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--N", "96", "--M", "3", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--N", "96", "--M", "3", "--steps", "2", "--warmup", "1",
            "--cpu-evals", "1"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -61,6 +61,37 @@ def test_bench_prints_one_valid_json_line(extra):
         assert "grad" not in rec and "gradients" in rec["config"]["host_reads_per_step"]
     assert rl["traffic"] is None and rl["traffic_note"]          # no PMC measurement exists for this toy size
     assert np.isfinite(rec["value"]) and rec["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the headline line without the side measurements, and --dump-outputs writes the last timed
+    step's results (out, status, grad) in float64; they agree with the CPU oracle."""
+    from conftest import relerr, vec_relerr
+    B = 3
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--N", "96", "--M", "3", "--steps", "2", "--warmup", "1", "--chains", str(B),
+           "--grad", "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "config"):
+        assert k in rec, k
+    assert rec["steps"] == 2 and rec["full"] is False and rec["value"] > 0 and rec["config"]["chains_ok"] == B
+    assert not any(k in rec for k in ("cpu_baseline", "grad", "hmc", "roofline"))
+    assert rec["dumped_outputs"] == ["grad", "out", "status"]
+    o, st, g = (np.load(os.path.join(str(tmp_path), n + ".npy")) for n in ("out", "status", "grad"))
+    assert o.dtype == g.dtype == np.float64 and o.shape == (B, 5) and g.shape[0] == B and np.all(st == 0)
+    sys.path.insert(0, ROOT)
+    import bench
+    from nonstationary_multivariate_gaussian_process_amd import sim
+    from oracle import nmgp_oracle as O
+    d = sim.simulate_nonseparable(96, 3, seed=2222)
+    allp = bench.chain_parameters(sim, d, B)
+    for b in range(B):
+        ref, gref = O.nlogpos_obj_SVC(allp[b], d["Y"], d["x"], **sim.HYPER_SVC, verbose=True, grad=True)
+        assert relerr(o[b, 0], ref[0]) < 1e-6 and vec_relerr(g[b], gref) < 1e-5
 
 
 def test_profile_tools_replay_the_launch_schedule_of_the_throughput_path():

@@ -167,7 +167,7 @@ def test_bench_dist_selftest_runs_rccl_next_to_the_library_streams():
     three streams -- the part of the multi-GPU path (HipBackend.init_dist + collectives on CUDA tensors) a single-GPU box can execute."""
     env = dict(os.environ)
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dist-selftest", "--chains", "3", "--N", "96", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dist-selftest", "--chains", "3", "--N", "96", "--steps", "2",
                           "--warmup", "1", "--grad-steps", "1", "--hmc-samples", "0", "--no-cpu-baseline"], capture_output=True,
                          text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -240,7 +240,7 @@ def test_bench_launches_two_ranks_by_itself_and_rehearses_the_multi_process_path
     streams on the box's one GPU and runs the real evaluations; barrier, max-over-ranks, gathers and the final reduction go through a
     gloo process group (RCCL refuses two ranks on one device).  What a one-GPU box can execute of the N > 1 path, as one command."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--chains", "3", "--N", "96",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-on-one-gpu", "--chains", "3", "--N", "96",
                           "--steps", "2", "--warmup", "1", "--grad-steps", "1", "--hmc-samples", "1", "--hmc-all-ranks", "--hmc-mass", "identity",
                           "--cpu-evals", "1", "--cpu-grad-evals", "0"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)

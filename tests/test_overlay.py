@@ -1,10 +1,12 @@
-"""The drop-in recipe of INTEGRATION.md section 1 against the script it cites: the import block of the reference's
-``Nonseparable_Model/Nonseparable_model.py`` (lines 22-37) must run unchanged with the mirror installed, the hot-path
-names must be the MI355X ones and everything else must come from the user's own reference checkout.
+"""The drop-in recipe of INTEGRATION.md section 1 against the layout of the scripts it cites: a model script's import block
+(``sys.path.append(".."); import HMC_Sampler; from Utility import ...``) must run unchanged with the mirror installed, the
+hot-path names must be the MI355X ones and everything else must come from the user's own checkout of the reference.
 
-Build-container only: skipped where /root/reference is absent (the GPU box).  The reference's lines are READ from the
-checkout at test time and executed in a child process whose working directory is the script's folder (so that its
-``sys.path.append("..")`` means what it means for the script); nothing of the reference lives in this repository.
+The checkout is a stand-in written by the tests themselves (``ref_checkout`` below): the reference's directory layout, model
+scripts whose only content is their import lines, and a ``Utility`` folder whose modules define the helpers the scripts call
+with trivial bodies -- nothing of the reference lives in this repository or is read at test time.  Its copies of the modules
+the mirror provides refuse to be imported, so every test also shows that the mirror wins.  Scripts run in a child process
+whose working directory is the script's folder (so that ``sys.path.append("..")`` means what it means for the script).
 CPU only: importing never touches the GPU."""
 import os
 import subprocess
@@ -14,17 +16,68 @@ import textwrap
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-SCRIPT = os.path.join(REF, "Nonseparable_Model", "Nonseparable_model.py")
 
-pytestmark = pytest.mark.skipif(not os.path.isfile(SCRIPT), reason="reference checkout not present")
+# modules the mirror does not provide, as the user's checkout has them (helper names only; `from . import utils` shows that a
+# passed-through module binds its package-relative imports to the mirror)
+PASS_THROUGH = {
+    "visualization": "def Plot_posterior(*args, **kwargs):\n    return None\n",
+    "posterior_analysis": "from . import utils\n\n\ndef cov2cor(C):\n    return C\n",
+    "model_validation": "def get_AIC(*args):\n    return 0.0\n",
+    "preprocess_realdata": "def orig2adj(*args):\n    return args\n",
+    "empirical_estimation": "from . import utils\n\n\ndef local_estimation(*args):\n    return args\n",
+}
+# partly mirrored modules: the names the mirror lacks are taken from the user's module of the same name
+PARTLY_MIRRORED = {
+    "logpos": "from . import kernels, distributions\n\n\ndef nlogpos_obj_hadamard_SVC(*args):\n    return 0.0\n",
+    "utils": "".join("def %s(*args):\n    return args\n\n\n" % f for f in ("data_split", "MSE", "RMSE", "LPD")),
+    "prediction": "".join("def %s(*args):\n    return args\n\n\n" % f for f in (
+        "vec2pars", "vec2list", "pointwise_predsample_inhomogeneous", "test_predmap_inhomogeneous_sampling")),
+}
+# modules the mirror provides in full: the user's copies must never be imported
+MIRRORED = ("kernels", "kronecker_operation", "distributions", "settings")
+# model scripts of the three families and the post-processing folder: their import lines only
+MAIN_SCRIPT = os.path.join("Nonseparable_Model", "Nonseparable_model.py")
+SCRIPTS = {
+    MAIN_SCRIPT: ("import sys\n"
+                  "sys.path.append(\"..\")\n"
+                  "import HMC_Sampler\n"
+                  "from Utility import logpos, settings, utils, prediction\n"
+                  "from Utility import model_validation, visualization, posterior_analysis, preprocess_realdata, empirical_estimation\n"),
+    os.path.join("Nonseparable_Model", "Nonseparable_model_mpisim.py"): (
+        "import sys\nsys.path.append('..')\nfrom Utility import logpos\nfrom Utility import utils\nfrom Utility import settings\n"),
+    os.path.join("Separable_Model", "Separable_model.py"): (
+        "import sys\nsys.path.append('..')\nfrom Utility import kernels, kronecker_operation, distributions\n"
+        "from Utility import logpos, prediction, visualization\n"),
+    os.path.join("Stationary_Model", "Stationary_model.py"): (
+        "import sys\nsys.path.append('..')\nfrom Utility import logpos, utils\n"
+        "from Utility import empirical_estimation, model_validation\n"),
+    os.path.join("Post_Process", "posterior_summary.py"): (
+        "import sys\nsys.path.append('..')\nfrom Utility import posterior_analysis, visualization, utils\n"),
+}
+
+
+@pytest.fixture(scope="module")
+def ref_checkout(tmp_path_factory):
+    """A stand-in checkout of the reference: returns (root, Utility dir, main script)."""
+    root = tmp_path_factory.mktemp("reference_checkout")
+    util = root / "Utility"
+    util.mkdir()
+    (util / "__init__.py").write_text("")
+    for name, body in list(PASS_THROUGH.items()) + list(PARTLY_MIRRORED.items()):
+        (util / (name + ".py")).write_text(body)
+    for name in MIRRORED:
+        (util / (name + ".py")).write_text("raise ImportError('the user\\'s %s.py was imported: the mirror must win')\n" % name)
+    for rel, body in SCRIPTS.items():
+        p = root / rel
+        p.parent.mkdir(exist_ok=True)
+        p.write_text(body)
+    return str(root), str(util), str(root / MAIN_SCRIPT)
+
 
 CHILD = textwrap.dedent('''
     import os, sys, types
     sys.dont_write_bytecode = True
-    # stand-in for what the image lacks: seaborn.  (The external HMC package of line 25 -- absent from the reference tree -- is
-    # served by the mirror's own HMC_Sampler package: no stub.)
-    sys.modules["seaborn"] = types.ModuleType("seaborn")
+    # (the script's external HMC package is served by the mirror's own HMC_Sampler package: no stub)
     MODE = sys.argv[1]
     if MODE == "alias":
         sys.path.insert(0, {root!r})
@@ -36,12 +89,11 @@ CHILD = textwrap.dedent('''
         nmgp_amd.install_utility_alias(reference_utility_dir={refutil!r})
     else:                       # PYTHONPATH variant: the mirror's parent first on the path, script untouched
         assert any(p.endswith("nonstationary_multivariate_gaussian_process_amd") for p in sys.path), sys.path
-    lines = open({script!r}).read().split("\\n")
-    block = "\\n".join(lines[21:37])          # lines 22-37: "# import private library" ... "from Utility import empirical_estimation"
+    block = open({script!r}).read()          # the script's import block, run as it stands
     assert "from Utility import logpos" in block and "empirical_estimation" in block
     exec(compile(block, {script!r}, "exec"))
     mirror = os.path.join({root!r}, "nonstationary_multivariate_gaussian_process_amd", "Utility")
-    # line 25 `import HMC_Sampler` got the mirror's sampler package, with the entry point the script calls at lines 228-231
+    # the script's `import HMC_Sampler` got the mirror's sampler package, with the entry point the model scripts call
     import inspect as _insp
     assert os.path.dirname(os.path.abspath(_insp.getsourcefile(HMC_Sampler.HMC_sampler.sampler))) == os.path.join(
         {root!r}, "nonstationary_multivariate_gaussian_process_amd", "HMC_Sampler"), HMC_Sampler
@@ -86,14 +138,15 @@ CHILD = textwrap.dedent('''
 
 
 @pytest.mark.parametrize("mode", ["alias", "alias_explicit", "pythonpath"])
-def test_reference_script_import_block_runs_on_the_overlay(mode, tmp_path):
-    code = CHILD.format(root=ROOT, script=SCRIPT, refutil=os.path.join(REF, "Utility"))
+def test_reference_script_import_block_runs_on_the_overlay(mode, ref_checkout):
+    _, refutil, script = ref_checkout
+    code = CHILD.format(root=ROOT, script=script, refutil=refutil)
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", MPLBACKEND="Agg")
     env.pop("NMGP_REFERENCE_UTILITY", None)
     if mode == "pythonpath":
         env["PYTHONPATH"] = os.path.join(ROOT, "nonstationary_multivariate_gaussian_process_amd") + os.pathsep + \
             env.get("PYTHONPATH", "")
-    r = subprocess.run([sys.executable, "-c", code, mode], cwd=os.path.dirname(SCRIPT), env=env, capture_output=True,
+    r = subprocess.run([sys.executable, "-c", code, mode], cwd=os.path.dirname(script), env=env, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0 and "OVERLAY-OK" in r.stdout, r.stdout + r.stderr
 
@@ -127,15 +180,15 @@ def test_mirror_alone_names_what_is_missing():
     assert r.returncode == 0 and "ALONE-OK" in r.stdout, r.stdout + r.stderr
 
 
-def test_utility_imports_of_every_reference_script_resolve_on_the_overlay():
-    """All 17 scripts of the reference that import from ``Utility`` (the three model families, their MPI / simulation / real-data
-    variants, the post-processing and simulation tools): their ``from Utility import ...`` lines -- read from the checkout at
-    test time -- run on the overlay from the script's own directory, and every imported module is either a mirror module or
-    the user's own file."""
+def test_utility_imports_of_every_reference_script_resolve_on_the_overlay(ref_checkout):
+    """Every script of the checkout that imports from ``Utility`` (the three model families, an MPI variant, the post-processing
+    folder): its ``from Utility import ...`` lines run on the overlay from the script's own directory, and every imported module
+    is either a mirror module or the user's own file."""
     import glob
-    scripts = sorted(p for p in glob.glob(os.path.join(REF, "*", "*.py"))
-                     if os.path.dirname(p) != os.path.join(REF, "Utility") and "from Utility import" in open(p).read())
-    assert len(scripts) >= 15
+    ref, refutil, _ = ref_checkout
+    scripts = sorted(p for p in glob.glob(os.path.join(ref, "*", "*.py"))
+                     if os.path.dirname(p) != refutil and "from Utility import" in open(p).read())
+    assert len(scripts) == len(SCRIPTS)
     code = textwrap.dedent('''
         import os, sys, types, re
         sys.dont_write_bytecode = True
@@ -164,10 +217,10 @@ def test_utility_imports_of_every_reference_script_resolve_on_the_overlay():
         assert {"logpos", "kernels", "kronecker_operation", "distributions", "utils", "settings", "prediction"} <= mirrored, mirrored
         assert {"posterior_analysis", "visualization", "empirical_estimation"} <= {k for k, m in seen if not m}
         print("IMPORTS-OK", len(sys.argv) - 1)
-    ''') % (ROOT, ROOT, os.path.join(REF, "Utility"))
+    ''') % (ROOT, ROOT, refutil)
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", MPLBACKEND="Agg")
     env.pop("NMGP_REFERENCE_UTILITY", None)
-    r = subprocess.run([sys.executable, "-c", code] + scripts, cwd=os.path.join(REF, "Nonseparable_Model"), env=env,
+    r = subprocess.run([sys.executable, "-c", code] + scripts, cwd=os.path.join(ref, "Nonseparable_Model"), env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "IMPORTS-OK" in r.stdout, r.stdout + r.stderr
 

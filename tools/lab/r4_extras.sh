@@ -1,6 +1,6 @@
 # round-4 side measurements quoted in DESIGN section 5 (one call on the GPU box) -> gpurun_out/r4x/
 mkdir -p gpurun_out/r4x
-Q="--hmc-samples 0 --no-cpu-baseline"
+Q="--full --hmc-samples 0 --no-cpu-baseline"
 run() { tag=$1; shift; python bench.py $Q "$@" 2>gpurun_out/r4x/$tag.err | tail -1 > gpurun_out/r4x/$tag.json; python -c "import json;r=json.load(open('gpurun_out/r4x/$tag.json'));print('$tag', round(r['value'],1), round(r['ms_per_step'],3), round(r['roofline']['frac'],3), round(r.get('grad',{}).get('value',0),1))"; }
 run cfg2_chains1N1024 --chains 1 --N 1024 --steps 50 --warmup 5 --grad-steps 20
 run c1 --chains 1 --steps 30 --warmup 5 --grad-steps 10

@@ -12,7 +12,7 @@ O=$R/gpurun_out/$1
 P=${2:-r05}
 mkdir -p "$O"
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --hmc-samples 0"
+Q="--full --no-cpu-baseline --hmc-samples 0"
 cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 600 rocprofv3 --pmc $c -d "$O/raw_pmc_$c" -o pmc --output-format csv -- python3 "$R/bench.py" $Q --chains 128 --grad --steps 1 --warmup 1 \
@@ -43,7 +43,7 @@ python3 tools/pin_traffic.py "profiles/${P}_g128_pmc_traffic.json" 2048 3 128 1 
 python3 tools/pin_traffic.py "profiles/${P}_s8_pmc_traffic.json" 1024 3 8 0 subjects
 python3 tools/pin_traffic.py "profiles/${P}_sep16_pmc_traffic.json" 4096 5 16 0 separable
 cp profiles/traffic.json "$O/traffic.json"
-python3 bench.py --no-cpu-baseline --hmc-samples 0 --steps 3 --grad-steps 2 > "$O/bench_after_pin.json" 2> "$O/bench_after_pin.err"
+python3 bench.py --full --no-cpu-baseline --hmc-samples 0 --steps 3 --grad-steps 2 > "$O/bench_after_pin.json" 2> "$O/bench_after_pin.err"
 python3 - <<PY
 import json
 r = json.loads(open("$O/bench_after_pin.json").read().strip().splitlines()[-1])

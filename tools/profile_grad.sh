@@ -11,7 +11,7 @@ B=${2:-128}
 mkdir -p "$O"
 cd /tmp
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --hmc-samples 0 --chains $B --grad"
+Q="--full --no-cpu-baseline --hmc-samples 0 --chains $B --grad"
 t=g$B
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$O/raw_$t" -o "$t" --output-format csv -- python3 "$R/bench.py" $Q --steps 2 --warmup 1 \
     > "$O/$t.json" 2> "$O/$t.err"

@@ -7,7 +7,7 @@ O=$R/gpurun_out/$1
 mkdir -p "$O"
 cd /tmp
 export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/raw_hmc" -o hmc128 --output-format csv -- python3 "$R/bench.py" --no-cpu-baseline \
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/raw_hmc" -o hmc128 --output-format csv -- python3 "$R/bench.py" --full --no-cpu-baseline \
     --steps 2 --warmup 1 --grad-steps 1 --hmc-samples 2 > "$O/hmc128.json" 2> "$O/hmc128.err"
 cp "$(find "$O/raw_hmc" -name '*kernel_stats.csv' | head -1)" "$O/hmc128_kernel_stats.csv"
 rm -rf "$O/raw_hmc"

@@ -8,7 +8,7 @@ O=$R/gpurun_out/$1
 mkdir -p "$O"
 cd /tmp
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --hmc-samples 0 --grad-steps 0"
+Q="--full --no-cpu-baseline --hmc-samples 0 --grad-steps 0"
 timeout -k 10 500 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d "$O/raw_v" -o pmc --output-format csv -- \
     python3 "$R/bench.py" $Q --steps 2 --warmup 1 > "$O/v128_pmc_mfma_bench.json" 2> "$O/v128_pmc_mfma.err"
 cp "$(find "$O/raw_v" -name '*counter_collection.csv' | head -1)" "$O/v128_pmc_MFMA_BUSY.csv"

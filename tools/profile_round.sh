@@ -10,7 +10,7 @@ O=$R/gpurun_out/$1
 mkdir -p "$O"
 cd /tmp
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --grad-steps 0 --hmc-samples 0"
+Q="--full --no-cpu-baseline --grad-steps 0 --hmc-samples 0"
 
 trace() {      # trace <tag> <marker> <program args...>
     local tag=$1 marker=$2
@@ -66,5 +66,5 @@ python3 tools/pmc_summary.py "$O/s8_pmc_FETCH_SIZE.csv" "$O/s8_pmc_WRITE_SIZE.cs
 cp "$O/s8_pmc_traffic.json" "profiles/${2:-r02}_s8_pmc_traffic.json"
 python3 tools/pin_traffic.py "profiles/${2:-r02}_s8_pmc_traffic.json" 1024 3 8 0 subjects
 cp profiles/traffic.json "$O/traffic.json"
-python3 bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"
+python3 bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"
 tail -1 "$O/bench_default.json" | cut -c1-400

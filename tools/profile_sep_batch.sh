@@ -11,7 +11,7 @@ mkdir -p "$O"
 cd /tmp
 export TMPDIR=/tmp
 for mode in v g; do
-    Q="--workload separable --chains $B --no-cpu-baseline --grad-steps 0 --steps 3 --warmup 1"
+    Q="--full --workload separable --chains $B --no-cpu-baseline --grad-steps 0 --steps 3 --warmup 1"
     marker=k_col_sumsq
     if [ $mode = g ]; then Q="$Q --grad"; marker=k_sep_grad_sum_b; fi
     t=sep${B}$mode

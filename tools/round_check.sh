@@ -12,11 +12,11 @@ cp gpurun_out/parity_$NMGP_ROUND.json $O/parity_$NMGP_ROUND.json 2>/dev/null || 
 python -c "import __graft_entry__ as g; g.smoke()"
 timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
 tail -1 $O/bench_default.json | cut -c1-700
-timeout -k 10 600 python bench.py --hmc-mass identity,prior --no-cpu-baseline --steps 4 --grad-steps 2 > $O/bench_hmc_both.json 2> $O/bench_hmc_both.err
-timeout -k 10 600 python bench.py --workload separable > $O/bench_sep16.json 2> $O/bench_sep16.err
+timeout -k 10 600 python bench.py --full --hmc-mass identity,prior --no-cpu-baseline --steps 4 --grad-steps 2 > $O/bench_hmc_both.json 2> $O/bench_hmc_both.err
+timeout -k 10 600 python bench.py --full --workload separable > $O/bench_sep16.json 2> $O/bench_sep16.err
 tail -1 $O/bench_sep16.json | cut -c1-500
-timeout -k 10 600 python bench.py --workload separable --chains 32 --no-cpu-baseline > $O/bench_sep32.json 2> $O/bench_sep32.err
-timeout -k 10 600 python bench.py --workload subjects --N 1024 > $O/bench_s8.json 2> $O/bench_s8.err
+timeout -k 10 600 python bench.py --full --workload separable --chains 32 --no-cpu-baseline > $O/bench_sep32.json 2> $O/bench_sep32.err
+timeout -k 10 600 python bench.py --full --workload subjects --N 1024 > $O/bench_s8.json 2> $O/bench_s8.err
 tail -1 $O/bench_s8.json | cut -c1-500
-timeout -k 10 600 python bench.py --workload subjects --N 1024 --subjects-total 64 --no-cpu-baseline > $O/bench_s64_strong.json 2> $O/bench_s64_strong.err
+timeout -k 10 600 python bench.py --full --workload subjects --N 1024 --subjects-total 64 --no-cpu-baseline > $O/bench_s64_strong.json 2> $O/bench_s64_strong.err
 echo done
