@@ -170,7 +170,7 @@ static void free_subject(nmgp_ctx* c) {
     free_priors(c);
     {
         double** bp[] = {&c->b_pars, &c->b_ell, &c->b_Lv, &c->b_S, &c->b_z, &c->b_R, &c->b_scal, &c->b_q,
-                         &c->b_S2, &c->b_Sinv, &c->b_alpha, &c->b_part, &c->b_grad, &c->b_R2, &c->b_tr};
+                         &c->b_S2, &c->b_Sinv, &c->b_alpha, &c->b_part, &c->b_grad, &c->b_R2, &c->b_tr, &c->b_u, &c->b_schur};
         c->b_grad_ready = false;
         c->b_multi = false;
         if (c->b_x) hipFree(c->b_x);
@@ -186,7 +186,9 @@ static void free_subject(nmgp_ctx* c) {
             *p = nullptr;
         }
         if (c->b_info) hipFree(c->b_info);
-        c->b_info = nullptr;
+        if (c->b_info2) hipFree(c->b_info2);
+        c->b_info = c->b_info2 = nullptr;
+        c->b_schur_stride = 0;
         c->batch = 0;
     }
 }
@@ -221,6 +223,7 @@ extern "C" int nmgp_ctx_create(int device, nmgp_ctx** out) {
         c->prior_trsv_all = std::strcmp(e, "trsv") == 0;
     }
     if (const char* e = std::getenv("NMGP_SEP")) c->sep_algo = (std::strcmp(e, "eig") == 0) ? 0 : 1;
+    if (const char* e = std::getenv("NMGP_SVC_SCHUR")) c->svc_schur = std::atoi(e) != 0 ? 1 : 0;
     {
         // Two streams for the look-ahead factorisation: the main stream carries the latency-bound panel steps (and
         // everything else of an evaluation), stream2 the far trailing updates that run under the NEXT panel's steps.
@@ -665,7 +668,8 @@ static void free_batch(nmgp_ctx* c) {
     double** ptrs[] = {&c->b_pars, &c->b_ell, &c->b_Lv, &c->b_S, &c->b_z, &c->b_R, &c->b_scal, &c->b_q,
                        &c->b_S2, &c->b_Sinv, &c->b_alpha, &c->b_part, &c->b_grad, &c->b_R2, &c->b_tr,
                        &c->b_mom, &c->b_q0, &c->b_g0, &c->b_am, &c->b_av, &c->b_minv, &c->b_vel, &c->b_mchol, &c->b_kin,
-                       &c->b_mU, &c->b_mw, &c->b_mc};
+                       &c->b_mU, &c->b_mw, &c->b_mc, &c->b_u, &c->b_schur};
+    c->b_schur_stride = 0;
     c->b_mass_kind = 0;
     c->b_mrank = 0;
     c->b_cps = 1;
@@ -690,7 +694,8 @@ static void free_batch(nmgp_ctx* c) {
         *p = nullptr;
     }
     if (c->b_info) hipFree(c->b_info);
-    c->b_info = nullptr;
+    if (c->b_info2) hipFree(c->b_info2);
+    c->b_info = c->b_info2 = nullptr;
     c->batch = 0;
 }
 
@@ -734,7 +739,9 @@ extern "C" int nmgp_svc_batch_alloc(nmgp_ctx* c, int B) {
     NMGP_TRY(nmgp_dev_alloc(c, &c->b_R, N * (size_t)B * (1 + T)));
     NMGP_TRY(nmgp_dev_alloc(c, &c->b_scal, (size_t)B * 16));
     NMGP_TRY(nmgp_dev_alloc(c, &c->b_q, (size_t)B * (1 + T)));
+    NMGP_TRY(nmgp_dev_alloc(c, &c->b_u, (size_t)B * N));
     HIP_TRY(c, hipMalloc((void**)&c->b_info, (size_t)B * sizeof(int)));
+    HIP_TRY(c, hipMalloc((void**)&c->b_info2, (size_t)B * sizeof(int)));
     HIP_TRY(c, hipMemsetAsync(c->b_pars, 0, (size_t)B * P * sizeof(double), c->stream));
     c->batch = B;
     return 0;
@@ -855,6 +862,98 @@ static int batch_grad_alloc(nmgp_ctx* c) {
     return 0;
 }
 
+// Structured value path (M >= 2; the algebra is at k_svc_schur_cov in nmgp_kernels.hip): output 0 of Sigma is eliminated in
+// closed form, so only A = K_x + diag(E) (N x N) and the Schur complement Sigma' ((M-1) N square) are factored, plus the
+// explicit -A^-1 that Sigma' needs: ((M-1)^3 + 3) / M^3 of the dense factorisation's flop (M = 3: 0.41).  Per chain slice
+// (b_S's own when large enough, which it is for every M >= 2: 3 N^2 + O(N) of 4 N^2 at M = 2):
+//   [0, ldA N)        A's buffer, ldA = ld(2N + 2): rows 0..N-1 A -> L_A -> -A^-1 (both triangles), row N v -> w = L_A^-1 v,
+//                     pad, rows N+1+pad.. X = L_A^-T (the gradient path's riding rows)
+//   [offP, ..)        Sigma' and its right-hand-side row y' -> w' (the value path's layout at n' = (M-1) N)
+//   [offPart, ..)     block sums of u = X w (tri_gemv_upper)
+// w and w' share b_z ([B, N] then [B, n']); u is b_u.  A chain's status is the first failing leading minor of Sigma.
+static bool schur_selected(const nmgp_ctx* c, int want_grad) {
+    if (want_grad || c->M < 2 || c->svc_schur == 0) return false;
+    // by default as well: measured at N = 2048, D = 3, the structured batch is faster from one chain on (1 / 4 / 16 / 32 / 64 / 128
+    // chains: 1.08 / 1.53 / 1.86 / 1.93 / 2.02 / 2.05x; 8 / 64 subjects of N = 1024: 1.27 / 1.65x) -- even in the latency schedule,
+    // whose N / 64 + (M - 1) N / 64 dependent steps are as many as the dense factorisation's, the steps of A are narrower
+    return true;
+}
+
+static int svc_batch_value_schur(nmgp_ctx* c, const double* xs, int xstride, const double* ys, long long ystride, int cps) {
+    const int N = c->N, M = c->M, B = c->batch, n1 = (M - 1) * N;
+    const long long P = c->P_svc;
+    const int xpad = (N + 1) & 1, xoffA = N + 1 + xpad;
+    const int ldA = (int)nmgp_ld((size_t)2 * N + 2), ldP = (int)nmgp_ld((size_t)n1 + 1);
+    auto r64 = [](size_t v) { return (v + 63) / 64 * 64; };
+    const size_t offP = r64((size_t)ldA * N), offPart = r64(offP + (size_t)ldP * n1);
+    const size_t need = offPart + (size_t)N * ((N + 255) / 256);
+    const size_t bsS = nmgp_ld((size_t)c->n + 1) * (size_t)c->n;
+    double* base = c->b_S;
+    size_t bsz = bsS;
+    if (need > bsS) {
+        if (c->b_schur_stride != need) {
+            NMGP_TRY(nmgp_dev_alloc(c, &c->b_schur, (size_t)B * need));
+            c->b_schur_stride = need;
+        }
+        base = c->b_schur;
+        bsz = need;
+    }
+    const long long bs = (long long)bsz;
+    double* A = base;
+    double* Sp = base + offP;
+    double* part = base + offPart;
+    double* w = c->b_z;
+    double* w1 = c->b_z + (size_t)B * N;
+    const double* tse = c->b_pars + (P - 1);
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemsetAsync(c->b_info2, 0, (size_t)B * sizeof(int), s));
+    {
+        StageScope sp(c, NMGP_STAGE_COV);
+        svc_prep(s, c->b_pars, N, M, c->b_ell, c->b_Lv, B);
+        int r = svc_schur_build(s, 0, xs, c->b_ell, c->b_Lv, tse, ys, A, ldA, nullptr, nullptr, 0, N, M, B, bs, xstride, ystride, cps);
+        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+    }
+    {
+        StageScope sp(c, NMGP_STAGE_CHOL);
+        identity_rows(s, A, ldA, N + 1, N, xpad, B, bs);
+        potrf_lower(s, c->stream2, nmgp_chol_events(c, N), A, ldA, N, 1 + xpad, N, c->chol_nb1, c->b_info, B, bs, 1,
+                    nmgp_syrk_hook(c));
+    }
+    {
+        StageScope sp(c, NMGP_STAGE_SOLVE);
+        get_row(s, A, ldA, N, w, N, B, bs, N);
+        tri_gemv_upper(s, A + xoffA, ldA, N, w, c->b_u, part, B, bs, bs);     // u = A^-1 v = X w
+    }
+    {
+        StageScope sp(c, NMGP_STAGE_REDUCE);
+        chol_logdet_quad(s, A, ldA, N, w, c->b_scal + 2, c->b_scal + 3, B, bs, 16);    // (reads L_A before the SYRK overwrites it)
+    }
+    {
+        StageScope sp(c, NMGP_STAGE_INVERSE);
+        syrk_lower(s, A + xoffA, ldA, A, ldA, N, N, N, B, bs, bs, 2);     // -A^-1 = -X X^T into rows 0..N-1, both triangles
+    }
+    {
+        StageScope sp(c, NMGP_STAGE_COV);
+        int r = svc_schur_build(s, 1, xs, c->b_ell, c->b_Lv, tse, ys, A, ldA, c->b_u, Sp, ldP, N, M, B, bs, xstride, ystride, cps);
+        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+    }
+    {
+        StageScope sp(c, NMGP_STAGE_CHOL);
+        potrf_lower(s, c->stream2, nmgp_chol_events(c, n1), Sp, ldP, n1, 1, 0, c->chol_nb1, c->b_info2, B, bs, 1,
+                    nmgp_syrk_hook(c));
+    }
+    {
+        StageScope sp(c, NMGP_STAGE_SOLVE);
+        get_row(s, Sp, ldP, n1, w1, n1, B, bs, n1);
+    }
+    {
+        StageScope sp(c, NMGP_STAGE_REDUCE);
+        chol_logdet_quad(s, Sp, ldP, n1, w1, c->b_scal + 4, c->b_scal + 5, B, bs, 16);
+        svc_schur_combine(s, c->b_Lv, N, M, c->b_scal, 16, c->b_info, c->b_info2, B);
+    }
+    return 0;
+}
+
 extern "C" int nmgp_svc_batch_eval(nmgp_ctx* c, const double hyper[8], int prior, int want_grad) {
     if (!c) return NMGP_E_NULL;
     if (!hyper) return nmgp_fail(c, NMGP_E_NULL, "hyper must not be NULL");
@@ -890,32 +989,36 @@ extern "C" int nmgp_svc_batch_eval(nmgp_ctx* c, const double hyper[8], int prior
     HIP_TRY(c, hipMemsetAsync(c->b_info, 0, (size_t)B * sizeof(int), s));
     if (nmgp_poison()) HIP_TRY(c, hipMemsetAsync(c->b_scal, 0xFF, (size_t)B * 16 * sizeof(double), s));
     PriorStreamScope ps(c);          // fork now, enqueue the prior solves after the factorisation (see svc_enqueue)
-    {
-        StageScope sp(c, NMGP_STAGE_COV);
-        svc_prep(s, c->b_pars, N, M, c->b_ell, c->b_Lv, B);
-        int r = svc_cov_build(s, xs, c->b_ell, c->b_Lv, c->b_pars + (P - 1), S, ld, N, M, false, B, bs, xstride, cps);
-        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-    }
-    {
-        StageScope sp(c, NMGP_STAGE_CHOL);
-        // one subject: every chain shares y (vstride 0); multi-subject: y of batch element b
-        set_row(s, S, ld, n, multi ? c->b_y : c->d_y, n, B, bs, multi ? n : 0, cps);
-        if (want_grad) identity_rows(s, S, ld, n + 1, n, xpad, B, bs);
-        potrf_lower(s, c->stream2, nmgp_chol_events(c, n), S, ld, n, want_grad ? 1 + xpad : 1, want_grad ? n : 0, c->chol_nb1,
-                    c->b_info, B, bs, 1, nmgp_syrk_hook(c));
-    }
-    {
-        StageScope sp(c, NMGP_STAGE_SOLVE);
-        get_row(s, S, ld, n, c->b_z, n, B, bs, n);
-        if (want_grad) {
-            // alpha_b = X_b z_b (b_part is free until the adjoint pass: scratch for the block sums)
-            tri_gemv_upper(s, S + xoff, (int)ld, n, c->b_z, c->b_alpha, c->b_part, (int)B, bs,
-                           (long long)n * ((n + 255) / 256));
+    if (schur_selected(c, want_grad)) {
+        NMGP_TRY(svc_batch_value_schur(c, xs, xstride, multi ? c->b_y : c->d_y, multi ? n : 0, cps));
+    } else {
+        {
+            StageScope sp(c, NMGP_STAGE_COV);
+            svc_prep(s, c->b_pars, N, M, c->b_ell, c->b_Lv, B);
+            int r = svc_cov_build(s, xs, c->b_ell, c->b_Lv, c->b_pars + (P - 1), S, ld, N, M, false, B, bs, xstride, cps);
+            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
         }
-    }
-    {
-        StageScope sp(c, NMGP_STAGE_REDUCE);
-        chol_logdet_quad(s, S, ld, n, c->b_z, c->b_scal, c->b_scal + 1, B, bs, 16);
+        {
+            StageScope sp(c, NMGP_STAGE_CHOL);
+            // one subject: every chain shares y (vstride 0); multi-subject: y of batch element b
+            set_row(s, S, ld, n, multi ? c->b_y : c->d_y, n, B, bs, multi ? n : 0, cps);
+            if (want_grad) identity_rows(s, S, ld, n + 1, n, xpad, B, bs);
+            potrf_lower(s, c->stream2, nmgp_chol_events(c, n), S, ld, n, want_grad ? 1 + xpad : 1, want_grad ? n : 0, c->chol_nb1,
+                        c->b_info, B, bs, 1, nmgp_syrk_hook(c));
+        }
+        {
+            StageScope sp(c, NMGP_STAGE_SOLVE);
+            get_row(s, S, ld, n, c->b_z, n, B, bs, n);
+            if (want_grad) {
+                // alpha_b = X_b z_b (b_part is free until the adjoint pass: scratch for the block sums)
+                tri_gemv_upper(s, S + xoff, (int)ld, n, c->b_z, c->b_alpha, c->b_part, (int)B, bs,
+                               (long long)n * ((n + 255) / 256));
+            }
+        }
+        {
+            StageScope sp(c, NMGP_STAGE_REDUCE);
+            chol_logdet_quad(s, S, ld, n, c->b_z, c->b_scal, c->b_scal + 1, B, bs, 16);
+        }
     }
     {
         NmgpStage sp(c, NMGP_STAGE_PRIOR, ps.sp, 0.0, 0.0);

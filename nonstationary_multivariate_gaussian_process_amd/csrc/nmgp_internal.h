@@ -64,6 +64,8 @@ struct nmgp_ctx {
     int chol_lookahead = 1;                   // far trailing update on stream2 under the next panel (small batches only)
     SyrkHook syrk_hook;
     int sep_algo = 1;                         // separable/stationary likelihood: 1 = M batched Cholesky blocks, 0 = dsyevd
+    int svc_schur = -1;                       // batched nonseparable value path: 1 structured (output 0 in closed form), 0 dense,
+                                              // -1 by batch size (NMGP_SVC_SCHUR)
     rocblas_handle blas = nullptr;
     std::string err;
 
@@ -113,6 +115,11 @@ struct nmgp_ctx {
     double* b_scal = nullptr;   // [B, 16] : logdet, quad, out5...
     double* b_q = nullptr;      // [B (1 + T)]
     int* b_info = nullptr;      // [B]
+    // structured value path (nmgp_svc_batch_eval, M >= 2: output 0 eliminated in closed form, see k_svc_schur_cov)
+    double* b_u = nullptr;      // [B, N] u = A^-1 v
+    int* b_info2 = nullptr;     // [B] status of the Schur complement's factorisation
+    double* b_schur = nullptr;  // [B] x b_schur_stride: A, -A^-1, Sigma' when they do not fit in b_S's chain slices
+    size_t b_schur_stride = 0;
     // batched gradient state (allocated on the first batched value+gradient evaluation)
     bool b_grad_ready = false;
     double* b_S2 = nullptr;     // [B] x (ld2 x n): covariance + y row + pad + identity rows -> L^-T
@@ -269,6 +276,14 @@ void svc_prep(hipStream_t s, const double* pars, int N, int M, double* ell, doub
 int svc_cov_build(hipStream_t s, const double* x, const double* ell, const double* Lv, const double* tse,
                   double* S, int ld, int N, int M, bool full, int batch = 1, long long sstride = 0, int xstride = 0, int cps = 1);
 // symmetric N x N builds (lower triangle unless full)
+// structured value path: phase 0 writes A = K_x + diag(E) (lower) and v into row N of A; phase 1 writes Sigma' (lower, n' = (M-1) N)
+// and y' into row n' of S from -A^-1 (rows 0..N-1 of A, both triangles) and u.  A and S of chain z are z * bstride apart.
+int svc_schur_build(hipStream_t s, int phase, const double* x, const double* ell, const double* Lv, const double* tse,
+                    const double* y, double* A, int lda, const double* u, double* S, int ld, int N, int M, int batch,
+                    long long bstride, int xstride, long long ystride, int cps);
+// sc[0] / sc[1] = log det / quadratic form of Sigma from the parts in sc[2..5]; info = first failing leading minor of Sigma
+void svc_schur_combine(hipStream_t s, const double* Lv, int N, int M, double* sc, int sstride, int* info, const int* info2,
+                       int batch);
 void rbf_cov_sym(hipStream_t s, const double* x, int N, double alpha, double beta, double* out, int ld, bool full,
                  int batch = 1);
 void gibbs_cov_sym(hipStream_t s, const double* x, const double* sig, const double* ell, int N, double* out, int ld,

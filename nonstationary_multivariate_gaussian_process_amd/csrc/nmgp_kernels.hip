@@ -164,6 +164,207 @@ int svc_cov_build(hipStream_t s, const double* x, const double* ell, const doubl
 }
 
 // ---------------------------------------------------------------------------------------------
+// Structured value path (M >= 2): output 0 eliminated in closed form.  Because L_i[0, c] = 0 for c > 0,
+//   Sigma_00 = D0 A D0  with  A = K_x + diag(E),  E_i = sigma2 / L_i00^2,  D0 = diag(L_i00),
+//   Sigma_a0 = diag(L_i[a, 0]) K_x D0,
+// and the Schur complement of Sigma_00 loses its K_x term exactly (K_x A^-1 K_x = K_x - E + E A^-1 E):
+//   Sigma'[(a,i),(b,j)] = K_x[i,j] sum_{c=1..min(a,b)} L_i[a,c] L_j[b,c] + d_ij sigma2 (d_ab + L_i[a,0] L_i[b,0] / L_i00^2)
+//                         - g_i[a] A^-1[i,j] g_j[b],          g_i[a] = sigma2 L_i[a,0] / L_i00^2,
+//   y'[(a,i)] = Y[i,a] - L_i[a,0] (v_i - E_i u_i),     v = Y[:,0] / L_00,  u = A^-1 v,
+//   log det Sigma = 2 sum_i log L_i00 + log det A + log det Sigma',   y^T Sigma^-1 y = v^T A^-1 v + y'^T Sigma'^-1 y'.
+// ---------------------------------------------------------------------------------------------
+// A (lower triangle, N x N) and v in row N of A's buffer; the tile shape, chain / subject indexing and K_x formula of k_svc_cov
+template <int M>
+__global__ __launch_bounds__(256) void k_svc_schur_a(const double* __restrict__ x, const double* __restrict__ ell,
+                                                      const double* __restrict__ Lv, const double* __restrict__ tse,
+                                                      const double* __restrict__ y, double* __restrict__ A, int ld, int N,
+                                                      long long astride, int xstride, long long ystride, int cps) {
+    constexpr int T = M * (M + 1) / 2;
+    constexpr int TJ = 64;
+    __shared__ double sx[TJ], sl[TJ];
+    const int I = blockIdx.x, J = blockIdx.y;
+    if (I < J) return;
+    x += (size_t)(blockIdx.z / cps) * xstride;
+    y += (size_t)(blockIdx.z / cps) * ystride;
+    ell += (size_t)blockIdx.z * N;
+    Lv += (size_t)blockIdx.z * N * T;
+    tse += (size_t)blockIdx.z * ((size_t)N * (1 + T) + 1);
+    A += (size_t)blockIdx.z * astride;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    if (tid < TJ) {
+        int j = j0 + tid;
+        sx[tid] = (j < N) ? x[j] : 0.0;
+        sl[tid] = (j < N) ? ell[j] : 1.0;
+    }
+    __syncthreads();
+    const int i = I * 64 + lane;
+    if (i >= N) return;
+    const double sigma2 = exp(tse[0]);
+    const double l00 = Lv[(size_t)i * T];
+    const double Ei = sigma2 / (l00 * l00);
+    if (J == 0 && w == 0) A[(size_t)i * ld + N] = y[i] / l00;     // v_i: the right-hand-side row
+    const double xi = x[i], li = ell[i];
+    const double xi2 = xi * xi, li2 = li * li;
+#pragma unroll 2
+    for (int jj = 0; jj < TJ / 4; ++jj) {
+        const int k = w * (TJ / 4) + jj;
+        const int j = j0 + k;
+        if (j >= N || j > i) break;
+        const double xj = sx[k], lj = sl[k];
+        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
+        const double Aa = li2 + lj * lj;
+        double kv = sqrt(2.0 * (li * lj) / Aa) * exp(-dist / Aa);
+        if (i == j) kv = (NMGP_JITTER + kv) + Ei;
+        A[(size_t)j * ld + i] = kv;
+    }
+}
+
+// Sigma' (lower triangle, outputs 1..M-1 output-major, n' = (M-1) N) and y' in its row n'.  nAinv = -A^-1 (both triangles,
+// leading dimension lda), u = A^-1 v ([B, N]).  64 x 64 location tiles, lanes along i, chain on blockIdx.z.
+template <int M>
+__global__ __launch_bounds__(256) void k_svc_schur_cov(const double* __restrict__ x, const double* __restrict__ ell,
+                                                        const double* __restrict__ Lv, const double* __restrict__ tse,
+                                                        const double* __restrict__ y, const double* __restrict__ nAinv, int lda,
+                                                        const double* __restrict__ u, double* __restrict__ S, int ld, int N,
+                                                        long long bstride, int xstride, long long ystride, int cps) {
+    constexpr int T = M * (M + 1) / 2;
+    constexpr int TJ = 64;
+    constexpr int M1 = M - 1;
+    __shared__ double sx[TJ], sl[TJ], sL[TJ * T], sg[TJ * M1];
+    const int I = blockIdx.x, J = blockIdx.y;
+    x += (size_t)(blockIdx.z / cps) * xstride;
+    y += (size_t)(blockIdx.z / cps) * ystride;
+    ell += (size_t)blockIdx.z * N;
+    Lv += (size_t)blockIdx.z * N * T;
+    tse += (size_t)blockIdx.z * ((size_t)N * (1 + T) + 1);
+    nAinv += (size_t)blockIdx.z * bstride;
+    u += (size_t)blockIdx.z * N;
+    S += (size_t)blockIdx.z * bstride;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    const double sigma2 = exp(tse[0]);
+    if (tid < TJ) {
+        int j = j0 + tid;
+        sx[tid] = (j < N) ? x[j] : 0.0;
+        sl[tid] = (j < N) ? ell[j] : 1.0;
+    }
+    for (int k = tid; k < TJ * T; k += 256) {
+        size_t g = (size_t)j0 * T + k;
+        sL[k] = (g < (size_t)N * T) ? Lv[g] : 0.0;
+    }
+    __syncthreads();
+    if (tid < TJ) {
+        const double l00 = sL[tid * T];
+#pragma unroll
+        for (int b = 1; b < M; ++b) sg[tid * M1 + b - 1] = sigma2 * sL[tid * T + b * (b + 1) / 2] / (l00 * l00);
+    }
+    __syncthreads();
+    const int i = I * 64 + lane;
+    if (i >= N) return;
+    const size_t Ns = (size_t)N;
+    const int n1 = M1 * N;
+    double Li[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) Li[t] = Lv[(size_t)i * T + t];
+    const double l00 = Li[0];
+    const double il2 = 1.0 / (l00 * l00);
+    double gi[M1];
+#pragma unroll
+    for (int a = 1; a < M; ++a) gi[a - 1] = sigma2 * Li[a * (a + 1) / 2] * il2;
+    if (J == 0 && w == 0) {
+        // y'[(a,i)] = Y[i,a] - L_i[a,0] (v_i - E_i u_i)
+        const double vi = y[i] / l00;
+        const double r = vi - (sigma2 * il2) * u[i];
+#pragma unroll
+        for (int a = 1; a < M; ++a)
+            S[((size_t)(a - 1) * Ns + i) * ld + n1] = y[(size_t)a * Ns + i] - Li[a * (a + 1) / 2] * r;
+    }
+    // (tiles with I < J have i < j throughout: there only the blocks a > b hold lower-triangle entries)
+    const double xi = x[i], li = ell[i];
+    const double xi2 = xi * xi, li2 = li * li;
+#pragma unroll 2
+    for (int jj = 0; jj < TJ / 4; ++jj) {
+        const int k = w * (TJ / 4) + jj;
+        const int j = j0 + k;
+        if (j >= N) break;
+        const double xj = sx[k], lj = sl[k];
+        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
+        const double Aa = li2 + lj * lj;
+        double kv = sqrt(2.0 * (li * lj) / Aa) * exp(-dist / Aa);
+        if (i == j) kv = NMGP_JITTER + kv;
+        const double nai = nAinv[(size_t)j * lda + i];
+#pragma unroll
+        for (int a = 1; a < M; ++a) {
+#pragma unroll
+            for (int b = 1; b <= a; ++b) {
+                if (b == a && i < j) continue;
+                double s = 0.0;
+#pragma unroll
+                for (int c = 1; c <= b; ++c) s += Li[a * (a + 1) / 2 + c] * sL[k * T + b * (b + 1) / 2 + c];
+                double v = kv * s;
+                if (i == j) v += sigma2 * ((a == b ? 1.0 : 0.0) + Li[a * (a + 1) / 2] * Li[b * (b + 1) / 2] * il2);
+                v += gi[a - 1] * nai * sg[k * M1 + b - 1];
+                S[((size_t)(b - 1) * Ns + j) * ld + ((size_t)(a - 1) * Ns + i)] = v;
+            }
+        }
+    }
+}
+
+// phase 0: k_svc_schur_a, phase 1: k_svc_schur_cov (all N/64 x N/64 tiles: Sigma' blocks a > b are full)
+template <int M>
+static void launch_svc_schur(hipStream_t s, const double* x, const double* ell, const double* Lv, const double* tse,
+                             const double* y, double* A, int lda, const double* u, double* S, int ld, int N, int batch,
+                             long long bstride, int xstride, long long ystride, int cps, int phase) {
+    dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);
+    if (phase == 0)
+        NMGP_LAUNCH((k_svc_schur_a<M>), grid, dim3(256), 0, s, x, ell, Lv, tse, y, A, lda, N, bstride, xstride, ystride, cps);
+    else
+        NMGP_LAUNCH((k_svc_schur_cov<M>), grid, dim3(256), 0, s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, bstride, xstride,
+                    ystride, cps);
+}
+
+int svc_schur_build(hipStream_t s, int phase, const double* x, const double* ell, const double* Lv, const double* tse,
+                    const double* y, double* A, int lda, const double* u, double* S, int ld, int N, int M, int batch,
+                    long long bstride, int xstride, long long ystride, int cps) {
+    if (cps < 1) cps = 1;
+    switch (M) {
+        case 2: launch_svc_schur<2>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
+        case 3: launch_svc_schur<3>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
+        case 4: launch_svc_schur<4>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
+        case 5: launch_svc_schur<5>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
+        case 6: launch_svc_schur<6>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
+        case 7: launch_svc_schur<7>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
+        case 8: launch_svc_schur<8>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
+        default: return NMGP_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// sc[0] = 2 sum_i log L_i00 + log det A + log det Sigma' (sc[2], sc[4]),  sc[1] = |w|^2 + |w'|^2 (sc[3], sc[5]): the layout
+// svc_finalize reads.  The chain's status is the first failing leading minor of Sigma: A's (that of Sigma_00 = D0 A D0), else
+// N + Sigma''s.
+__global__ __launch_bounds__(256) void k_svc_schur_combine(const double* __restrict__ Lv, int N, int T, double* __restrict__ sc,
+                                                            int sstride, int* __restrict__ info, const int* __restrict__ info2) {
+    __shared__ double sh[16];
+    Lv += (size_t)blockIdx.x * N * T;
+    sc += (size_t)blockIdx.x * sstride;
+    double a = 0.0;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) a += log(Lv[(size_t)i * T]);
+    a = block_sum(a, sh);
+    if (threadIdx.x == 0) {
+        sc[0] = (2.0 * a + sc[2]) + sc[4];
+        sc[1] = sc[3] + sc[5];
+        if (info[blockIdx.x] == 0 && info2[blockIdx.x] != 0) info[blockIdx.x] = N + info2[blockIdx.x];
+    }
+}
+
+void svc_schur_combine(hipStream_t s, const double* Lv, int N, int M, double* sc, int sstride, int* info, const int* info2,
+                       int batch) {
+    NMGP_LAUNCH(k_svc_schur_combine, dim3(batch), dim3(256), 0, s, Lv, N, M * (M + 1) / 2, sc, sstride, info, info2);
+}
+
+// ---------------------------------------------------------------------------------------------
 // symmetric N x N kernels on 1-D inputs (GP priors, separable K_x); column-major == row-major (symmetric)
 // ---------------------------------------------------------------------------------------------
 template <bool GIBBS, bool FULL>
