@@ -862,12 +862,13 @@ static int batch_grad_alloc(nmgp_ctx* c) {
     return 0;
 }
 
-// Structured value path (M >= 2; the algebra is at k_svc_schur_cov in nmgp_kernels.hip): output 0 of Sigma is eliminated in
+// Structured value path (M >= 2; the algebra is above k_svc_schur_a in nmgp_kernels.hip): output 0 of Sigma is eliminated in
 // closed form, so only A = K_x + diag(E) (N x N) and the Schur complement Sigma' ((M-1) N square) are factored, plus the
-// explicit -A^-1 that Sigma' needs: ((M-1)^3 + 3) / M^3 of the dense factorisation's flop (M = 3: 0.41).  Per chain slice
-// (b_S's own when large enough, which it is for every M >= 2: 3 N^2 + O(N) of 4 N^2 at M = 2):
-//   [0, ldA N)        A's buffer, ldA = ld(2N + 2): rows 0..N-1 A -> L_A -> -A^-1 (both triangles), row N v -> w = L_A^-1 v,
-//                     pad, rows N+1+pad.. X = L_A^-T (the gradient path's riding rows)
+// -A^-1 = -X X^T that Sigma' needs: ((M-1)^3 + 3) / M^3 of the dense factorisation's flop (M = 3: 0.41).  -A^-1 is never stored:
+// the inverse SYRK's tiles write Sigma' and y' from their accumulators (k_syrk_schur).  Per chain slice (b_S's own when large
+// enough, which it is for every M >= 2: 3 N^2 + O(N) of 4 N^2 at M = 2):
+//   [0, ldA N)        A's buffer, ldA = ld(2N + 2): rows 0..N-1 A -> L_A, row N v -> w = L_A^-1 v, pad,
+//                     rows N+1+pad.. X = L_A^-T (the gradient path's riding rows)
 //   [offP, ..)        Sigma' and its right-hand-side row y' -> w' (the value path's layout at n' = (M-1) N)
 //   [offPart, ..)     block sums of u = X w (tri_gemv_upper)
 // w and w' share b_z ([B, N] then [B, n']); u is b_u.  A chain's status is the first failing leading minor of Sigma.
@@ -886,7 +887,7 @@ static int svc_batch_value_schur(nmgp_ctx* c, const double* xs, int xstride, con
     const int ldA = (int)nmgp_ld((size_t)2 * N + 2), ldP = (int)nmgp_ld((size_t)n1 + 1);
     auto r64 = [](size_t v) { return (v + 63) / 64 * 64; };
     const size_t offP = r64((size_t)ldA * N), offPart = r64(offP + (size_t)ldP * n1);
-    const size_t need = offPart + (size_t)N * ((N + 255) / 256);
+    const size_t need = r64(offPart + (size_t)N * ((N + 255) / 256));     // (chain slices 16-byte aligned: k_svc_schur_a)
     const size_t bsS = nmgp_ld((size_t)c->n + 1) * (size_t)c->n;
     double* base = c->b_S;
     size_t bsz = bsS;
@@ -910,12 +911,12 @@ static int svc_batch_value_schur(nmgp_ctx* c, const double* xs, int xstride, con
     {
         StageScope sp(c, NMGP_STAGE_COV);
         svc_prep(s, c->b_pars, N, M, c->b_ell, c->b_Lv, B);
-        int r = svc_schur_build(s, 0, xs, c->b_ell, c->b_Lv, tse, ys, A, ldA, nullptr, nullptr, 0, N, M, B, bs, xstride, ystride, cps);
+        // A, v, the pad rows and the seeded band of X (identity_rows' part)
+        int r = svc_schur_a(s, xs, c->b_ell, c->b_Lv, tse, ys, A, ldA, xpad, N, M, B, bs, xstride, ystride, cps);
         if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
     }
     {
         StageScope sp(c, NMGP_STAGE_CHOL);
-        identity_rows(s, A, ldA, N + 1, N, xpad, B, bs);
         potrf_lower(s, c->stream2, nmgp_chol_events(c, N), A, ldA, N, 1 + xpad, N, c->chol_nb1, c->b_info, B, bs, 1,
                     nmgp_syrk_hook(c));
     }
@@ -926,15 +927,13 @@ static int svc_batch_value_schur(nmgp_ctx* c, const double* xs, int xstride, con
     }
     {
         StageScope sp(c, NMGP_STAGE_REDUCE);
-        chol_logdet_quad(s, A, ldA, N, w, c->b_scal + 2, c->b_scal + 3, B, bs, 16);    // (reads L_A before the SYRK overwrites it)
+        chol_logdet_quad(s, A, ldA, N, w, c->b_scal + 2, c->b_scal + 3, B, bs, 16);
     }
     {
         StageScope sp(c, NMGP_STAGE_INVERSE);
-        syrk_lower(s, A + xoffA, ldA, A, ldA, N, N, N, B, bs, bs, 2);     // -A^-1 = -X X^T into rows 0..N-1, both triangles
-    }
-    {
-        StageScope sp(c, NMGP_STAGE_COV);
-        int r = svc_schur_build(s, 1, xs, c->b_ell, c->b_Lv, tse, ys, A, ldA, c->b_u, Sp, ldP, N, M, B, bs, xstride, ystride, cps);
+        // -A^-1 = -X X^T, consumed tile by tile: Sigma' (lower) and y' into [offP, ..)
+        const SchurEpi e{xs, c->b_ell, c->b_Lv, tse, ys, c->b_u, Sp, ldP, N, xstride, cps, ystride, bs};
+        int r = syrk_schur(s, A + xoffA, ldA, N, M, B, e);
         if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
     }
     {

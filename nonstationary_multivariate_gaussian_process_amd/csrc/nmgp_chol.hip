@@ -162,11 +162,162 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void syrk_fused_first_block(double* lds, const v4d (&acc)[2][2][2], bool owner, int wj,
                                                        double* __restrict__ C, int ldc, int* __restrict__ info, int goff);
 
+// ---- epilogue of k_syrk_schur (the structured value path's inverse SYRK; the algebra is above k_svc_schur_a in nmgp_kernels.hip) ----
+// The expressions, in their order, of the separate kernel this replaced: bit-identical results under -ffp-contract=off.  After the
+// k-loop's last barrier the operand buffers hold one 32 x 33 patch per wave (-A^-1 on a 32-row half of the wave's sub-tile) and,
+// for M <= 4, a table of the tile's 128 column and 128 row locations: g_c[b] = sigma2 L_c[b,0] / L_c00^2 (b = 1..M-1), 1 / L_c00^2,
+// x_c and ell_c (larger M compute / load them where they are used).  k_syrk_schur's LDS: SY_SCHUR_SMEM doubles (two workgroups per CU).
+#define SY_SMEM (4 * SY_BK * SY_LD)
+#define SCHUR_PATCH (32 * 33)
+#define SY_SCHUR_SMEM (8 * SCHUR_PATCH + 6 * 256)
+static_assert(SY_SCHUR_SMEM >= SY_SMEM && SY_SCHUR_SMEM * 8 * 2 <= 160 * 1024, "Schur epilogue LDS");
+
+// Sigma'[(a,r),(b,c)] from kv = K_x[r, c] and nai = -A^-1[r, c]: row location r (L row Lr, il2 = 1 / L_r00^2), column location c
+// (L row Lc, gcb = g_c[b])
+template <int M>
+__device__ __forceinline__ double svc_schur_value(double sigma2, int a, int b, bool rc, const double* __restrict__ Lr, double il2,
+                                                  const double* __restrict__ Lc, double kv, double nai, double gcb) {
+    constexpr int UR = M <= 3 ? 8 : 1;
+    const double gra = sigma2 * Lr[a * (a + 1) / 2] * il2;
+    double s = 0.0;
+#pragma unroll UR
+    for (int q = 1; q <= b; ++q) s += Lr[a * (a + 1) / 2 + q] * Lc[b * (b + 1) / 2 + q];
+    double v = kv * s;
+    if (rc) v += sigma2 * ((a == b ? 1.0 : 0.0) + Lr[a * (a + 1) / 2] * Lr[b * (b + 1) / 2] * il2);
+    v += gra * nai * gcb;
+    return v;
+}
+
+// the entries (a,r),(b,c) for 1 <= b <= a <= M-1 (b < a only when !ALLB); gc: g_c[1..M-1] in LDS (M <= 4).  Sigma' column-major with
+// leading dimension e.ld.  Unrolled for M <= 3; from M = 4 on, rolled loops keep the kernel within 128 VGPRs without scratch.
+template <int M, bool ALLB>
+__device__ __forceinline__ void svc_schur_entries(const SchurEpi& e, double sigma2, int r, const double* __restrict__ Lr, double il2,
+                                                  int c, double kv, double nai, const double* gc) {
+    constexpr int T = M * (M + 1) / 2;
+    constexpr int UR = M <= 3 ? 8 : 1;
+    const size_t Ns = (size_t)e.N;
+    const double* __restrict__ Lc = e.Lv + (size_t)c * T;
+    const double lcc = M <= 4 ? 0.0 : Lc[0];
+#pragma unroll UR
+    for (int a = 1; a < M; ++a) {
+#pragma unroll UR
+        for (int b = 1; b <= (ALLB ? a : a - 1); ++b) {
+            const double gcb = M <= 4 ? gc[b - 1] : sigma2 * Lc[b * (b + 1) / 2] / (lcc * lcc);
+            e.S[((size_t)(b - 1) * Ns + c) * e.ld + ((size_t)(a - 1) * Ns + r)] =
+                svc_schur_value<M>(sigma2, a, b, r == c, Lr, il2, Lc, kv, nai, gcb);
+        }
+    }
+}
+
+constexpr int svc_gstride(int M) { return M + 2; }     // g_c[1..M-1], 1 / L_c00^2, x_c, ell_c
+
+// the table (M <= 4): entry k < 128 = column location col0 + k, k >= 128 = row location row0 + k - 128.  Workgroup-uniform call
+// after the k-loop's last barrier; ends on a barrier.
+template <int M>
+__device__ __forceinline__ void svc_schur_gtable(const SchurEpi& e, double* lds, int row0, int col0, int tid) {
+    constexpr int T = M * (M + 1) / 2, GS = svc_gstride(M);
+    if constexpr (M <= 4) {
+        double* gt = lds + 8 * SCHUR_PATCH;
+        if (tid < 256) {
+            const int loc = tid < 128 ? col0 + tid : row0 + tid - 128;
+            if (loc < e.N) {
+                const double sigma2 = exp(e.tse[0]);
+                const double* Lc = e.Lv + (size_t)loc * T;
+                const double l00 = Lc[0];
+#pragma unroll
+                for (int b = 1; b < M; ++b) gt[tid * GS + b - 1] = sigma2 * Lc[b * (b + 1) / 2] / (l00 * l00);
+                gt[tid * GS + M - 1] = 1.0 / (l00 * l00);
+                gt[tid * GS + M] = e.x[loc];
+                gt[tid * GS + M + 1] = e.ell[loc];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// One wave's 32 x 32 patch P[il * 33 + jl] = -A^-1[i0 + il, j0 + jl] (written by this wave).  Pass 1, lanes along i: every
+// lower-triangle element (i >= j) gives K_x[i, j] and the entries (a,i),(b,j), b <= a; at M = 3 it also computes the element's one
+// mirrored entry (2,j),(1,i) (i > j; K_x is bitwise symmetric) and leaves it in P.  Pass 2, lanes along j: the mirrored entries
+// (a,j),(b,i), b < a, of every element with i > j -- copied from P at M = 3, computed (K_x again) otherwise.  Every store runs along
+// the Sigma' row index: 256 contiguous bytes per column.
+template <int M>
+__device__ __forceinline__ void svc_schur_patch(const SchurEpi& e, double* P, const double* lds, int i0, int j0, int row0, int col0,
+                                                int lane) {
+    constexpr int T_ = M * (M + 1) / 2, GS = svc_gstride(M);
+    constexpr int QU = M <= 3 ? 2 : 1;
+    const int N = e.N;
+    const size_t Ns = (size_t)N;
+    const double sigma2 = exp(e.tse[0]);
+    const double* gt = lds + 8 * SCHUR_PATCH;
+    const int lo = lane & 31, hi = lane >> 5;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1 && M == 2) break;
+        const int r = (pass == 0 ? i0 : j0) + lo;          // the lane's own location: row location of its entries
+        if (r < N) {
+            const double* __restrict__ Lr = e.Lv + (size_t)r * T_;
+            const double xr = e.x[r], lr = e.ell[r];
+            const double xr2 = xr * xr, lr2 = lr * lr;
+            const double l00 = Lr[0];
+            const double il2 = 1.0 / (l00 * l00);
+#pragma unroll QU
+            for (int q = 0; q < 16; ++q) {
+                const int o = 2 * q + hi;
+                const int il = pass == 0 ? lo : o, jl = pass == 0 ? o : lo;
+                const int c = (pass == 0 ? j0 : i0) + o;
+                if (pass == 0 ? (c > r || c >= N) : (c <= r || c >= N)) continue;
+                const double* gc = gt + (pass == 0 ? c - col0 : 128 + c - row0) * GS;
+                if (pass == 1 && M == 3) {
+                    e.S[(size_t)c * e.ld + (Ns + r)] = P[il * 33 + jl];
+                    continue;
+                }
+                const double xc = M <= 4 ? gc[M] : e.x[c], lc = M <= 4 ? gc[M + 1] : e.ell[c];
+                const double dist = (xr2 + xc * xc) - 2.0 * (xr * xc);
+                const double Aa = lr2 + lc * lc;
+                double kv = sqrt(2.0 * (lr * lc) / Aa) * exp(-dist / Aa);
+                if (r == c) kv = NMGP_JITTER + kv;
+                const double nai = P[il * 33 + jl];
+                if (pass == 0) {
+                    svc_schur_entries<M, true>(e, sigma2, r, Lr, il2, c, kv, nai, gc);
+                    if (M == 3 && c < r) {
+                        // the mirrored entry: row location c (its 1 / L_c00^2 from the table), column location r (g_r[1])
+                        const double* Lc = e.Lv + (size_t)c * T_;
+                        P[il * 33 + jl] = svc_schur_value<M>(sigma2, 2, 1, false, Lc, gc[M - 1], Lr, kv, nai, gt[(128 + r - row0) * GS]);
+                    }
+                } else {
+                    svc_schur_entries<M, false>(e, sigma2, r, Lr, il2, c, kv, nai, gc);
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// y'[(a,i)] = Y[i,a] - L_i[a,0] (v_i - E_i u_i) (row n' of Sigma'): one lane per location, the diagonal tiles own their rows
+template <int M>
+__device__ __forceinline__ void svc_schur_yrow(const SchurEpi& e, int i) {
+    constexpr int T = M * (M + 1) / 2;
+    if (i >= e.N) return;
+    const size_t Ns = (size_t)e.N;
+    const int n1 = (M - 1) * e.N;
+    const double sigma2 = exp(e.tse[0]);
+    const double* Li = e.Lv + (size_t)i * T;
+    const double l00 = Li[0];
+    const double il2 = 1.0 / (l00 * l00);
+    const double vi = e.y[i] / l00;
+    const double r = vi - (sigma2 * il2) * e.u[i];
+#pragma unroll
+    for (int a = 1; a < M; ++a) e.S[((size_t)(a - 1) * Ns + i) * e.ld + n1] = e.y[(size_t)a * Ns + i] - Li[a * (a + 1) / 2] * r;
+}
+
+// SM > 0: k_syrk_schur (M = SM outputs, se = the chain's epilogue arguments): the tile goes into Sigma' instead of C
+template <int SM = 0>
 __device__ __forceinline__ void syrk_tile_fast(const double* __restrict__ A, int lda, double* __restrict__ C, int ldc, int K,
                                                int row0, int col0, bool diag, int kt0, bool beta0, int ncw, int yrow,
                                                int nyr, double* sA0, double* sB0, bool skip00 = false,
                                                int* __restrict__ finfo = nullptr, int fgoff = 0, bool mirror = false,
-                                               int fresh0 = 0x7fffffff) {
+                                               int fresh0 = 0x7fffffff, const SchurEpi* se = nullptr) {
     // fresh0: rows i >= fresh0 (relative to C) are rows of L^-T that take part in an update for the first time (gradient
     // evaluation; see potrf_lower): their C entries have never been written -- the accumulators start from zero instead of a
     // load -- and their A entries left of the diagonal (k < i - fresh0) are structural zeros that nobody wrote either.
@@ -321,6 +472,25 @@ __device__ __forceinline__ void syrk_tile_fast(const double* __restrict__ A, int
         if (kt + 2 < nk) sstore(0);
         __syncthreads();
     }
+    if constexpr (SM > 0) {
+        // the k-loop ended on a barrier: each wave moves its sub-tile, 32 rows at a time, through its patch into Sigma'
+        svc_schur_gtable<SM>(*se, sA0, row0, col0, tid);
+        if (active) {
+            double* P = sA0 + w * SCHUR_PATCH;
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+#pragma unroll
+                for (int sx = 0; sx < 2; ++sx)
+#pragma unroll
+                    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) P[(2 * l15 + sx) * 33 + 2 * (l4 + 4 * r) + tj] = -acc[p][sx][tj][r];
+                svc_schur_patch<SM>(*se, P, sA0, row0 + wi * 64 + 32 * p, col0 + wj * 32, row0, col0, lane);
+            }
+        }
+        if (diag && wj == 0) svc_schur_yrow<SM>(*se, row0 + wi * 64 + lane);
+        return;
+    }
     if (ywave && l15 < nyr) {
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -381,12 +551,13 @@ __device__ __forceinline__ void syrk_tile_fast(const double* __restrict__ A, int
 // C[i, j] -= sum_k A[i, k] A[j, k]   for 0 <= j < ncols, j <= i < mrows    (A: mrows x K, C: mrows x ncols)
 // NWJ = column groups of waves per 128x128 tile: 2 -> 4 waves of 64x64 (16 MFMA tiles each), 4 -> 8 waves of 64x32
 // (8 MFMA tiles each, ~110 VGPRs, so four waves per SIMD hide each other's barrier / LDS / prologue stalls).
-template <int NWJ, int BK>
+// SM > 0: k_syrk_schur's tiles (C unused; se: the launch's epilogue arguments, see syrk_tile_fast)
+template <int NWJ, int BK, int SM = 0>
 __device__ __forceinline__ void syrk_tile_body(const double* __restrict__ A, int lda, double* __restrict__ C, int ldc, int mrows,
                                                int ncols, int K, long long bstride, long long cstride, int ktri, int swz,
                                                int nbatch, int bx, int by, int bz0, double* sAb, double* sBb,
                                                int tri_row0 = 0x7fffffff, int tri_k0 = 0, int* __restrict__ finfo = nullptr,
-                                               int fistride = 0, int fgoff = 0) {
+                                               int fistride = 0, int fgoff = 0, const SchurEpi* sep = nullptr) {
     // tri_row0 / tri_k0: rows i >= tri_row0 of A are rows of an upper-triangular matrix riding below the factorisation (L^-T of
     // the gradient evaluation): A[i, k] == 0 for k < (i - tri_row0) - tri_k0, so a tile made of such rows starts its k-loop
     // there instead of multiplying zeros (with 1024-wide panels that was 12 % of the update flop, with 2048-wide ones 25 %)
@@ -494,6 +665,19 @@ __device__ __forceinline__ void syrk_tile_body(const double* __restrict__ A, int
     bz = __builtin_amdgcn_readfirstlane(bz);
     A += (size_t)bz * bstride;       // batch of independent matrices (one per chain), same shape
     C += (size_t)bz * cstride;
+    SchurEpi se{};
+    if constexpr (SM > 0) {
+        static_assert(NWJ == 4 && BK == 16, "the Schur epilogue assumes 8 waves of 64 x 32");
+        constexpr int T = SM * (SM + 1) / 2;
+        se = *sep;
+        se.x += (size_t)(bz / se.cps) * se.xstride;
+        se.y += (size_t)(bz / se.cps) * se.ystride;
+        se.ell += (size_t)bz * se.N;
+        se.Lv += (size_t)bz * se.N * T;
+        se.tse += (size_t)bz * ((size_t)se.N * (1 + T) + 1);
+        se.u += (size_t)bz * se.N;
+        se.S += (size_t)bz * se.bstride;
+    }
     const bool diag = (bi == bj);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wi = w & 1, wj = w >> 1;
@@ -511,9 +695,9 @@ __device__ __forceinline__ void syrk_tile_body(const double* __restrict__ A, int
                 kt0f = z > 0 ? (z & ~1) : 0;                          // (the unrolled loop wants an even number of panels)
             }
             // finfo: tile (0, 0) goes on to factor its leading 64x64 block (the host sets it only when that tile takes this path)
-            syrk_tile_fast(A, lda, C, ldc, K, row0, col0, diag, kt0f, ktri != 0, ncw, yrow, nyr, &sA[0][0], &sB[0][0],
-                           skipq && bi == 0 && bj == 0, (finfo != nullptr && bi == 0 && bj == 0) ? finfo + (size_t)bz * fistride : nullptr,
-                           fgoff, mirror, fresh0);
+            syrk_tile_fast<SM>(A, lda, C, ldc, K, row0, col0, diag, kt0f, ktri != 0, ncw, yrow, nyr, &sA[0][0], &sB[0][0],
+                               skipq && bi == 0 && bj == 0, (finfo != nullptr && bi == 0 && bj == 0) ? finfo + (size_t)bz * fistride : nullptr,
+                               fgoff, mirror, fresh0, &se);
             return;
         }
     }
@@ -623,6 +807,26 @@ __device__ __forceinline__ void syrk_tile_body(const double* __restrict__ A, int
         if (kt + 1 < nk) sstore(cur ^ 1, (kt + 1) * BK);
         __syncthreads();
     }
+    if constexpr (SM > 0) {
+        // as in syrk_tile_fast: acc holds -A^-1 here; half h of the wave's rows = MFMA tiles ti = 2h, 2h + 1
+        svc_schur_gtable<SM>(se, sAb, row0, col0, tid);
+        if (active) {
+            double* P = sAb + w * SCHUR_PATCH;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int tj = 0; tj < TJ; ++tj)
+#pragma unroll
+                    for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            P[(t2 * 16 + (lane & 15)) * 33 + tj * 16 + (lane >> 4) + 4 * r] = acc[tj][2 * h + t2][r];
+                svc_schur_patch<SM>(se, P, sAb, row0 + wi * 64 + 32 * h, col0 + wj * CW, row0, col0, lane);
+            }
+        }
+        if (diag && wj == 0) svc_schur_yrow<SM>(se, row0 + wi * 64 + lane);
+        return;
+    }
     if (active) {
 #pragma unroll
         for (int tj = 0; tj < TJ; ++tj)
@@ -646,6 +850,16 @@ __global__ __launch_bounds__(512, 4) void k_syrk_lower(const double* __restrict_
     __shared__ __attribute__((aligned(16))) double smem[4 * SY_BK * SY_LD];      // A panels | B panels (contiguous: see finfo)
     syrk_tile_body<4, SY_BK>(A, lda, C, ldc, mrows, ncols, K, bstride, cstride, ktri, swz, nbatch, blockIdx.x, blockIdx.y,
                              blockIdx.z, smem, smem + 2 * SY_BK * SY_LD, tri_row0, tri_k0, finfo, fistride, fgoff);
+}
+
+// The structured value path's inverse SYRK (syrk_schur): the triangular-operand launch of k_syrk_lower (ktri = 2) whose tiles write
+// Sigma' and y' instead of -A^-1 (syrk_tile_fast / syrk_tile_body with SM = M)
+template <int M>
+__global__ __launch_bounds__(512, 4) void k_syrk_schur(const double* __restrict__ A, int lda, int N, long long bstride, int kflags,
+                                                        int swz, int nbatch, SchurEpi se) {
+    __shared__ __attribute__((aligned(16))) double smem[SY_SCHUR_SMEM];
+    syrk_tile_body<4, SY_BK, M>(A, lda, nullptr, 0, N, N, N, bstride, 0, kflags, swz, nbatch, blockIdx.x, blockIdx.y, blockIdx.z,
+                                smem, smem + 2 * SY_BK * SY_LD, 0x7fffffff, 0, nullptr, 0, 0, &se);
 }
 
 static thread_local const SyrkHook* g_hook = nullptr;   // set by potrf_lower for the duration of one factorisation
@@ -1230,6 +1444,28 @@ void syrk_lower(hipStream_t s, const double* A, int lda, double* C, int ldc, int
                 pf.swz, batch, tri_row0, tri_k0, fzb ? fuse.info : (int*)nullptr, fuse.istride, fuse.goff);
     if (fzb) g_first_block_done = 1;
     if (tok && g_hook->end) g_hook->end(g_hook->user, tok);
+}
+
+int syrk_schur(hipStream_t s, const double* X, int lda, int N, int M, int batch, const SchurEpi& e) {
+    if (N <= 0) return 0;
+    if (M < 2 || M > 8) return NMGP_E_UNSUPPORTED;
+    // the tile plan of syrk_lower(X, lda, C, ., N, N, N, batch, bs, bs, 2)
+    const SyrkPlan pl = syrk_plan(lda, lda, N, N, N, batch, 2, false);
+    void* tok = nullptr;
+    if (g_hook && g_hook->begin) {
+        // flop of the inverse SYRK; bytes: X read once, Sigma' (lower) and y' written (-A^-1 itself never leaves the chip)
+        const double elems = (double)N * N - 0.5 * (double)N * (N - 1);
+        const double n1 = (double)(M - 1) * N;
+        tok = g_hook->begin(g_hook->user, s, 2.0 * N * elems * batch, 8.0 * batch * ((double)N * N + 0.5 * n1 * (n1 + 1) + n1));
+    }
+    switch (M) {
+#define SCHUR_CASE(m) \
+        case m: NMGP_LAUNCH(k_syrk_schur<m>, pl.grid, dim3(512), 0, s, X, lda, pl.mrows, e.bstride, pl.kflags, pl.swz, batch, e); break;
+        SCHUR_CASE(2) SCHUR_CASE(3) SCHUR_CASE(4) SCHUR_CASE(5) SCHUR_CASE(6) SCHUR_CASE(7) SCHUR_CASE(8)
+#undef SCHUR_CASE
+    }
+    if (tok && g_hook->end) g_hook->end(g_hook->user, tok);
+    return 0;
 }
 
 

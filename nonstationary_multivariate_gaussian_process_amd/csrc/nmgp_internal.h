@@ -115,10 +115,10 @@ struct nmgp_ctx {
     double* b_scal = nullptr;   // [B, 16] : logdet, quad, out5...
     double* b_q = nullptr;      // [B (1 + T)]
     int* b_info = nullptr;      // [B]
-    // structured value path (nmgp_svc_batch_eval, M >= 2: output 0 eliminated in closed form, see k_svc_schur_cov)
+    // structured value path (nmgp_svc_batch_eval, M >= 2: output 0 eliminated in closed form, see k_svc_schur_a)
     double* b_u = nullptr;      // [B, N] u = A^-1 v
     int* b_info2 = nullptr;     // [B] status of the Schur complement's factorisation
-    double* b_schur = nullptr;  // [B] x b_schur_stride: A, -A^-1, Sigma' when they do not fit in b_S's chain slices
+    double* b_schur = nullptr;  // [B] x b_schur_stride: A, Sigma' when they do not fit in b_S's chain slices
     size_t b_schur_stride = 0;
     // batched gradient state (allocated on the first batched value+gradient evaluation)
     bool b_grad_ready = false;
@@ -276,11 +276,10 @@ void svc_prep(hipStream_t s, const double* pars, int N, int M, double* ell, doub
 int svc_cov_build(hipStream_t s, const double* x, const double* ell, const double* Lv, const double* tse,
                   double* S, int ld, int N, int M, bool full, int batch = 1, long long sstride = 0, int xstride = 0, int cps = 1);
 // symmetric N x N builds (lower triangle unless full)
-// structured value path: phase 0 writes A = K_x + diag(E) (lower) and v into row N of A; phase 1 writes Sigma' (lower, n' = (M-1) N)
-// and y' into row n' of S from -A^-1 (rows 0..N-1 of A, both triangles) and u.  A and S of chain z are z * bstride apart.
-int svc_schur_build(hipStream_t s, int phase, const double* x, const double* ell, const double* Lv, const double* tse,
-                    const double* y, double* A, int lda, const double* u, double* S, int ld, int N, int M, int batch,
-                    long long bstride, int xstride, long long ystride, int cps);
+// structured value path: A = K_x + diag(E) (lower), v into row N of A, then the `pad` zero rows and the seeded band of the identity
+// rows below it (those of identity_rows(A, lda, N + 1, N, pad)), in one launch.  A of chain z is z * bstride further on.
+int svc_schur_a(hipStream_t s, const double* x, const double* ell, const double* Lv, const double* tse, const double* y, double* A,
+                int lda, int pad, int N, int M, int batch, long long bstride, int xstride, long long ystride, int cps);
 // sc[0] / sc[1] = log det / quadratic form of Sigma from the parts in sc[2..5]; info = first failing leading minor of Sigma
 void svc_schur_combine(hipStream_t s, const double* Lv, int N, int M, double* sc, int sstride, int* info, const int* info2,
                        int batch);
@@ -410,6 +409,25 @@ void two_col_rhs_b(hipStream_t s, const double* pars, long long P, double mu_a, 
 // ---- nmgp_chol.hip ----
 void syrk_lower(hipStream_t s, const double* A, int lda, double* C, int ldc, int mrows, int ncols, int K, int batch,
                 long long bstride, long long cstride = -1, int ktri = 0, int tri_row0 = 0x7fffffff, int tri_k0 = 0);
+// the structured value path's inverse SYRK (k_syrk_schur): -A^-1 = -X X^T (X = L_A^-T: N x N upper triangular, rows
+// xoff.. of A's buffer) is not stored; each tile writes the Sigma' entries it determines (and the diagonal tiles y') straight
+// from its accumulators.  Per chain z: X, S and u at z * bstride, z * bstride, z * N; x, y of subject z / cps.
+struct SchurEpi {
+    const double* x;
+    const double* ell;
+    const double* Lv;
+    const double* tse;
+    const double* y;
+    const double* u;
+    double* S;           // Sigma' (lower, n' = (M-1) N) and y' in its row n'
+    int ld;
+    int N;
+    int xstride;
+    int cps;
+    long long ystride;
+    long long bstride;
+};
+int syrk_schur(hipStream_t s, const double* X, int lda, int N, int M, int batch, const SchurEpi& e);
 void identity_rows(hipStream_t s, double* A, int lda, int row0, int n, int pad, int batch = 1, long long bstride = 0);
 void potf2_64(hipStream_t s, double* A, int lda, int nb, int* info, int goff, int batch, long long bstride,
               int istride);

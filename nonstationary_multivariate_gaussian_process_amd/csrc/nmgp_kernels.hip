@@ -173,17 +173,34 @@ int svc_cov_build(hipStream_t s, const double* x, const double* ell, const doubl
 //   y'[(a,i)] = Y[i,a] - L_i[a,0] (v_i - E_i u_i),     v = Y[:,0] / L_00,  u = A^-1 v,
 //   log det Sigma = 2 sum_i log L_i00 + log det A + log det Sigma',   y^T Sigma^-1 y = v^T A^-1 v + y'^T Sigma'^-1 y'.
 // ---------------------------------------------------------------------------------------------
-// A (lower triangle, N x N) and v in row N of A's buffer; the tile shape, chain / subject indexing and K_x formula of k_svc_cov
+// Sigma' itself is written by the inverse SYRK's epilogue (k_syrk_schur, nmgp_chol.hip): -A^-1 never goes to memory.
+//
+// Everything of A's buffer that the factorisation reads, in one launch: A (lower triangle, N x N), v in row N, the `pad` zero rows
+// and the seeded band of the identity rows below (what identity_rows / k_xtri_seed writes: in column c, the 1 of row c of X and
+// zeros over the rows of its 64-row block and the NMGP_XTRI_SEED_BLOCKS blocks below).  Per chain (blockIdx.z) the work list is
+// enumerated column strip by column strip (32 columns): the lower 128 x 32 tiles of the strip, then its tail (rows N..: v, pad, band,
+// one contiguous run per column).  Consecutive list entries go to the same XCD, so that each L2 hands HBM long runs of a column;
+// a lane of a tile owns a row pair (16-byte stores).  K_x formula and chain / subject indexing of k_svc_cov.
 template <int M>
 __global__ __launch_bounds__(256) void k_svc_schur_a(const double* __restrict__ x, const double* __restrict__ ell,
                                                       const double* __restrict__ Lv, const double* __restrict__ tse,
-                                                      const double* __restrict__ y, double* __restrict__ A, int ld, int N,
+                                                      const double* __restrict__ y, double* __restrict__ A, int ld, int pad, int N,
                                                       long long astride, int xstride, long long ystride, int cps) {
     constexpr int T = M * (M + 1) / 2;
-    constexpr int TJ = 64;
+    constexpr int TJ = 32, TI = 128;
+    constexpr int BAND = 64 * (NMGP_XTRI_SEED_BLOCKS + 1);
     __shared__ double sx[TJ], sl[TJ];
-    const int I = blockIdx.x, J = blockIdx.y;
-    if (I < J) return;
+    const int NI = (N + TI - 1) / TI, NJ = (N + TJ - 1) / TJ;
+    int ntl = 0;                                            // entries of the list: per strip J, row tiles J / 4 .. NI - 1 + the tail
+    for (int J = 0; J < NJ; ++J) ntl += NI - J / 4 + 1;
+    const int per = (ntl + 7) / 8;
+    const int g = blockIdx.x, t = (g & 7) * per + (g >> 3);
+    if ((g >> 3) >= per || t >= ntl) return;
+    int rem = t, J = 0;
+    while (rem >= NI - J / 4 + 1) {
+        rem -= NI - J / 4 + 1;
+        ++J;
+    }
     x += (size_t)(blockIdx.z / cps) * xstride;
     y += (size_t)(blockIdx.z / cps) * ystride;
     ell += (size_t)blockIdx.z * N;
@@ -192,150 +209,89 @@ __global__ __launch_bounds__(256) void k_svc_schur_a(const double* __restrict__ 
     A += (size_t)blockIdx.z * astride;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int j0 = J * TJ;
-    if (tid < TJ) {
-        int j = j0 + tid;
-        sx[tid] = (j < N) ? x[j] : 0.0;
-        sl[tid] = (j < N) ? ell[j] : 1.0;
-    }
-    __syncthreads();
-    const int i = I * 64 + lane;
-    if (i >= N) return;
-    const double sigma2 = exp(tse[0]);
-    const double l00 = Lv[(size_t)i * T];
-    const double Ei = sigma2 / (l00 * l00);
-    if (J == 0 && w == 0) A[(size_t)i * ld + N] = y[i] / l00;     // v_i: the right-hand-side row
-    const double xi = x[i], li = ell[i];
-    const double xi2 = xi * xi, li2 = li * li;
-#pragma unroll 2
-    for (int jj = 0; jj < TJ / 4; ++jj) {
-        const int k = w * (TJ / 4) + jj;
-        const int j = j0 + k;
-        if (j >= N || j > i) break;
-        const double xj = sx[k], lj = sl[k];
-        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
-        const double Aa = li2 + lj * lj;
-        double kv = sqrt(2.0 * (li * lj) / Aa) * exp(-dist / Aa);
-        if (i == j) kv = (NMGP_JITTER + kv) + Ei;
-        A[(size_t)j * ld + i] = kv;
-    }
-}
-
-// Sigma' (lower triangle, outputs 1..M-1 output-major, n' = (M-1) N) and y' in its row n'.  nAinv = -A^-1 (both triangles,
-// leading dimension lda), u = A^-1 v ([B, N]).  64 x 64 location tiles, lanes along i, chain on blockIdx.z.
-template <int M>
-__global__ __launch_bounds__(256) void k_svc_schur_cov(const double* __restrict__ x, const double* __restrict__ ell,
-                                                        const double* __restrict__ Lv, const double* __restrict__ tse,
-                                                        const double* __restrict__ y, const double* __restrict__ nAinv, int lda,
-                                                        const double* __restrict__ u, double* __restrict__ S, int ld, int N,
-                                                        long long bstride, int xstride, long long ystride, int cps) {
-    constexpr int T = M * (M + 1) / 2;
-    constexpr int TJ = 64;
-    constexpr int M1 = M - 1;
-    __shared__ double sx[TJ], sl[TJ], sL[TJ * T], sg[TJ * M1];
-    const int I = blockIdx.x, J = blockIdx.y;
-    x += (size_t)(blockIdx.z / cps) * xstride;
-    y += (size_t)(blockIdx.z / cps) * ystride;
-    ell += (size_t)blockIdx.z * N;
-    Lv += (size_t)blockIdx.z * N * T;
-    tse += (size_t)blockIdx.z * ((size_t)N * (1 + T) + 1);
-    nAinv += (size_t)blockIdx.z * bstride;
-    u += (size_t)blockIdx.z * N;
-    S += (size_t)blockIdx.z * bstride;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j0 = J * TJ;
-    const double sigma2 = exp(tse[0]);
-    if (tid < TJ) {
-        int j = j0 + tid;
-        sx[tid] = (j < N) ? x[j] : 0.0;
-        sl[tid] = (j < N) ? ell[j] : 1.0;
-    }
-    for (int k = tid; k < TJ * T; k += 256) {
-        size_t g = (size_t)j0 * T + k;
-        sL[k] = (g < (size_t)N * T) ? Lv[g] : 0.0;
-    }
-    __syncthreads();
-    if (tid < TJ) {
-        const double l00 = sL[tid * T];
-#pragma unroll
-        for (int b = 1; b < M; ++b) sg[tid * M1 + b - 1] = sigma2 * sL[tid * T + b * (b + 1) / 2] / (l00 * l00);
-    }
-    __syncthreads();
-    const int i = I * 64 + lane;
-    if (i >= N) return;
-    const size_t Ns = (size_t)N;
-    const int n1 = M1 * N;
-    double Li[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) Li[t] = Lv[(size_t)i * T + t];
-    const double l00 = Li[0];
-    const double il2 = 1.0 / (l00 * l00);
-    double gi[M1];
-#pragma unroll
-    for (int a = 1; a < M; ++a) gi[a - 1] = sigma2 * Li[a * (a + 1) / 2] * il2;
-    if (J == 0 && w == 0) {
-        // y'[(a,i)] = Y[i,a] - L_i[a,0] (v_i - E_i u_i)
-        const double vi = y[i] / l00;
-        const double r = vi - (sigma2 * il2) * u[i];
-#pragma unroll
-        for (int a = 1; a < M; ++a)
-            S[((size_t)(a - 1) * Ns + i) * ld + n1] = y[(size_t)a * Ns + i] - Li[a * (a + 1) / 2] * r;
-    }
-    // (tiles with I < J have i < j throughout: there only the blocks a > b hold lower-triangle entries)
-    const double xi = x[i], li = ell[i];
-    const double xi2 = xi * xi, li2 = li * li;
-#pragma unroll 2
-    for (int jj = 0; jj < TJ / 4; ++jj) {
-        const int k = w * (TJ / 4) + jj;
-        const int j = j0 + k;
-        if (j >= N) break;
-        const double xj = sx[k], lj = sl[k];
-        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
-        const double Aa = li2 + lj * lj;
-        double kv = sqrt(2.0 * (li * lj) / Aa) * exp(-dist / Aa);
-        if (i == j) kv = NMGP_JITTER + kv;
-        const double nai = nAinv[(size_t)j * lda + i];
-#pragma unroll
-        for (int a = 1; a < M; ++a) {
-#pragma unroll
-            for (int b = 1; b <= a; ++b) {
-                if (b == a && i < j) continue;
-                double s = 0.0;
-#pragma unroll
-                for (int c = 1; c <= b; ++c) s += Li[a * (a + 1) / 2 + c] * sL[k * T + b * (b + 1) / 2 + c];
-                double v = kv * s;
-                if (i == j) v += sigma2 * ((a == b ? 1.0 : 0.0) + Li[a * (a + 1) / 2] * Li[b * (b + 1) / 2] * il2);
-                v += gi[a - 1] * nai * sg[k * M1 + b - 1];
-                S[((size_t)(b - 1) * Ns + j) * ld + ((size_t)(a - 1) * Ns + i)] = v;
+    if (rem == NI - J / 4) {
+        // the strip's tail: wave w, columns c = j0 + 8 w ..; lanes along the rows N .. N + pad, then along the band
+        const int row0 = N + 1 + pad;                       // row of X[0, .]
+        for (int k = 0; k < TJ / 4; ++k) {
+            const int c = j0 + w * (TJ / 4) + k;
+            if (c >= N) break;
+            const int rb = c / 64 * 64;                     // the band of column c: X rows rb .. rb + BAND - 1
+            const int nq = 1 + pad + ((rb + BAND < N ? rb + BAND : N) - rb);
+            double* col = A + (size_t)c * ld;
+            for (int q = lane; q < nq; q += 64) {
+                const int r = q <= pad ? N + q : row0 + rb + (q - 1 - pad);
+                double v = 0.0;
+                if (q == 0) v = y[c] / Lv[(size_t)c * T];  // v_c: the right-hand-side row
+                else if (r == row0 + c) v = 1.0;
+                col[r] = v;
             }
         }
+        return;
+    }
+    const int I = J / 4 + rem;
+    if (tid < TJ) {
+        const int j = j0 + tid;
+        sx[tid] = (j < N) ? x[j] : 0.0;
+        sl[tid] = (j < N) ? ell[j] : 1.0;
+    }
+    __syncthreads();
+    const int i = I * TI + 2 * lane;                        // rows i, i + 1
+    if (i >= N) return;
+    const bool two = i + 1 < N;
+    const double sigma2 = exp(tse[0]);
+    double xi[2], li[2], xi2[2], li2[2], Ei[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int ih = two ? i + h : i;
+        const double l00 = Lv[(size_t)ih * T];
+        Ei[h] = sigma2 / (l00 * l00);
+        xi[h] = x[ih];
+        li[h] = ell[ih];
+        xi2[h] = xi[h] * xi[h];
+        li2[h] = li[h] * li[h];
+    }
+    for (int jj = 0; jj < TJ / 4; ++jj) {
+        const int k = w * (TJ / 4) + jj;
+        const int j = j0 + k;
+        if (j >= N || j > i + 1) break;
+        const double xj = sx[k], lj = sl[k];
+        double kv[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const double dist = (xi2[h] + xj * xj) - 2.0 * (xi[h] * xj);
+            const double Aa = li2[h] + lj * lj;
+            kv[h] = sqrt(2.0 * (li[h] * lj) / Aa) * exp(-dist / Aa);
+            if (i + h == j) kv[h] = (NMGP_JITTER + kv[h]) + Ei[h];
+        }
+        double* dst = A + (size_t)j * ld + i;
+        if (two && j <= i) *reinterpret_cast<double2*>(dst) = make_double2(kv[0], kv[1]);
+        else if (two) dst[1] = kv[1];                      // the pair straddles the diagonal: (i, i + 1) is upper
+        else dst[0] = kv[0];                               // the last row of an odd N
     }
 }
 
-// phase 0: k_svc_schur_a, phase 1: k_svc_schur_cov (all N/64 x N/64 tiles: Sigma' blocks a > b are full)
 template <int M>
-static void launch_svc_schur(hipStream_t s, const double* x, const double* ell, const double* Lv, const double* tse,
-                             const double* y, double* A, int lda, const double* u, double* S, int ld, int N, int batch,
-                             long long bstride, int xstride, long long ystride, int cps, int phase) {
-    dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);
-    if (phase == 0)
-        NMGP_LAUNCH((k_svc_schur_a<M>), grid, dim3(256), 0, s, x, ell, Lv, tse, y, A, lda, N, bstride, xstride, ystride, cps);
-    else
-        NMGP_LAUNCH((k_svc_schur_cov<M>), grid, dim3(256), 0, s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, bstride, xstride,
-                    ystride, cps);
+static void launch_svc_schur_a(hipStream_t s, const double* x, const double* ell, const double* Lv, const double* tse,
+                               const double* y, double* A, int lda, int pad, int N, int batch, long long bstride, int xstride,
+                               long long ystride, int cps) {
+    const int NI = cdiv(N, 128), NJ = cdiv(N, 32);
+    int ntl = 0;
+    for (int J = 0; J < NJ; ++J) ntl += NI - J / 4 + 1;
+    NMGP_LAUNCH((k_svc_schur_a<M>), dim3(8 * cdiv(ntl, 8), 1, batch), dim3(256), 0, s, x, ell, Lv, tse, y, A, lda, pad, N, bstride,
+                xstride, ystride, cps);
 }
 
-int svc_schur_build(hipStream_t s, int phase, const double* x, const double* ell, const double* Lv, const double* tse,
-                    const double* y, double* A, int lda, const double* u, double* S, int ld, int N, int M, int batch,
-                    long long bstride, int xstride, long long ystride, int cps) {
+int svc_schur_a(hipStream_t s, const double* x, const double* ell, const double* Lv, const double* tse, const double* y, double* A,
+                int lda, int pad, int N, int M, int batch, long long bstride, int xstride, long long ystride, int cps) {
     if (cps < 1) cps = 1;
     switch (M) {
-        case 2: launch_svc_schur<2>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
-        case 3: launch_svc_schur<3>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
-        case 4: launch_svc_schur<4>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
-        case 5: launch_svc_schur<5>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
-        case 6: launch_svc_schur<6>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
-        case 7: launch_svc_schur<7>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
-        case 8: launch_svc_schur<8>(s, x, ell, Lv, tse, y, A, lda, u, S, ld, N, batch, bstride, xstride, ystride, cps, phase); break;
+        case 2: launch_svc_schur_a<2>(s, x, ell, Lv, tse, y, A, lda, pad, N, batch, bstride, xstride, ystride, cps); break;
+        case 3: launch_svc_schur_a<3>(s, x, ell, Lv, tse, y, A, lda, pad, N, batch, bstride, xstride, ystride, cps); break;
+        case 4: launch_svc_schur_a<4>(s, x, ell, Lv, tse, y, A, lda, pad, N, batch, bstride, xstride, ystride, cps); break;
+        case 5: launch_svc_schur_a<5>(s, x, ell, Lv, tse, y, A, lda, pad, N, batch, bstride, xstride, ystride, cps); break;
+        case 6: launch_svc_schur_a<6>(s, x, ell, Lv, tse, y, A, lda, pad, N, batch, bstride, xstride, ystride, cps); break;
+        case 7: launch_svc_schur_a<7>(s, x, ell, Lv, tse, y, A, lda, pad, N, batch, bstride, xstride, ystride, cps); break;
+        case 8: launch_svc_schur_a<8>(s, x, ell, Lv, tse, y, A, lda, pad, N, batch, bstride, xstride, ystride, cps); break;
         default: return NMGP_E_UNSUPPORTED;
     }
     return 0;
