@@ -863,8 +863,6 @@ __global__ __launch_bounds__(512, 4) void k_syrk_schur(const double* __restrict_
 }
 
 static thread_local const SyrkHook* g_hook = nullptr;   // set by potrf_lower for the duration of one factorisation
-static int g_syrk_env = 0;     // 0 = environment not read yet
-static int g_syrk_yrow = 1;    // NMGP_SYRK_YROW=0: the right-hand-side row keeps its own (masked) tile row
 
 // launch geometry of one trapezoid update: grid, tile-order mode and kernel flags (shared with the fused panel step)
 struct SyrkPlan {
@@ -877,17 +875,13 @@ struct SyrkPlan {
 
 static SyrkPlan syrk_plan(int lda, int ldc, int mrows, int ncols, int K, int batch, int ktri, bool compact_only,
                           bool tri_rows = false) {
-    if (!g_syrk_env) {
-        g_syrk_env = 1;
-        if (const char* z = std::getenv("NMGP_SYRK_YROW")) g_syrk_yrow = std::atoi(z) != 0;
-    }
     SyrkPlan pl;
     // evaluations carry a few extra rows below a whole number of tiles (value: the right-hand side; gradient: two more rows
     // of L^-T): the diagonal tiles take them along (syrk_tile_fast) and the masked tile row disappears.  Needs every tile
     // of the launch on the fast path.
     int yflag = 0;
     const int nyr = mrows % SY_BM;                      // rows below the last full tile
-    if (g_syrk_yrow && !ktri && mrows > SY_BM && nyr >= 1 && nyr <= 16 && ncols % SY_BM == 0 && (K & 31) == 0 &&
+    if (!ktri && mrows > SY_BM && nyr >= 1 && nyr <= 16 && ncols % SY_BM == 0 && (K & 31) == 0 &&
         (long long)(K + 16) * lda * 8 < 0x7fff0000LL && (lda & 1) == 0 && (ldc & 1) == 0) {
         yflag = nyr << 2;
         mrows -= nyr;
@@ -911,16 +905,12 @@ static SyrkPlan syrk_plan(int lda, int ldc, int mrows, int ncols, int K, int bat
         }
     }
     pl.kflags = (ktri ? 1 : 0) | (ktri == 2 ? 512 : 0) | yflag;          // ktri = 2: triangular A, C overwritten, both triangles
-    static const int tri_rowmajor = [] {
-        const char* e = std::getenv("NMGP_SYRK_TRI_ORDER");      // strips: the chunked strip order also for triangular operands
-        return (e && std::strcmp(e, "strips") == 0) ? 0 : 1;
-    }();
     // (measured, 128 chains value+gradient, same box: strips 257.6-258.2 evals/s, row-major for the inverse SYRK only 258.7-259.0,
     // also for the factorisation's updates with K >= 1024: 262.7-263.1; from K >= 512 / 256 / 64 on: 1.3 / 2.6 / 1.7 evals/s less --
     // there the tiles of L^-T rows are a small share and the L2 reuse of the strip order is worth more)
     // (the inverse SYRK of SMALL batches -- compact enumeration, a few rounds of tiles -- gains most: longest tile rows first is also
     // the better schedule for the launch's tail; one chain value+gradient 163 -> 168 evals/s, its inverse SYRK 1.47 -> 1.22 ms)
-    if ((ktri || (tri_rows && K >= 1024)) && tri_rowmajor && gx >= gy && (pl.swz > 0 || (ktri && pl.swz < 0))) {
+    if ((ktri || (tri_rows && K >= 1024)) && gx >= gy && (pl.swz > 0 || (ktri && pl.swz < 0))) {
         // triangular-operand launch (the inverse SYRK; the big updates of a gradient factorisation, whose L^-T rows skip their
         // leading zero k-panels): tiles of very different length -- row-major order, dealt to the XCDs tile by tile (see
         // syrk_tile_body)
@@ -1194,29 +1184,18 @@ __global__ __launch_bounds__(256) void k_potf2_64b(double* __restrict__ A, int l
     potf2b_store(A, lda, nb, P, tid, 256);
 }
 
-static int g_potf2_valu = -1;     // NMGP_POTF2=valu selects the unblocked kernel (k_potf2_64)
 // set by potrf_lower(precise = 1): substitution-based panel kernels (no inverted 16x16 blocks) for the ill-conditioned,
-// cached prior covariances (RBF + 1e-6 I, condition number up to 1e11), where the inverse-based solves cost parity digits
+// cached prior covariances (RBF + 1e-6 I, condition number up to 1e11), where the inverse-based solves cost parity digits.
+// Otherwise the diagonal blocks come from k_potf2_64b and carry inv(L_qq)^T in their strict upper part, which the
+// matrix-core solves and the fused schedules read.
 static thread_local int g_precise = 0;
 
 void potf2_64(hipStream_t s, double* A, int lda, int nb, int* info, int goff, int batch, long long bstride,
               int istride) {
-    if (g_potf2_valu < 0) {
-        const char* e = std::getenv("NMGP_POTF2");
-        g_potf2_valu = (e && std::strcmp(e, "valu") == 0) ? 1 : 0;
-    }
-    if (g_potf2_valu || g_precise)
+    if (g_precise)
         NMGP_LAUNCH(k_potf2_64, dim3(batch), dim3(256), 0, s, A, lda, nb, info, goff, bstride, istride);
     else
         NMGP_LAUNCH(k_potf2_64b, dim3(batch), dim3(256), 0, s, A, lda, nb, info, goff, bstride, istride);
-}
-
-static int g_potf2_exports_inv() {
-    if (g_potf2_valu < 0) {
-        const char* e = std::getenv("NMGP_POTF2");
-        g_potf2_valu = (e && std::strcmp(e, "valu") == 0) ? 1 : 0;
-    }
-    return (g_potf2_valu || g_precise) ? 0 : 1;
 }
 
 // look-ahead schedule -> syrk_lower -> factor_panel_fused: the near update may factor the next panel's first diagonal block in
@@ -1560,14 +1539,15 @@ __global__ __launch_bounds__(256) void k_trsm_64(const double* __restrict__ L, i
 // panel solve on the matrix cores.  The VALU substitution above spends ~550 FP64 FMAs + LDS reads per lane and, on
 // gfx950, FP64 VALU work and FP64 MFMAs share the SIMD: k_trsm_64 ran at 2.4 TB/s.  Here the 64 columns are split
 // into four 16-column blocks:  X_q = (A_q - sum_{p<q} X_p L_qp^T) inv(L_qq)^T  with every product a chain of
-// v_mfma_f64_16x16x4_f64.  The workgroup first inverts the four 16x16 diagonal blocks of L (one wave each, 16 lanes,
-// forward substitution on the identity) and lays -L_qp and inv(L_qq) out in LDS in MFMA A-operand order.  The
+// v_mfma_f64_16x16x4_f64.  The workgroup stages L in LDS -- the inverted 16x16 diagonal blocks come with it: k_potf2_64b
+// leaves inv(L_qq)^T in their strict upper part -- and lays -L_qp and inv(L_qq) out in LDS in MFMA A-operand order.  The
 // accumulator layout of one product (lane: matrix row l & 15, columns (l >> 4) + 4 reg) IS the B-operand layout of
 // the next one (k-slice reg), so the rows stay in registers from load to store.
 // A workgroup (4 waves) handles 128 rows, a wave two interleaved 16-row chunks (rows 2(l & 15) + s: 16-byte accesses).
+// trsm_64 launches it for the partial blocks (nb < 64); full blocks take k_trsm_64h below.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_trsm_64m(const double* __restrict__ L, int ldl, int nb, double* __restrict__ A,
-                                                   int lda, int rows, long long bstride, int have_inv, int reps) {
+                                                   int lda, int rows, long long bstride, int reps) {
     L += (size_t)blockIdx.y * bstride;
     A += (size_t)blockIdx.y * bstride;
     __shared__ double Lm[64][65];
@@ -1601,8 +1581,8 @@ __global__ __launch_bounds__(256) void k_trsm_64m(const double* __restrict__ L, 
             const int idx = tid + 256 * q;
             const int r = idx & 63, c = idx >> 6;
             double v = (r == c) ? 1.0 : 0.0;
-            // have_inv: the strict upper part of the diagonal 16x16 blocks holds inv(L_qq)^T (written by k_potf2_64b)
-            if (r < nb && c < nb && (c <= r || (have_inv && (c >> 4) == (r >> 4)))) v = L[(size_t)c * ldl + r];
+            // the strict upper part of the diagonal 16x16 blocks holds inv(L_qq)^T (written by k_potf2_64b)
+            if (r < nb && c < nb && (c <= r || (c >> 4) == (r >> 4))) v = L[(size_t)c * ldl + r];
             lv[q] = v;
         }
 #pragma unroll
@@ -1612,7 +1592,7 @@ __global__ __launch_bounds__(256) void k_trsm_64m(const double* __restrict__ L, 
         }
     }
     __syncthreads();
-    if (have_inv) {
+    {
         // inv(L_qq)[i][j] (i > j) sits at Lm[16 q + j][16 q + i]; the diagonal is 1 / L_ii
         const int qq = tid >> 6, i = (tid >> 2) & 15, j0 = (tid & 3) * 4;
 #pragma unroll
@@ -1622,17 +1602,6 @@ __global__ __launch_bounds__(256) void k_trsm_64m(const double* __restrict__ L, 
             if (j < i) v = Lm[16 * qq + j][16 * qq + i];
             else if (j == i) v = 1.0 / Lm[16 * qq + i][16 * qq + i];
             Linv[qq][i][j] = v;
-        }
-    } else if (lane < 16) {
-        // wave w inverts diagonal block w: lane j carries column j of the inverse (forward substitution on e_j)
-        double x[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            double sacc = (i == lane) ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = 0; k < i; ++k) sacc = fma(-Lm[16 * w + i][16 * w + k], x[k], sacc);
-            x[i] = sacc / Lm[16 * w + i][16 * w + i];
-            Linv[w][i][lane] = x[i];
         }
     }
     __syncthreads();
@@ -1695,88 +1664,14 @@ __global__ __launch_bounds__(256) void k_trsm_64m(const double* __restrict__ L, 
     }
 }
 
-// The common case of k_trsm_64m -- a full 64-column block whose factor carries the inverted diagonal 16x16 blocks
-// (k_potf2_64b) -- with the operands built straight from global memory / L2: no staging of L, no inversion, 20 KB of
-// LDS and <= 128 VGPRs, so FOUR workgroups share a CU instead of two.  The solve is a chain of dependent MFMAs (two
-// interleaved row chunks per wave); only more waves per SIMD put more independent chains on the matrix pipe.
-__global__ __launch_bounds__(256, 4) void k_trsm_64f(const double* __restrict__ L, int ldl, double* __restrict__ A, int lda,
-                                                      int rows, long long bstride) {
-    L += (size_t)blockIdx.y * bstride;
-    A += (size_t)blockIdx.y * bstride;
-    __shared__ v4d ops[10][64];                   // ops[blk][lane] = the four k-slices of the lane's A operand
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const int rbase = blockIdx.x * 128 + w * 32 + 2 * l15;       // rows rbase, rbase + 1
-    const bool v0 = rbase < rows, v1 = rbase + 1 < rows;
-    v4d T[2][4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int col = 16 * q + 4 * r + l4;
-            double2 v = make_double2(0.0, 0.0);
-            if (v0) v = *reinterpret_cast<const double2*>(&A[(size_t)col * lda + rbase]);
-            T[0][q][r] = v.x;
-            T[1][q][r] = v1 ? v.y : 0.0;
-        }
-    // entry [row = l & 15][k = 4 kk + (l >> 4)]; blk 0..5 = -L_qp (q = 1: p0; q = 2: p0, p1; q = 3: p0, p1, p2), blk 6 + q = inv(L_qq)
-#pragma unroll
-    for (int e = 0; e < 10; ++e) {
-        const int idx = tid + 256 * e;               // 0 .. 2559
-        const int blk = idx >> 8, kk = (idx >> 6) & 3, l = idx & 63;
-        const int rr = l & 15, kc = 4 * kk + (l >> 4);
-        double v;
-        if (blk < 6) {
-            const int q = blk == 0 ? 1 : (blk < 3 ? 2 : 3);
-            const int pp = blk == 0 ? 0 : (blk < 3 ? blk - 1 : blk - 3);
-            v = -L[(size_t)(16 * pp + kc) * ldl + 16 * q + rr];
-        } else {
-            const int q = blk - 6;                   // inv(L_qq)[rr][kc] (kc < rr) sits at row 16 q + kc, column 16 q + rr
-            if (kc < rr) v = L[(size_t)(16 * q + rr) * ldl + 16 * q + kc];
-            else if (kc == rr) v = 1.0 / L[(size_t)(16 * q + rr) * ldl + 16 * q + rr];
-            else v = 0.0;
-        }
-        reinterpret_cast<double*>(&ops[blk][l])[kk] = v;
-    }
-    __syncthreads();
-    if (blockIdx.x * 128 + w * 32 >= rows) return;               // wave-uniform (the MFMAs need every lane)
-    // right-looking order: once X_p is solved, its updates of the blocks q > p are independent of each other (up to six
-    // accumulator chains in flight instead of two)
-#pragma unroll
-    for (int pp = 0; pp < 4; ++pp) {
-        const v4d ai = ops[6 + pp][lane];
-        v4d x0 = {0.0, 0.0, 0.0, 0.0}, x1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            x0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[kk], T[0][pp][kk], x0, 0, 0, 0);
-            x1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[kk], T[1][pp][kk], x1, 0, 0, 0);
-        }
-        T[0][pp] = x0;
-        T[1][pp] = x1;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int q = pp + 1; q < 4; ++q) {
-                const double a = reinterpret_cast<const double*>(&ops[(q == 1 ? 0 : (q == 2 ? 1 : 3)) + pp][lane])[kk];
-                T[0][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, T[0][pp][kk], T[0][q], 0, 0, 0);
-                T[1][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, T[1][pp][kk], T[1][q], 0, 0, 0);
-            }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int col = 16 * q + 4 * r + l4;
-            if (v1) *reinterpret_cast<double2*>(&A[(size_t)col * lda + rbase]) = make_double2(T[0][q][r], T[1][q][r]);
-            else if (v0) A[(size_t)col * lda + rbase] = T[0][q][r];
-        }
-}
-
-// The same with ONE 16-row chunk per wave (64 rows per workgroup, 84 VGPRs, no spills): six workgroups per CU instead of four.  The
-// solve is bound by HBM at 81 % of what in-place panel accesses reach on this chip; what limits it is how many
-// workgroups of a CU are in their load phase at a time, not the matrix pipe (40 MFMAs per wave against 64 KB moved per workgroup).
-// Measured (same box, alternating): 128 chains 775.4-776.7 -> 779.3-780.3 evals/s, value+gradient 256.4 -> 258.9, 16 chains
-// 667 -> 676, one chain unchanged; with __launch_bounds__(256, 6) the compiler spills 4 registers and half the gain is lost.
+// The common case -- a full 64-column block -- with the operands built straight from global memory / L2: no staging of L, no
+// inversion, 20 KB of LDS.  The solve is a chain of dependent MFMAs; only more waves per SIMD put more independent chains on the
+// matrix pipe.  ONE 16-row chunk per wave (64 rows per workgroup, 84 VGPRs, no spills): six workgroups per CU.  The solve is bound
+// by HBM at 81 % of what in-place panel accesses reach on this chip; what limits it is how many workgroups of a CU are in
+// their load phase at a time, not the matrix pipe (40 MFMAs per wave against 64 KB moved per workgroup).
+// Measured against two interleaved 16-row chunks per wave at four workgroups per CU (same box, alternating): 128 chains
+// 775.4-776.7 -> 779.3-780.3 evals/s, value+gradient 256.4 -> 258.9, 16 chains 667 -> 676, one chain unchanged; with
+// __launch_bounds__(256, 6) the compiler spills 4 registers and half the gain is lost.
 template <int OCC>
 __global__ __launch_bounds__(256, OCC) void k_trsm_64h(const double* __restrict__ L, int ldl, double* __restrict__ A, int lda,
                                                         int rows, long long bstride) {
@@ -1813,6 +1708,8 @@ __global__ __launch_bounds__(256, OCC) void k_trsm_64h(const double* __restrict_
     }
     __syncthreads();
     if (blockIdx.x * 64 + w * 16 >= rows) return;               // wave-uniform (the MFMAs need every lane)
+    // right-looking order: once X_p is solved, its updates of the blocks q > p are independent of each other (up to three
+    // accumulator chains in flight instead of one)
 #pragma unroll
     for (int pp = 0; pp < 4; ++pp) {
         const v4d ai = ops[6 + pp][lane];
@@ -1836,33 +1733,19 @@ __global__ __launch_bounds__(256, OCC) void k_trsm_64h(const double* __restrict_
     }
 }
 
-static int g_trsm_valu = -1;     // NMGP_TRSM=valu selects the substitution kernel (k_trsm_64)
-static int g_potf2_exports_inv();  // 1 when the block factorisation in use leaves inv(L_qq) in the diagonal blocks
-
 void trsm_64(hipStream_t s, const double* L, int ldl, int nb, double* A, int lda, int rows, int batch,
              long long bstride) {
     if (rows <= 0) return;
-    if (g_trsm_valu < 0) {
-        const char* e = std::getenv("NMGP_TRSM");
-        g_trsm_valu = (e && std::strcmp(e, "valu") == 0) ? 1 : 0;
-    }
-    if (g_trsm_valu || g_precise) {
+    if (g_precise) {
         NMGP_LAUNCH(k_trsm_64, dim3(cdiv_c(rows, 64), batch), dim3(256), 0, s, L, ldl, nb, A, lda, rows, bstride);
-    } else if (nb == 64 && g_potf2_exports_inv()) {
-        // default: one 16-row chunk per wave (k_trsm_64h); NMGP_TRSM=f: two interleaved chunks per wave (k_trsm_64f, the round-2 kernel)
-        static const int two_chunks = [] {
-            const char* e = std::getenv("NMGP_TRSM");
-            return (e && std::strcmp(e, "f") == 0) ? 1 : 0;
-        }();
-        if (!two_chunks) NMGP_LAUNCH(k_trsm_64h<5>, dim3(cdiv_c(rows, 64), batch), dim3(256), 0, s, L, ldl, A, lda, rows, bstride);
-        else NMGP_LAUNCH(k_trsm_64f, dim3(cdiv_c(rows, 128), batch), dim3(256), 0, s, L, ldl, A, lda, rows, bstride);
+    } else if (nb == 64) {
+        NMGP_LAUNCH(k_trsm_64h<5>, dim3(cdiv_c(rows, 64), batch), dim3(256), 0, s, L, ldl, A, lda, rows, bstride);
     } else {
         // groups of 128 rows per workgroup: more of them amortise the factor preparation once the launch would fill the
         // chip (512 resident workgroups) several times over anyway
         const long long wgs = (long long)cdiv_c(rows, 128) * batch;
         const int reps = wgs >= 4096 ? 4 : (wgs >= 2048 ? 2 : 1);
-        NMGP_LAUNCH(k_trsm_64m, dim3(cdiv_c(rows, 128 * reps), batch), dim3(256), 0, s, L, ldl, nb, A, lda, rows, bstride,
-                           g_potf2_exports_inv(), reps);
+        NMGP_LAUNCH(k_trsm_64m, dim3(cdiv_c(rows, 128 * reps), batch), dim3(256), 0, s, L, ldl, nb, A, lda, rows, bstride, reps);
     }
 }
 
@@ -1880,7 +1763,7 @@ void trsm_64(hipStream_t s, const double* L, int ldl, int nb, double* A, int lda
 //   8 waves x 16 rows each):
 //     1. catch-up: C[rows, block k] and C[rows, block k+1] -= X[rows, block k-1] L[.., block k-1]^T   (K = 64, MFMA; the
 //        operands are final since the previous launch, so no workgroup waits for another);
-//     2. solve: X[rows, block k] = C[rows, block k] inv(L_kk)^T  (the 16x16-blocked scheme of k_trsm_64f);
+//     2. solve: X[rows, block k] = C[rows, block k] inv(L_kk)^T  (the 16x16-blocked scheme of k_trsm_64h);
 //     3. workgroup 0 only -- it owns block row k+1: D = C[k+1, k+1] - X[k+1, k] X[k+1, k]^T, factor D (potf2b_core) and
 //        store it: the diagonal block of step k + 1 is ready when this launch ends;
 //   workgroups T .. ("update" role): the catch-up of the remaining panel columns >= ck + 128, rows >= ck + 128, with the
@@ -1901,10 +1784,9 @@ void trsm_64(hipStream_t s, const double* L, int ldl, int nb, double* A, int lda
 //   MODE 2 = second step (a previous block, no next one): catch-up + solve; 52 KB of LDS.
 // With the flags known at compile time at most two 64-column row blocks are live per thread: 96 / 110 VGPRs (OCC = 4), two workgroups
 // per CU, so that one's loads travel under the other's MFMAs and stores (the general step holds three blocks in 191 VGPRs, one per
-// CU).  OCC = 6: three workgroups per CU (80 VGPRs, 3 x 53 KB of LDS) -- the second step gets there without spilling by issuing its
-// row loads only after its operands have gone to LDS (default for it: 128 chains +0.35 %, 64 subjects +0.8 %); the first step does
-// not (its critical workgroup's factorisation wants ~100 registers: 168 spilled, -1 % at 16 chains), it stays at 4.
-// NMGP_LEAF1_OCC / NMGP_LEAF2_OCC select.
+// CU).  The second step runs at OCC = 6: three workgroups per CU (80 VGPRs, 3 x 53 KB of LDS), which it reaches without spilling by
+// issuing its row loads only after its operands have gone to LDS (against OCC = 4: 128 chains +0.35 %, 64 subjects +0.8 %); the
+// first step does not (its critical workgroup's factorisation wants ~100 registers: 168 spilled, -1 % at 16 chains), it stays at 4.
 template <int MODE, int OCC = 2>
 __global__ __launch_bounds__(512, OCC) void k_panel_step(double* __restrict__ Ab, int lda, int ck, int has_prev_a,
                                                         int has_next_a,
@@ -1953,7 +1835,7 @@ __global__ __launch_bounds__(512, OCC) void k_panel_step(double* __restrict__ Ab
     // ---- solve role ----
     double* A = Ab + (size_t)by * bstride;
     v4d* opsC = reinterpret_cast<v4d*>(smem);                    // [4 q][4 sg][64 lanes]: -L[cb + 16 q + i][4 (4 sg + kk) + l4]
-    v4d* opsT = reinterpret_cast<v4d*>(smem + kOpsT);            // [10][64 lanes], as in k_trsm_64f
+    v4d* opsT = reinterpret_cast<v4d*>(smem + kOpsT);            // [10][64 lanes], as in k_trsm_64h
     double* Xps = smem + (MODE == 0 ? kXps : 0);                 // [64][PS_XLD]: X[k+2, k-1] (the P waves; MODE 0 only)
     double* Xs = smem + (MODE == 2 ? 0 : kXs);                   // [64][PS_XLD]: X[k+1, k]   (workgroup 0; not in MODE 2)
     // Workgroup 0 owns the critical block row k + 1 ("C", waves 0..3: its diagonal block is factored at the end of this
@@ -2018,7 +1900,7 @@ __global__ __launch_bounds__(512, OCC) void k_panel_step(double* __restrict__ Ab
                 Un[q][r] = (rv && un_used && row < un_fresh) ? A[(size_t)(ck + 64 + c) * lda + rowc] : 0.0;
             }
     };
-    if constexpr (!(MODE == 2 && OCC == 6)) load_rows();
+    if constexpr (MODE != 2) load_rows();
     // (2) operands to LDS
     if (has_prev) {
 #pragma unroll
@@ -2039,7 +1921,7 @@ __global__ __launch_bounds__(512, OCC) void k_panel_step(double* __restrict__ Ab
         const int blk = idx >> 8, kk = (idx >> 6) & 3, l = idx & 63;
         smem[kOpsT + (blk * 64 + l) * 4 + kk] = ot[j];
     }
-    if constexpr (MODE == 2 && OCC == 6) load_rows();      // (the operand registers are free again: 80 VGPRs, three workgroups per CU)
+    if constexpr (MODE == 2) load_rows();      // (the operand registers are free again: 80 VGPRs, three workgroups per CU)
     __syncthreads();
     PS_STAMP(1);
     // operands of the second catch-up (column block k + 1) travel while the first one computes (workgroup 0 takes them
@@ -2064,7 +1946,7 @@ __global__ __launch_bounds__(512, OCC) void k_panel_step(double* __restrict__ Ab
                 }
     }
     PS_STAMP(2);
-    // (4) solve against the diagonal block (right-looking over the four 16-column blocks, see k_trsm_64f)
+    // (4) solve against the diagonal block (right-looking over the four 16-column blocks, see k_trsm_64h)
 #pragma unroll
     for (int pp = 0; pp < 4; ++pp) {
         const v4d ai = opsT[(6 + pp) * 64 + lane];
@@ -2199,7 +2081,7 @@ __global__ __launch_bounds__(512, OCC) void k_panel_step(double* __restrict__ Ab
     }
     __syncthreads();
     PS_STAMP(6);
-    potf2b_core_mfma(P, info + (size_t)by * istride, ck + 64);     // (the fused schedule needs NMGP_POTF2 at its default)
+    potf2b_core_mfma(P, info + (size_t)by * istride, ck + 64);
     PS_STAMP(7);
     potf2b_store(A + (size_t)(ck + 64) * lda + (ck + 64), lda, 64, P, tid, 512);
     PS_STAMP(8);
@@ -2239,15 +2121,10 @@ static inline int active_rows(int n, int extra, int xtri, int cend) { return n +
 //  * recursive halving (left half, ONE update of the right half with K = half width, right half): touches the panel's
 //    C entries log2(w/64) times instead of w/128 times and runs only a quarter of the update flop at K = 64 (HBM-bound
 //    at 8 flop/byte), the rest at K = 128 / 256: used for batches, where the launches are throughput-bound.
-static const int g_fuse_potf2 = [] {   // NMGP_CHOL_FUSE_POTF2=0: every diagonal block in a launch of its own (A/B)
-    const char* e = std::getenv("NMGP_CHOL_FUSE_POTF2");
-    return e ? std::atoi(e) : 1;
-}();
-
 // Arm the next syrk_lower call: its tile (0, 0) is the diagonal block at column `goff`, `wnext` columns are left in the panel
 // part that starts there (a full 64-column block is what the fused form factors).
 static void arm_fused_block(int* info, int istride, int goff, int wnext) {
-    if (!g_fuse_potf2 || wnext < 64 || !g_potf2_exports_inv()) return;
+    if (wnext < 64 || g_precise) return;
     g_fuse_next.info = info;
     g_fuse_next.istride = istride;
     g_fuse_next.goff = goff;
@@ -2329,19 +2206,12 @@ static void factor_panel_fused(hipStream_t s, double* A, int lda, int n, int ext
         const int un_fresh = xtri > 0 ? n + extra + (has_prev ? ck - 64 : ck) : 0x7fffffff;
         const int u_tri = xtri > 0 ? n + extra - 64 * NMGP_XTRI_SEED_BLOCKS : 0x7fffffff;
         if (leaf && pl.tiles == 0 && !pre && nk == 2) {
-            static const int occ1 = [] { const char* e = std::getenv("NMGP_LEAF1_OCC"); return e ? std::atoi(e) : 4; }();
-            static const int occ2 = [] { const char* e = std::getenv("NMGP_LEAF2_OCC"); return e ? std::atoi(e) : 6; }();
-#define NMGP_LEAF_LAUNCH(M, O, hp, hn)                                                                                          \
-    NMGP_LAUNCH((k_panel_step<M, O>), dim3((unsigned)(T * batch)), dim3(512), 0, s, A, lda, ck, hp, hn, m_act, c0 + w, bs, info, is, T, \
-                0, 0, 0, 0, batch, 0, un_fresh, u_tri, st)
-            if (k == 0) {
-                if (occ1 == 6) NMGP_LEAF_LAUNCH(1, 6, 0, 1);
-                else NMGP_LEAF_LAUNCH(1, 4, 0, 1);
-            } else {
-                if (occ2 == 6) NMGP_LEAF_LAUNCH(2, 6, 1, 0);
-                else NMGP_LEAF_LAUNCH(2, 4, 1, 0);
-            }
-#undef NMGP_LEAF_LAUNCH
+            if (k == 0)
+                NMGP_LAUNCH((k_panel_step<1, 4>), dim3((unsigned)(T * batch)), dim3(512), 0, s, A, lda, ck, 0, 1, m_act, c0 + w, bs, info,
+                            is, T, 0, 0, 0, 0, batch, 0, un_fresh, u_tri, st);
+            else
+                NMGP_LAUNCH((k_panel_step<2, 6>), dim3((unsigned)(T * batch)), dim3(512), 0, s, A, lda, ck, 1, 0, m_act, c0 + w, bs, info,
+                            is, T, 0, 0, 0, 0, batch, 0, un_fresh, u_tri, st);
         } else {
             NMGP_LAUNCH((k_panel_step<0, 2>), dim3((unsigned)((T + pl.tiles) * batch)), dim3(512), 0, s, A, lda, ck, has_prev, has_next, m_act,
                         c0 + w, bs, info, is, T, pl.mrows, u_n, pl.kflags, pl.tiles, batch, pre, un_fresh, u_tri, st);
@@ -2361,7 +2231,7 @@ static bool panel_takes_fused_steps(int n, int w, int lda, int batch) {
         g_panel_mode = !e ? 0 : (std::strcmp(e, "fused") == 0 ? 1 : (std::strcmp(e, "rec") == 0 ? 2 : (std::strcmp(e, "rl") == 0 ? 3 : 0)));
         if (const char* m = std::getenv("NMGP_CHOL_FUSED_MAX_BATCH")) g_fused_max_batch = std::atoi(m);
     }
-    const bool can_fuse = w > 0 && (w % 64 == 0) && g_potf2_exports_inv() && (lda % 2 == 0);
+    const bool can_fuse = w > 0 && (w % 64 == 0) && !g_precise && (lda % 2 == 0);
     const bool small = g_fused_max_batch >= 0 ? batch <= g_fused_max_batch : (long long)batch * n <= 73728;
     return can_fuse && (g_panel_mode == 1 || (g_panel_mode == 0 && small));
 }
@@ -2418,16 +2288,9 @@ static int fused_base_width(int n, int extra, int xtri, int c0, int w, int batch
 static void factor_panel(hipStream_t s, double* A, int lda, int n, int extra, int xtri, int c0, int w, int* info,
                          int batch, long long bs, int is) {
     const int rec_min_batch = 4;                 // smallest batch that takes the recursive panels
-    // NMGP_CHOL_LEAF=0: the throughput schedule's 128-column pieces as five launches (diagonal block, solve, K = 64 update with
-    // the next diagonal block, solve) instead of the two leaf launches
-    static const int leaf_on = [] {
-        const char* e = std::getenv("NMGP_CHOL_LEAF");
-        return e ? std::atoi(e) : 1;
-    }();
     if (panel_takes_fused_steps(n, w, lda, batch))
         factor_panel_fused_split(s, A, lda, n, extra, xtri, c0, w, fused_base_width(n, extra, xtri, c0, w, batch), info, batch, bs, is);
-    else if (leaf_on && g_panel_mode == 0 && batch >= rec_min_batch && w >= 128 && (w % 64 == 0) && (lda % 2 == 0) &&
-             g_potf2_exports_inv())
+    else if (g_panel_mode == 0 && batch >= rec_min_batch && w >= 128 && (w % 64 == 0) && (lda % 2 == 0) && !g_precise)
         factor_panel_fused_split(s, A, lda, n, extra, xtri, c0, w, 128, info, batch, bs, is, true);
     else if (g_panel_mode == 3 || (g_panel_mode != 2 && batch < rec_min_batch))
         factor_panel_rl(s, A, lda, n, extra, xtri, c0, w, info, batch, bs, is);
@@ -2459,13 +2322,6 @@ struct HookScope {
 
 void potrf_lower(hipStream_t s, hipStream_t s2, hipEvent_t* ev, double* A, int lda, int n, int extra, int xtri,
                  int nb1, int* info, int batch, long long bstride, int istride, const SyrkHook* hook, int precise) {
-    if (xtri > 0 && trtri_post_applies(n, xtri, lda, batch)) {
-        // the rows of L^-T do not ride through the factorisation: value-form factorisation (the `extra` dense rows only), then
-        // the blocked triangular inversion of nmgp_trtri.hip writes X = L^-T where the riding rows would have ended up
-        potrf_lower(s, s2, ev, A, lda, n, extra, 0, nb1, info, batch, bstride, istride, hook, precise);
-        trtri_upper_post(s, A, lda, n, n + extra, batch, bstride, hook);
-        return;
-    }
     HookScope hs(hook);
     struct StampScope {          // allocate before, dump after the factorisation (synchronises: developer aid only)
         hipStream_t s;

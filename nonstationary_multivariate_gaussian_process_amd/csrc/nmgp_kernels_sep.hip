@@ -61,33 +61,29 @@ void sep_prep_b(hipStream_t s, const double* pars, long long P, const double* Y,
 // Lower triangles of the M blocks of chain b = blockIdx.z, and of K_x,b itself when Kout != nullptr (kernels.py:46-73 with the
 // jitter on the diagonal, then logpos.py:258-262's B kron K + sigma2 I in B's eigenbasis).  64 x 64 location tile per workgroup,
 // j-side inputs in LDS, lanes along i: every store instruction writes 512 contiguous bytes of a column.  M is a template parameter
-// so that the block weights live in registers and the M stores of an element are straight-line code.
+// so that the block weights live in registers and the M stores of an element are straight-line code.  The launcher takes this
+// kernel for odd N, where k_sep_blocks_b4's 16-byte stores would be misaligned.
 template <int M>
 __global__ __launch_bounds__(256) void k_sep_blocks_b(const double* __restrict__ x, const double* __restrict__ ell,
                                                        const double* __restrict__ sig, const double* __restrict__ small,
                                                        int small_per, int N, double* __restrict__ S, int ldo, long long bstride,
-                                                       double* __restrict__ Kout, int remap) {
+                                                       double* __restrict__ Kout) {
     constexpr int TJ = 64;
     __shared__ double sx[TJ], sl[TJ], ss[TJ];
-    int I = blockIdx.x, J = blockIdx.y;
     const int b = blockIdx.z;
-    if (remap) {
-        // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (each with its own L2), so workgroup g of the launch
-        // takes tile t = (g mod 8) * per + g / 8 of the lower-triangular tile list, enumerated column by column (J, then I = J ..):
-        // the tiles ONE XCD works on at a time are vertical neighbours -- the adjacent 512-byte segments of the same 64 columns --
-        // and its L2 hands HBM runs of several KB per column instead of eight L2s handing over 512 bytes each.
-        const int NI = (N + 63) / 64, ntl = NI * (NI + 1) / 2, per = (ntl + 7) / 8;
-        const int g = blockIdx.x, t = (g & 7) * per + (g >> 3);
-        if ((g >> 3) >= per || t >= ntl) return;
-        int rem = t;
-        J = 0;
-        while (rem >= NI - J) {
-            rem -= NI - J;
-            ++J;
-        }
-        I = J + rem;
+    // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (each with its own L2), so workgroup g of the launch
+    // takes tile t = (g mod 8) * per + g / 8 of the lower-triangular tile list, enumerated column by column (J, then I = J ..):
+    // the tiles ONE XCD works on at a time are vertical neighbours -- the adjacent 512-byte segments of the same 64 columns --
+    // and its L2 hands HBM runs of several KB per column instead of eight L2s handing over 512 bytes each.
+    const int NI = (N + 63) / 64, ntl = NI * (NI + 1) / 2, per = (ntl + 7) / 8;
+    const int g = blockIdx.x, t = (g & 7) * per + (g >> 3);
+    if ((g >> 3) >= per || t >= ntl) return;
+    int rem = t, J = 0;
+    while (rem >= NI - J) {
+        rem -= NI - J;
+        ++J;
     }
-    if (I < J) return;
+    const int I = J + rem;
     const double* eb = ell + (size_t)b * N;
     const double* sb = sig + (size_t)b * N;
     const double* sm = small + (size_t)b * small_per;
@@ -148,8 +144,8 @@ __global__ __launch_bounds__(256) void k_sep_blocks_b(const double* __restrict__
     }
 }
 
-// The same blocks from 128 x 32 location tiles (the default; NMGP_SEP_BLOCKS=4): a lane owns the row pair (i, i + 1), so every store instruction
-// of a wave writes ONE KILOBYTE of a column (16 bytes per lane), in the XCD-aware tile order of the remapped kernel above (a column
+// The same blocks from 128 x 32 location tiles (the default): a lane owns the row pair (i, i + 1), so every store instruction
+// of a wave writes ONE KILOBYTE of a column (16 bytes per lane), in the XCD-aware tile order of the kernel above (a column
 // of tiles per XCD at a time: its L2 hands HBM runs of many KB).  A wave takes 8 of the tile's 32 columns.  Even N only (16-byte
 // alignment of K_x's columns); the launcher falls back to the 64 x 64 kernel otherwise.  Row pairs that straddle the diagonal are
 // written whole (the element above the diagonal is scratch to every consumer: DESIGN section 2).
@@ -238,22 +234,17 @@ __global__ __launch_bounds__(256) void k_sep_blocks_b4(const double* __restrict_
 template <int M>
 static void launch_sep_blocks_b(hipStream_t s, const double* x, const double* ell, const double* sig, const double* small, int small_per,
                                 int N, double* S, int ldo, long long bstride, double* Kout, int B) {
-    // NMGP_SEP_BLOCKS: 4 (default) 128 x 32 tiles, 1 KB stores, XCD-aware order; 3: 64 x 64 tiles in the XCD-aware order (also the
-    // fallback for odd N); 1: 64 x 64 tiles in grid order (round 5's first form, kept for the A/B: 2.43 / 1.69 / 1.49 ms for 16 chains
-    // of N = 4096, D = 5 -- 1 / 3 / 4)
-    static const int variant = [] { const char* e = std::getenv("NMGP_SEP_BLOCKS"); return e ? std::atoi(e) : 4; }();
-    if (variant == 4 && (N & 1) == 0) {
+    // 128 x 32 tiles with 1 KB stores for even N, 64 x 64 tiles otherwise; both in the XCD-aware order (measured for 16 chains of
+    // N = 4096, D = 5: 64 x 64 tiles in grid order 2.43 ms, in the XCD-aware order 1.69 ms, 128 x 32 tiles 1.49 ms)
+    if ((N & 1) == 0) {
         const int NI = cdiv_s(N, 128), NJ = cdiv_s(N, 32);
         int ntl = 0;
         for (int J = 0; J < NJ; ++J) ntl += NI - J / 4;
         NMGP_LAUNCH((k_sep_blocks_b4<M>), dim3(8 * ((ntl + 7) / 8), 1, B), dim3(256), 0, s, x, ell, sig, small, small_per, N, S, ldo, bstride,
                     Kout);
-    } else if (variant == 3 || variant == 4) {
-        const int NI = cdiv_s(N, 64), ntl = NI * (NI + 1) / 2, per = (ntl + 7) / 8;
-        NMGP_LAUNCH((k_sep_blocks_b<M>), dim3(8 * per, 1, B), dim3(256), 0, s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, 1);
     } else {
-        NMGP_LAUNCH((k_sep_blocks_b<M>), dim3(cdiv_s(N, 64), cdiv_s(N, 64), B), dim3(256), 0, s, x, ell, sig, small, small_per, N, S, ldo,
-                    bstride, Kout, 0);
+        const int NI = cdiv_s(N, 64), ntl = NI * (NI + 1) / 2, per = (ntl + 7) / 8;
+        NMGP_LAUNCH((k_sep_blocks_b<M>), dim3(8 * per, 1, B), dim3(256), 0, s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout);
     }
 }
 

@@ -97,7 +97,8 @@ def test_plain_bench_run_is_lean_and_dumps_the_last_step(tmp_path):
 def test_profile_tools_replay_the_launch_schedule_of_the_throughput_path():
     """tools/syrk_classes.py attaches (rows, columns, K) to the k_syrk_lower launches of a trace by replaying the host
     schedule: recursive halving of 2048-wide outer panels down to the 128-column leaves (two k_panel_step launches, no
-    update launch) -- or down to 64 columns when NMGP_CHOL_LEAF=0.  Flop of the replayed launches + the leaves' K = 64 share
+    update launch) -- or, with syrk_classes.LEAF = False, down to 64 columns (the pre-leaf schedule of the committed r02 traces).
+    Flop of the replayed launches + the leaves' K = 64 share
     must add up to the factorisation's update flop."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import syrk_classes

@@ -298,10 +298,10 @@ def test_measured_traffic_lookup_is_keyed_by_workload_and_pinned_to_the_kernel_s
     v, why, scope = bench.measured_traffic(512, 3, 4)
     assert v is None and "stale" in why and "nmgp_chol.hip" in why
     # a schedule-changing switch in the environment: the committed passes ran the default schedule
-    monkeypatch.setenv("NMGP_TRTRI", "1")
+    monkeypatch.setenv("NMGP_CHOL_PANEL", "rec")
     v, why, _ = bench.measured_traffic(2048, 3, 128, True)
-    assert v is None and "NMGP_TRTRI" in why
-    monkeypatch.delenv("NMGP_TRTRI")
+    assert v is None and "NMGP_CHOL_PANEL" in why
+    monkeypatch.delenv("NMGP_CHOL_PANEL")
     monkeypatch.setenv("NMGP_ROUND", "r05")             # (not a schedule switch)
     assert bench.measured_traffic(2048, 3, 128, True)[0] == 2.0
     # the committed file itself: entries for the headline, its value+gradient step and config 4's per-GPU shape

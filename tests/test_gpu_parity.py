@@ -304,18 +304,21 @@ def test_separable_chains_batched_equal_single_chain_evaluations(ctx):
             assert relerr(out[k][1], so[1]) < 1e-10 and relerr(out[k], so) < 1e-9, (name, k, out[k], so)
             assert relerr(outv[k], so) < 1e-9
             assert vec_relerr(grad[k], sg) < 1e-8, (name, k, vec_relerr(grad[k], sg))
-    # throughput schedule
-    N, M, B = 1024, 5, 16
-    d = sim.simulate_separable(N, M, seed=21)
+    # throughput schedule; and an odd N, whose blocks the 64 x 64 assembly kernel writes (value and value+gradient)
     hv = [sim.HYPER_SEP[k] for k in SEP_KEYS]
-    pars = np.stack([sim.perturb(d["pars_true"], 0.03, 0.3 + 0.2 * k) for k in range(B)])
-    ctx.set_data(d["x"], d["Y"])
-    out, grad, st = ctx.sep_batch_eval(pars, hv, True, True)
-    assert np.all(st == 0) and np.all(np.isfinite(out)) and np.all(np.isfinite(grad))
-    for k in (0, 7, 15):
-        so, sg = ctx.logpos_sep(pars[k], hv, True, True)
-        record_parity("sepbatch16_N1024_M5_chain%d_vs_single" % k, loglik=(relerr(out[k][1], so[1]), 1e-10), grad=(vec_relerr(grad[k], sg), 1e-8))
-        assert relerr(out[k][1], so[1]) < 1e-10 and relerr(out[k], so) < 1e-9 and vec_relerr(grad[k], sg) < 1e-8
+    for N, M, B, seed, chains in ((1024, 5, 16, 21, (0, 7, 15)), (201, 5, 3, 22, (0, 1, 2))):
+        d = sim.simulate_separable(N, M, seed=seed)
+        pars = np.stack([sim.perturb(d["pars_true"], 0.03, 0.3 + 0.2 * k) for k in range(B)])
+        ctx.set_data(d["x"], d["Y"])
+        out, grad, st = ctx.sep_batch_eval(pars, hv, True, True)
+        outv, _, stv = ctx.sep_batch_eval(pars, hv, True, False)
+        assert np.all(st == 0) and np.all(stv == 0) and np.all(np.isfinite(out)) and np.all(np.isfinite(grad))
+        for k in chains:
+            so, sg = ctx.logpos_sep(pars[k], hv, True, True)
+            record_parity("sepbatch%d_N%d_M%d_chain%d_vs_single" % (B, N, M, k), loglik=(relerr(out[k][1], so[1]), 1e-10),
+                          grad=(vec_relerr(grad[k], sg), 1e-8))
+            assert relerr(out[k][1], so[1]) < 1e-10 and relerr(out[k], so) < 1e-9 and vec_relerr(grad[k], sg) < 1e-8
+            assert relerr(outv[k], so) < 1e-9
     # config 5's real shape, 4 chains = 20 blocks of n = 4096 (2048-wide outer panels): chain 0 is the reference golden
     g = golden("sep_sim_N4096_M5")
     ctx.set_data(g["x"], g["Y"])

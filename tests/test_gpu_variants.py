@@ -59,24 +59,19 @@ print(json.dumps({"out3": list(map(float, out3)), "grad3": list(map(float, grad3
                   "grad2": list(map(float, grad2)), "batch2": bout2.tolist(), "bgrad2": bgrad2.tolist()}))
 """
 
-VARIANTS = [{}, {"NMGP_TRSM": "valu"}, {"NMGP_TRSM": "f"}, {"NMGP_POTF2": "valu"}, {"NMGP_TRSM": "valu", "NMGP_POTF2": "valu"},
-            {"NMGP_SYRK_YROW": "0"},
+VARIANTS = [{},
             {"NMGP_CHOL_PANEL": "fused"}, {"NMGP_CHOL_PANEL": "rec"}, {"NMGP_CHOL_PANEL": "rl"},
             {"NMGP_CHOL_PANEL": "fused", "NMGP_CHOL_NB1": "128"},
             {"NMGP_CHOL_LOOKAHEAD": "1", "NMGP_CHOL_NB1": "128"}, {"NMGP_CHOL_NB1": "256"},
             {"NMGP_CHOL_LOOKAHEAD": "0"}, {"NMGP_LOOKAHEAD_CUS": "0", "NMGP_CHOL_NB1": "128"}, {"NMGP_PRIOR_OVERLAP": "0"},
             {"NMGP_CHOL_FUSED_MAX_BATCH": "0"}, {"NMGP_PRIOR_SOLVE": "rocblas"},
-            {"NMGP_CHOL_FUSE_POTF2": "0"}, {"NMGP_SYRK_SMALL_MAX": "0"}, {"NMGP_SYRK_SMALL_MAX": "100000"},
+            {"NMGP_SYRK_SMALL_MAX": "0"}, {"NMGP_SYRK_SMALL_MAX": "100000"},
             {"NMGP_POISON": "1"}, {"NMGP_POISON": "1", "NMGP_CHOL_PANEL": "fused"},
             # fused steps under a recursive split (round 3), with the L^-T rows that enter panel by panel; substitution prior solves
             {"NMGP_CHOL_FUSED_BASE": "128"}, {"NMGP_CHOL_FUSED_BASE": "256", "NMGP_CHOL_PANEL": "fused"},
             {"NMGP_CHOL_FUSED_BASE": "128", "NMGP_CHOL_PANEL": "fused", "NMGP_POISON": "1"}, {"NMGP_PRIOR_SOLVE": "trsv"},
-            {"NMGP_SYRK_TRI_ORDER": "strips"},
-            # the throughput schedule on the snippet's small batches: leaf launches (default), with poisoned buffers, and the
-            # five-launch form they replace
-            {"NMGP_CHOL_FUSED_MAX_BATCH": "0", "NMGP_POISON": "1"}, {"NMGP_CHOL_FUSED_MAX_BATCH": "0", "NMGP_CHOL_LEAF": "0"},
-            # ... and the other register budgets of the two leaf kernels (defaults: first step 4 waves per SIMD, second step 6)
-            {"NMGP_CHOL_FUSED_MAX_BATCH": "0", "NMGP_LEAF1_OCC": "6", "NMGP_LEAF2_OCC": "4"}]
+            # the throughput schedule's leaf launches on the snippet's small batches, with poisoned buffers
+            {"NMGP_CHOL_FUSED_MAX_BATCH": "0", "NMGP_POISON": "1"}]
 
 
 def run_variant(env_extra):
@@ -130,19 +125,6 @@ def test_parity_suite_passes_with_nan_poisoned_device_buffers():
     assert out.returncode == 0, out.stdout[-3000:]
 
 
-@pytest.mark.parametrize("variant", ["1", "3"])
-def test_separable_batch_under_the_selectable_block_assembly_kernels(variant):
-    """NMGP_SEP_BLOCKS: the batched separable evaluation's block-assembly kernel in its other forms (64 x 64 tiles in grid order /
-    in the XCD-aware order; the default is 128 x 32 tiles with 16-byte stores) against the same goldens and single-chain evaluations."""
-    env = dict(os.environ)
-    env["NMGP_SEP_BLOCKS"] = variant
-    env["NMGP_ROUND"] = "variants"
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-q", "-m", "gpu", "-x",
-                          "-p", "no:cacheprovider", "-k", "separable_chains_batched"], capture_output=True, text=True, timeout=900,
-                         env=env, cwd=ROOT)
-    assert out.returncode == 0, out.stdout[-3000:]
-
-
 @pytest.mark.parametrize("env_extra", [
     {"NMGP_SYRK_SMALL_MAX": "100000", "NMGP_CHOL_NB1": "128"},      # every K >= 128 update on 64x64 tiles, look-ahead from n > 256
     {"NMGP_SYRK_SMALL_MAX": "100000", "NMGP_CHOL_NB1": "192", "NMGP_CHOL_PANEL": "rl"},   # panels that are no multiple of 128
@@ -175,63 +157,6 @@ def test_bench_dist_selftest_runs_rccl_next_to_the_library_streams():
     assert rec["distributed"]["process_group"] == {"backend": "nccl", "world_size": 1, "rank": 0}
     assert rec["config"]["chains_ok"] == 3 and rec["config"]["chain_table_rows"] == 3 and rec["value"] > 0
     assert rec["grad"]["chains_ok"] == 3
-
-
-TRTRI_SNIPPET = r"""
-import json, sys
-import numpy as np
-sys.path.insert(0, %(root)r)
-from nonstationary_multivariate_gaussian_process_amd import _lib, sim
-from oracle import nmgp_oracle as O          # checker
-hv = [sim.HYPER_SVC[k] for k in ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_L", "beta_L", "a", "b")]
-res = {}
-ctx = _lib.Context(0)
-for (N, M, B) in ((128, 2, 3), (128, 3, 1), (256, 3, 5), (512, 3, 2)):       # n = 256, 384, 768, 1536: 2, 3, 6, 12 leaf blocks
-    d = sim.simulate_nonseparable(N, M, seed=11 + N + M)
-    ctx.set_data(d["x"], d["Y"])
-    p0 = sim.perturb(d["pars_true"], 0.05, 0.2)
-    out, grad = ctx.logpos_svc(p0, hv, prior=True, want_grad=True)
-    ref, gref = O.nlogpos_obj_SVC(p0, d["Y"], d["x"], **sim.HYPER_SVC, verbose=True, grad=True)
-    key = "N%%d_M%%d" %% (N, M)
-    res[key] = {"out": list(map(float, out)), "grad": list(map(float, grad)),
-                "oracle_rel": float(abs(out[0] - ref[0]) / abs(ref[0])),
-                "oracle_grad_rel": float(np.linalg.norm(grad - gref) / np.linalg.norm(gref))}
-    if B > 1:
-        ctx.svc_batch_alloc(B)
-        allp = np.stack([sim.perturb(d["pars_true"], 0.05, 0.2 + 0.1 * b) for b in range(B)])
-        ctx.svc_batch_set_pars(allp)
-        ctx.svc_batch_eval(hv, True, want_grad=True)
-        bout, status = ctx.svc_batch_fetch()
-        res[key].update(batch=bout.tolist(), bgrad=ctx.svc_batch_fetch_grad().tolist(), status=status.tolist())
-print(json.dumps(res))
-"""
-
-
-def test_blocked_triangular_inversion_agrees_with_the_riding_rows_and_the_oracle():
-    """NMGP_TRTRI=1: gradient evaluations whose n is a multiple of 128 build X = L^-T AFTER the factorisation (nmgp_trtri.hip: leaf
-    blocks by substitution, then products with explicit inverses of the diagonal blocks) instead of the default (identity rows
-    riding through the factorisation).  Both must give the same objective and gradient -- sizes with 2, 3, 6 and 12 leaf blocks, i.e.
-    power-of-two levels only, the left-to-right top combine only, and both --, with NaN-poisoned buffers too, and match the oracle."""
-    def run(env_extra):
-        env = dict(os.environ)
-        env.update(env_extra)
-        out = subprocess.run([sys.executable, "-c", TRTRI_SNIPPET % {"root": ROOT}], capture_output=True, text=True, timeout=900,
-                             env=env, cwd=ROOT)
-        assert out.returncode == 0, (env_extra, out.stderr[-2000:])
-        return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
-    ref = run({"NMGP_TRTRI": "0"})
-    for env_extra in ({"NMGP_TRTRI": "1"}, {"NMGP_TRTRI": "1", "NMGP_POISON": "1"}, {"NMGP_TRTRI": "1", "NMGP_CHOL_FUSED_MAX_BATCH": "0"},
-                      {"NMGP_TRTRI": "1", "NMGP_TRTRI_ORDER": "lockstep"}, {"NMGP_TRTRI": "1", "NMGP_TRTRI_ORDER": "rows"}):
-        r = run(env_extra)
-        for key, a in r.items():
-            b = ref[key]
-            assert a["oracle_rel"] < 1e-6 and a["oracle_grad_rel"] < 1e-5, (env_extra, key, a["oracle_rel"], a["oracle_grad_rel"])
-            assert relerr(a["out"][1], b["out"][1]) < 1e-11, (env_extra, key)
-            assert vec_relerr(np.array(a["grad"]), np.array(b["grad"])) < 1e-7, (env_extra, key)
-            if "batch" in a:
-                assert all(s == 0 for s in a["status"])
-                assert relerr(np.array(a["batch"]), np.array(b["batch"])) < 1e-7, (env_extra, key)
-                assert vec_relerr(np.array(a["bgrad"]), np.array(b["bgrad"])) < 1e-7, (env_extra, key)
 
 
 def test_bench_launches_two_ranks_by_itself_and_rehearses_the_multi_process_path_on_one_gpu():
