@@ -85,7 +85,7 @@ static void* syrk_hook_begin(void* user, hipStream_t s, double flop, double byte
 }
 static void syrk_hook_end(void*, void* token) { delete static_cast<NmgpStage*>(token); }
 
-const SyrkHook* nmgp_syrk_hook(nmgp_ctx* c) {
+static const SyrkHook* nmgp_syrk_hook(nmgp_ctx* c) {
     c->syrk_hook.user = c;
     c->syrk_hook.begin = syrk_hook_begin;
     c->syrk_hook.end = syrk_hook_end;
@@ -419,7 +419,7 @@ int nmgp_get_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor** out) {
 }
 
 // events for the look-ahead factorisation (created once, reused by every evaluation)
-hipEvent_t* nmgp_chol_events(nmgp_ctx* c, int n) {
+static hipEvent_t* nmgp_chol_events(nmgp_ctx* c, int n) {
     if (!c->chol_lookahead) return nullptr;
     const int nbmin = c->chol_nb1 > 0 ? c->chol_nb1 : 512;
     const size_t need = 2 * (size_t)((n + nbmin - 1) / nbmin) + 3;
@@ -431,10 +431,16 @@ hipEvent_t* nmgp_chol_events(nmgp_ctx* c, int n) {
     return c->chol_ev.data();
 }
 
+void nmgp_potrf(nmgp_ctx* c, double* A, int ld, int n, int extra, int xtri, int* info, int batch, long long bstride, int istride,
+                int precise) {
+    potrf_lower(c->stream, c->stream2, nmgp_chol_events(c, n), A, ld, n, extra, xtri, c->chol_nb1, info, batch, bstride, istride,
+                nmgp_syrk_hook(c), precise);
+}
+
 int nmgp_chol_factor(nmgp_ctx* c, double* A, int ld, int n, int extra, int* d_info) {
     if (c->chol_algo == 1 && (ld % 2 == 0)) {
         // used for the cached prior covariances, the dense-MVN primitive and prediction: accuracy before speed
-        potrf_lower(c->stream, c->stream2, nmgp_chol_events(c, n), A, ld, n, extra, 0, c->chol_nb1, d_info, 1, 0, 0, nmgp_syrk_hook(c), 1);
+        nmgp_potrf(c, A, ld, n, extra, 0, d_info, 1, 0, 0, 1);
         return 0;
     }
     if (extra != 0) return nmgp_fail(c, NMGP_E_STATE, "rocSOLVER path cannot carry extra rows");
@@ -492,8 +498,7 @@ static int svc_enqueue(nmgp_ctx* c, const double hyper[8], int prior, int want_g
             // with gradient: a zero pad row (keeps the next block at an even offset) and n identity rows -> X = L^-T
             if (want_grad) identity_rows(s, c->d_S, ld, n + 1, n, xpad);
             // row n becomes z = L^-1 y
-            potrf_lower(s, c->stream2, nmgp_chol_events(c, n), c->d_S, ld, n, want_grad ? 1 + xpad : 1, want_grad ? n : 0,
-                        c->chol_nb1, c->d_info, 1, 0, 0, nmgp_syrk_hook(c));
+            nmgp_potrf(c, c->d_S, ld, n, want_grad ? 1 + xpad : 1, want_grad ? n : 0, c->d_info);
         }
         {
             StageScope sp(c, NMGP_STAGE_SOLVE);
@@ -823,8 +828,7 @@ static int get_batch_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor**
     HIP_TRY(c, hipMalloc((void**)&info, B * sizeof(int)));
     hipMemsetAsync(info, 0, B * sizeof(int), c->stream);
     rbf_cov_sym(c->stream, c->b_x, c->N, alpha, beta, pf.L, pf.ld, false, (int)B);
-    potrf_lower(c->stream, c->stream2, nmgp_chol_events(c, c->N), pf.L, pf.ld, c->N, 0, 0, c->chol_nb1, info, (int)B,
-                (long long)pf.ld * N, 1, nmgp_syrk_hook(c), 1);
+    nmgp_potrf(c, pf.L, pf.ld, c->N, 0, 0, info, (int)B, (long long)pf.ld * N, 1, 1);
     half_logdet(c->stream, pf.L, pf.ld, c->N, pf.logdet, (int)B);
     std::vector<int> hi(B);
     hipMemcpyAsync(hi.data(), info, B * sizeof(int), hipMemcpyDeviceToHost, c->stream);
@@ -917,8 +921,7 @@ static int svc_batch_value_schur(nmgp_ctx* c, const double* xs, int xstride, con
     }
     {
         StageScope sp(c, NMGP_STAGE_CHOL);
-        potrf_lower(s, c->stream2, nmgp_chol_events(c, N), A, ldA, N, 1 + xpad, N, c->chol_nb1, c->b_info, B, bs, 1,
-                    nmgp_syrk_hook(c));
+        nmgp_potrf(c, A, ldA, N, 1 + xpad, N, c->b_info, B, bs, 1);
     }
     {
         StageScope sp(c, NMGP_STAGE_SOLVE);
@@ -938,8 +941,7 @@ static int svc_batch_value_schur(nmgp_ctx* c, const double* xs, int xstride, con
     }
     {
         StageScope sp(c, NMGP_STAGE_CHOL);
-        potrf_lower(s, c->stream2, nmgp_chol_events(c, n1), Sp, ldP, n1, 1, 0, c->chol_nb1, c->b_info2, B, bs, 1,
-                    nmgp_syrk_hook(c));
+        nmgp_potrf(c, Sp, ldP, n1, 1, 0, c->b_info2, B, bs, 1);
     }
     {
         StageScope sp(c, NMGP_STAGE_SOLVE);
@@ -1002,8 +1004,7 @@ extern "C" int nmgp_svc_batch_eval(nmgp_ctx* c, const double hyper[8], int prior
             // one subject: every chain shares y (vstride 0); multi-subject: y of batch element b
             set_row(s, S, ld, n, multi ? c->b_y : c->d_y, n, B, bs, multi ? n : 0, cps);
             if (want_grad) identity_rows(s, S, ld, n + 1, n, xpad, B, bs);
-            potrf_lower(s, c->stream2, nmgp_chol_events(c, n), S, ld, n, want_grad ? 1 + xpad : 1, want_grad ? n : 0, c->chol_nb1,
-                        c->b_info, B, bs, 1, nmgp_syrk_hook(c));
+            nmgp_potrf(c, S, ld, n, want_grad ? 1 + xpad : 1, want_grad ? n : 0, c->b_info, B, bs, 1);
         }
         {
             StageScope sp(c, NMGP_STAGE_SOLVE);
@@ -1664,7 +1665,7 @@ extern "C" int nmgp_cholesky(nmgp_ctx* c, const double* A, int n, const double* 
     if (algo == 1) {
         StageScope sp(c, NMGP_STAGE_CHOL);
         if (rhs) set_row(s, dA, (int)ld, n, dv, n, 1, 0, 0);
-        potrf_lower(s, c->stream2, nmgp_chol_events(c, n), dA, (int)ld, n, rhs ? 1 : 0, 0, c->chol_nb1, c->d_info + 5, 1, 0, 0, nmgp_syrk_hook(c));
+        nmgp_potrf(c, dA, (int)ld, n, rhs ? 1 : 0, 0, c->d_info + 5);
         if (rhs) get_row(s, dA, (int)ld, n, dv + n, n, 1, 0, 0);
     } else {
         StageScope sp(c, NMGP_STAGE_CHOL);

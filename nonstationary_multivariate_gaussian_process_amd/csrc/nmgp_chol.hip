@@ -862,7 +862,65 @@ __global__ __launch_bounds__(512, 4) void k_syrk_schur(const double* __restrict_
                                 smem, smem + 2 * SY_BK * SY_LD, 0x7fffffff, 0, nullptr, 0, 0, &se);
 }
 
-static thread_local const SyrkHook* g_hook = nullptr;   // set by potrf_lower for the duration of one factorisation
+// The host schedule's switches, read once per process on first use.
+struct Switches {
+    enum Panel { kAuto, kFused, kRec, kRl };
+    Panel panel = kAuto;            // NMGP_CHOL_PANEL = fused | rec | rl | auto (default): the panel schedule, see Factorisation::panel
+    int fused_max_batch = -1;       // NMGP_CHOL_FUSED_MAX_BATCH: largest batch that takes the fused steps under auto (< 0: by size)
+    int fused_base = 0;             // NMGP_CHOL_FUSED_BASE=<128|256|512|...>: width of the pieces that run as fused steps (0: auto)
+    int la_max_batch = 16;          // NMGP_CHOL_LA_MAX_BATCH: largest batch that takes the two-stream look-ahead
+    int syrk_small_max = 256;       // NMGP_SYRK_SMALL_MAX: most 128x128 tiles of an update that runs on 64x64 tiles instead
+    const char* step_stamps = nullptr;   // NMGP_STEP_STAMPS=<file>: see StepStamps
+};
+static const Switches& switches() {
+    static const Switches sw = [] {
+        Switches w;
+        if (const char* e = std::getenv("NMGP_CHOL_PANEL"))
+            w.panel = std::strcmp(e, "fused") == 0 ? Switches::kFused
+                      : std::strcmp(e, "rec") == 0 ? Switches::kRec : std::strcmp(e, "rl") == 0 ? Switches::kRl : Switches::kAuto;
+        if (const char* e = std::getenv("NMGP_CHOL_FUSED_MAX_BATCH")) w.fused_max_batch = std::atoi(e);
+        if (const char* e = std::getenv("NMGP_CHOL_FUSED_BASE")) w.fused_base = (std::atoi(e) / 64) * 64;
+        if (const char* e = std::getenv("NMGP_CHOL_LA_MAX_BATCH")) w.la_max_batch = std::atoi(e);
+        if (const char* e = std::getenv("NMGP_SYRK_SMALL_MAX")) w.syrk_small_max = std::atoi(e);
+        w.step_stamps = std::getenv("NMGP_STEP_STAMPS");
+        return w;
+    }();
+    return sw;
+}
+
+// NMGP_STEP_STAMPS=<file>: per-step phase stamps of the critical workgroup (developer aid, tools/step_stamps.py).  The device
+// buffer (16 slots per 64-column step) is cleared before a factorisation and dumped after it (synchronises).
+struct StepStamps {
+    long long* dev = nullptr;
+    int cap = 0;
+    long long* begin(hipStream_t s, int nsteps) {
+        if (!switches().step_stamps) return nullptr;
+        if (cap < nsteps) {
+            if (dev) hipFree(dev);
+            if (hipMalloc((void**)&dev, (size_t)nsteps * 16 * sizeof(long long)) != hipSuccess) dev = nullptr;
+            cap = dev ? nsteps : 0;
+        }
+        if (dev) hipMemsetAsync(dev, 0, (size_t)cap * 16 * sizeof(long long), s);
+        return dev;
+    }
+    void dump(hipStream_t s, int nsteps) const {
+        if (!switches().step_stamps || !dev) return;
+        std::vector<long long> h((size_t)nsteps * 16);
+        hipStreamSynchronize(s);
+        hipMemcpy(h.data(), dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
+        if (FILE* f = std::fopen(switches().step_stamps, "w")) {
+            for (int k = 0; k < nsteps; ++k) {
+                for (int j = 0; j < 9; ++j) std::fprintf(f, "%lld ", h[(size_t)k * 16 + j]);
+                std::fprintf(f, "\n");
+            }
+            std::fclose(f);
+        }
+    }
+};
+static StepStamps g_step_stamps;
+
+// tri_row0 / un_fresh / u_tri of a launch without rows of L^-T (what the kernels' defaults say)
+static constexpr int kNoTriRows = 0x7fffffff;
 
 // launch geometry of one trapezoid update: grid, tile-order mode and kernel flags (shared with the fused panel step)
 struct SyrkPlan {
@@ -1184,29 +1242,17 @@ __global__ __launch_bounds__(256) void k_potf2_64b(double* __restrict__ A, int l
     potf2b_store(A, lda, nb, P, tid, 256);
 }
 
-// set by potrf_lower(precise = 1): substitution-based panel kernels (no inverted 16x16 blocks) for the ill-conditioned,
+// precise (potrf_lower(precise = 1)): substitution-based panel kernels (no inverted 16x16 blocks) for the ill-conditioned,
 // cached prior covariances (RBF + 1e-6 I, condition number up to 1e11), where the inverse-based solves cost parity digits.
 // Otherwise the diagonal blocks come from k_potf2_64b and carry inv(L_qq)^T in their strict upper part, which the
 // matrix-core solves and the fused schedules read.
-static thread_local int g_precise = 0;
-
-void potf2_64(hipStream_t s, double* A, int lda, int nb, int* info, int goff, int batch, long long bstride,
-              int istride) {
-    if (g_precise)
+static void potf2_64(hipStream_t s, double* A, int lda, int nb, int* info, int goff, int batch, long long bstride,
+                     int istride, bool precise) {
+    if (precise)
         NMGP_LAUNCH(k_potf2_64, dim3(batch), dim3(256), 0, s, A, lda, nb, info, goff, bstride, istride);
     else
         NMGP_LAUNCH(k_potf2_64b, dim3(batch), dim3(256), 0, s, A, lda, nb, info, goff, bstride, istride);
 }
-
-// look-ahead schedule -> syrk_lower -> factor_panel_fused: the near update may factor the next panel's first diagonal block in
-// the same launch (k_syrk_small); armed by potrf_lower for exactly one syrk_lower call, answered through g_first_block_done
-struct FuseNext {
-    int* info = nullptr;
-    int istride = 0;
-    int goff = 0;
-};
-static thread_local FuseNext g_fuse_next;
-static thread_local int g_first_block_done = 0;
 
 // ---------------------------------------------------------------------------------------------
 // The same update on 64x64 tiles, for launches with FEW tiles on the critical path of a latency-bound factorisation (the
@@ -1373,56 +1419,49 @@ __global__ __launch_bounds__(256) void k_syrk_small(const double* __restrict__ A
     }
 }
 
-void syrk_lower(hipStream_t s, const double* A, int lda, double* C, int ldc, int mrows, int ncols, int K, int batch,
-                long long bstride, long long cstride, int ktri, int tri_row0, int tri_k0) {
-    if (mrows <= 0 || ncols <= 0 || K <= 0) return;
-    const SyrkPlan pl = syrk_plan(lda, ldc, mrows, ncols, K, batch, ktri, false, tri_row0 != 0x7fffffff);
+// finfo != nullptr asks the launch to go on and factor the diagonal block in its tile (0, 0) -- the first block of the panel
+// part that starts at column `goff`, status words finfo + b * fistride (k_syrk_small / k_syrk_lower: potf2b_core, as k_potf2_64b
+// would in a launch of its own).  Returns whether the launch does so (its shape must allow it).
+bool syrk_lower(hipStream_t s, const double* A, int lda, double* C, int ldc, int mrows, int ncols, int K, int batch,
+                long long bstride, long long cstride, int ktri, int tri_row0, int tri_k0, int* finfo, int fistride, int goff,
+                const SyrkHook* hook) {
+    if (mrows <= 0 || ncols <= 0 || K <= 0) return false;
+    const SyrkPlan pl = syrk_plan(lda, ldc, mrows, ncols, K, batch, ktri, false, tri_row0 != kNoTriRows);
     const long long cs = cstride < 0 ? bstride : cstride;
+    void* tok = nullptr;
+    if (hook && hook->begin) {
+        // algorithmic flop of this launch: 2 K per element (i >= j) of the mrows x ncols lower trapezoid
+        const double elems = (double)ncols * mrows - 0.5 * (double)ncols * (ncols - 1);
+        tok = hook->begin(hook->user, s, 2.0 * K * elems * batch, 8.0 * batch * (2.0 * elems + (double)mrows * K));
+    }
+    bool fused;
     // few 128x128 tiles (at most one per CU) and a k-loop long enough to matter: 64x64 tiles (k_syrk_small)
-    const FuseNext fuse = g_fuse_next;
-    g_fuse_next.info = nullptr;
-    static const int small_max = [] {
-        const char* e = std::getenv("NMGP_SYRK_SMALL_MAX");
-        return e ? std::atoi(e) : 256;
-    }();
     // (latency regime only: the throughput batches keep one update kernel, whose launches the profiling tools replay)
     // (round 3 tried the 64x64-tile kernel -- three workgroups per CU -- for the K = 64 / 128 updates of the big batches as well: 128
     // chains +0.3 % at K <= 64, -0.5 % at K <= 128; not kept)
-    if (!ktri && K >= 128 && batch <= 16 && (long long)pl.tiles * batch <= small_max && cs == bstride && (lda & 1) == 0 && mrows >= 2) {
+    if (!ktri && K >= 128 && batch <= 16 && (long long)pl.tiles * batch <= switches().syrk_small_max && cs == bstride &&
+        (lda & 1) == 0 && mrows >= 2) {
         const int gx = (mrows + 63) / 64, gy = (ncols + 63) / 64;
         int tiles = 0;
         for (int bj = 0; bj < gy; ++bj) tiles += gx - bj > 0 ? gx - bj : 0;
-        void* tk = nullptr;
-        if (g_hook && g_hook->begin) {
-            const double elems = (double)ncols * mrows - 0.5 * (double)ncols * (ncols - 1);
-            tk = g_hook->begin(g_hook->user, s, 2.0 * K * elems * batch, 8.0 * batch * (2.0 * elems + (double)mrows * K));
-        }
-        const bool fz = fuse.info != nullptr && mrows >= 64 && ncols >= 64;
+        fused = finfo != nullptr && mrows >= 64 && ncols >= 64;
         NMGP_LAUNCH(k_syrk_small, dim3((unsigned)(tiles * batch)), dim3(256), 0, s, A, lda, C, ldc, mrows, ncols, K, bstride, tiles,
-                    batch, tri_row0, tri_k0, fz ? fuse.info : (int*)nullptr, fuse.istride, fuse.goff);
-        if (fz) g_first_block_done = 1;
-        if (tk && g_hook->end) g_hook->end(g_hook->user, tk);
-        return;
+                    batch, tri_row0, tri_k0, fused ? finfo : (int*)nullptr, fistride, goff);
+    } else {
+        // the NEXT diagonal block inside tile (0, 0): only where that tile takes the mask-free path (the conditions of
+        // syrk_tile_body); the launch then uses the compact 1-D enumeration, whose fused form deals tile (0, 0) of every matrix first
+        fused = finfo != nullptr && !ktri && cs == bstride && pl.mrows >= SY_BM && (ncols >= SY_BM || ncols == 64) &&
+                (K & 31) == 0 && (long long)(K + 16) * lda * 8 < 0x7fff0000LL;
+        SyrkPlan pf = pl;
+        if (fused && pf.swz == 0) {
+            pf.grid = dim3((unsigned)((long long)pf.tiles * batch), 1, 1);
+            pf.swz = -pf.tiles;
+        }
+        NMGP_LAUNCH(k_syrk_lower, pf.grid, dim3(512), 0, s, A, lda, C, ldc, pf.mrows, ncols, K, bstride, cs, pf.kflags,
+                    pf.swz, batch, tri_row0, tri_k0, fused ? finfo : (int*)nullptr, fistride, goff);
     }
-    void* tok = nullptr;
-    if (g_hook && g_hook->begin) {
-        // algorithmic flop of this launch: 2 K per element (i >= j) of the mrows x ncols lower trapezoid
-        const double elems = (double)ncols * mrows - 0.5 * (double)ncols * (ncols - 1);
-        tok = g_hook->begin(g_hook->user, s, 2.0 * K * elems * batch, 8.0 * batch * (2.0 * elems + (double)mrows * K));
-    }
-    // the NEXT diagonal block inside tile (0, 0): only where that tile takes the mask-free path (the conditions of
-    // syrk_tile_body); the launch then uses the compact 1-D enumeration, whose fused form deals tile (0, 0) of every matrix first
-    const bool fzb = fuse.info != nullptr && !ktri && cs == bstride && pl.mrows >= SY_BM && (ncols >= SY_BM || ncols == 64) &&
-                     (K & 31) == 0 && (long long)(K + 16) * lda * 8 < 0x7fff0000LL;
-    SyrkPlan pf = pl;
-    if (fzb && pf.swz == 0) {
-        pf.grid = dim3((unsigned)((long long)pf.tiles * batch), 1, 1);
-        pf.swz = -pf.tiles;
-    }
-    NMGP_LAUNCH(k_syrk_lower, pf.grid, dim3(512), 0, s, A, lda, C, ldc, pf.mrows, ncols, K, bstride, cs, pf.kflags,
-                pf.swz, batch, tri_row0, tri_k0, fzb ? fuse.info : (int*)nullptr, fuse.istride, fuse.goff);
-    if (fzb) g_first_block_done = 1;
-    if (tok && g_hook->end) g_hook->end(g_hook->user, tok);
+    if (tok && hook->end) hook->end(hook->user, tok);
+    return fused;
 }
 
 int syrk_schur(hipStream_t s, const double* X, int lda, int N, int M, int batch, const SchurEpi& e) {
@@ -1430,20 +1469,12 @@ int syrk_schur(hipStream_t s, const double* X, int lda, int N, int M, int batch,
     if (M < 2 || M > 8) return NMGP_E_UNSUPPORTED;
     // the tile plan of syrk_lower(X, lda, C, ., N, N, N, batch, bs, bs, 2)
     const SyrkPlan pl = syrk_plan(lda, lda, N, N, N, batch, 2, false);
-    void* tok = nullptr;
-    if (g_hook && g_hook->begin) {
-        // flop of the inverse SYRK; bytes: X read once, Sigma' (lower) and y' written (-A^-1 itself never leaves the chip)
-        const double elems = (double)N * N - 0.5 * (double)N * (N - 1);
-        const double n1 = (double)(M - 1) * N;
-        tok = g_hook->begin(g_hook->user, s, 2.0 * N * elems * batch, 8.0 * batch * ((double)N * N + 0.5 * n1 * (n1 + 1) + n1));
-    }
     switch (M) {
 #define SCHUR_CASE(m) \
         case m: NMGP_LAUNCH(k_syrk_schur<m>, pl.grid, dim3(512), 0, s, X, lda, pl.mrows, e.bstride, pl.kflags, pl.swz, batch, e); break;
         SCHUR_CASE(2) SCHUR_CASE(3) SCHUR_CASE(4) SCHUR_CASE(5) SCHUR_CASE(6) SCHUR_CASE(7) SCHUR_CASE(8)
 #undef SCHUR_CASE
     }
-    if (tok && g_hook->end) g_hook->end(g_hook->user, tok);
     return 0;
 }
 
@@ -1733,10 +1764,10 @@ __global__ __launch_bounds__(256, OCC) void k_trsm_64h(const double* __restrict_
     }
 }
 
-void trsm_64(hipStream_t s, const double* L, int ldl, int nb, double* A, int lda, int rows, int batch,
-             long long bstride) {
+static void trsm_64(hipStream_t s, const double* L, int ldl, int nb, double* A, int lda, int rows, int batch,
+                    long long bstride, bool precise) {
     if (rows <= 0) return;
-    if (g_precise) {
+    if (precise) {
         NMGP_LAUNCH(k_trsm_64, dim3(cdiv_c(rows, 64), batch), dim3(256), 0, s, L, ldl, nb, A, lda, rows, bstride);
     } else if (nb == 64) {
         NMGP_LAUNCH(k_trsm_64h<5>, dim3(cdiv_c(rows, 64), batch), dim3(256), 0, s, L, ldl, A, lda, rows, bstride);
@@ -2110,194 +2141,6 @@ void get_row(hipStream_t s, const double* A, int lda, int row, double* v, int n,
     NMGP_LAUNCH(k_get_row, dim3(cdiv_c(n, 256), batch), dim3(256), 0, s, A, lda, row, v, n, bstride, vstride);
 }
 
-// rows that take part when the factorisation has reached column `cend`: the n matrix rows, the `extra` dense rows
-// (right-hand sides) and the first `cend` of the `xtri` identity rows (row r of L^-T is zero left of column r)
-static inline int active_rows(int n, int extra, int xtri, int cend) { return n + extra + (cend < xtri ? cend : xtri); }
-
-// Factor the panel of columns [c0, c0 + w) (already up to date) together with all active rows below it.
-// Two schedules with the same launch count:
-//  * right-looking 64-wide steps (each step updates the rest of the panel with K = 64): shortest critical path, used
-//    for a single matrix, where every launch is latency-bound anyway;
-//  * recursive halving (left half, ONE update of the right half with K = half width, right half): touches the panel's
-//    C entries log2(w/64) times instead of w/128 times and runs only a quarter of the update flop at K = 64 (HBM-bound
-//    at 8 flop/byte), the rest at K = 128 / 256: used for batches, where the launches are throughput-bound.
-// Arm the next syrk_lower call: its tile (0, 0) is the diagonal block at column `goff`, `wnext` columns are left in the panel
-// part that starts there (a full 64-column block is what the fused form factors).
-static void arm_fused_block(int* info, int istride, int goff, int wnext) {
-    if (wnext < 64 || g_precise) return;
-    g_fuse_next.info = info;
-    g_fuse_next.istride = istride;
-    g_fuse_next.goff = goff;
-}
-
-static void factor_panel_rl(hipStream_t s, double* A, int lda, int n, int extra, int xtri, int c0, int w1, int* info,
-                            int batch, long long bs, int is) {
-    for (int j0 = c0; j0 < c0 + w1; j0 += 64) {
-        const int jb = (c0 + w1 - j0 < 64) ? (c0 + w1 - j0) : 64;
-        double* Ajj = A + (size_t)j0 * lda + j0;
-        if (!g_first_block_done) potf2_64(s, Ajj, lda, jb, info, j0, batch, bs, is);     // (unless the preceding update factored it)
-        g_first_block_done = 0;
-        const int below = active_rows(n, extra, xtri, j0 + jb) - (j0 + jb);
-        if (below > 0) {
-            double* Apan = A + (size_t)j0 * lda + (j0 + jb);
-            trsm_64(s, Ajj, lda, jb, Apan, lda, below, batch, bs);
-            const int ncols = c0 + w1 - (j0 + jb);
-            if (ncols > 0) {
-                arm_fused_block(info, is, j0 + jb, ncols);
-                syrk_lower(s, Apan, lda, A + (size_t)(j0 + jb) * lda + (j0 + jb), lda, below, ncols, jb, batch, bs, -1, 0,
-                           xtri > 0 ? n + extra - (j0 + jb) : 0x7fffffff, j0);
-                g_fuse_next.info = nullptr;
-            }
-        }
-    }
-}
-
-static void factor_panel_rec(hipStream_t s, double* A, int lda, int n, int extra, int xtri, int c0, int w, int* info,
-                             int batch, long long bs, int is) {
-    if (w <= 64) {
-        double* Ajj = A + (size_t)c0 * lda + c0;
-        if (!g_first_block_done) potf2_64(s, Ajj, lda, w, info, c0, batch, bs, is);     // (unless the preceding update factored it)
-        g_first_block_done = 0;
-        const int below = active_rows(n, extra, xtri, c0 + w) - (c0 + w);
-        if (below > 0) trsm_64(s, Ajj, lda, w, A + (size_t)c0 * lda + (c0 + w), lda, below, batch, bs);
-        return;
-    }
-    int h = ((w / 2 + 63) / 64) * 64;                       // left width: a multiple of 64, at least half
-    if (h >= w) h = ((w - 1) / 64) * 64;
-    factor_panel_rec(s, A, lda, n, extra, xtri, c0, h, info, batch, bs, is);
-    const int c1 = c0 + h;
-    const int below = active_rows(n, extra, xtri, c1) - c1;
-    if (below > 0) {
-        arm_fused_block(info, is, c1, w - h);           // the update's tile (0, 0) holds the diagonal block the right half starts with
-        syrk_lower(s, A + (size_t)c0 * lda + c1, lda, A + (size_t)c1 * lda + c1, lda, below, w - h, h, batch, bs, -1, 0,
-                   xtri > 0 ? n + extra - c1 : 0x7fffffff, c0);
-        g_fuse_next.info = nullptr;
-    }
-    factor_panel_rec(s, A, lda, n, extra, xtri, c1, w - h, info, batch, bs, is);
-}
-
-// NMGP_STEP_STAMPS=<file>: per-step phase stamps of the critical workgroup (developer aid, tools/step_stamps.py)
-static long long* g_stamps = nullptr;        // device, 16 slots per 64-column step
-static int g_stamps_cap = 0;
-static const char* g_stamps_path = nullptr;
-
-static void factor_panel_fused(hipStream_t s, double* A, int lda, int n, int extra, int xtri, int c0, int w, int* info,
-                               int batch, long long bs, int is, bool leaf = false) {
-    if (!g_first_block_done)                                                       // the panel's first diagonal block
-        potf2_64(s, A + (size_t)c0 * lda + c0, lda, 64, info, c0, batch, bs, is);  // (unless the near update factored it)
-    g_first_block_done = 0;
-    const int nk = w / 64;
-    for (int k = 0; k < nk; ++k) {
-        const int ck = c0 + 64 * k;
-        const int m_act = active_rows(n, extra, xtri, ck + 64);
-        const int rows = m_act - (ck + 64);
-        if (rows <= 0) continue;                     // last block of the matrix and nothing below it
-        const int has_prev = k > 0, has_next = k + 1 < nk;
-        const int T = 1 + (rows > 64 ? cdiv_c(rows - 64, 128) : 0);     // workgroup 0: block row k + 1 alone
-        SyrkPlan pl;
-        const int u_m = m_act - (ck + 128), u_n = c0 + w - (ck + 128);
-        if (has_prev && u_m > 0 && u_n > 0) pl = syrk_plan(lda, lda, u_m, u_n, 64, 1, 0, true);
-        const int pre = (ck + 192 <= c0 + w) ? 1 : 0;            // block (k+2, k+2) lies inside the panel: see the P waves
-        if (pre) pl.kflags |= 128;                                // ... which own it: the update role skips that block
-        long long* st = (g_stamps && ck / 64 < g_stamps_cap) ? g_stamps + (size_t)(ck / 64) * 16 : nullptr;
-        // rows of L^-T that nobody has written yet in the columns this step touches first (see potrf_lower): row r of L^-T
-        // (absolute row n + extra + r) enters with step r / 64 of its panel; its column block k + 1 is first touched by the
-        // solve role of that step and of the next one, everything further right by the update role one step later
-        const int un_fresh = xtri > 0 ? n + extra + (has_prev ? ck - 64 : ck) : 0x7fffffff;
-        const int u_tri = xtri > 0 ? n + extra - 64 * NMGP_XTRI_SEED_BLOCKS : 0x7fffffff;
-        if (leaf && pl.tiles == 0 && !pre && nk == 2) {
-            if (k == 0)
-                NMGP_LAUNCH((k_panel_step<1, 4>), dim3((unsigned)(T * batch)), dim3(512), 0, s, A, lda, ck, 0, 1, m_act, c0 + w, bs, info,
-                            is, T, 0, 0, 0, 0, batch, 0, un_fresh, u_tri, st);
-            else
-                NMGP_LAUNCH((k_panel_step<2, 6>), dim3((unsigned)(T * batch)), dim3(512), 0, s, A, lda, ck, 1, 0, m_act, c0 + w, bs, info,
-                            is, T, 0, 0, 0, 0, batch, 0, un_fresh, u_tri, st);
-        } else {
-            NMGP_LAUNCH((k_panel_step<0, 2>), dim3((unsigned)((T + pl.tiles) * batch)), dim3(512), 0, s, A, lda, ck, has_prev, has_next, m_act,
-                        c0 + w, bs, info, is, T, pl.mrows, u_n, pl.kflags, pl.tiles, batch, pre, un_fresh, u_tri, st);
-        }
-    }
-}
-
-// panel schedule: NMGP_CHOL_PANEL = fused | rec | rl | auto (default)
-static int g_panel_mode = -1;      // 0 auto, 1 fused, 2 rec, 3 rl
-static int g_fused_max_batch = -1; // NMGP_CHOL_FUSED_MAX_BATCH: largest batch that takes the fused steps under auto; default:
-                                   // batch * n <= 73728 (measured: n = 6144: 8 chains 523 vs 503 evals/s, 16 chains 418 vs 616;
-                                   // n = 3072: 16 subjects 3211 vs 2729, 24 subjects 3563, 32 subjects 2877 vs 3714)
-
-static bool panel_takes_fused_steps(int n, int w, int lda, int batch) {
-    if (g_panel_mode < 0) {
-        const char* e = std::getenv("NMGP_CHOL_PANEL");
-        g_panel_mode = !e ? 0 : (std::strcmp(e, "fused") == 0 ? 1 : (std::strcmp(e, "rec") == 0 ? 2 : (std::strcmp(e, "rl") == 0 ? 3 : 0)));
-        if (const char* m = std::getenv("NMGP_CHOL_FUSED_MAX_BATCH")) g_fused_max_batch = std::atoi(m);
-    }
-    const bool can_fuse = w > 0 && (w % 64 == 0) && !g_precise && (lda % 2 == 0);
-    const bool small = g_fused_max_batch >= 0 ? batch <= g_fused_max_batch : (long long)batch * n <= 73728;
-    return can_fuse && (g_panel_mode == 1 || (g_panel_mode == 0 && small));
-}
-
-// Fused steps under a recursive split.  A fused step re-reads and re-writes ALL remaining columns of its panel (the delayed
-// K = 64 update): 1792 column-block passes per 512-wide panel against 768 for recursive halving.  For one matrix that is free --
-// a step's ~190 workgroups fit the 256 CUs in one round and the step is latency-bound (~25 us) -- but with 8 subjects a step of
-// the first panel is 720 workgroups at one per CU (118 KB of LDS) = three rounds, 72 us, bound by that traffic.  So the panel is
-// halved recursively (one K = w/2 update per level, ordinary update kernel with the next diagonal block fused) until the
-// pieces are `base` wide, and only those run as fused steps: base = 128 keeps recursive halving's 768 passes with 11 launches
-// per 512 columns instead of 23.  NMGP_CHOL_FUSED_BASE=<128|256|512|...>; auto: fused_base_width() below.
-static void factor_panel_rec(hipStream_t s, double* A, int lda, int n, int extra, int xtri, int c0, int w, int* info,
-                             int batch, long long bs, int is);
-
-static void factor_panel_fused_split(hipStream_t s, double* A, int lda, int n, int extra, int xtri, int c0, int w, int base,
-                                     int* info, int batch, long long bs, int is, bool leaf = false) {
-    if (w <= base) {
-        // leaf = the throughput schedule: 128-column pieces take the two leaf launches (k_panel_step<1>, <2>), a 64-column
-        // remainder the plain diagonal block + solve
-        if (leaf && w != 128) factor_panel_rec(s, A, lda, n, extra, xtri, c0, w, info, batch, bs, is);
-        else factor_panel_fused(s, A, lda, n, extra, xtri, c0, w, info, batch, bs, is, leaf);
-        return;
-    }
-    int h = ((w / 2 + 63) / 64) * 64;
-    if (h >= w) h = ((w - 1) / 64) * 64;
-    factor_panel_fused_split(s, A, lda, n, extra, xtri, c0, h, base, info, batch, bs, is, leaf);
-    const int c1 = c0 + h;
-    const int below = active_rows(n, extra, xtri, c1) - c1;
-    if (below > 0) {
-        arm_fused_block(info, is, c1, w - h);
-        syrk_lower(s, A + (size_t)c0 * lda + c1, lda, A + (size_t)c1 * lda + c1, lda, below, w - h, h, batch, bs, -1, 0,
-                   xtri > 0 ? n + extra - c1 : 0x7fffffff, c0);
-        g_fuse_next.info = nullptr;
-    }
-    factor_panel_fused_split(s, A, lda, n, extra, xtri, c1, w - h, base, info, batch, bs, is, leaf);
-}
-
-static int fused_base_width(int n, int extra, int xtri, int c0, int w, int batch) {
-    static const int env_base = [] {
-        const char* e = std::getenv("NMGP_CHOL_FUSED_BASE");
-        return e ? (std::atoi(e) / 64) * 64 : 0;
-    }();
-    if (env_base >= 64) return env_base;
-    // measured (MI355X, profiles/r03_fused_base.txt; evals/s at base 512 / 256 / 128): one chain 301 / 286 / 271; 4 chains 537 / 526 /
-    // 504; 8 chains 609 / 606 / 587; 8 subjects x N=1024 2935 / 2925 / 2779, value+gradient 1275 / 1338 / 1301; 16 subjects 3603 /
-    // 3828 / 3745; separable N=4096 D=5 3.92 / 4.01 / 4.12 ms, value+gradient 9.32 / 9.23 / 9.54 ms.  The K = 256 update a split
-    // inserts costs what the steps save until a step is well over two rounds of workgroups: 256 from 16 matrices on, and for
-    // gradient evaluations (twice the rows) from 5 matrices on.
-    (void)n; (void)extra; (void)c0;
-    if (w > 256 && (batch >= 16 || (xtri > 0 && batch >= 5))) return 256;
-    return w;
-}
-
-static void factor_panel(hipStream_t s, double* A, int lda, int n, int extra, int xtri, int c0, int w, int* info,
-                         int batch, long long bs, int is) {
-    const int rec_min_batch = 4;                 // smallest batch that takes the recursive panels
-    if (panel_takes_fused_steps(n, w, lda, batch))
-        factor_panel_fused_split(s, A, lda, n, extra, xtri, c0, w, fused_base_width(n, extra, xtri, c0, w, batch), info, batch, bs, is);
-    else if (g_panel_mode == 0 && batch >= rec_min_batch && w >= 128 && (w % 64 == 0) && (lda % 2 == 0) && !g_precise)
-        factor_panel_fused_split(s, A, lda, n, extra, xtri, c0, w, 128, info, batch, bs, is, true);
-    else if (g_panel_mode == 3 || (g_panel_mode != 2 && batch < rec_min_batch))
-        factor_panel_rl(s, A, lda, n, extra, xtri, c0, w, info, batch, bs, is);
-    else
-        factor_panel_rec(s, A, lda, n, extra, xtri, c0, w, info, batch, bs, is);
-}
-
 // Blocked Cholesky of the n x n lower triangle of A.  Below the matrix the same array may hold
 //   * `extra` dense rows R (rows n .. n+extra-1): on exit R L^-T (a right-hand side y becomes z = L^-1 y), and
 //   * `xtri` identity rows (rows n+extra .. n+extra+xtri-1, seeded by identity_rows()): on exit L^-T, from which
@@ -2308,54 +2151,208 @@ static void factor_panel(hipStream_t s, double* A, int lda, int n, int extra, in
 //     start the launch's last c1 - c0 rows ("fresh" rows: tri_row0 + tri_k0 onwards) from zero instead of loading them,
 //     and every later launch finds them written.  Every update call of a gradient factorisation therefore passes
 //     (tri_row0, tri_k0).
-// Look-ahead over two streams: after panel k is factored on `s`, only the NEXT panel's columns are updated on `s`
-// (so that panel k+1 can start at once) while the rest of the trailing matrix is updated on `s2`, concurrently with
-// the latency-bound 64-wide steps of panel k+1.  ev[] must hold at least 2 * ceil(n / nb1) + 1 events; s2 == nullptr
-// (or ev == nullptr) selects the plain single-stream order.
 // batch > 1 factors `batch` matrices of identical shape at once (matrix b at A + b * bstride, status word at
 // info + b * istride): every launch covers all of them, so the latency of the 64-wide steps is paid once per batch.
-struct HookScope {
-    const SyrkHook* prev;
-    explicit HookScope(const SyrkHook* h) : prev(g_hook) { g_hook = h; }
-    ~HookScope() { g_hook = prev; }
+//
+// One potrf_lower call: what is constant for it, and the one piece of state its launches hand to each other.
+struct Factorisation {
+    hipStream_t s, s2;           // panels and near updates on s; far updates of the look-ahead schedule on s2
+    double* A;
+    int lda, n, extra, xtri;
+    int* info;
+    int batch;
+    long long bs;
+    int is;
+    bool precise;
+    const SyrkHook* hook;
+    long long* stamps;           // StepStamps' device buffer, or nullptr
+    // the preceding update has already factored the next diagonal block (set by update(), taken by whichever panel routine
+    // runs next: every update that may set it is followed by the panel part that starts with that block)
+    bool block_done = false;
+
+    double* at(int row, int col) const { return A + (size_t)col * lda + row; }
+    // rows that take part when the factorisation has reached column `cend`: the n matrix rows, the `extra` dense rows
+    // (right-hand sides) and the first `cend` of the `xtri` identity rows (row r of L^-T is zero left of column r)
+    int active_rows(int cend) const { return n + extra + (cend < xtri ? cend : xtri); }
+    bool take_block_done() {
+        const bool done = block_done;
+        block_done = false;
+        return done;
+    }
+
+    // Trailing update: the factored columns [c0, c0 + k) applied to the columns [c1, c1 + ncols), all rows active at c0 + k.
+    // fuse_width: columns left in the panel part that starts at c1 when that part is factored NEXT on the same stream (a full
+    // 64-column block is what the fused form factors: the launch's tile (0, 0) holds that diagonal block); 0: nobody asks.
+    void update(hipStream_t st, int c0, int k, int c1, int ncols, int fuse_width) {
+        const bool fuse = fuse_width >= 64 && !precise;
+        const bool done = syrk_lower(st, at(c1, c0), lda, at(c1, c1), lda, active_rows(c0 + k) - c1, ncols, k, batch, bs, -1, 0,
+                                     xtri > 0 ? n + extra - c1 : kNoTriRows, c0, fuse ? info : nullptr, is, c1, hook);
+        if (fuse) block_done = done;
+    }
+
+    // diagonal block (at most 64 columns) + solve of the rows below it
+    void block_solve(int c0, int w) {
+        if (!take_block_done()) potf2_64(s, at(c0, c0), lda, w, info, c0, batch, bs, is, precise);
+        trsm_64(s, at(c0, c0), lda, w, at(c0 + w, c0), lda, active_rows(c0 + w) - (c0 + w), batch, bs, precise);
+    }
+
+    // columns [c0, c0 + w), w a multiple of 64, as fused steps: one k_panel_step launch per 64 columns
+    void fused_steps(int c0, int w, bool leaf) {
+        if (!take_block_done()) potf2_64(s, at(c0, c0), lda, 64, info, c0, batch, bs, is, precise);   // the first diagonal block
+        const int nk = w / 64;
+        for (int k = 0; k < nk; ++k) {
+            const int ck = c0 + 64 * k;
+            const int m_act = active_rows(ck + 64);
+            const int rows = m_act - (ck + 64);
+            if (rows <= 0) continue;                     // last block of the matrix and nothing below it
+            const int has_prev = k > 0, has_next = k + 1 < nk;
+            const int T = 1 + (rows > 64 ? cdiv_c(rows - 64, 128) : 0);     // workgroup 0: block row k + 1 alone
+            SyrkPlan pl;
+            const int u_m = m_act - (ck + 128), u_n = c0 + w - (ck + 128);
+            if (has_prev && u_m > 0 && u_n > 0) pl = syrk_plan(lda, lda, u_m, u_n, 64, 1, 0, true);
+            const int pre = (ck + 192 <= c0 + w) ? 1 : 0;            // block (k+2, k+2) lies inside the panel: see the P waves
+            if (pre) pl.kflags |= 128;                                // ... which own it: the update role skips that block
+            long long* st = stamps ? stamps + (size_t)(ck / 64) * 16 : nullptr;
+            // rows of L^-T that nobody has written yet in the columns this step touches first (see above): row r of L^-T
+            // (absolute row n + extra + r) enters with step r / 64 of its panel; its column block k + 1 is first touched by the
+            // solve role of that step and of the next one, everything further right by the update role one step later
+            const int un_fresh = xtri > 0 ? n + extra + (has_prev ? ck - 64 : ck) : kNoTriRows;
+            const int u_tri = xtri > 0 ? n + extra - 64 * NMGP_XTRI_SEED_BLOCKS : kNoTriRows;
+            if (leaf && pl.tiles == 0 && !pre && nk == 2) {
+                if (k == 0)
+                    NMGP_LAUNCH((k_panel_step<1, 4>), dim3((unsigned)(T * batch)), dim3(512), 0, s, A, lda, ck, 0, 1, m_act, c0 + w, bs, info,
+                                is, T, 0, 0, 0, 0, batch, 0, un_fresh, u_tri, st);
+                else
+                    NMGP_LAUNCH((k_panel_step<2, 6>), dim3((unsigned)(T * batch)), dim3(512), 0, s, A, lda, ck, 1, 0, m_act, c0 + w, bs, info,
+                                is, T, 0, 0, 0, 0, batch, 0, un_fresh, u_tri, st);
+            } else {
+                NMGP_LAUNCH((k_panel_step<0, 2>), dim3((unsigned)((T + pl.tiles) * batch)), dim3(512), 0, s, A, lda, ck, has_prev, has_next, m_act,
+                            c0 + w, bs, info, is, T, pl.mrows, u_n, pl.kflags, pl.tiles, batch, pre, un_fresh, u_tri, st);
+            }
+        }
+    }
+
+    // right-looking 64-wide steps (each step updates the rest of the panel with K = 64)
+    void panel_rl(int c0, int w) {
+        for (int j0 = c0; j0 < c0 + w; j0 += 64) {
+            const int jb = (c0 + w - j0 < 64) ? (c0 + w - j0) : 64;
+            block_solve(j0, jb);
+            update(s, j0, jb, j0 + jb, c0 + w - (j0 + jb), c0 + w - (j0 + jb));
+        }
+    }
+
+    // Recursive halving (left part, ONE update of the right part with K = left width, right part) down to pieces of at most
+    // `base` columns.  The leaf rule:
+    enum Leaf {
+        kBlockSolve,     // base = 64: diagonal block + solve
+        kFusedSteps,     // pieces of `base` columns run as fused steps
+        kLeaf128         // the throughput schedule, base = 128: 128-column pieces take the two leaf launches (k_panel_step<1>,
+    };                   // <2>), a 64-column remainder the plain diagonal block + solve
+    void panel_halving(int c0, int w, int base, Leaf leaf) {
+        if (w <= base) {
+            if (leaf == kBlockSolve || (leaf == kLeaf128 && w != 128)) block_solve(c0, w);
+            else fused_steps(c0, w, leaf == kLeaf128);
+            return;
+        }
+        int h = ((w / 2 + 63) / 64) * 64;                       // left width: a multiple of 64, at least half
+        if (h >= w) h = ((w - 1) / 64) * 64;
+        panel_halving(c0, h, base, leaf);
+        update(s, c0, h, c0 + h, w - h, w - h);                 // tile (0, 0) holds the diagonal block the right part starts with
+        panel_halving(c0 + h, w - h, base, leaf);
+    }
+
+    // Factor the panel of columns [c0, c0 + w) (already up to date) together with all active rows below it.  The schedules:
+    //  * right-looking 64-wide steps: shortest critical path of the three-launch forms, for a single matrix, where every
+    //    launch is latency-bound anyway;
+    //  * recursive halving: touches the panel's C entries log2(w/64) times instead of w/128 times and runs only a quarter of
+    //    the update flop at K = 64 (HBM-bound at 8 flop/byte), the rest at K = 128 / 256: for batches, where the launches are
+    //    throughput-bound;
+    //  * fused steps (k_panel_step: ONE launch per 64 columns) under a recursive split.  A fused step re-reads and re-writes ALL
+    //    remaining columns of its panel (the delayed K = 64 update): 1792 column-block passes per 512-wide panel against 768
+    //    for recursive halving.  For one matrix that is free -- a step's ~190 workgroups fit the 256 CUs in one round and the
+    //    step is latency-bound (~25 us) -- but with 8 subjects a step of the first panel is 720 workgroups at one per CU (118 KB
+    //    of LDS) = three rounds, 72 us, bound by that traffic.  So the panel is halved recursively (one K = w/2 update per level,
+    //    ordinary update kernel with the next diagonal block fused) until the pieces are `base` wide, and only those run as
+    //    fused steps: base = 128 keeps recursive halving's 768 passes with 11 launches per 512 columns instead of 23.
+    void panel(int c0, int w) {
+        const Switches& sw = switches();
+        // the matrix-core panel kernels: whole 64-column blocks, 16-byte loads, diagonal blocks with inverted 16x16 blocks
+        const bool mfma_ok = w > 0 && (w % 64 == 0) && (lda % 2 == 0) && !precise;
+        // latency regime, auto: batch * n <= 73728 (measured: n = 6144: 8 chains 523 vs 503 evals/s, 16 chains 418 vs 616;
+        // n = 3072: 16 subjects 3211 vs 2729, 24 subjects 3563, 32 subjects 2877 vs 3714)
+        const bool small = sw.fused_max_batch >= 0 ? batch <= sw.fused_max_batch : (long long)batch * n <= 73728;
+        const int rec_min_batch = 4;                 // smallest batch that takes the recursive panels
+        if (mfma_ok && (sw.panel == Switches::kFused || (sw.panel == Switches::kAuto && small)))
+            panel_halving(c0, w, fused_base(w), kFusedSteps);
+        else if (mfma_ok && sw.panel == Switches::kAuto && batch >= rec_min_batch && w >= 128)
+            panel_halving(c0, w, 128, kLeaf128);
+        else if (sw.panel == Switches::kRl || (sw.panel != Switches::kRec && batch < rec_min_batch))
+            panel_rl(c0, w);
+        else
+            panel_halving(c0, w, 64, kBlockSolve);
+    }
+    int fused_base(int w) const {
+        if (switches().fused_base >= 64) return switches().fused_base;
+        // measured (MI355X, profiles/r03_fused_base.txt; evals/s at base 512 / 256 / 128): one chain 301 / 286 / 271; 4 chains 537 / 526 /
+        // 504; 8 chains 609 / 606 / 587; 8 subjects x N=1024 2935 / 2925 / 2779, value+gradient 1275 / 1338 / 1301; 16 subjects 3603 /
+        // 3828 / 3745; separable N=4096 D=5 3.92 / 4.01 / 4.12 ms, value+gradient 9.32 / 9.23 / 9.54 ms.  The K = 256 update a split
+        // inserts costs what the steps save until a step is well over two rounds of workgroups: 256 from 16 matrices on, and for
+        // gradient evaluations (twice the rows) from 5 matrices on.
+        if (w > 256 && (batch >= 16 || (xtri > 0 && batch >= 5))) return 256;
+        return w;
+    }
+
+    // All panels of nb1 columns.  Look-ahead over two streams: after panel k is factored on `s`, only the NEXT panel's columns
+    // are updated on `s` (so that panel k+1 can start at once) while the rest of the trailing matrix is updated on `s2`,
+    // concurrently with the latency-bound 64-wide steps of panel k+1.  ev[] must hold at least 2 * ceil(n / nb1) + 1 events;
+    // s2 == nullptr (or ev == nullptr) selects the plain single-stream order.
+    void run(int nb1, hipEvent_t* ev) {
+        // look-ahead pays where the panel steps are latency-bound: one matrix or a handful of subjects (the batched throughput
+        // path keeps every kernel exclusive); NMGP_CHOL_LA_MAX_BATCH moves the limit
+        const bool la = (s2 != nullptr && ev != nullptr && n > 2 * nb1 && batch <= switches().la_max_batch && !precise);
+        if (!la) {
+            for (int c0 = 0; c0 < n; c0 += nb1) {
+                const int w1 = (n - c0 < nb1) ? (n - c0) : nb1;
+                const int c1 = c0 + w1;
+                panel(c0, w1);
+                update(s, c0, w1, c1, n - c1, n - c1 < nb1 ? n - c1 : nb1);
+            }
+            return;
+        }
+        // everything queued on s so far (covariance build, right-hand side row) must be visible to s2
+        hipEventRecord(ev[0], s);
+        hipStreamWaitEvent(s2, ev[0], 0);
+        int k = 0;
+        bool prevB = false;
+        for (int c0 = 0; c0 < n; c0 += nb1, ++k) {
+            const int w1 = (n - c0 < nb1) ? (n - c0) : nb1;
+            const int c1 = c0 + w1;
+            const int w1n = (c1 < n) ? ((n - c1 < nb1) ? (n - c1) : nb1) : 0;
+            const int c2 = c1 + w1n;
+            hipEvent_t evPanel = ev[1 + 2 * k], evB = ev[2 + 2 * k];
+            panel(c0, w1);
+            if (c1 >= n) break;
+            // the previous far update also wrote the next panel's columns
+            if (prevB) hipStreamWaitEvent(s, ev[2 + 2 * (k - 1)], 0);
+            update(s, c0, w1, c1, w1n, w1n);                    // near: the next panel's columns, its first block fused
+            // the far update starts only when the NEAR one is through: started together they share the chip and the near
+            // update -- which the next panel waits for -- takes 2-4x as long (96-227 us instead of ~45 in the kernel trace)
+            hipEventRecord(evPanel, s);
+            prevB = false;
+            if (c2 < n) {
+                hipStreamWaitEvent(s2, evPanel, 0);
+                update(s2, c0, w1, c2, n - c2, 0);              // far: everything right of the next panel
+                hipEventRecord(evB, s2);
+                prevB = true;
+            }
+        }
+        // the caller continues on s: it must see the last far update
+        if (prevB) hipStreamWaitEvent(s, ev[2 + 2 * (k - 1)], 0);
+    }
 };
 
 void potrf_lower(hipStream_t s, hipStream_t s2, hipEvent_t* ev, double* A, int lda, int n, int extra, int xtri,
                  int nb1, int* info, int batch, long long bstride, int istride, const SyrkHook* hook, int precise) {
-    HookScope hs(hook);
-    struct StampScope {          // allocate before, dump after the factorisation (synchronises: developer aid only)
-        hipStream_t s;
-        int nsteps;
-        StampScope(hipStream_t st, int n) : s(st), nsteps((n + 63) / 64) {
-            static const char* path = std::getenv("NMGP_STEP_STAMPS");
-            g_stamps_path = path;
-            if (!path) return;
-            if (g_stamps_cap < nsteps) {
-                if (g_stamps) hipFree(g_stamps);
-                if (hipMalloc((void**)&g_stamps, (size_t)nsteps * 16 * sizeof(long long)) != hipSuccess) g_stamps = nullptr;
-                g_stamps_cap = g_stamps ? nsteps : 0;
-            }
-            if (g_stamps) hipMemsetAsync(g_stamps, 0, (size_t)g_stamps_cap * 16 * sizeof(long long), s);
-        }
-        ~StampScope() {
-            if (!g_stamps_path || !g_stamps) return;
-            std::vector<long long> h((size_t)nsteps * 16);
-            hipStreamSynchronize(s);
-            hipMemcpy(h.data(), g_stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
-            if (FILE* f = std::fopen(g_stamps_path, "w")) {
-                for (int k = 0; k < nsteps; ++k) {
-                    for (int j = 0; j < 9; ++j) std::fprintf(f, "%lld ", h[(size_t)k * 16 + j]);
-                    std::fprintf(f, "\n");
-                }
-                std::fclose(f);
-            }
-        }
-    } stamp_scope(s, n);
-    struct PreciseScope {
-        int prev;
-        explicit PreciseScope(int p) : prev(g_precise) { g_precise = p; }
-        ~PreciseScope() { g_precise = prev; }
-    } ps(precise);
     // auto panel width (512 / 1024 / 2048; 64 chains of n = 6144: 673 / 716 / 728 evals/s): a wider panel halves the passes over the trailing matrix (each tile's C load / store and launch tail) and
     // pays with one more K = 512 level inside the panel; +1.5 % for 32 chains of n = 6144, +2 % for 64 subjects of
     // n = 3072, slower for one chain or 8 subjects; with the L^-T rows (gradient) 2048 wins since their zero k-panels are skipped
@@ -2364,64 +2361,10 @@ void potrf_lower(hipStream_t s, hipStream_t s2, hipEvent_t* ev, double* A, int l
         nb1 = (batch >= 16 && n >= 4096) ? 2048         // (n = 4096: 80 blocks of the batched separable model 418.9 -> 430.6 evals/s)
               : (((batch >= 4 && n >= 4096) || (batch >= 32 && n >= 2048)) && (long long)batch * n > 73728) ? 1024 : 512;
     // (batches small enough for the fused panel steps keep 512: separable N = 4096, D = 5: 4.39 ms against 4.55 with 1024)
-    const int is = istride;
-    const long long bs = bstride;
-    // look-ahead pays where the panel steps are latency-bound: one matrix or a handful of subjects (the batched throughput
-    // path keeps every kernel exclusive); NMGP_CHOL_LA_MAX_BATCH moves the limit
-    static const int la_max_batch = [] {
-        const char* e = std::getenv("NMGP_CHOL_LA_MAX_BATCH");
-        return e ? std::atoi(e) : 16;
-    }();
-    const bool la = (s2 != nullptr && ev != nullptr && n > 2 * nb1 && batch <= la_max_batch && !precise);
-    if (!la) {
-        for (int c0 = 0; c0 < n; c0 += nb1) {
-            const int w1 = (n - c0 < nb1) ? (n - c0) : nb1;
-            factor_panel(s, A, lda, n, extra, xtri, c0, w1, info, batch, bs, is);
-            const int c1 = c0 + w1;
-            if (c1 < n) {
-                arm_fused_block(info, is, c1, n - c1 < nb1 ? n - c1 : nb1);
-                syrk_lower(s, A + (size_t)c0 * lda + c1, lda, A + (size_t)c1 * lda + c1, lda,
-                           active_rows(n, extra, xtri, c1) - c1, n - c1, w1, batch, bs, -1, 0,
-                           xtri > 0 ? n + extra - c1 : 0x7fffffff, c0);
-                g_fuse_next.info = nullptr;
-            }
-        }
-        return;
-    }
-    // everything queued on s so far (covariance build, right-hand side row) must be visible to s2
-    hipEventRecord(ev[0], s);
-    hipStreamWaitEvent(s2, ev[0], 0);
-    int k = 0;
-    bool prevB = false;
-    for (int c0 = 0; c0 < n; c0 += nb1, ++k) {
-        const int w1 = (n - c0 < nb1) ? (n - c0) : nb1;
-        const int c1 = c0 + w1;
-        const int w1n = (c1 < n) ? ((n - c1 < nb1) ? (n - c1) : nb1) : 0;
-        const int c2 = c1 + w1n;
-        hipEvent_t evPanel = ev[1 + 2 * k], evB = ev[2 + 2 * k];
-        factor_panel(s, A, lda, n, extra, xtri, c0, w1, info, batch, bs, is);
-        if (c1 >= n) break;
-        // the previous far update also wrote the next panel's columns
-        if (prevB) hipStreamWaitEvent(s, ev[2 + 2 * (k - 1)], 0);
-        const int mact = active_rows(n, extra, xtri, c1);
-        arm_fused_block(info, is, c1, w1n);
-        syrk_lower(s, A + (size_t)c0 * lda + c1, lda, A + (size_t)c1 * lda + c1, lda, mact - c1, w1n, w1, batch, bs, -1,
-                   0, xtri > 0 ? n + extra - c1 : 0x7fffffff, c0);
-        g_fuse_next.info = nullptr;
-        // the far update starts only when the NEAR one is through: started together they share the chip and the near
-        // update -- which the next panel waits for -- takes 2-4x as long (96-227 us instead of ~45 in the kernel trace)
-        hipEventRecord(evPanel, s);
-        prevB = false;
-        if (c2 < n) {
-            hipStreamWaitEvent(s2, evPanel, 0);
-            syrk_lower(s2, A + (size_t)c0 * lda + c2, lda, A + (size_t)c2 * lda + c2, lda, mact - c2, n - c2, w1, batch,
-                       bs, -1, 0, xtri > 0 ? n + extra - c2 : 0x7fffffff, c0);
-            hipEventRecord(evB, s2);
-            prevB = true;
-        }
-    }
-    // the caller continues on s: it must see the last far update
-    if (prevB) hipStreamWaitEvent(s, ev[2 + 2 * (k - 1)], 0);
+    const int nsteps = (n + 63) / 64;
+    Factorisation f{s, s2, A, lda, n, extra, xtri, info, batch, bstride, istride, precise != 0, hook, g_step_stamps.begin(s, nsteps)};
+    f.run(nb1, ev);
+    g_step_stamps.dump(s, nsteps);
 }
 
 // Seed of the rows that turn into X = L^-T during a gradient evaluation (rows row0 + pad .. row0 + pad + n - 1 of the

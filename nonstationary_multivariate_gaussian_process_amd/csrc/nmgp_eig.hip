@@ -308,8 +308,7 @@ int kron_chol_loglik(nmgp_ctx* c, EigWork& w, double sigma2, bool want_grad, dou
         NmgpStage sp(c, NMGP_STAGE_CHOL);
         set_row(s, S, ld, N, yt, N, M, bs, N);
         if (want_grad) identity_rows(s, S, ld, N + 1, N, xpad, M, bs);
-        potrf_lower(s, c->stream2, nmgp_chol_events(c, N), S, ld, N, want_grad ? 1 + xpad : 1, want_grad ? N : 0,
-                    c->chol_nb1, info, M, bs, 1, nmgp_syrk_hook(c));
+        nmgp_potrf(c, S, ld, N, want_grad ? 1 + xpad : 1, want_grad ? N : 0, info, M, bs, 1);
         get_row(s, S, ld, N, z, N, M, bs, N);
     }
     {
@@ -667,8 +666,7 @@ int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9]
         NmgpStage sp(c, NMGP_STAGE_CHOL);
         set_row(s, S, ld, N, yt, N, BM, bs, N);
         if (want_grad) identity_rows(s, S, ld, N + 1, N, xpad, BM, bs);
-        potrf_lower(s, c->stream2, nmgp_chol_events(c, N), S, ld, N, want_grad ? 1 + xpad : 1, want_grad ? N : 0, c->chol_nb1, info,
-                    BM, bs, 1, nmgp_syrk_hook(c));
+        nmgp_potrf(c, S, ld, N, want_grad ? 1 + xpad : 1, want_grad ? N : 0, info, BM, bs, 1);
         get_row(s, S, ld, N, z, N, BM, bs, N);
     }
     {
@@ -1206,8 +1204,7 @@ extern "C" int nmgp_predict_svc(nmgp_ctx* c, const double* pars, const double hy
         set_row(s, c->d_S, ld, n, c->d_y, n, 1, 0, 0);
         svc_crosscov_rows(s, c->d_x, c->d_ell, c->d_Lv, N, M, d_xs + s0, tl_star + s0, Ls + (size_t)s0 * T, Sc, c->d_S, ld, n + 1);
         if (c->chol_algo == 1) {
-            potrf_lower(s, c->stream2, nmgp_chol_events(c, n), c->d_S, ld, n, 1 + E, 0, c->chol_nb1, c->d_info, 1, 0, 0,
-                        nmgp_syrk_hook(c));
+            nmgp_potrf(c, c->d_S, ld, n, 1 + E, 0, c->d_info);
         } else {
             // comparison path (NMGP_CHOL=rocsolver): library factorisation, the extra rows solved as right-hand sides X L^T = R
             const double one = 1.0;
@@ -1288,7 +1285,7 @@ static int chol_predict(nmgp_ctx* c, EigWork& w, double sigma2, int mode, const 
         sep_blocks(s, c->d_K, w.wB, w.sig2, N, M, Sbuf, ld, bs);
         set_row(s, Sbuf, ld, N, yt, N, M, bs, N);
         cols_to_rows(s, KX + (size_t)s0 * N, N, Sc, Sbuf, ld, N + 1, M, bs);
-        potrf_lower(s, c->stream2, nmgp_chol_events(c, N), Sbuf, ld, N, 1 + Sc, 0, c->chol_nb1, info, M, bs, 1, nmgp_syrk_hook(c));
+        nmgp_potrf(c, Sbuf, ld, N, 1 + Sc, 0, info, M, bs, 1);
         for (int p = 0; p < M; ++p)
             pred_rows_reduce(s, Sbuf + (size_t)p * bs, ld, N, N + 1, N, Sc, part, dots + (size_t)p * S + s0, sqs + (size_t)p * S + s0);
     }

@@ -186,8 +186,10 @@ int nmgp_ensure_S(nmgp_ctx* c);
 // Cholesky of the n x n lower triangle (custom gfx950 factorisation or rocSOLVER, per ctx->chol_algo); `extra` rows
 // below the matrix are carried along by the custom path only (must be 0 for rocSOLVER).
 int nmgp_chol_factor(nmgp_ctx* c, double* A, int ld, int n, int extra, int* d_info);
+// the custom factorisation (potrf_lower) on the context's streams, with its look-ahead events, panel width and SYRK hook
+void nmgp_potrf(nmgp_ctx* c, double* A, int ld, int n, int extra, int xtri, int* info, int batch = 1, long long bstride = 0,
+                int istride = 0, int precise = 0);
 bool nmgp_poison();
-hipEvent_t* nmgp_chol_events(nmgp_ctx* c, int n);
 struct NmgpStage {   // RAII HIP-event timer of one stage on the context's stream (or on an explicit stream)
     nmgp_ctx* c; int stage; hipStream_t stream; hipEvent_t e0 = nullptr, e1 = nullptr;
     NmgpStage(nmgp_ctx* ctx, int st);
@@ -266,7 +268,6 @@ struct PriorStreamScope {
 };
 
 // ---- kernel launchers (nmgp_kernels.hip) -------------------------------------------------------
-const SyrkHook* nmgp_syrk_hook(nmgp_ctx* c);
 
 namespace nmgpk {
 
@@ -407,8 +408,11 @@ void sep_adjoint_b(hipStream_t s, const double* x, const double* ell, const doub
                    int small_per, int M, const double* C, int N, double* part, double* g, int B);
 void two_col_rhs_b(hipStream_t s, const double* pars, long long P, double mu_a, double mu_b, int N, double* R, int B);
 // ---- nmgp_chol.hip ----
-void syrk_lower(hipStream_t s, const double* A, int lda, double* C, int ldc, int mrows, int ncols, int K, int batch,
-                long long bstride, long long cstride = -1, int ktri = 0, int tri_row0 = 0x7fffffff, int tri_k0 = 0);
+// C -= A A^T on the lower trapezoid.  finfo / fistride / goff: the launch also factors the diagonal block in its tile (0, 0) where
+// its shape allows (returned); hook: per-launch profiling.  Defaults: neither.
+bool syrk_lower(hipStream_t s, const double* A, int lda, double* C, int ldc, int mrows, int ncols, int K, int batch,
+                long long bstride, long long cstride = -1, int ktri = 0, int tri_row0 = 0x7fffffff, int tri_k0 = 0,
+                int* finfo = nullptr, int fistride = 0, int goff = 0, const SyrkHook* hook = nullptr);
 // the structured value path's inverse SYRK (k_syrk_schur): -A^-1 = -X X^T (X = L_A^-T: N x N upper triangular, rows
 // xoff.. of A's buffer) is not stored; each tile writes the Sigma' entries it determines (and the diagonal tiles y') straight
 // from its accumulators.  Per chain z: X, S and u at z * bstride, z * bstride, z * N; x, y of subject z / cps.
@@ -429,10 +433,6 @@ struct SchurEpi {
 };
 int syrk_schur(hipStream_t s, const double* X, int lda, int N, int M, int batch, const SchurEpi& e);
 void identity_rows(hipStream_t s, double* A, int lda, int row0, int n, int pad, int batch = 1, long long bstride = 0);
-void potf2_64(hipStream_t s, double* A, int lda, int nb, int* info, int goff, int batch, long long bstride,
-              int istride);
-void trsm_64(hipStream_t s, const double* L, int ldl, int nb, double* A, int lda, int rows, int batch,
-             long long bstride);
 void set_row(hipStream_t s, double* A, int lda, int row, const double* v, int n, int batch, long long bstride,
              long long vstride, int cps = 1);
 void get_row(hipStream_t s, const double* A, int lda, int row, double* v, int n, int batch, long long bstride,
