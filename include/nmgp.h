@@ -264,6 +264,35 @@ int nmgp_predict_sep(nmgp_ctx* ctx, const double* pars, const double hyper[9], c
 int nmgp_predict_sta(nmgp_ctx* ctx, const double* pars, const double* xs, int S, double* mean,
                      double* var);
 
+/* ---- posterior-draw prediction (prediction.py:1265-1398 and :1038-1262) ---------------------- */
+/* The nonseparable predictor for H parameter vectors (posterior draws) of the resident subject at S new inputs, in batched
+ * launch sequences.  Per draw h and new input s: the latent curves are regressed onto xs_s under their RBF priors, noise of the
+ * conditional variance is added (z: [H,S,1+T] standard normals, slot 0 for tilde_l*, 1..T for L*; NULL = zeros, the conditional
+ * mean), and mean / var [H,S,M] of y follow from the draw's covariance as in nmgp_predict_svc.  y* = mean + sqrt(var) z_y is the
+ * caller's.
+ *   constrained = 1 : the `predsample` family (:1300-1308): the regression runs on the CONSTRAINED L_vecs (exp applied on the
+ *                     diagonal slots) and the sampled vector enters vec2lowtriangle with no exp afterwards;
+ *   constrained = 0 : the `predmap_*_sampling` family (:1128-1137): the regression runs on the unconstrained uL_vecs, exp is
+ *                     applied on the diagonal slots after the noise; with z = NULL this is nmgp_predict_svc's predictor.
+ *   star_in         : [H,S,1+T] starred values (tilde_l*, the T slots of L* as they enter vec2lowtriangle) to use instead of
+ *                     regressing; z must then be NULL (NMGP_E_STATE otherwise).  star_out (optional): the values used.
+ * One conditional variance per prior, (alpha^2 + 1e-6) - proj . k, serves all T slots; a value < 0 is replaced by 1e-6
+ * (settings.precision), as is a predictive variance <= 0.
+ * status [H] (optional) follows nmgp_svc_batch_fetch: 0 ok, k > 0 the draw's covariance is not positive definite (leading minor
+ * k), NMGP_NUM_NAN; such a draw's rows of mean / var are NaN and the call still returns 0.
+ * The draws go through in chunks of B: one batched covariance build and one batched blocked Cholesky per chunk and grid slice,
+ * with y and the (grid points x M) cross-covariance rows of each draw's own starred values riding below each matrix; more than
+ * MN riding rows go through in slices of MN / M grid points.  A batch of draws gives the bits of the same draws one call each.
+ * Device workspace: B (MN + 1 + min(S M, MN)) MN doubles for the factorisations + 2 N S for the projections + O(B (P + S (T + M))),
+ * independent of H.  B = what keeps the factorisation buffers below NMGP_PREDSAMPLE_SLAB_GB (environment, default 16), at most
+ * 64; NMGP_PREDSAMPLE_CHUNK overrides.  The workspace is the entry's own (kept until nmgp_set_data / nmgp_ctx_destroy): the
+ * call invalidates nothing -- the resident parameters, a pending batched evaluation, its gradients and a begun trajectory stay
+ * valid.  It synchronises the context's stream.  Runs on the custom factorisation only (NMGP_E_UNSUPPORTED under
+ * NMGP_CHOL=rocsolver). */
+int nmgp_predsample_svc(nmgp_ctx* ctx, const double* pars /*[H,P]*/, int H, const double hyper[8], const double* xs /*[S]*/,
+                        int S, int constrained, const double* z, const double* star_in, double* mean, double* var,
+                        double* star_out, int* status);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Per-stage HIP-event timing on the context's stream (bench.py roofline figures).  Stages: */
 enum {

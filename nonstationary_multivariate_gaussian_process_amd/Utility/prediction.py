@@ -5,7 +5,11 @@ In scope: ``point_predmap_inhomogeneous`` (
 ``pointwise_predmap_S`` / ``test_predmap_S`` (:1566-1638).  The reference rebuilds and eigendecomposes the full
 MN x MN covariance for every grid point; here all grid points share ONE Cholesky factor on the GPU and the
 cross-covariances are solved as one multi-right-hand-side triangular solve (nmgp_predict_*).
-The stochastic ``*_sampling`` / ``predsample*`` and the Hadamard variants are out of scope (no parity target).
+The nonseparable posterior-draw families (``*_predsample_inhomogeneous``, ``*_predmap_inhomogeneous_sampling``) live in
+``nonstationary_multivariate_gaussian_process_amd.predsample`` (one batched device call for all draws and grid points) and are
+served under this module's name only with ``NMGP_PREDSAMPLE=1`` in the environment: by default these names keep resolving to the
+user's checkout, as every name outside the mirrored path does.  The separable / stationary ``predsample`` variants and the
+Hadamard variants are out of scope (no parity target).
 """
 import numpy as np
 import torch
@@ -108,5 +112,8 @@ def test_predmap_S(tilde_l, tilde_sigma, uL_vec, tilde_sigma2_err, Y, x, test_x,
 
 def __getattr__(name):
     """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py)."""
+    from .. import predsample
+    if name in predsample.NAMES and predsample.enabled():
+        return getattr(predsample, name)
     from . import _overlay
     return _overlay.module_getattr(__name__, name)

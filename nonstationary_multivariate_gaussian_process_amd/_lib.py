@@ -78,6 +78,7 @@ SIGNATURES = {
     "nmgp_predict_svc": (I, [V, P, P, P, I, P, P, P]),
     "nmgp_predict_sep": (I, [V, P, P, P, I, P, P]),
     "nmgp_predict_sta": (I, [V, P, P, I, P, P]),
+    "nmgp_predsample_svc": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_profile_enable": (I, [V, I]),
     "nmgp_profile_read": (I, [V, P, c_ll_p]),
     "nmgp_profile_reset": (I, [V]),
@@ -555,6 +556,40 @@ class Context:
         mean, var = np.empty((S, self.M)), np.empty((S, self.M))
         self.check(self.lib.nmgp_predict_sta(self.h, ptr(pars), ptr(xs), S, ptr(mean), ptr(var)))
         return mean, var
+
+    def predsample_svc(self, pars_hist, hyper, xs, z=None, star=None, constrained=True):
+        """Posterior-draw prediction: H parameter vectors pars_hist [H, P] of the resident subject at the new inputs xs [S].
+        z [H, S, 1+T]: standard normals of the latent regression (None: the conditional means); star [H, S, 1+T]: starred values
+        (tilde_l*, the T slots of L*) to use instead of regressing (z must then be None).  constrained=True is the `predsample`
+        family's regression on the constrained L_vecs, False the `predmap_*_sampling` family's on uL_vecs (nmgp.h).
+        Returns (mean [H, S, M], var [H, S, M], star [H, S, 1+T], status [H]); a draw with non-zero status has NaN rows."""
+        pars = as_f64(pars_hist)
+        if pars.ndim == 1:
+            pars = pars[None]
+        P_ = self.N * (1 + self.T) + 1
+        if pars.ndim != 2 or pars.shape[1] != P_:
+            raise NmgpError("draws must be [H, P=%d], got %s" % (P_, pars.shape))
+        hyper, xs = as_f64(hyper), as_f64(xs).reshape(-1)
+        H, S = pars.shape[0], xs.shape[0]
+        if z is not None and star is not None:
+            raise NmgpError("star= replaces the regression: z must be None")
+        za = sa = None
+        for name, a in (("z", z), ("star", star)):
+            if a is not None:
+                a = as_f64(a)
+                if a.shape != (H, S, 1 + self.T):
+                    raise NmgpError("%s must be [H=%d, S=%d, 1+T=%d], got %s" % (name, H, S, 1 + self.T, a.shape))
+                if name == "z":
+                    za = a
+                else:
+                    sa = a
+        mean, var = np.empty((H, S, self.M)), np.empty((H, S, self.M))
+        star_out = np.empty((H, S, 1 + self.T))
+        status = np.zeros(H, dtype=np.int32)
+        self.check(self.lib.nmgp_predsample_svc(self.h, ptr(pars), H, ptr(hyper), ptr(xs), S, int(bool(constrained)), ptr(za),
+                                                ptr(sa), ptr(mean), ptr(var), ptr(star_out),
+                                                status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return mean, var, star_out, status
 
     # -- measurement ----------------------------------------------------------------------------
     def profile_enable(self, on=True):

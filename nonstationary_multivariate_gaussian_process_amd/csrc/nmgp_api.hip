@@ -167,6 +167,9 @@ static void free_subject(nmgp_ctx* c) {
         *p = nullptr;
     }
     c->S_cap = c->K_cap = c->part_cap = 0;
+    if (c->ps_buf) hipFree(c->ps_buf);       // workspace of nmgp_predsample_svc: sized for the subject
+    c->ps_buf = nullptr;
+    c->ps_cap = 0;
     free_priors(c);
     {
         double** bp[] = {&c->b_pars, &c->b_ell, &c->b_Lv, &c->b_S, &c->b_z, &c->b_R, &c->b_scal, &c->b_q,

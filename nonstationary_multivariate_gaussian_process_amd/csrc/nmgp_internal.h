@@ -160,6 +160,9 @@ struct nmgp_ctx {
     double* b_mU = nullptr;     // [S, r, P]: subject s's orthonormal directions as r rows of length P
     double* b_mw = nullptr;     // [3, S, r]: sqrt(1 + lam) - 1 (draw), -lam / (1 + lam) (velocity), lam / (1 + lam) (kinetic energy)
     double* b_mc = nullptr;     // [B, r] projections U^T u
+    // posterior-draw prediction (nmgp_predsample.hip): ONE workspace for a chunk of draws, its own (no batch buffer is touched)
+    double* ps_buf = nullptr;
+    size_t ps_cap = 0;          // elements
     int last_sep_attempts = 0;  // jitter retries the last separable / stationary evaluation needed (0 = the exact covariance)
     bool last_want_grad = false;
     int last_kind = 0;          // 1 svc
@@ -183,6 +186,7 @@ int nmgp_dev_alloc(nmgp_ctx* c, double** p, size_t nelem);
 int nmgp_scratch_get(nmgp_ctx* c, int slot, size_t nelem, double** out);
 int nmgp_get_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor** out);
 int nmgp_ensure_S(nmgp_ctx* c);
+size_t nmgp_ld(size_t rows);      // leading dimension of a factorisation buffer with `rows` rows
 // Cholesky of the n x n lower triangle (custom gfx950 factorisation or rocSOLVER, per ctx->chol_algo); `extra` rows
 // below the matrix are carried along by the custom path only (must be 0 for rocSOLVER).
 int nmgp_chol_factor(nmgp_ctx* c, double* A, int ld, int n, int extra, int* d_info);

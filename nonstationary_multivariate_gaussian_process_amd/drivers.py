@@ -1156,3 +1156,46 @@ def sample_separable(x, Y, hyper_pars, pars0, chains=8, iters=1000, num_steps_in
                                                               batch=batch),
                           make_sampler, pars0, chains, iters, warm, warm_step, windows, window_iters, step_size, step_candidates,
                           target_accept, progress, segment)
+
+
+def summarize_posterior_predictive(mean, var, y_samples, tilde_l_star, status, quantiles=(2.5, 50.0, 97.5)):
+    """Posterior-predictive summary over H draws (pure NumPy).  mean, var, y_samples: [H, S, M] per-draw predictive moments and
+    one sampled y* per draw; tilde_l_star: [H, S]; status: [H] (0 = the draw's covariance factored).  Draws with non-zero status
+    are left out and counted.  Returns a dict: ``mean`` [S, M] (mean of the per-draw means), ``var`` [S, M] by the law of total
+    variance (mean of the per-draw variances + variance of the per-draw means), ``quantiles`` [len(quantiles), S, M] of the
+    sampled y*, ``tilde_l_star`` [H_used, S], ``status`` [H], ``n_used``, ``n_failed``."""
+    mean, var, y_samples = np.asarray(mean, dtype=np.float64), np.asarray(var, dtype=np.float64), np.asarray(y_samples, dtype=np.float64)
+    status = np.asarray(status)
+    ok = status == 0
+    if not ok.any():
+        raise RuntimeError("no posterior draw could be used: every covariance failed to factor (status %s)" % status.tolist())
+    m = mean[ok]
+    return {"mean": m.mean(axis=0), "var": var[ok].mean(axis=0) + m.var(axis=0),
+            "quantiles": np.percentile(y_samples[ok], list(quantiles), axis=0),
+            "tilde_l_star": np.asarray(tilde_l_star, dtype=np.float64)[ok], "status": status, "n_used": int(ok.sum()),
+            "n_failed": int((~ok).sum())}
+
+
+def posterior_predict(x, Y, hyper_pars, samples, xs, draws=None, seed=0, ctx=None):
+    """Posterior-predictive band of the nonseparable model from the sampler's draws (what ``Nonseparable_model_mpiKAISER.py:516-534``
+    does with ``pointwise_predsample_inhomogeneous``): ``samples`` [iters, chains, P] or [H, P] as :func:`sample_nonseparable`
+    returns them, ``xs`` [S] the new inputs; ``draws`` thins the history evenly to that many.  Per draw and new input the latent
+    curves are regressed and sampled and y* is sampled (``seed``: NumPy generator of all the normals); all draws and inputs go
+    through one batched device call (``Context.predsample_svc``).  Returns :func:`summarize_posterior_predictive`'s dict."""
+    from . import _lib
+    ctx = ctx if ctx is not None else _lib.default_context()
+    x, Y = np.asarray(x, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1)
+    S_ = np.asarray(samples, dtype=np.float64)
+    S_ = S_.reshape(-1, S_.shape[-1])
+    if draws is not None and int(draws) < S_.shape[0]:
+        S_ = S_[np.unique(np.round(np.linspace(0, S_.shape[0] - 1, int(draws))).astype(int))]
+    hyper = np.array([float(hyper_pars[k]) for k in SVC_HYPER_KEYS])
+    M = Y.shape[1]
+    T = M * (M + 1) // 2
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal((S_.shape[0], xs.shape[0], 1 + T))
+    zy = rng.standard_normal((S_.shape[0], xs.shape[0], M))
+    ctx.set_data(x, Y)
+    mean, var, star, status = ctx.predsample_svc(S_, hyper, xs, z=z, constrained=True)
+    return summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
