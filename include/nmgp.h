@@ -293,6 +293,28 @@ int nmgp_predsample_svc(nmgp_ctx* ctx, const double* pars /*[H,P]*/, int H, cons
                         int S, int constrained, const double* z, const double* star_in, double* mean, double* var,
                         double* star_out, int* status);
 
+/* The same for the SEPARABLE model (prediction.py:34-334; pars [H, 2N+T+1], hyper as for nmgp_logpos_sep) and the STATIONARY one
+ * (:1640-1692; pars [H, T+3], no hyper-parameters: nothing is regressed).  Per draw h: B = L L^T is eigendecomposed on the host
+ * and the M blocks wB[p] K_x + sigma2 I of all draws of a chunk are ONE batch of the blocked Cholesky (B M matrices of order N),
+ * with the rotated data row and the cross-covariance row of every grid point riding below each block, as nmgp_predict_sep does
+ * for one parameter vector.
+ *   separable : the UNCONSTRAINED tilde_l and tilde_sigma are regressed onto xs_s, each under its own RBF prior; z, star_in,
+ *               star_out: [H,S,2] (slot 0 tilde_l*, slot 1 tilde_sigma*, both before exp); K_x is the Gibbs kernel + 1e-6 I;
+ *               kss_jitter = 1: a2 = B_mm (sigma*^2 + 1e-6), the `predsample` family (:98); kss_jitter = 0: a2 = B_mm sigma*^2,
+ *               the `predmap_sampling` family (:251).  One draw, z = NULL, kss_jitter = 1 is nmgp_predict_sep's predictor.
+ *               A conditional variance < 0 and a predictive variance <= 0 are replaced by 1e-6.
+ *   stationary: K_x = RBF_cov(x; alpha = exp(tilde_sigma), beta = exp(tilde_l)) + 1e-6 I, a2 = B_mm sigma^2; a predictive
+ *               variance < 0 (strict) is replaced by 1e-6.  One draw is nmgp_predict_sta's predictor.
+ * mean, var: [H,S,M]; status, chunking (NMGP_PREDSAMPLE_SLAB_GB / NMGP_PREDSAMPLE_CHUNK: a draw takes 8 M (N + 1 + min(S, N - 2)) N
+ * bytes of factorisation buffer), the entry's own workspace, the synchronisation and batch = single bits as for
+ * nmgp_predsample_svc; more than N - 2 grid points go through in slices.  NMGP_E_UNSUPPORTED under NMGP_CHOL=rocsolver or
+ * NMGP_SEP=eig; NMGP_E_SHAPE if a block with its riding rows exceeds 2 GiB (the block build's 32-bit byte offsets). */
+int nmgp_predsample_sep(nmgp_ctx* ctx, const double* pars /*[H,2N+T+1]*/, int H, const double hyper[9], const double* xs /*[S]*/,
+                        int S, int kss_jitter, const double* z, const double* star_in, double* mean, double* var,
+                        double* star_out, int* status);
+int nmgp_predsample_sta(nmgp_ctx* ctx, const double* pars /*[H,T+3]*/, int H, const double* xs /*[S]*/, int S, double* mean,
+                        double* var, int* status);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Per-stage HIP-event timing on the context's stream (bench.py roofline figures).  Stages: */
 enum {

@@ -8,8 +8,9 @@ cross-covariances are solved as one multi-right-hand-side triangular solve (nmgp
 The nonseparable posterior-draw families (``*_predsample_inhomogeneous``, ``*_predmap_inhomogeneous_sampling``) live in
 ``nonstationary_multivariate_gaussian_process_amd.predsample`` (one batched device call for all draws and grid points) and are
 served under this module's name only with ``NMGP_PREDSAMPLE=1`` in the environment: by default these names keep resolving to the
-user's checkout, as every name outside the mirrored path does.  The separable / stationary ``predsample`` variants and the
-Hadamard variants are out of scope (no parity target).
+user's checkout, as every name outside the mirrored path does.  The separable and stationary posterior-draw families
+(``*_predsample``, ``*_predmap_sampling``, ``*_predsample_S``) live in ``...predsample_sep`` under the same opt-in.  The Hadamard
+variants are out of scope (no caller of their objective in any script).
 """
 import numpy as np
 import torch
@@ -112,8 +113,9 @@ def test_predmap_S(tilde_l, tilde_sigma, uL_vec, tilde_sigma2_err, Y, x, test_x,
 
 def __getattr__(name):
     """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py)."""
-    from .. import predsample
-    if name in predsample.NAMES and predsample.enabled():
-        return getattr(predsample, name)
+    from .. import predsample, predsample_sep
+    for mod in (predsample, predsample_sep):
+        if name in mod.NAMES and predsample.enabled():
+            return getattr(mod, name)
     from . import _overlay
     return _overlay.module_getattr(__name__, name)

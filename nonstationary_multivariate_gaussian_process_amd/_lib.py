@@ -79,6 +79,8 @@ SIGNATURES = {
     "nmgp_predict_sep": (I, [V, P, P, P, I, P, P]),
     "nmgp_predict_sta": (I, [V, P, P, I, P, P]),
     "nmgp_predsample_svc": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_predsample_sep": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_predsample_sta": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_profile_enable": (I, [V, I]),
     "nmgp_profile_read": (I, [V, P, c_ll_p]),
     "nmgp_profile_reset": (I, [V]),
@@ -590,6 +592,56 @@ class Context:
                                                 ptr(sa), ptr(mean), ptr(var), ptr(star_out),
                                                 status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return mean, var, star_out, status
+
+    def predsample_sep(self, pars_hist, hyper, xs, z=None, star=None, kss_jitter=True):
+        """Posterior-draw prediction of the SEPARABLE model: pars_hist [H, 2N+T+1] of the resident subject at the new inputs xs [S].
+        z [H, S, 2]: standard normals of the latent regression of (tilde_l*, tilde_sigma*) (None: the conditional means); star
+        [H, S, 2]: starred values to use instead of regressing (z must then be None).  kss_jitter=True is the `predsample` family's
+        a2 = B_mm (sigma*^2 + 1e-6), False the `predmap_sampling` family's B_mm sigma*^2 (nmgp.h).
+        Returns (mean [H, S, M], var [H, S, M], star [H, S, 2], status [H]); a draw with non-zero status has NaN rows."""
+        pars = as_f64(pars_hist)
+        if pars.ndim == 1:
+            pars = pars[None]
+        P_ = 2 * self.N + self.T + 1
+        if pars.ndim != 2 or pars.shape[1] != P_:
+            raise NmgpError("draws must be [H, P=%d], got %s" % (P_, pars.shape))
+        hyper, xs = as_f64(hyper), as_f64(xs).reshape(-1)
+        H, S = pars.shape[0], xs.shape[0]
+        if z is not None and star is not None:
+            raise NmgpError("star= replaces the regression: z must be None")
+        za = sa = None
+        for name, a in (("z", z), ("star", star)):
+            if a is not None:
+                a = as_f64(a)
+                if a.shape != (H, S, 2):
+                    raise NmgpError("%s must be [H=%d, S=%d, 2], got %s" % (name, H, S, a.shape))
+                if name == "z":
+                    za = a
+                else:
+                    sa = a
+        mean, var = np.empty((H, S, self.M)), np.empty((H, S, self.M))
+        star_out = np.empty((H, S, 2))
+        status = np.zeros(H, dtype=np.int32)
+        self.check(self.lib.nmgp_predsample_sep(self.h, ptr(pars), H, ptr(hyper), ptr(xs), S, int(bool(kss_jitter)), ptr(za),
+                                                ptr(sa), ptr(mean), ptr(var), ptr(star_out),
+                                                status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return mean, var, star_out, status
+
+    def predsample_sta(self, pars_hist, xs):
+        """Posterior-draw prediction of the STATIONARY model: pars_hist [H, T+3] at xs [S] (nothing is regressed, so there is no
+        noise to inject).  Returns (mean [H, S, M], var [H, S, M], status [H])."""
+        pars = as_f64(pars_hist)
+        if pars.ndim == 1:
+            pars = pars[None]
+        if pars.ndim != 2 or pars.shape[1] != self.T + 3:
+            raise NmgpError("draws must be [H, P=%d], got %s" % (self.T + 3, pars.shape))
+        xs = as_f64(xs).reshape(-1)
+        H, S = pars.shape[0], xs.shape[0]
+        mean, var = np.empty((H, S, self.M)), np.empty((H, S, self.M))
+        status = np.zeros(H, dtype=np.int32)
+        self.check(self.lib.nmgp_predsample_sta(self.h, ptr(pars), H, ptr(xs), S, ptr(mean), ptr(var),
+                                                status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return mean, var, status
 
     # -- measurement ----------------------------------------------------------------------------
     def profile_enable(self, on=True):

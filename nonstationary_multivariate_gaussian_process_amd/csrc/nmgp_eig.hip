@@ -1111,6 +1111,19 @@ extern "C" int nmgp_kron_inv_logdet(nmgp_ctx* c, double sigma2, const double* B,
     return 0;
 }
 
+void nmgp_small_eig(const double* uL, int M, double* wB, double* VB, double* Bdiag) {
+    std::vector<double> L, B, w, V;
+    build_B(uL, M, true, L, B);
+    bool finite = true;
+    for (double v : B) finite = finite && std::isfinite(v);
+    if (finite) jacobi_eigh(M, B.data(), w, V);
+    for (int p = 0; p < M; ++p) {
+        wB[p] = finite ? w[p] : std::nan("");
+        Bdiag[p] = B[(size_t)p * M + p];
+        for (int m = 0; m < M; ++m) VB[(size_t)m * M + p] = finite ? V[(size_t)m * M + p] : std::nan("");
+    }
+}
+
 // =================================================================================================
 // deterministic prediction
 // =================================================================================================

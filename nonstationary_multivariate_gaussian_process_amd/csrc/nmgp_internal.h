@@ -271,9 +271,33 @@ struct PriorStreamScope {
     }
 };
 
+// ---- pieces shared by the posterior-draw entries (nmgp_predsample.hip, nmgp_predsample_sep.hip) ----
+// W = Sigma_prior^-1 K*(xs) ([S, N] row-major, substitution solve) and the clipped conditional variances cv [S] of one GP prior
+int nmgp_ps_project(nmgp_ctx* c, PriorFactor* pf, const double* d_xs, int S, double* W, double* cv);
+// draws per chunk for factorisation buffers of `per_draw_doubles` per draw (NMGP_PREDSAMPLE_SLAB_GB / NMGP_PREDSAMPLE_CHUNK)
+int nmgp_ps_chunk(int H, size_t per_draw_doubles);
+// B = L L^T of a packed unconstrained tril vector (exp on the diagonal slots) and its eigenpairs by the host Jacobi
+// (nmgp_eig.hip): wB [M] ascending, VB [M, M] row-major (VB[m M + p] = component m of eigenvector p), Bdiag [M]; all NaN
+// if B is not finite
+void nmgp_small_eig(const double* uL, int M, double* wB, double* VB, double* Bdiag);
+
 // ---- kernel launchers (nmgp_kernels.hip) -------------------------------------------------------
 
 namespace nmgpk {
+
+// sum over the 256 threads of a workgroup in a fixed order (tree over LDS); every thread returns the total
+__device__ inline double block_sum_256(double v, double* sh /*[256]*/) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
 
 // parameter unpacking: ell = exp(tilde_l), Lv = tril factors with exp on the diagonal slots
 void svc_prep(hipStream_t s, const double* pars, int N, int M, double* ell, double* Lv, int batch = 1);
@@ -411,6 +435,11 @@ void sep_reduce_b(hipStream_t s, const double* Cneg, const double* K, const doub
 void sep_adjoint_b(hipStream_t s, const double* x, const double* ell, const double* sig, const double* U, const double* small,
                    int small_per, int M, const double* C, int N, double* part, double* g, int B);
 void two_col_rhs_b(hipStream_t s, const double* pars, long long P, double mu_a, double mu_b, int N, double* R, int B);
+// ---- nmgp_predsample.hip ----
+// after a factorisation with riding rows, for each of `batch` matrices (stride bstride): dots[z ostride + o0 + e] = row (R0 + e) . row
+// zrow, sqs[..] = |row (R0 + e)|^2 over the n columns, e < E, in a fixed order; part: batch * 2 * E * ceil(n / 128) doubles
+void ps_rows_reduce(hipStream_t s, const double* A, int ld, long long bstride, int n, int R0, int zrow, int E, double* part,
+                    int batch, double* dots, double* sqs, long long ostride, long long o0);
 // ---- nmgp_chol.hip ----
 // C -= A A^T on the lower trapezoid.  finfo / fistride / goff: the launch also factors the diagonal block in its tile (0, 0) where
 // its shape allows (returned); hook: per-launch profiling.  Defaults: neither.

@@ -17,19 +17,6 @@ using namespace nmgpk;
 
 namespace nmgpk {
 
-// sum over the 256 threads of a workgroup in a fixed order (tree over LDS); every thread returns the total
-__device__ inline double block_sum_256(double v, double* sh /*[256]*/) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // Conditional variance of the GP regression at xs_s (prediction.py:1289, 1305): (alpha^2 + jitter) - proj_s . k_s, the
 // `+ jitter` being RBF_cov(x*) called with X2 = None; a value < 0 is replaced by settings.precision.  W: [S, N] row-major
 // (row s = Sigma^-1 k_s); k_s is rebuilt with RBF_cov's expressions.  One workgroup per new input.
@@ -185,6 +172,14 @@ __global__ void k_ps_predvar(const double* __restrict__ star, const double* __re
     var[(size_t)h * S * M + k] = v;
 }
 
+// the two kernels above for `batch` matrices in one launch each (the separable / stationary entries pass draw x block)
+void ps_rows_reduce(hipStream_t s, const double* A, int ld, long long bstride, int n, int R0, int zrow, int E, double* part,
+                    int batch, double* dots, double* sqs, long long ostride, long long o0) {
+    const int chunks = (n + 127) / 128;
+    NMGP_LAUNCH(k_ps_rows_part, dim3((E + 63) / 64, chunks, batch), dim3(256), 0, s, A, ld, bstride, n, R0, zrow, E, part);
+    NMGP_LAUNCH(k_ps_rows_sum, dim3((E + 255) / 256, batch), dim3(256), 0, s, part, chunks, E, dots, sqs, ostride, o0);
+}
+
 }  // namespace nmgpk
 
 namespace {
@@ -218,10 +213,17 @@ int env_int(const char* name, int dflt) {
 
 }  // namespace
 
+// W = Sigma_prior^-1 K*(xs) ([S, N] row-major) and the clipped conditional variances cv [S] of one GP prior
+int nmgp_ps_project(nmgp_ctx* c, PriorFactor* pf, const double* d_xs, int S, double* W, double* cv) {
+    NMGP_TRY(project_rows(c, pf, d_xs, S, W));
+    NMGP_LAUNCH(k_ps_condvar, dim3(S), dim3(256), 0, c->stream, W, c->d_x, c->N, d_xs, pf->alpha, pf->beta, cv);
+    return 0;
+}
+
 // Draws per chunk: as many as keep the factorisation buffers (8 ld n bytes per draw, ld = n + 1 + riding rows) below
 // NMGP_PREDSAMPLE_SLAB_GB (default 16) and at most 64; NMGP_PREDSAMPLE_CHUNK overrides.  At N = 2048, D = 3 with the 201-point
 // grid a draw takes 0.33 GB: 51 draws per chunk, well inside the throughput schedule of the blocked Cholesky (from 13 on).
-static int predsample_chunk(int H, size_t per_draw_doubles) {
+int nmgp_ps_chunk(int H, size_t per_draw_doubles) {
     int B = env_int("NMGP_PREDSAMPLE_CHUNK", 0);
     if (B <= 0) {
         const double slab = std::max(1, env_int("NMGP_PREDSAMPLE_SLAB_GB", 16)) * 1073741824.0;
@@ -250,7 +252,7 @@ extern "C" int nmgp_predsample_svc(nmgp_ctx* c, const double* pars, int H, const
     const int ld = (int)nmgp_ld((size_t)n + 1 + Emax);
     const long long bs = (long long)ld * n;
     const int chunks = (n + 127) / 128;
-    const int B = predsample_chunk(H, (size_t)bs);
+    const int B = nmgp_ps_chunk(H, (size_t)bs);
     const size_t SC = (size_t)S * (1 + T), SMo = (size_t)S * M;
 
     // one workspace, carved; its size depends on (N, M, S, B), not on H

@@ -1,0 +1,311 @@
+// Posterior-draw prediction of the separable and the stationary model (prediction.py:34-334 and :1640-1692): H parameter vectors
+// of the resident subject, S new inputs, in batched launch sequences.  Entry points declared in include/nmgp.h.
+//
+// Per draw h: B = L L^T = V_B diag(wB) V_B^T (M x M, host Jacobi), Sigma = B kron K_x + sigma2 I =
+// (V_B kron I) blockdiag_p(wB[p] K_x + sigma2 I) (V_B^T kron I).  A chunk of Bc draws is ONE batched block build and ONE batched
+// blocked Cholesky over Bc M matrices of order N, with the rotated data row yt_p and the Sc cross-covariance rows k_s of the
+// draw's own starred values riding below block p (rows become r L_p^-T), as chol_predict (nmgp_eig.hip) does for one vector:
+//   dots[p, s] = (L_p^-1 k_s) . (L_p^-1 yt_p),  sqs[p, s] = |L_p^-1 k_s|^2,
+//   mean[s, m] = sum_p wB[p] VB[m, p] dots[p, s],   var[s, m] = B[m, m] kss_s - sum_p (wB[p] VB[m, p])^2 sqs[p, s] + sigma2.
+// Separable: the unconstrained tilde_l, tilde_sigma are regressed onto xs under their RBF priors (proj-first, once per call) and
+// N(0, conditional variance) noise is added (k_pss_star); K_x is the Gibbs kernel + 1e-6 I (sep_prep_b / sep_blocks_b).
+// Stationary: K_x = RBF_cov(x; alpha = sigma, beta = l) + 1e-6 I with the draw's scalars, no latent regression.
+// Every kernel below is per-draw independent with a fixed summation order: a batch of B draws gives the bits of B single calls.
+#include <algorithm>
+
+#include "nmgp_internal.h"
+
+using namespace nmgpk;
+
+namespace nmgpk {
+
+// per-draw small block (device and host): wB [M] | VB row-major [M, M] | sigma2 | pad | diag(B) [M] | l0 | sig0
+// (the first M + M M + 1 entries are the layout sep_prep_b / sep_blocks_b read; l0, sig0: the stationary draw's exp'd scalars)
+__host__ __device__ inline int pss_small_per(int M) { return M + M * M + 2 + M + 2; }
+__host__ __device__ inline int pss_o_s2(int M) { return M + M * M; }
+__host__ __device__ inline int pss_o_bd(int M) { return M + M * M + 2; }
+__host__ __device__ inline int pss_o_l0(int M) { return M + M * M + 2 + M; }
+
+// Starred values of draw h = blockIdx.z at new input s = blockIdx.x, slot c = blockIdx.y (0: tilde_l*, 1: tilde_sigma*):
+//   star = mu + proj_s . (curve - mu) + sqrt(cv_s) z          (prediction.py:56-61, :66-71; the curves are the UNCONSTRAINED ones)
+// z == nullptr: no noise (the conditional mean).  star, z: [B, S, 2]; W0 / W1: [S, N]; cv0 / cv1: [S].
+__global__ __launch_bounds__(256) void k_pss_star(const double* __restrict__ W0, const double* __restrict__ W1,
+                                                   const double* __restrict__ cv0, const double* __restrict__ cv1,
+                                                   const double* __restrict__ pars, long long P, const double* __restrict__ z, int N,
+                                                   int S, double mu_l, double mu_s, double* __restrict__ star) {
+    __shared__ double sh[256];
+    const int s = blockIdx.x, cidx = blockIdx.y, h = blockIdx.z;
+    const double* p = pars + (size_t)h * P + (size_t)cidx * N;
+    const double* W = (cidx == 0 ? W0 : W1) + (size_t)s * N;
+    const double mu = cidx == 0 ? mu_l : mu_s;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < N; i += 256) acc += W[i] * (p[i] - mu);
+    acc = block_sum_256(acc, sh);
+    if (threadIdx.x != 0) return;
+    const size_t o = ((size_t)h * S + s) * 2 + cidx;
+    double v = mu + acc;
+    if (z) v = v + sqrt((cidx == 0 ? cv0 : cv1)[s]) * z[o];
+    star[o] = v;
+}
+
+// Riding row R0 + e below EVERY one of the M blocks of draw h = blockIdx.z: the cross-covariance vector of grid point s0 + e, built
+// once and written M times.  Lanes along the riding-row index (contiguous in the factor's column-major storage), i = blockIdx.x.
+//   MODE 0 (separable, prediction.py:88 / :241): Gibbs with (sig_i, ell_i) of the draw against (exp(tilde_sigma*), exp(tilde_l*))
+//   MODE 1 (stationary, :1656): RBF_cov(x, xs; alpha = sig0, beta = l0) with the draw's scalars
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pss_cross_rows(const double* __restrict__ x, const double* __restrict__ ell,
+                                                         const double* __restrict__ sig, const double* __restrict__ small, int N,
+                                                         int M, const double* __restrict__ xs, const double* __restrict__ star,
+                                                         int S, int s0, int Sc, double* __restrict__ A, int ld, long long bstride,
+                                                         int R0) {
+    const int e = blockIdx.y * 256 + threadIdx.x;
+    const int i = blockIdx.x, h = blockIdx.z;
+    if (e >= Sc) return;
+    const int s = s0 + e;
+    double v;
+    if (MODE == 0) {
+        const double* st = star + ((size_t)h * S + s) * 2;
+        const double xi = x[i], li = ell[(size_t)h * N + i], xj = xs[s];
+        const double lj = exp(st[0]), sj = exp(st[1]);
+        const double dist = (xi * xi + xj * xj) - 2.0 * (xi * xj);
+        const double Aij = li * li + lj * lj;
+        v = (sig[(size_t)h * N + i] * sj) * sqrt(2.0 * (li * lj) / Aij) * exp(-dist / Aij);
+    } else {
+        const double* sm = small + (size_t)h * pss_small_per(M) + pss_o_l0(M);
+        const double l0 = sm[0], sig0 = sm[1];
+        const double xi = x[i] / l0, xj = xs[s] / l0;
+        const double dist = (xi * xi + xj * xj) - 2.0 * (xi * xj);
+        v = exp(-0.5 * dist) * (sig0 * sig0);
+    }
+    double* Ah = A + (size_t)h * M * bstride + (size_t)i * ld + R0 + e;
+    for (int p = 0; p < M; ++p) Ah[(size_t)p * bstride] = v;
+}
+
+// Stationary draw h = blockIdx.z: lower triangles of its M blocks wB[p] (RBF_cov(x; sig0, l0) + 1e-6 I) + sigma2 I, column
+// j = blockIdx.y, lanes along i (rbf_cov_sym's expressions, then sep_blocks')
+__global__ __launch_bounds__(256) void k_pss_sta_blocks(const double* __restrict__ x, const double* __restrict__ small, int N, int M,
+                                                         double* __restrict__ S, int ld, long long bstride) {
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, h = blockIdx.z;
+    if (i >= N || i < j) return;
+    const double* sm = small + (size_t)h * pss_small_per(M);
+    const double l0 = sm[pss_o_l0(M)], sig0 = sm[pss_o_l0(M) + 1], sigma2 = sm[pss_o_s2(M)];
+    const double xi = x[i] / l0, xj = x[j] / l0;
+    const double dist = (xi * xi + xj * xj) - 2.0 * (xi * xj);
+    double v = exp(-0.5 * dist) * (sig0 * sig0);
+    if (i == j) v = NMGP_JITTER + v;
+    double* o = S + (size_t)h * M * bstride + (size_t)j * ld + i;
+    for (int p = 0; p < M; ++p) {
+        double b = sm[p] * v;
+        if (i == j) b += sigma2;
+        o[(size_t)p * bstride] = b;
+    }
+}
+
+// yt[(h M + p) N + i] = sum_m Y[i, m] VB_h[m, p] (k_sep_prep_b's rotation for a model without per-location parameters)
+__global__ __launch_bounds__(256) void k_pss_rotate_y(const double* __restrict__ Y, const double* __restrict__ small, int N, int M,
+                                                       double* __restrict__ yt) {
+    const int i = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
+    if (i >= N) return;
+    const double* VB = small + (size_t)h * pss_small_per(M) + M;
+    for (int p = 0; p < M; ++p) {
+        double s = 0.0;
+        for (int m = 0; m < M; ++m) s += Y[(size_t)i * M + m] * VB[m * M + p];
+        yt[((size_t)h * M + p) * N + i] = s;
+    }
+}
+
+// k_sep_predict_chol with the draw as blockIdx.y: dots / sqs [B, M, S] -> mean / var [B, S, M].
+//   kss (separable): exp(tilde_sigma*)^2, + 1e-6 with kss_jitter (prediction.py:98 against :251); (stationary) sig0^2 (:1659)
+//   a variance <= 0 (strict: < 0, the stationary functions) is replaced by settings.precision
+__global__ void k_pss_combine(const double* __restrict__ dots, const double* __restrict__ sqs, const double* __restrict__ small,
+                              const double* __restrict__ star, int S, int M, int stationary, int kss_jitter,
+                              double* __restrict__ mean, double* __restrict__ var) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, h = blockIdx.y;
+    if (k >= S * M) return;
+    const int s = k / M, m = k - s * M;
+    const double* sm = small + (size_t)h * pss_small_per(M);
+    const double* wB = sm;
+    const double* VB = sm + M;
+    double mu = 0.0, vv = 0.0;
+    for (int p = 0; p < M; ++p) {
+        const double am = wB[p] * VB[m * M + p];
+        mu += am * dots[((size_t)h * M + p) * S + s];
+        vv += (am * am) * sqs[((size_t)h * M + p) * S + s];
+    }
+    double kss;
+    if (stationary) {
+        const double sig0 = sm[pss_o_l0(M) + 1];
+        kss = sig0 * sig0;
+    } else {
+        const double sg = exp(star[((size_t)h * S + s) * 2 + 1]);
+        kss = kss_jitter ? NMGP_JITTER + (sg * sg) : sg * sg;
+    }
+    double v = (sm[pss_o_bd(M) + m] * kss - vv) + sm[pss_o_s2(M)];
+    if (stationary ? (v < 0.0) : (v <= 0.0)) v = NMGP_PRECISION;
+    mean[(size_t)h * S * M + k] = mu;
+    var[(size_t)h * S * M + k] = v;
+}
+
+}  // namespace nmgpk
+
+namespace {
+
+inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
+
+// both entries: stationary = the model without per-location parameters and without a latent regression
+int predsample_kron(nmgp_ctx* c, bool stationary, const double* pars, int H, const double* hyper, const double* xs, int S,
+                    int kss_jitter, const double* z, const double* star_in, double* mean, double* var, double* star_out,
+                    int* status) {
+    if (!pars || !xs || !mean || !var || (!stationary && !hyper)) return nmgp_fail(c, NMGP_E_NULL, "null argument");
+    if (H <= 0 || S <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "H and S must be positive (H=%d, S=%d)", H, S);
+    if (z && star_in) return nmgp_fail(c, NMGP_E_STATE, "with star_in given the regression is skipped: z must be NULL");
+    if (!c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
+    if (c->chol_algo != 1 || c->sep_algo != 1)
+        return nmgp_fail(c, NMGP_E_UNSUPPORTED, "posterior-draw prediction runs on the custom factorisation of the M blocks only "
+                                                "(riding rows): not under NMGP_CHOL=rocsolver or NMGP_SEP=eig");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->N, M = c->M, T = c->T;
+    const long long P = stationary ? T + 3 : 2LL * N + T + 1;
+    hipStream_t s = c->stream;
+    // grid points per factorisation: up to N - 2 riding cross-covariance rows besides the data row (as chol_predict)
+    const int smax = std::max(1, N - 2), Sm = std::min(S, smax);
+    const int ld = (int)nmgp_ld((size_t)N + 1 + Sm);
+    const long long bs = (long long)ld * N;
+    // (sep_blocks_b addresses a block with 32-bit byte offsets)
+    if (8LL * ld * N >= 0x7fffffffLL)
+        return nmgp_fail(c, NMGP_E_SHAPE, "a block of order N = %d with %d riding rows exceeds the 2 GiB the block build addresses", N,
+                         ld - N);
+    const int chunks = (N + 127) / 128;
+    const int B = nmgp_ps_chunk(H, (size_t)M * bs);
+    const int sp = pss_small_per(M);
+    const size_t S2 = (size_t)S * 2, SMo = (size_t)S * M;
+
+    const bool regress = !stationary && star_in == nullptr;
+    PriorFactor *pl = nullptr, *pg = nullptr;
+    if (regress) {
+        // (the factor cache is a vector: the second look-up may grow it and move its elements, so the first pointer is re-resolved)
+        NMGP_TRY(nmgp_get_prior(c, hyper[1], hyper[2], &pl));
+        NMGP_TRY(nmgp_get_prior(c, hyper[4], hyper[5], &pg));
+        NMGP_TRY(nmgp_get_prior(c, hyper[1], hyper[2], &pl));
+    }
+    const bool same = pl == pg;
+    // one workspace, carved; its size depends on (N, M, S, B), not on H
+    size_t off = 0;
+    auto take = [&off](size_t nelem) {
+        const size_t o = off;
+        off += (nelem + 15) / 16 * 16;
+        return o;
+    };
+    const size_t o_xs = take(S), o_W0 = take(regress ? (size_t)N * S : 0), o_W1 = take(regress && !same ? (size_t)N * S : 0),
+                 o_cv = take(regress ? S2 : 0), o_pars = take((size_t)B * P), o_small = take((size_t)B * sp),
+                 o_ell = take(stationary ? 0 : (size_t)B * N), o_sig = take(stationary ? 0 : (size_t)B * N),
+                 o_yt = take((size_t)B * M * N), o_star = take(stationary ? 0 : B * S2), o_z = take(z ? B * S2 : 0),
+                 o_dots = take((size_t)B * M * S), o_sqs = take((size_t)B * M * S), o_mean = take(B * SMo), o_var = take(B * SMo),
+                 o_part = take((size_t)B * M * 2 * Sm * chunks), o_info = take(((size_t)B * M + 1) / 2), o_S = take((size_t)B * M * bs);
+    if (c->ps_cap < off) {
+        c->ps_cap = 0;
+        NMGP_TRY(nmgp_dev_alloc(c, &c->ps_buf, off));
+        c->ps_cap = off;
+    } else if (nmgp_poison()) {
+        HIP_TRY(c, hipMemsetAsync(c->ps_buf, 0xFF, off * sizeof(double), s));
+    }
+    double* w = c->ps_buf;
+    double *d_xs = w + o_xs, *W0 = w + o_W0, *W1 = same ? W0 : w + o_W1, *cv0 = w + o_cv, *cv1 = same ? cv0 : cv0 + S,
+           *d_pars = w + o_pars, *d_small = w + o_small, *d_ell = w + o_ell, *d_sig = w + o_sig, *yt = w + o_yt, *d_star = w + o_star,
+           *d_z = z ? w + o_z : nullptr, *dots = w + o_dots, *sqs = w + o_sqs, *d_mean = w + o_mean, *d_var = w + o_var,
+           *part = w + o_part, *Sb = w + o_S;
+    int* d_info = reinterpret_cast<int*>(w + o_info);
+
+    HIP_TRY(c, hipMemcpyAsync(d_xs, xs, (size_t)S * sizeof(double), hipMemcpyHostToDevice, s));
+    if (regress) {
+        NMGP_TRY(nmgp_ps_project(c, pl, d_xs, S, W0, cv0));
+        if (!same) NMGP_TRY(nmgp_ps_project(c, pg, d_xs, S, W1, cv1));
+    }
+    std::vector<int> hinfo((size_t)B * M);
+    std::vector<double> hsmall((size_t)B * sp);
+    for (int h0 = 0; h0 < H; h0 += B) {
+        const int Bc = std::min(B, H - h0), BM = Bc * M;
+        // host: B = L L^T and its eigenpairs per draw (M x M: known before the first launch)
+        for (int b = 0; b < Bc; ++b) {
+            const double* pb = pars + (size_t)(h0 + b) * P;
+            double* hs = hsmall.data() + (size_t)b * sp;
+            nmgp_small_eig(pb + (stationary ? 2 : 2 * (size_t)N), M, hs, hs + M, hs + pss_o_bd(M));
+            hs[pss_o_s2(M)] = std::exp(pb[P - 1]);
+            hs[pss_o_s2(M) + 1] = 0.0;
+            hs[pss_o_l0(M)] = stationary ? std::exp(pb[0]) : 1.0;
+            hs[pss_o_l0(M) + 1] = stationary ? std::exp(pb[1]) : 1.0;
+        }
+        HIP_TRY(c, hipMemcpyAsync(d_pars, pars + (size_t)h0 * P, (size_t)Bc * P * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_small, hsmall.data(), (size_t)Bc * sp * sizeof(double), hipMemcpyHostToDevice, s));
+        if (stationary) {
+            NMGP_LAUNCH(k_pss_rotate_y, dim3(cdiv(N, 256), Bc), dim3(256), 0, s, c->d_Y, d_small, N, M, yt);
+        } else {
+            sep_prep_b(s, d_pars, P, c->d_Y, d_small, sp, N, M, d_ell, d_sig, yt, Bc);
+            if (regress) {
+                if (z) HIP_TRY(c, hipMemcpyAsync(d_z, z + (size_t)h0 * S2, Bc * S2 * sizeof(double), hipMemcpyHostToDevice, s));
+                NMGP_LAUNCH(k_pss_star, dim3(S, 2, Bc), dim3(256), 0, s, W0, W1, cv0, cv1, d_pars, P, d_z, N, S, hyper[0], hyper[3],
+                            d_star);
+            } else {
+                HIP_TRY(c, hipMemcpyAsync(d_star, star_in + (size_t)h0 * S2, Bc * S2 * sizeof(double), hipMemcpyHostToDevice, s));
+            }
+        }
+        HIP_TRY(c, hipMemsetAsync(d_info, 0, (size_t)BM * sizeof(int), s));
+        for (int s0 = 0; s0 < S; s0 += smax) {
+            const int Sc = std::min(smax, S - s0);
+            const dim3 gx(N, cdiv(Sc, 256), Bc);
+            if (stationary) {
+                NMGP_LAUNCH(k_pss_sta_blocks, dim3(cdiv(N, 256), N, Bc), dim3(256), 0, s, c->d_x, d_small, N, M, Sb, ld, bs);
+                NMGP_LAUNCH((k_pss_cross_rows<1>), gx, dim3(256), 0, s, c->d_x, nullptr, nullptr, d_small, N, M, d_xs, nullptr, S, s0, Sc,
+                            Sb, ld, bs, N + 1);
+            } else {
+                sep_blocks_b(s, c->d_x, d_ell, d_sig, d_small, sp, N, M, Sb, ld, bs, nullptr, Bc);
+                NMGP_LAUNCH((k_pss_cross_rows<0>), gx, dim3(256), 0, s, c->d_x, d_ell, d_sig, d_small, N, M, d_xs, d_star, S, s0, Sc, Sb,
+                            ld, bs, N + 1);
+            }
+            set_row(s, Sb, ld, N, yt, N, BM, bs, N);
+            nmgp_potrf(c, Sb, ld, N, 1 + Sc, 0, d_info, BM, bs, 1);
+            ps_rows_reduce(s, Sb, ld, bs, N, N + 1, N, Sc, part, BM, dots, sqs, (long long)S, (long long)s0);
+        }
+        NMGP_LAUNCH(k_pss_combine, dim3(cdiv((long long)SMo, 256), Bc), dim3(256), 0, s, dots, sqs, d_small, d_star, S, M,
+                    stationary ? 1 : 0, kss_jitter ? 1 : 0, d_mean, d_var);
+        double* hm = mean + (size_t)h0 * SMo;
+        double* hv = var + (size_t)h0 * SMo;
+        HIP_TRY(c, hipMemcpyAsync(hm, d_mean, Bc * SMo * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(hv, d_var, Bc * SMo * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (star_out && !stationary)
+            HIP_TRY(c, hipMemcpyAsync(star_out + (size_t)h0 * S2, d_star, Bc * S2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(hinfo.data(), d_info, (size_t)BM * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        NMGP_TRY(nmgp_take_launch_error(c));
+        // per-draw status as nmgp_predsample_svc reports it: a failing draw yields NaN rows, not a failed call
+        for (int b = 0; b < Bc; ++b) {
+            int st = 0;
+            for (int p = 0; p < M && st == 0; ++p) st = hinfo[(size_t)b * M + p];
+            if (st == 0)
+                for (size_t k = 0; k < SMo; ++k)
+                    if (!std::isfinite(hm[b * SMo + k]) || !std::isfinite(hv[b * SMo + k])) {
+                        st = NMGP_NUM_NAN;
+                        break;
+                    }
+            if (st != 0)
+                for (size_t k = 0; k < SMo; ++k) hm[b * SMo + k] = hv[b * SMo + k] = std::nan("");
+            if (status) status[h0 + b] = st;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int nmgp_predsample_sep(nmgp_ctx* c, const double* pars, int H, const double hyper[9], const double* xs, int S,
+                                   int kss_jitter, const double* z, const double* star_in, double* mean, double* var,
+                                   double* star_out, int* status) {
+    if (!c) return NMGP_E_NULL;
+    return predsample_kron(c, false, pars, H, hyper, xs, S, kss_jitter, z, star_in, mean, var, star_out, status);
+}
+
+extern "C" int nmgp_predsample_sta(nmgp_ctx* c, const double* pars, int H, const double* xs, int S, double* mean, double* var,
+                                   int* status) {
+    if (!c) return NMGP_E_NULL;
+    return predsample_kron(c, true, pars, H, nullptr, xs, S, 0, nullptr, nullptr, mean, var, nullptr, status);
+}

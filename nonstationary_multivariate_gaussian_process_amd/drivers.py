@@ -1199,3 +1199,29 @@ def posterior_predict(x, Y, hyper_pars, samples, xs, draws=None, seed=0, ctx=Non
     ctx.set_data(x, Y)
     mean, var, star, status = ctx.predsample_svc(S_, hyper, xs, z=z, constrained=True)
     return summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
+
+
+def posterior_predict_separable(x, Y, hyper_pars, samples, xs, draws=None, seed=0, ctx=None):
+    """Posterior-predictive band of the SEPARABLE model from the sampler's draws (what ``Separable_model.py:307-316`` does with
+    ``pointwise_predsample``): ``samples`` [iters, chains, 2N+T+1] or [H, 2N+T+1] as :func:`sample_separable` returns them, ``xs``
+    [S] the new inputs; ``draws`` thins the history evenly to that many.  Per draw and new input tilde_l* and tilde_sigma* are
+    regressed and sampled and y* is sampled (``seed``: NumPy generator of all the normals); all draws and inputs go through one
+    batched device call (``Context.predsample_sep``).  Returns :func:`summarize_posterior_predictive`'s dict plus
+    ``tilde_sigma_star`` [H_used, S]."""
+    from . import _lib
+    ctx = ctx if ctx is not None else _lib.default_context()
+    x, Y = np.asarray(x, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1)
+    S_ = np.asarray(samples, dtype=np.float64)
+    S_ = S_.reshape(-1, S_.shape[-1])
+    if draws is not None and int(draws) < S_.shape[0]:
+        S_ = S_[np.unique(np.round(np.linspace(0, S_.shape[0] - 1, int(draws))).astype(int))]
+    hyper = np.array([float(hyper_pars[k]) for k in SEP_HYPER_KEYS])
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal((S_.shape[0], xs.shape[0], 2))
+    zy = rng.standard_normal((S_.shape[0], xs.shape[0], Y.shape[1]))
+    ctx.set_data(x, Y)
+    mean, var, star, status = ctx.predsample_sep(S_, hyper, xs, z=z, kss_jitter=True)
+    out = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
+    out["tilde_sigma_star"] = star[:, :, 1][status == 0]
+    return out
