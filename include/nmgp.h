@@ -68,6 +68,30 @@ int nmgp_device_count(void);
  * per-call tensor plumbing of logpos.py:337-338.  May be called again with another subject. */
 int nmgp_set_data(nmgp_ctx* ctx, const double* x, const double* Y, int N, int M);
 
+/* ---- Hadamard form of the nonseparable model: irregularly observed outputs --------------------
+ * logpos.nlogpos_obj_hadamard_SVC / logpos_hadamard_SVC (logpos.py:566-659), prediction.point_predmap_SVC_hadamard /
+ * pointwise_predmap_SVC_hadamard (prediction.py:1401-1478).  The data are N single observations (x[i], indx[i], y[i]), indx[i] in
+ * [0, M) naming the output measured at x[i].  pars = [tilde_l (N) | L_vecs (N*T, row-major per observation) | tilde_sigma2_err],
+ * P = N(1+T)+1; the L_vecs slots are taken as they are (no exp) and only row indx[i] of L_i reaches the likelihood.
+ *
+ * nmgp_had_set_data makes the Hadamard subject the resident one: NMGP_E_SHAPE unless every label is in [0, M) and every label
+ * occurs.  The complete-data entries then return NMGP_E_STATE until nmgp_set_data is called again, and the entries below return
+ * NMGP_E_STATE while a complete-data subject (or none) is resident. */
+int nmgp_had_set_data(nmgp_ctx* ctx, const double* x, const int* indx, const double* y, int N, int M);
+/* B parameter vectors pars [B, P] in one launch sequence (one synchronisation per chunk of chains; chunks keep the entry's own
+ * device workspace below NMGP_HAD_BATCH_SLAB_GB, default 96).  hyper[8] as for nmgp_logpos_svc.  out5 [B, 5] = the verbose tuples
+ * (NegLog, loglik, log_prior_tilde_l, log_prior_L_vecs, log_prior_sigma2_err); grad [B, P] = d NegLog / d pars, or NULL;
+ * status [B]: 0, k > 0 (leading minor k of the chain's covariance is not positive definite) or NMGP_NUM_NAN (a non-finite
+ * parameter or result).  A failing chain has a NaN row in out5 and a zero row in grad; the call still returns 0. */
+int nmgp_had_batch_eval(nmgp_ctx* ctx, const double* pars, int B, const double hyper[8], int prior, double* out5, double* grad,
+                        int* status);
+/* out [N, N]: the full symmetric covariance K_x o (R R^T) + sigma2 I of one parameter vector. */
+int nmgp_had_covariance(nmgp_ctx* ctx, const double* pars, double* out);
+/* MAP prediction of all M outputs at the new inputs xs [S]: mean, var [S, M] (a variance <= 0 is replaced by 1e-6);
+ * star [S, 1+T] = the regressed tilde_l* and the T slots of L* (no exp), or NULL. */
+int nmgp_predict_had(nmgp_ctx* ctx, const double* pars, const double hyper[8], const double* xs, int S, double* mean, double* var,
+                     double* star);
+
 /* ---- nonseparable ("SVC") objective:  logpos.nlogpos_obj_SVC / logpos_SVC, logpos.py:299-380 -- */
 /* hyper[8] = {mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L, a, b}.
  * out5 = {NegLog, loglik, log_prior_tilde_l, log_prior_uL_vecs, log_prior_sigma2_err} (the verbose tuple).

@@ -238,6 +238,10 @@ def deviance(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, Y, x):
 
 
 def __getattr__(name):
-    """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py)."""
+    """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py); the Hadamard objective
+    of the nonseparable model from ``..hadamard`` with ``NMGP_HADAMARD=1`` in the environment (opt-in, read at every look-up)."""
+    from .. import hadamard
+    if name in hadamard.LOGPOS_NAMES and hadamard.enabled():
+        return getattr(hadamard, name)
     from . import _overlay
     return _overlay.module_getattr(__name__, name)

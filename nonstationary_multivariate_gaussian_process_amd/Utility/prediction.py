@@ -9,8 +9,11 @@ The nonseparable posterior-draw families (``*_predsample_inhomogeneous``, ``*_pr
 ``nonstationary_multivariate_gaussian_process_amd.predsample`` (one batched device call for all draws and grid points) and are
 served under this module's name only with ``NMGP_PREDSAMPLE=1`` in the environment: by default these names keep resolving to the
 user's checkout, as every name outside the mirrored path does.  The separable and stationary posterior-draw families
-(``*_predsample``, ``*_predmap_sampling``, ``*_predsample_S``) live in ``...predsample_sep`` under the same opt-in.  The Hadamard
-variants are out of scope (no caller of their objective in any script).
+(``*_predsample``, ``*_predmap_sampling``, ``*_predsample_S``) live in ``...predsample_sep`` under the same opt-in.
+The MAP predictors of the Hadamard nonseparable model (irregularly observed outputs: ``point_`` / ``pointwise_predmap_SVC_hadamard``,
+:1401-1478) live in ``...hadamard`` and are served under this module's name only with ``NMGP_HADAMARD=1``.  The other Hadamard
+names (``indexedpoint_`` / ``test_predmap_SVC_hadamard``, the ``predsample_hadamard`` families, the separable and stationary
+variants) keep resolving to the user's checkout.
 """
 import numpy as np
 import torch
@@ -113,7 +116,9 @@ def test_predmap_S(tilde_l, tilde_sigma, uL_vec, tilde_sigma2_err, Y, x, test_x,
 
 def __getattr__(name):
     """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py)."""
-    from .. import predsample, predsample_sep
+    from .. import hadamard, predsample, predsample_sep
+    if name in hadamard.PREDICTION_NAMES and hadamard.enabled():
+        return getattr(hadamard, name)
     for mod in (predsample, predsample_sep):
         if name in mod.NAMES and predsample.enabled():
             return getattr(mod, name)

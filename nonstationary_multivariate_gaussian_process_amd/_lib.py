@@ -78,6 +78,10 @@ SIGNATURES = {
     "nmgp_predict_svc": (I, [V, P, P, P, I, P, P, P]),
     "nmgp_predict_sep": (I, [V, P, P, P, I, P, P]),
     "nmgp_predict_sta": (I, [V, P, P, I, P, P]),
+    "nmgp_had_set_data": (I, [V, P, ctypes.POINTER(ctypes.c_int), P, I, I]),
+    "nmgp_had_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_had_covariance": (I, [V, P, P]),
+    "nmgp_predict_had": (I, [V, P, P, P, I, P, P, P]),
     "nmgp_predsample_svc": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sep": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sta": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
@@ -197,7 +201,7 @@ class Context:
         Y = as_f64(Y)
         if Y.ndim != 2 or Y.shape[0] != x.shape[0]:
             raise NmgpError("Y must be [N, M] with N == len(x); got Y%s x%s" % (Y.shape, x.shape))
-        key = (x.shape, Y.shape, hash(x.tobytes()), hash(Y.tobytes()))
+        key = ("complete", x.shape, Y.shape, hash(x.tobytes()), hash(Y.tobytes()))
         if key == self._data_key:
             return
         self.check(self.lib.nmgp_set_data(self.h, ptr(x), ptr(Y), Y.shape[0], Y.shape[1]))
@@ -642,6 +646,64 @@ class Context:
         self.check(self.lib.nmgp_predsample_sta(self.h, ptr(pars), H, ptr(xs), S, ptr(mean), ptr(var),
                                                 status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return mean, var, status
+
+    # -- Hadamard form of the nonseparable model (irregularly observed outputs) -------------------
+    def had_set_data(self, x, indx, y, M=None):
+        """N single observations (x[i], indx[i], y[i]); M defaults to the number of distinct labels, as the reference infers it
+        (logpos.py:579).  Replaces the resident subject: the complete-data entries raise until ``set_data`` is called again."""
+        x, y = as_f64(x).reshape(-1), as_f64(y).reshape(-1)
+        if hasattr(indx, "detach"):
+            indx = indx.detach().cpu().numpy()
+        indx = np.ascontiguousarray(np.asarray(indx).reshape(-1).astype(np.int32))
+        if not (x.shape == y.shape == indx.shape):
+            raise NmgpError("x, indx and y must have one length; got x%s indx%s y%s" % (x.shape, indx.shape, y.shape))
+        M = int(np.unique(indx).shape[0]) if M is None else int(M)
+        key = ("hadamard", M, x.shape, hash(x.tobytes()), hash(indx.tobytes()), hash(y.tobytes()))
+        if key == self._data_key:
+            return
+        self._data_key = None            # whatever was resident is gone even if the call fails
+        self.check(self.lib.nmgp_had_set_data(self.h, ptr(x), indx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ptr(y),
+                                              x.shape[0], M))
+        self.N, self.M = x.shape[0], M
+        self.T = M * (M + 1) // 2
+        self._data_key = key
+
+    def had_batch_eval(self, pars, hyper, prior=True, want_grad=False):
+        """B parameter vectors of the resident Hadamard subject in one launch sequence: pars [B, N(1+T)+1] (or one vector) ->
+        (out [B, 5], grad [B, P] or None, status [B]: 0, a leading-minor index or NUM_NAN; a failing chain has a NaN row and a
+        zero gradient row)."""
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        P_ = self.N * (1 + self.T) + 1
+        if pars.ndim != 2 or pars.shape[1] != P_:
+            raise NmgpError("parameters must be [B, N(1+T)+1 = %d], got %s" % (P_, pars.shape))
+        hyper = as_f64(hyper)
+        B = pars.shape[0]
+        out = np.empty((B, 5))
+        grad = np.empty((B, P_)) if want_grad else None
+        status = np.zeros(B, dtype=np.int32)
+        self.check(self.lib.nmgp_had_batch_eval(self.h, ptr(pars), B, ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
+                                                status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out, grad, status
+
+    def had_covariance(self, pars):
+        pars = as_f64(pars).reshape(-1)
+        if pars.shape[0] != self.N * (1 + self.T) + 1:
+            raise NmgpError("bad parameter vector length %d" % pars.shape[0])
+        out = np.empty((self.N, self.N))
+        self.check(self.lib.nmgp_had_covariance(self.h, ptr(pars), ptr(out)))
+        return out
+
+    def predict_had(self, pars, hyper, xs):
+        """(mean [S, M], var [S, M], star [S, 1+T]) of the resident Hadamard subject at the new inputs xs."""
+        pars, hyper, xs = as_f64(pars).reshape(-1), as_f64(hyper), as_f64(xs).reshape(-1)
+        if pars.shape[0] != self.N * (1 + self.T) + 1:
+            raise NmgpError("bad parameter vector length %d" % pars.shape[0])
+        S = xs.shape[0]
+        mean, var, star = np.empty((S, self.M)), np.empty((S, self.M)), np.empty((S, 1 + self.T))
+        self.check(self.lib.nmgp_predict_had(self.h, ptr(pars), ptr(hyper), ptr(xs), S, ptr(mean), ptr(var), ptr(star)))
+        return mean, var, star
 
     # -- measurement ----------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -167,6 +167,11 @@ static void free_subject(nmgp_ctx* c) {
         *p = nullptr;
     }
     c->S_cap = c->K_cap = c->part_cap = 0;
+    if (c->had_indx) hipFree(c->had_indx);
+    if (c->had_y) hipFree(c->had_y);
+    c->had_indx = nullptr;
+    c->had_y = nullptr;
+    c->had = false;
     if (c->ps_buf) hipFree(c->ps_buf);       // workspace of nmgp_predsample_svc: sized for the subject
     c->ps_buf = nullptr;
     c->ps_cap = 0;
@@ -370,6 +375,45 @@ extern "C" int nmgp_set_data(nmgp_ctx* c, const double* x, const double* Y, int 
     return 0;
 }
 
+// The Hadamard subject: N single observations (x_i, indx_i, y_i), labels 0 .. M - 1, every label present (the reference takes
+// M = number of distinct values of indx, logpos.py:579).  It replaces whatever subject was resident; the complete-data entries
+// return NMGP_E_STATE until nmgp_set_data is called again.
+extern "C" int nmgp_had_set_data(nmgp_ctx* c, const double* x, const int* indx, const double* y, int N, int M) {
+    if (!c) return NMGP_E_NULL;
+    if (!x || !indx || !y) return nmgp_fail(c, NMGP_E_NULL, "nmgp_had_set_data: x, indx and y must not be NULL");
+    if (N <= 0 || M <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "nmgp_had_set_data: N=%d, M=%d must be positive", N, M);
+    if (M > NMGP_MAX_OUTPUTS)
+        return nmgp_fail(c, NMGP_E_UNSUPPORTED, "nmgp_had_set_data: M=%d exceeds NMGP_MAX_OUTPUTS=%d", M, NMGP_MAX_OUTPUTS);
+    {
+        std::vector<char> seen(M, 0);
+        for (int i = 0; i < N; ++i) {
+            if (indx[i] < 0 || indx[i] >= M)
+                return nmgp_fail(c, NMGP_E_SHAPE, "nmgp_had_set_data: indx[%d] = %d is outside [0, %d)", i, indx[i], M);
+            seen[indx[i]] = 1;
+        }
+        for (int m = 0; m < M; ++m)
+            if (!seen[m]) return nmgp_fail(c, NMGP_E_SHAPE, "nmgp_had_set_data: output label %d of %d never occurs in indx", m, M);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    free_subject(c);
+    c->N = N;
+    c->M = M;
+    c->T = M * (M + 1) / 2;
+    c->n = N;
+    c->P_svc = (long long)((size_t)N * (1 + c->T) + 1);
+    NMGP_TRY(nmgp_dev_alloc(c, &c->d_x, (size_t)N));
+    NMGP_TRY(nmgp_dev_alloc(c, &c->had_y, (size_t)N));
+    HIP_TRY(c, hipMalloc((void**)&c->had_indx, (size_t)N * sizeof(int)));
+    c->had = true;
+    HIP_TRY(c, hipMemcpyAsync(c->d_x, x, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->had_y, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->had_indx, indx, (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->last_kind = 0;
+    return 0;
+}
+
 int nmgp_ensure_S(nmgp_ctx* c) {
     const size_t n = c->n;
     // rows: n (matrix) + 1 (right-hand side y) + n (identity -> L^-T, gradient path); even leading dimension
@@ -453,7 +497,7 @@ int nmgp_chol_factor(nmgp_ctx* c, double* A, int ld, int n, int extra, int* d_in
 
 // ---- nonseparable objective --------------------------------------------------------------------
 static int svc_enqueue(nmgp_ctx* c, const double hyper[8], int prior, int want_grad) {
-    if (!c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called before evaluating");
+    if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called before evaluating");
     if (!hyper) return nmgp_fail(c, NMGP_E_NULL, "hyper must not be NULL");
     HIP_TRY(c, hipSetDevice(c->device));
     NMGP_TRY(nmgp_ensure_S(c));
@@ -709,7 +753,7 @@ static void free_batch(nmgp_ctx* c) {
 
 extern "C" int nmgp_svc_batch_alloc(nmgp_ctx* c, int B) {
     if (!c) return NMGP_E_NULL;
-    if (!c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
+    if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
     if (B <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "batch size must be positive");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1398,7 +1442,7 @@ extern "C" int nmgp_svc_batch_prior_apply(nmgp_ctx* c, const double hyper[8], in
 extern "C" int nmgp_sep_prior_apply(nmgp_ctx* c, const double hyper[9], int trans, int B, const double* in, double* out) {
     if (!c) return NMGP_E_NULL;
     if (!hyper || !in || !out) return nmgp_fail(c, NMGP_E_NULL, "NULL argument");
-    if (!c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
+    if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
     if (B <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "B must be positive");
     HIP_TRY(c, hipSetDevice(c->device));
     const int N = c->N, T = c->T;

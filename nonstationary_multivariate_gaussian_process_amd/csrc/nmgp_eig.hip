@@ -442,7 +442,7 @@ int kron_likelihood_with_retry(nmgp_ctx* c, EigWork& w, int M, int N, double sig
 }
 
 int require_data(nmgp_ctx* c) {
-    if (!c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called before evaluating");
+    if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called before evaluating");
     return 0;
 }
 

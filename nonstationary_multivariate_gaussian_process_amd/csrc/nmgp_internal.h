@@ -74,6 +74,11 @@ struct nmgp_ctx {
     double* d_x = nullptr;   // [N]
     double* d_Y = nullptr;   // [N, M] row-major
     double* d_y = nullptr;   // [n] output-major
+    // Hadamard subject (nmgp_had_set_data): N single observations (x_i, indx_i, y_i); d_x / N / M / T as above, n = N.  While it is
+    // resident the complete-data entries refuse to run (nmgp_complete_subject), and the other way round
+    bool had = false;
+    int* had_indx = nullptr; // [N] output label of each observation
+    double* had_y = nullptr; // [N]
     // nonseparable state
     long long P_svc = 0;
     double* d_pars = nullptr;   // [P]  (largest of the three parameter layouts)
@@ -181,6 +186,8 @@ struct nmgp_ctx {
 };
 
 int nmgp_fail(nmgp_ctx* ctx, int code, const char* fmt, ...);
+// a complete-data subject (nmgp_set_data: every output observed at every input) is resident
+inline bool nmgp_complete_subject(const nmgp_ctx* c) { return c->d_x != nullptr && !c->had; }
 // helpers shared between the translation units (defined in nmgp_api.hip)
 int nmgp_dev_alloc(nmgp_ctx* c, double** p, size_t nelem);
 int nmgp_scratch_get(nmgp_ctx* c, int slot, size_t nelem, double** out);

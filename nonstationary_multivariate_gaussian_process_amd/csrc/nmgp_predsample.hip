@@ -239,7 +239,7 @@ extern "C" int nmgp_predsample_svc(nmgp_ctx* c, const double* pars, int H, const
     if (!pars || !hyper || !xs || !mean || !var) return nmgp_fail(c, NMGP_E_NULL, "null argument");
     if (H <= 0 || S <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "H and S must be positive (H=%d, S=%d)", H, S);
     if (z && star_in) return nmgp_fail(c, NMGP_E_STATE, "with star_in given the regression is skipped: z must be NULL");
-    if (!c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
+    if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
     if (c->chol_algo != 1)
         return nmgp_fail(c, NMGP_E_UNSUPPORTED, "posterior-draw prediction runs on the custom factorisation only (riding rows)");
     HIP_TRY(c, hipSetDevice(c->device));

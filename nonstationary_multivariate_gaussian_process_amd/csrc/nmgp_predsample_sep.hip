@@ -159,7 +159,7 @@ int predsample_kron(nmgp_ctx* c, bool stationary, const double* pars, int H, con
     if (!pars || !xs || !mean || !var || (!stationary && !hyper)) return nmgp_fail(c, NMGP_E_NULL, "null argument");
     if (H <= 0 || S <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "H and S must be positive (H=%d, S=%d)", H, S);
     if (z && star_in) return nmgp_fail(c, NMGP_E_STATE, "with star_in given the regression is skipped: z must be NULL");
-    if (!c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
+    if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
     if (c->chol_algo != 1 || c->sep_algo != 1)
         return nmgp_fail(c, NMGP_E_UNSUPPORTED, "posterior-draw prediction runs on the custom factorisation of the M blocks only "
                                                 "(riding rows): not under NMGP_CHOL=rocsolver or NMGP_SEP=eig");

@@ -1036,6 +1036,61 @@ class BatchedHMCSeparable(LockStepHMC):
         return samples, {"accept_rate": accepted / sample_size, "energy_error": energy_err}
 
 
+# ---- Hadamard form of the nonseparable model (irregularly observed outputs) -------------------------------------------------------
+SVC_HYPER_KEYS = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_L", "beta_L", "a", "b")
+
+
+class _HadamardSubject:
+    """One Hadamard subject (x [N], indx [N], y [N]) on a context: the batched objective of ``hadamard.nlogpos_obj_hadamard_SVC``."""
+
+    def _bind(self, x, indx, y, hyper_pars, ctx):
+        from . import _lib
+        self.ctx = ctx if ctx is not None else _lib.default_context()
+        self.hyper = np.array([float(hyper_pars[k]) for k in SVC_HYPER_KEYS])
+        self.x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        self.indx = np.ascontiguousarray(np.asarray(indx).reshape(-1), dtype=np.int32)
+        self.y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+
+    def _eval(self, P):
+        self.ctx.had_set_data(self.x, self.indx, self.y)       # (a no-op while this subject is the resident one)
+        return self.ctx.had_batch_eval(P, self.hyper, True, True)
+
+
+class HadamardMAP(_HadamardSubject, LockStepMAP):
+    """B restarts of the MAP loop on ``logpos.nlogpos_obj_hadamard_SVC`` in lock-step: host-side Adam (the arithmetic of
+    ``torch.optim.Adam``, row by row), every iteration ONE ``nmgp_had_batch_eval`` for all restarts.  ``init_pars`` [B, N(1+T)+1]."""
+
+    def __init__(self, x, indx, y, hyper_pars, init_pars, lr=2e-1, ctx=None):
+        LockStepMAP.__init__(self, init_pars, lr=lr)
+        self._bind(x, indx, y, hyper_pars, ctx)
+
+    def value_and_grad(self, P):
+        return self._eval(P)
+
+
+class BatchedHMCHadamard(_HadamardSubject, LockStepHMC):
+    """B independent HMC chains of the Hadamard nonseparable model of one subject in lock-step: every leapfrog step evaluates
+    ``logpos.nlogpos_obj_hadamard_SVC`` and its gradient for all chains with one ``nmgp_had_batch_eval``.  The leapfrog update
+    runs on the host; identity, diagonal or dense mass matrix through the base class.  Chain b reproduces a one-chain run
+    started from the same state with seed ``seed + b``."""
+
+    def __init__(self, x, indx, y, hyper_pars, init_positions, step_size=1e-4, num_steps_in_leap=20, seed=None, ctx=None, M=None,
+                 Minv=None):
+        LockStepHMC.__init__(self, init_positions, step_size, num_steps_in_leap, seed, M, Minv)
+        if self.mass_kind >= 3:
+            raise NotImplementedError("the prior-factor metrics belong to the complete-data models")
+        self._bind(x, indx, y, hyper_pars, ctx)
+
+    def potential_and_grad(self, q):
+        """U [B] and dU/dq [B, P]; a chain whose covariance is not positive definite (or not finite) gets U = inf."""
+        out, g, status = self._eval(q)
+        U = out[:, 0].copy()
+        bad = (status != 0) | ~np.isfinite(U)
+        U[bad] = np.inf
+        g[bad] = 0.0
+        return U, g
+
+
 # ---- the whole recipe behind one call ---------------------------------------------------------------------------------------------
 def _sample_recipe(polish, build_metric, make_sampler, pars0, chains, iters, warm, warm_step, windows, window_iters, step_size,
                    step_candidates, target_accept, progress, segment):

@@ -1,0 +1,165 @@
+"""Hadamard form of the nonseparable model behind the reference's signatures: irregularly observed outputs.
+
+The data are N single observations ``(x[i], indx[i], y[i])``, ``indx[i]`` naming the output measured at ``x[i]`` (longitudinal
+measurements where each output has its own time stamps), instead of a complete ``Y[N, M]``.  Served here:
+
+* ``nlogpos_obj_hadamard_SVC`` / ``logpos_hadamard_SVC`` (reference ``Utility/logpos.py:566-659``): value and gradient from one
+  device evaluation (``nmgp_had_batch_eval``), attached to autograd like ``logpos.nlogpos_obj_SVC``;
+* ``point_predmap_SVC_hadamard`` / ``pointwise_predmap_SVC_hadamard`` (``Utility/prediction.py:1401-1478``): all grid points from
+  one device call (``nmgp_predict_had``), nothing printed per grid point;
+* ``generate_K_index_SVC_hadamard0`` (``logpos.py:121-124``) as a host helper.
+
+``M`` is inferred from ``indx`` as the reference does (the number of distinct labels), so the labels must be 0 .. M-1 and each
+must occur.  The parameter vector is ``[tilde_l (N) | L_vecs (N T) | tilde_sigma2_err]``; ``L_vecs`` enters ``vec2lowtriangle``
+as it is (no exp on the diagonal slots).
+
+Not provided: ``indexedpoint_predmap_SVC_hadamard`` / ``test_predmap_SVC_hadamard`` (INTEGRATION.md says why), the
+``predsample_hadamard`` families and the separable / stationary Hadamard objectives.
+
+The names are opt-in behind the reference's module names: with ``NMGP_HADAMARD=1`` in the environment ``Utility.logpos`` /
+``Utility.prediction`` serve them; otherwise they keep resolving to the user's checkout.  Importing this module directly always
+works.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+
+LOGPOS_NAMES = ("nlogpos_obj_hadamard_SVC", "logpos_hadamard_SVC", "generate_K_index_SVC_hadamard0")
+PREDICTION_NAMES = ("point_predmap_SVC_hadamard", "pointwise_predmap_SVC_hadamard")
+
+
+def enabled():
+    """NMGP_HADAMARD=1: ``Utility.logpos`` / ``Utility.prediction`` serve the names of this module."""
+    return os.environ.get("NMGP_HADAMARD", "") not in ("", "0")
+
+
+def _f(v):
+    return float(v.detach()) if isinstance(v, torch.Tensor) else float(v)
+
+
+def _np(t):
+    if isinstance(t, torch.Tensor):
+        t = t.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(t, dtype=np.float64))
+
+
+def _labels(indx):
+    if isinstance(indx, torch.Tensor):
+        indx = indx.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(indx).reshape(-1).astype(np.int32))
+
+
+def _as_tensor(v):
+    return v if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64)
+
+
+def generate_K_index_SVC_hadamard0(L_f_list, indexes):
+    """R R^T with R[i] = row indexes[i] of L_f_list[i] ([N, N]); reference logpos.py:121-124.  (The device objective never
+    materialises this matrix; the function is kept for callers that want it.)"""
+    L = torch.stack([L_f[int(index), :] for L_f, index in zip(L_f_list, indexes)])
+    return torch.mm(L, L.t())
+
+
+class _HadamardObjective(torch.autograd.Function):
+    """Value + gradient of the Hadamard objective from one C-ABI call: forward(flags, hyper, x, indx, y, tilde_l, L_vecs,
+    tilde_sigma2_err) -> (res, loglik, lp_tilde_l, lp_L_vecs, lp_sigma2_err), ``res`` the log posterior (NOT negated), the rest
+    non-differentiable.  The gradient is computed in the forward call whenever a parameter requires grad and autograd is
+    recording at the call site (see ``Utility.logpos._FusedObjective``)."""
+
+    @staticmethod
+    def forward(fctx, flags, hyper, x, indx, y, *pieces):
+        prior, grad_mode = flags
+        c = _lib.default_context()
+        c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
+        flat = np.concatenate([_np(p).reshape(-1) for p in pieces])
+        want_grad = bool(grad_mode) and any(isinstance(p, torch.Tensor) and p.requires_grad for p in pieces)
+        out, grad, status = c.had_batch_eval(flat[None], hyper, prior, want_grad)
+        if status[0] != 0:
+            # torch.inverse raises on a singular covariance (reference logpos.py:623)
+            raise RuntimeError("nlogpos_obj_hadamard_SVC: the covariance is not positive definite or not finite (status %d)"
+                               % int(status[0]))
+        fctx.shapes = [tuple(p.shape) if isinstance(p, torch.Tensor) else None for p in pieces]
+        fctx.grad_np = grad[0] if want_grad else None          # d NegLog / d pars
+        res = [torch.tensor(-float(out[0, 0]), dtype=torch.float64)]
+        res += [torch.tensor(float(v), dtype=torch.float64) for v in out[0, 1:]]
+        fctx.mark_non_differentiable(*res[1:])
+        return tuple(res)
+
+    @staticmethod
+    def backward(fctx, gres, *unused):
+        g = fctx.grad_np
+        outs = [None] * 5
+        if g is None:
+            return tuple(outs + [None] * len(fctx.shapes))
+        scale = -float(gres)          # grad_np is for NegLog = -res
+        k = 0
+        for shp in fctx.shapes:
+            if shp is None:
+                outs.append(None)
+                k += 1
+                continue
+            cnt = int(np.prod(shp)) if len(shp) else 1
+            outs.append(torch.from_numpy(g[k:k + cnt] * scale).type(torch.DoubleTensor).reshape(shp))
+            k += cnt
+        return tuple(outs)
+
+
+def nlogpos_obj_hadamard_SVC(pars, x, indx, y, mu_tilde_l=0., alpha_tilde_l=1., beta_tilde_l=1., mu_L=0., alpha_L=1., beta_L=1.,
+                             a=1, b=1, verbose=False, Prior=True):
+    """Negative log posterior of the Hadamard nonseparable model on the flat parameter vector [tilde_l | L_vecs |
+    tilde_sigma2_err]; verbose=True returns (NegLog, loglik, lp_tilde_l, lp_L_vecs, lp_sigma2_err).  reference logpos.py:566-585."""
+    N = y.size(0)
+    M = torch.unique(indx).size(0)
+    T = int(M * (M + 1) / 2)
+    tilde_l, L_vecs, tilde_sigma2_err = pars[:N], pars[N: N + N * T], pars[-1]
+    if verbose:
+        res, loglik, lp_l, lp_L, lp_s2 = logpos_hadamard_SVC(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, mu_tilde_l,
+                                                             alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L, a, b, verbose,
+                                                             Prior)
+        return -res, loglik, lp_l, lp_L, lp_s2
+    return -logpos_hadamard_SVC(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L,
+                                alpha_L, beta_L, a, b, verbose, Prior)
+
+
+def logpos_hadamard_SVC(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L,
+                        beta_L, a, b, verbose=False, Prior=True):
+    """Log joint posterior of the Hadamard nonseparable model; reference logpos.py:588-659.  One device evaluation: covariance
+    K_x o (R R^T) + sigma2 I of the N observations, blocked Cholesky, cached-factor GP priors on tilde_l and on the T raw
+    L_vecs columns, and -- when a parameter requires grad -- the analytic adjoint."""
+    hyper = [_f(mu_tilde_l), _f(alpha_tilde_l), _f(beta_tilde_l), _f(mu_L), _f(alpha_L), _f(beta_L), _f(a), _f(b)]
+    res = _HadamardObjective.apply((bool(Prior), torch.is_grad_enabled()), hyper, x, indx, y, _as_tensor(tilde_l),
+                                   _as_tensor(L_vecs), _as_tensor(tilde_sigma2_err))
+    return res if verbose else res[0]
+
+
+def _predict(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, xs, mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L):
+    c = _lib.default_context()
+    c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
+    hyper = [_f(mu_tilde_l), _f(alpha_tilde_l), _f(beta_tilde_l), _f(mu_L), _f(alpha_L), _f(beta_L), 1.0, 1.0]
+    pars = np.concatenate([_np(tilde_l).reshape(-1), _np(L_vecs).reshape(-1), _np(tilde_sigma2_err).reshape(-1)])
+    mean, var, _ = c.predict_had(pars, hyper, _np(xs).reshape(-1))
+    sd = np.sqrt(var)
+    pct = np.stack([mean - 1.96 * sd, mean, mean + 1.96 * sd], axis=1)          # [S, 3, M]
+    return torch.from_numpy(np.ascontiguousarray(pct)).type(torch.DoubleTensor)
+
+
+def point_predmap_SVC_hadamard(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, x_star, mu_tilde_l, alpha_tilde_l, beta_tilde_l,
+                               mu_L, alpha_L, beta_L, *args, **kwargs):
+    """[mu - 1.96 s, mu, mu + 1.96 s] of all M outputs at x_star ([3, M]); reference prediction.py:1401-1465."""
+    return _predict(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, x_star, mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L,
+                    alpha_L, beta_L)[0]
+
+
+def pointwise_predmap_SVC_hadamard(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, grids, *args, **kwargs):
+    """All grid points from one device call ([G, 3, M]); reference prediction.py:1467-1478, which forwards ``*args, **kwargs``
+    (the six GP-prior hyper-parameters, positionally or by keyword) to ``point_predmap_SVC_hadamard``."""
+    names = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_L", "beta_L")
+    vals = list(args[:6])
+    for k in names[len(vals):]:
+        if k not in kwargs:
+            raise TypeError("point_predmap_SVC_hadamard() missing required argument: %r" % k)
+        vals.append(kwargs[k])
+    return _predict(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, grids, *vals)

@@ -18,7 +18,8 @@ def main():
     prev_end = None
     for r in ev:
         s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
-        name = r["Kernel_Name"].replace("void ", "").split("(")[0][-40:]
+        # (kernels of an anonymous namespace are named "(anonymous namespace)::k_...": drop the prefix before cutting at the "(")
+        name = r["Kernel_Name"].replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0][-40:]
         agg[name].append((e - s) * 1e-3)
         if prev_end is not None and s > prev_end:
             gaps += (s - prev_end) * 1e-3
