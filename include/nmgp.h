@@ -92,6 +92,24 @@ int nmgp_had_covariance(nmgp_ctx* ctx, const double* pars, double* out);
 int nmgp_predict_had(nmgp_ctx* ctx, const double* pars, const double hyper[8], const double* xs, int S, double* mean, double* var,
                      double* star);
 
+/* ---- Hadamard form of the separable model: one cross-output matrix shared by all observations ----
+ * logpos.nlogpos_obj_hadamard / logpos_hadamard (logpos.py:465-563), prediction.point_predmap_hadamard / pointwise_predmap_hadmard
+ * (prediction.py:710-808).  The subject is the one nmgp_had_set_data made resident (NMGP_E_STATE otherwise).
+ * pars = [tilde_l (N) | tilde_sigma (N) | L_vec (T) | tilde_sigma2_err], P = 2N+T+1; the L_vec slots are taken as they are (no exp).
+ * hyper[9] = {mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_tilde_sigma, alpha_tilde_sigma, beta_tilde_sigma, a, b, c}. */
+/* B parameter vectors pars [B, P] in one launch sequence, chunked as nmgp_had_batch_eval.  out6 [B, 6] = the verbose tuples
+ * (NegLog, loglik, log_prior_tilde_l, log_prior_tilde_sigma, log_prior_L_vec, log_prior_sigma2_err; the last is the UNNORMALISED
+ * inverse gamma); grad [B, P] = d NegLog / d pars, or NULL; status [B] and the failure semantics as for nmgp_had_batch_eval: a
+ * failing chain has a NaN row in out6 and a zero row in grad, and the call still returns 0. */
+int nmgp_hads_batch_eval(nmgp_ctx* ctx, const double* pars, int B, const double hyper[9], int prior, double* out6, double* grad,
+                         int* status);
+/* out [N, N]: the full symmetric covariance K_x o (R R^T) + sigma2 I of one parameter vector. */
+int nmgp_hads_covariance(nmgp_ctx* ctx, const double* pars, double* out);
+/* MAP prediction of all M outputs at the new inputs xs [S]: mean, var [S, M] (a variance <= 0 is replaced by 1e-6);
+ * star [S, 2] = the regressed tilde_l* and tilde_sigma*, or NULL. */
+int nmgp_predict_hads(nmgp_ctx* ctx, const double* pars, const double hyper[9], const double* xs, int S, double* mean, double* var,
+                      double* star);
+
 /* ---- nonseparable ("SVC") objective:  logpos.nlogpos_obj_SVC / logpos_SVC, logpos.py:299-380 -- */
 /* hyper[8] = {mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L, a, b}.
  * out5 = {NegLog, loglik, log_prior_tilde_l, log_prior_uL_vecs, log_prior_sigma2_err} (the verbose tuple).

@@ -239,9 +239,11 @@ def deviance(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, Y, x):
 
 def __getattr__(name):
     """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py); the Hadamard objective
-    of the nonseparable model from ``..hadamard`` with ``NMGP_HADAMARD=1`` in the environment (opt-in, read at every look-up)."""
-    from .. import hadamard
-    if name in hadamard.LOGPOS_NAMES and hadamard.enabled():
-        return getattr(hadamard, name)
+    of the nonseparable model from ``..hadamard`` with ``NMGP_HADAMARD=1`` in the environment, that of the separable model from
+    ``..hadamard_sep`` with ``NMGP_HADAMARD_SEP=1`` (opt-in, each read at every look-up)."""
+    from .. import hadamard, hadamard_sep
+    for mod in (hadamard, hadamard_sep):
+        if name in mod.LOGPOS_NAMES and mod.enabled():
+            return getattr(mod, name)
     from . import _overlay
     return _overlay.module_getattr(__name__, name)

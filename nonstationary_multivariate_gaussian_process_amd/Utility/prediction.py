@@ -11,9 +11,10 @@ served under this module's name only with ``NMGP_PREDSAMPLE=1`` in the environme
 user's checkout, as every name outside the mirrored path does.  The separable and stationary posterior-draw families
 (``*_predsample``, ``*_predmap_sampling``, ``*_predsample_S``) live in ``...predsample_sep`` under the same opt-in.
 The MAP predictors of the Hadamard nonseparable model (irregularly observed outputs: ``point_`` / ``pointwise_predmap_SVC_hadamard``,
-:1401-1478) live in ``...hadamard`` and are served under this module's name only with ``NMGP_HADAMARD=1``.  The other Hadamard
-names (``indexedpoint_`` / ``test_predmap_SVC_hadamard``, the ``predsample_hadamard`` families, the separable and stationary
-variants) keep resolving to the user's checkout.
+:1401-1478) live in ``...hadamard`` and are served under this module's name only with ``NMGP_HADAMARD=1``; those of the Hadamard
+separable model (``point_predmap_hadamard`` / ``pointwise_predmap_hadmard``, :710-808) live in ``...hadamard_sep`` and are served only
+with ``NMGP_HADAMARD_SEP=1``.  The other Hadamard names (``indexedpoint_`` / ``test_predmap_SVC_hadamard`` and ``_hadamard``, the
+``predsample_hadamard`` families, the stationary ``*_hadamard_S`` variants) keep resolving to the user's checkout.
 """
 import numpy as np
 import torch
@@ -116,9 +117,10 @@ def test_predmap_S(tilde_l, tilde_sigma, uL_vec, tilde_sigma2_err, Y, x, test_x,
 
 def __getattr__(name):
     """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py)."""
-    from .. import hadamard, predsample, predsample_sep
-    if name in hadamard.PREDICTION_NAMES and hadamard.enabled():
-        return getattr(hadamard, name)
+    from .. import hadamard, hadamard_sep, predsample, predsample_sep
+    for mod in (hadamard, hadamard_sep):
+        if name in mod.PREDICTION_NAMES and mod.enabled():
+            return getattr(mod, name)
     for mod in (predsample, predsample_sep):
         if name in mod.NAMES and predsample.enabled():
             return getattr(mod, name)

@@ -82,6 +82,9 @@ SIGNATURES = {
     "nmgp_had_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_had_covariance": (I, [V, P, P]),
     "nmgp_predict_had": (I, [V, P, P, P, I, P, P, P]),
+    "nmgp_hads_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_hads_covariance": (I, [V, P, P]),
+    "nmgp_predict_hads": (I, [V, P, P, P, I, P, P, P]),
     "nmgp_predsample_svc": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sep": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sta": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
@@ -703,6 +706,51 @@ class Context:
         S = xs.shape[0]
         mean, var, star = np.empty((S, self.M)), np.empty((S, self.M)), np.empty((S, 1 + self.T))
         self.check(self.lib.nmgp_predict_had(self.h, ptr(pars), ptr(hyper), ptr(xs), S, ptr(mean), ptr(var), ptr(star)))
+        return mean, var, star
+
+    # -- Hadamard form of the separable model (the resident subject is had_set_data's) -------------
+    def _hads_len(self):
+        return 2 * self.N + self.T + 1
+
+    def hads_batch_eval(self, pars, hyper, prior=True, want_grad=False):
+        """B parameter vectors [tilde_l | tilde_sigma | L_vec | tilde_sigma2_err] of the resident Hadamard subject in one launch
+        sequence: pars [B, 2N+T+1] (or one vector), hyper [9] -> (out [B, 6], grad [B, P] or None, status [B]: 0, a leading-minor
+        index or NUM_NAN; a failing chain has a NaN row and a zero gradient row)."""
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        P_ = self._hads_len()
+        if pars.ndim != 2 or pars.shape[1] != P_:
+            raise NmgpError("parameters must be [B, 2N+T+1 = %d], got %s" % (P_, pars.shape))
+        hyper = as_f64(hyper).reshape(-1)
+        if hyper.shape[0] != 9:
+            raise NmgpError("hyper must have 9 entries, got %d" % hyper.shape[0])
+        B = pars.shape[0]
+        out = np.empty((B, 6))
+        grad = np.empty((B, P_)) if want_grad else None
+        status = np.zeros(B, dtype=np.int32)
+        self.check(self.lib.nmgp_hads_batch_eval(self.h, ptr(pars), B, ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
+                                                 status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out, grad, status
+
+    def hads_covariance(self, pars):
+        pars = as_f64(pars).reshape(-1)
+        if pars.shape[0] != self._hads_len():
+            raise NmgpError("bad parameter vector length %d (2N+T+1 = %d)" % (pars.shape[0], self._hads_len()))
+        out = np.empty((self.N, self.N))
+        self.check(self.lib.nmgp_hads_covariance(self.h, ptr(pars), ptr(out)))
+        return out
+
+    def predict_hads(self, pars, hyper, xs):
+        """(mean [S, M], var [S, M], star [S, 2] = tilde_l*, tilde_sigma*) of the resident Hadamard subject at the new inputs xs."""
+        pars, hyper, xs = as_f64(pars).reshape(-1), as_f64(hyper).reshape(-1), as_f64(xs).reshape(-1)
+        if pars.shape[0] != self._hads_len():
+            raise NmgpError("bad parameter vector length %d (2N+T+1 = %d)" % (pars.shape[0], self._hads_len()))
+        if hyper.shape[0] != 9:
+            raise NmgpError("hyper must have 9 entries, got %d" % hyper.shape[0])
+        S = xs.shape[0]
+        mean, var, star = np.empty((S, self.M)), np.empty((S, self.M)), np.empty((S, 2))
+        self.check(self.lib.nmgp_predict_hads(self.h, ptr(pars), ptr(hyper), ptr(xs), S, ptr(mean), ptr(var), ptr(star)))
         return mean, var, star
 
     # -- measurement ----------------------------------------------------------------------------

@@ -24,9 +24,6 @@ namespace {
 
 inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
-// scratch slots of the context (nmgp_eig.hip numbers them; an entry of this file never runs inside one of that file)
-enum { HSL_SMALL = 13, HSL_SLAB = 14, HSL_PRED = 15 };
-
 // ell = exp(tilde_l);  Rv[i, 0..M) = row c_i of L_i, zero-padded (the slots are taken as they are: no exp)
 __global__ void k_had_prep(const double* __restrict__ pars, const int* __restrict__ indx, int N, int M, int T,
                            double* __restrict__ ell, double* __restrict__ Rv) {
@@ -322,6 +319,9 @@ int had_crosscov_rows(hipStream_t s, const double* x, const double* ell, const d
     return 0;
 }
 
+}  // namespace
+
+// (the next three are shared with nmgp_hadamard_sep.hip: declared in nmgp_internal.h)
 int require_had(nmgp_ctx* c) {
     if (!c->had || !c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_data must be called first (the resident subject is not a Hadamard one)");
     if (c->chol_algo != 1)
@@ -330,7 +330,7 @@ int require_had(nmgp_ctx* c) {
 }
 
 // the two cached prior factors (the cache is a vector: the second look-up may move its elements, so the first is re-resolved)
-int had_priors(nmgp_ctx* c, const double hyper[8], PriorFactor** pl, PriorFactor** pL) {
+int had_priors(nmgp_ctx* c, const double* hyper, PriorFactor** pl, PriorFactor** pL) {
     NMGP_TRY(nmgp_get_prior(c, hyper[1], hyper[2], pl));
     NMGP_TRY(nmgp_get_prior(c, hyper[4], hyper[5], pL));
     NMGP_TRY(nmgp_get_prior(c, hyper[1], hyper[2], pl));
@@ -360,6 +360,8 @@ int had_prior_solve(nmgp_ctx* c, hipStream_t sp, rocblas_handle hb, bool trans, 
     }
     return 0;
 }
+
+namespace {
 
 // device workspace of a chunk of B chains, in doubles (every piece at an even offset)
 struct HadLayout {

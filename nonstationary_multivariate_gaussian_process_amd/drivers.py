@@ -1043,10 +1043,12 @@ SVC_HYPER_KEYS = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_
 class _HadamardSubject:
     """One Hadamard subject (x [N], indx [N], y [N]) on a context: the batched objective of ``hadamard.nlogpos_obj_hadamard_SVC``."""
 
+    HYPER_KEYS = SVC_HYPER_KEYS
+
     def _bind(self, x, indx, y, hyper_pars, ctx):
         from . import _lib
         self.ctx = ctx if ctx is not None else _lib.default_context()
-        self.hyper = np.array([float(hyper_pars[k]) for k in SVC_HYPER_KEYS])
+        self.hyper = np.array([float(hyper_pars[k]) for k in self.HYPER_KEYS])
         self.x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         self.indx = np.ascontiguousarray(np.asarray(indx).reshape(-1), dtype=np.int32)
         self.y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
@@ -1089,6 +1091,45 @@ class BatchedHMCHadamard(_HadamardSubject, LockStepHMC):
         U[bad] = np.inf
         g[bad] = 0.0
         return U, g
+
+
+# ---- Hadamard form of the separable model (one cross-output matrix shared by all observations) -------------------------------------
+class _HadamardSepSubject(_HadamardSubject):
+    """One Hadamard subject on a context under the separable model: the batched objective of ``hadamard_sep.nlogpos_obj_hadamard``."""
+
+    HYPER_KEYS = SEP_HYPER_KEYS
+
+    def _eval(self, P):
+        self.ctx.had_set_data(self.x, self.indx, self.y)       # (a no-op while this subject is the resident one)
+        return self.ctx.hads_batch_eval(P, self.hyper, True, True)
+
+
+class HadamardSepMAP(_HadamardSepSubject, LockStepMAP):
+    """B restarts of the MAP loop on ``logpos.nlogpos_obj_hadamard`` in lock-step: host-side Adam (the arithmetic of
+    ``torch.optim.Adam``, row by row), every iteration ONE ``nmgp_hads_batch_eval`` for all restarts.  ``init_pars`` [B, 2N+T+1]."""
+
+    def __init__(self, x, indx, y, hyper_pars, init_pars, lr=2e-1, ctx=None):
+        LockStepMAP.__init__(self, init_pars, lr=lr)
+        self._bind(x, indx, y, hyper_pars, ctx)
+
+    def value_and_grad(self, P):
+        return self._eval(P)
+
+
+class BatchedHMCHadamardSep(_HadamardSepSubject, LockStepHMC):
+    """B independent HMC chains of the separable Hadamard model of one subject in lock-step: every leapfrog step evaluates
+    ``logpos.nlogpos_obj_hadamard`` and its gradient for all chains with one ``nmgp_hads_batch_eval``.  The leapfrog update runs on
+    the host; identity, diagonal or dense mass matrix through the base class.  Chain b reproduces a one-chain run started from the
+    same state with seed ``seed + b``."""
+
+    def __init__(self, x, indx, y, hyper_pars, init_positions, step_size=1e-4, num_steps_in_leap=20, seed=None, ctx=None, M=None,
+                 Minv=None):
+        LockStepHMC.__init__(self, init_positions, step_size, num_steps_in_leap, seed, M, Minv)
+        if self.mass_kind >= 3:
+            raise NotImplementedError("the prior-factor metrics belong to the complete-data models")
+        self._bind(x, indx, y, hyper_pars, ctx)
+
+    potential_and_grad = BatchedHMCHadamard.potential_and_grad
 
 
 # ---- the whole recipe behind one call ---------------------------------------------------------------------------------------------

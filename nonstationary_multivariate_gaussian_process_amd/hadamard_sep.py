@@ -1,0 +1,136 @@
+"""Hadamard form of the separable model behind the reference's signatures: irregularly observed outputs, one cross-output matrix.
+
+The data are N single observations ``(x[i], indx[i], y[i])`` as in ``hadamard.py``.  Where that module's model gives every
+observation its own lower triangle (P = N(1+T)+1), this one has ONE ``B_f = L L^T`` shared by all locations and a nonstationary
+amplitude ``tilde_sigma``: ``pars = [tilde_l (N) | tilde_sigma (N) | L_vec (T) | tilde_sigma2_err]``, P = 2N+T+1.  Served here:
+
+* ``nlogpos_obj_hadamard`` / ``logpos_hadamard`` (reference ``Utility/logpos.py:465-563``): value and gradient from one device
+  evaluation (``nmgp_hads_batch_eval``), attached to autograd through one ``torch.autograd.Function``;
+* ``point_predmap_hadamard`` / ``pointwise_predmap_hadmard`` (``Utility/prediction.py:710-808``; the second name is the
+  reference's spelling, ``pointwise_predmap_hadamard`` is offered as an alias): all grid points from one device call
+  (``nmgp_predict_hads``), nothing printed per grid point.
+
+Quirks of the reference that are kept:
+
+* the verbose tuple has SIX entries (NegLog, loglik, lp_tilde_l, lp_tilde_sigma, lp_L_vec, lp_sigma2_err);
+* ``L_vec`` enters ``vec2lowtriangle`` as it is (no exp on the diagonal slots) and carries ``Normal(0, c)`` on every raw slot, with
+  ``c`` rounded to float32 as torch does for a Python number;
+* the inverse gamma on sigma2 is the UNNORMALISED one (``inverse_gamma_logpdf_u``);
+* the prior term of the predictive variance is ``B_f[m, m] (sigma*^2 + 1e-6)``: the jitter of ``Nonstationary_RBF_cov`` sits inside
+  it, while the cross-covariance carries none.
+
+``M`` is inferred from ``indx`` as the reference does (the number of distinct labels), so the labels must be 0 .. M-1 and each
+must occur.  The reference forms S^-1 of the predictor through ``symeig``; here it is the blocked Cholesky with riding rows.
+
+Not provided: the stationary ``*_hadamard_S`` names, ``indexedpoint_predmap_hadamard`` / ``test_predmap_hadamard`` and the
+``predsample_hadamard`` families.
+
+The names are opt-in behind the reference's module names: with ``NMGP_HADAMARD_SEP=1`` in the environment ``Utility.logpos`` /
+``Utility.prediction`` serve them; otherwise they keep resolving to the user's checkout (``NMGP_HADAMARD=1`` alone does not serve
+them).  Importing this module directly always works.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .hadamard import _HadamardObjective, _as_tensor, _f, _labels, _np
+
+LOGPOS_NAMES = ("nlogpos_obj_hadamard", "logpos_hadamard")
+PREDICTION_NAMES = ("point_predmap_hadamard", "pointwise_predmap_hadmard", "pointwise_predmap_hadamard")
+
+
+def enabled():
+    """NMGP_HADAMARD_SEP=1: ``Utility.logpos`` / ``Utility.prediction`` serve the names of this module."""
+    return os.environ.get("NMGP_HADAMARD_SEP", "") not in ("", "0")
+
+
+class _HadamardSepObjective(torch.autograd.Function):
+    """Value + gradient of the separable Hadamard objective from one C-ABI call: forward(flags, hyper, x, indx, y, tilde_l,
+    tilde_sigma, L_vec, tilde_sigma2_err) -> (res, loglik, lp_tilde_l, lp_tilde_sigma, lp_L_vec, lp_sigma2_err), ``res`` the log
+    posterior (NOT negated), the rest non-differentiable.  The gradient is computed in the forward call whenever a parameter
+    requires grad and autograd is recording at the call site."""
+
+    @staticmethod
+    def forward(fctx, flags, hyper, x, indx, y, *pieces):
+        prior, grad_mode = flags
+        c = _lib.default_context()
+        c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
+        flat = np.concatenate([_np(p).reshape(-1) for p in pieces])
+        want_grad = bool(grad_mode) and any(isinstance(p, torch.Tensor) and p.requires_grad for p in pieces)
+        out, grad, status = c.hads_batch_eval(flat[None], hyper, prior, want_grad)
+        if status[0] != 0:
+            # torch.inverse raises on a singular covariance (reference logpos.py:528)
+            raise RuntimeError("nlogpos_obj_hadamard: the covariance is not positive definite or not finite (status %d)"
+                               % int(status[0]))
+        fctx.shapes = [tuple(p.shape) if isinstance(p, torch.Tensor) else None for p in pieces]
+        fctx.grad_np = grad[0] if want_grad else None          # d NegLog / d pars
+        res = [torch.tensor(-float(out[0, 0]), dtype=torch.float64)]
+        res += [torch.tensor(float(v), dtype=torch.float64) for v in out[0, 1:]]
+        fctx.mark_non_differentiable(*res[1:])
+        return tuple(res)
+
+    # the parameter pieces follow five non-tensor arguments, as in hadamard._HadamardObjective: one scatter serves both
+    backward = staticmethod(_HadamardObjective.backward)
+
+
+def nlogpos_obj_hadamard(pars, x, indx, y, mu_tilde_l=0., alpha_tilde_l=1., beta_tilde_l=1., mu_tilde_sigma=0., alpha_tilde_sigma=1.,
+                         beta_tilde_sigma=1., a=1, b=1, c=10, verbose=False, Prior=True):
+    """Negative log posterior of the separable Hadamard model on the flat parameter vector [tilde_l | tilde_sigma | L_vec |
+    tilde_sigma2_err]; verbose=True returns the six-entry tuple (NegLog, loglik, lp_tilde_l, lp_tilde_sigma, lp_L_vec,
+    lp_sigma2_err).  reference logpos.py:465-499."""
+    N = y.size(0)
+    M = torch.unique(indx).size(0)
+    T = int(M * (M + 1) / 2)
+    tilde_l, tilde_sigma, L_vec, tilde_sigma2_err = pars[:N], pars[N: 2 * N], pars[2 * N: 2 * N + T], pars[-1]
+    if verbose:
+        res, loglik, lp_l, lp_s, lp_L, lp_s2 = logpos_hadamard(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, mu_tilde_l,
+                                                               alpha_tilde_l, beta_tilde_l, mu_tilde_sigma, alpha_tilde_sigma,
+                                                               beta_tilde_sigma, a, b, c, verbose, Prior)
+        return -res, loglik, lp_l, lp_s, lp_L, lp_s2
+    return -logpos_hadamard(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, mu_tilde_l, alpha_tilde_l, beta_tilde_l,
+                            mu_tilde_sigma, alpha_tilde_sigma, beta_tilde_sigma, a, b, c, verbose, Prior)
+
+
+def logpos_hadamard(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, mu_tilde_l, alpha_tilde_l, beta_tilde_l,
+                    mu_tilde_sigma, alpha_tilde_sigma, beta_tilde_sigma, a, b, c, verbose=False, Prior=True):
+    """Log joint posterior of the separable Hadamard model; reference logpos.py:502-563.  One device evaluation: covariance
+    K_x o (R R^T) + sigma2 I of the N observations (R[i] = row indx[i] of the shared L), blocked Cholesky, cached-factor GP priors
+    on tilde_l and tilde_sigma, and -- when a parameter requires grad -- the analytic adjoint."""
+    hyper = [_f(mu_tilde_l), _f(alpha_tilde_l), _f(beta_tilde_l), _f(mu_tilde_sigma), _f(alpha_tilde_sigma), _f(beta_tilde_sigma),
+             _f(a), _f(b), _f(c)]
+    res = _HadamardSepObjective.apply((bool(Prior), torch.is_grad_enabled()), hyper, x, indx, y, _as_tensor(tilde_l),
+                                      _as_tensor(tilde_sigma), _as_tensor(L_vec), _as_tensor(tilde_sigma2_err))
+    return res if verbose else res[0]
+
+
+def _predict(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, xs, mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_tilde_sigma,
+             alpha_tilde_sigma, beta_tilde_sigma):
+    c = _lib.default_context()
+    c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
+    hyper = [_f(mu_tilde_l), _f(alpha_tilde_l), _f(beta_tilde_l), _f(mu_tilde_sigma), _f(alpha_tilde_sigma), _f(beta_tilde_sigma),
+             1.0, 1.0, 1.0]
+    pars = np.concatenate([_np(tilde_l).reshape(-1), _np(tilde_sigma).reshape(-1), _np(L_vec).reshape(-1),
+                           _np(tilde_sigma2_err).reshape(-1)])
+    mean, var, _ = c.predict_hads(pars, hyper, _np(xs).reshape(-1))
+    sd = np.sqrt(var)
+    pct = np.stack([mean - 1.96 * sd, mean, mean + 1.96 * sd], axis=1)          # [S, 3, M]
+    return torch.from_numpy(np.ascontiguousarray(pct)).type(torch.DoubleTensor)
+
+
+def point_predmap_hadamard(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, x_star, mu_tilde_l, alpha_tilde_l, beta_tilde_l,
+                           mu_tilde_sigma, alpha_tilde_sigma, beta_tilde_sigma, *args, **kwargs):
+    """[mu - 1.96 s, mu, mu + 1.96 s] of all M outputs at x_star ([3, M]); reference prediction.py:710-785."""
+    return _predict(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, x_star, mu_tilde_l, alpha_tilde_l, beta_tilde_l,
+                    mu_tilde_sigma, alpha_tilde_sigma, beta_tilde_sigma)[0]
+
+
+def pointwise_predmap_hadmard(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, grids, mu_tilde_l, alpha_tilde_l,
+                              beta_tilde_l, mu_tilde_sigma, alpha_tilde_sigma, beta_tilde_sigma, *args, **kwargs):
+    """All grid points from one device call ([G, 3, M]); reference prediction.py:787-808 (its spelling of the name)."""
+    return _predict(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, grids, mu_tilde_l, alpha_tilde_l, beta_tilde_l,
+                    mu_tilde_sigma, alpha_tilde_sigma, beta_tilde_sigma)
+
+
+pointwise_predmap_hadamard = pointwise_predmap_hadmard
