@@ -356,6 +356,25 @@ int nmgp_predsample_sep(nmgp_ctx* ctx, const double* pars /*[H,2N+T+1]*/, int H,
                         double* star_out, int* status);
 int nmgp_predsample_sta(nmgp_ctx* ctx, const double* pars /*[H,T+3]*/, int H, const double* xs /*[S]*/, int S, double* mean,
                         double* var, int* status);
+/* The same for the separable Hadamard model (prediction.point_ / pointwise_ / indexedpoint_ / test_predsample_hadamard,
+ * prediction.py:461-707): H parameter vectors of the subject nmgp_had_set_data made resident (NMGP_E_STATE otherwise; pars and
+ * hyper as for nmgp_hads_batch_eval), S new inputs.  The covariance depends on the draw only, so a chunk of B draws is ONE
+ * batched factorisation of B matrices of order N with y and the cross-covariance rows of the draw's own starred values riding.
+ *   indx_star == NULL: all M outputs at every new input; mean, var: [H,S,M]; slices of max(1, N / M) grid points.
+ *   indx_star [S]    : output indx_star[s] only at xs[s] (the indexed family); mean, var: [H,S]; slices of N points.  A label
+ *                      outside [0, M) is NMGP_E_SHAPE.
+ * z, star_in, star_out: [H,S,2] (tilde_l*, tilde_sigma*, before exp) as for nmgp_predsample_sep; z == NULL gives the conditional
+ * means; with star_in the regression is skipped and z must be NULL.  var = B_f[m,m] (sigma*^2 + 1e-6) - |L_S^-1 k_f|^2 +
+ * sigma2_err; a conditional variance < 0 and a predictive variance <= 0 are replaced by 1e-6.  status [H] (or NULL): 0, a
+ * leading-minor index, NMGP_NUM_NAN (also for a parameter vector that is not finite); a failing draw has NaN rows and the call
+ * still returns 0.  Chunking by NMGP_PREDSAMPLE_SLAB_GB / NMGP_PREDSAMPLE_CHUNK with 8 (N + 1 + E) ld bytes per draw, E the riding
+ * rows of a slice; the workspace is the entry's own (a pending nmgp_hads_batch_eval result stays valid).  H draws in one call give
+ * the bits of H single-draw calls; one draw with z == NULL and indx_star == NULL is nmgp_predict_hads's predictor.
+ * NMGP_E_SHAPE if one draw's factorisation buffer reaches 2^31 elements (the row reduction and the row kernels shared with the
+ * other entries take in-matrix positions as 32-bit integers). */
+int nmgp_predsample_hads(nmgp_ctx* ctx, const double* pars /*[H,2N+T+1]*/, int H, const double hyper[9], const double* xs /*[S]*/,
+                         const int* indx_star /*[S] or NULL*/, int S, const double* z, const double* star_in, double* mean,
+                         double* var, double* star_out, int* status);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Per-stage HIP-event timing on the context's stream (bench.py roofline figures).  Stages: */

@@ -13,8 +13,12 @@ user's checkout, as every name outside the mirrored path does.  The separable an
 The MAP predictors of the Hadamard nonseparable model (irregularly observed outputs: ``point_`` / ``pointwise_predmap_SVC_hadamard``,
 :1401-1478) live in ``...hadamard`` and are served under this module's name only with ``NMGP_HADAMARD=1``; those of the Hadamard
 separable model (``point_predmap_hadamard`` / ``pointwise_predmap_hadmard``, :710-808) live in ``...hadamard_sep`` and are served only
-with ``NMGP_HADAMARD_SEP=1``.  The other Hadamard names (``indexedpoint_`` / ``test_predmap_SVC_hadamard`` and ``_hadamard``, the
-``predsample_hadamard`` families, the stationary ``*_hadamard_S`` variants) keep resolving to the user's checkout.
+with ``NMGP_HADAMARD_SEP=1``.  The posterior-draw families of the Hadamard separable model (``point_`` / ``pointwise_`` /
+``indexedpoint_`` / ``test_predsample_hadamard``, :461-707) and the MAP forms of its indexed predictor
+(``indexedpoint_predmap_hadamard`` / ``test_predmap_harmard``, :810-908, with ``test_predmap_hadamard`` as an alias) live in
+``...predsample_hadamard`` and are served only with ``NMGP_PREDSAMPLE_HADAMARD=1``, a switch of its own: none of ``NMGP_HADAMARD``,
+``NMGP_HADAMARD_SEP`` and ``NMGP_PREDSAMPLE`` serves them.  The other Hadamard names (``indexedpoint_`` /
+``test_predmap_SVC_hadamard``, the stationary ``*_hadamard_S`` variants) keep resolving to the user's checkout.
 """
 import numpy as np
 import torch
@@ -117,10 +121,12 @@ def test_predmap_S(tilde_l, tilde_sigma, uL_vec, tilde_sigma2_err, Y, x, test_x,
 
 def __getattr__(name):
     """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py)."""
-    from .. import hadamard, hadamard_sep, predsample, predsample_sep
+    from .. import hadamard, hadamard_sep, predsample, predsample_hadamard, predsample_sep
     for mod in (hadamard, hadamard_sep):
         if name in mod.PREDICTION_NAMES and mod.enabled():
             return getattr(mod, name)
+    if name in predsample_hadamard.NAMES and predsample_hadamard.enabled():
+        return getattr(predsample_hadamard, name)
     for mod in (predsample, predsample_sep):
         if name in mod.NAMES and predsample.enabled():
             return getattr(mod, name)

@@ -88,6 +88,7 @@ SIGNATURES = {
     "nmgp_predsample_svc": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sep": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sta": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_predsample_hads": (I, [V, P, I, P, P, ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_profile_enable": (I, [V, I]),
     "nmgp_profile_read": (I, [V, P, c_ll_p]),
     "nmgp_profile_reset": (I, [V]),
@@ -752,6 +753,50 @@ class Context:
         mean, var, star = np.empty((S, self.M)), np.empty((S, self.M)), np.empty((S, 2))
         self.check(self.lib.nmgp_predict_hads(self.h, ptr(pars), ptr(hyper), ptr(xs), S, ptr(mean), ptr(var), ptr(star)))
         return mean, var, star
+
+    def predsample_hads(self, pars_hist, hyper, xs, indx_star=None, z=None, star=None):
+        """Posterior-draw prediction of the separable HADAMARD model: pars_hist [H, 2N+T+1] of the resident Hadamard subject at the
+        new inputs xs [S].  indx_star=None: all M outputs at every input, moments [H, S, M]; indx_star [S]: output indx_star[s] only
+        at xs[s] (the reference's indexed family), moments [H, S].  z [H, S, 2]: standard normals of the latent regression of
+        (tilde_l*, tilde_sigma*) (None: the conditional means); star [H, S, 2]: starred values to use instead of regressing (z must
+        then be None).  Returns (mean, var, star [H, S, 2], status [H]); a draw with non-zero status has NaN rows."""
+        pars = as_f64(pars_hist)
+        if pars.ndim == 1:
+            pars = pars[None]
+        P_ = self._hads_len()
+        if pars.ndim != 2 or pars.shape[1] != P_:
+            raise NmgpError("draws must be [H, 2N+T+1 = %d], got %s" % (P_, pars.shape))
+        hyper, xs = as_f64(hyper).reshape(-1), as_f64(xs).reshape(-1)
+        if hyper.shape[0] != 9:
+            raise NmgpError("hyper must have 9 entries, got %d" % hyper.shape[0])
+        H, S = pars.shape[0], xs.shape[0]
+        ia = None
+        if indx_star is not None:
+            if hasattr(indx_star, "detach"):
+                indx_star = indx_star.detach().cpu().numpy()
+            ia = np.ascontiguousarray(np.asarray(indx_star).reshape(-1).astype(np.int32))
+            if ia.shape[0] != S:
+                raise NmgpError("indx_star must have one label per new input (S=%d), got %d" % (S, ia.shape[0]))
+        if z is not None and star is not None:
+            raise NmgpError("star= replaces the regression: z must be None")
+        za = sa = None
+        for name, a in (("z", z), ("star", star)):
+            if a is not None:
+                a = as_f64(a)
+                if a.shape != (H, S, 2):
+                    raise NmgpError("%s must be [H=%d, S=%d, 2], got %s" % (name, H, S, a.shape))
+                if name == "z":
+                    za = a
+                else:
+                    sa = a
+        shape = (H, S, self.M) if ia is None else (H, S)
+        mean, var = np.empty(shape), np.empty(shape)
+        star_out = np.empty((H, S, 2))
+        status = np.zeros(H, dtype=np.int32)
+        ip = None if ia is None else ia.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        self.check(self.lib.nmgp_predsample_hads(self.h, ptr(pars), H, ptr(hyper), ptr(xs), ip, S, ptr(za), ptr(sa), ptr(mean),
+                                                 ptr(var), ptr(star_out), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return mean, var, star_out, status
 
     # -- measurement ----------------------------------------------------------------------------
     def profile_enable(self, on=True):

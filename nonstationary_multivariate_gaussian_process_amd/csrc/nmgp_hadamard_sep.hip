@@ -340,19 +340,6 @@ __global__ void k_hads_predvar(const double* __restrict__ star, const double* __
     var[k] = v;
 }
 
-#define NMGP_HADS_SWITCH(M, CALL)               \
-    switch (M) {                                \
-        case 1: { constexpr int MM = 1; CALL; } break; \
-        case 2: { constexpr int MM = 2; CALL; } break; \
-        case 3: { constexpr int MM = 3; CALL; } break; \
-        case 4: { constexpr int MM = 4; CALL; } break; \
-        case 5: { constexpr int MM = 5; CALL; } break; \
-        case 6: { constexpr int MM = 6; CALL; } break; \
-        case 7: { constexpr int MM = 7; CALL; } break; \
-        case 8: { constexpr int MM = 8; CALL; } break; \
-        default: return NMGP_E_UNSUPPORTED;     \
-    }
-
 void hads_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* sig, double* Rv, int batch) {
     NMGP_LAUNCH(k_hads_prep, dim3(cdiv(N, 256), batch), dim3(256), 0, s, pars, indx, N, M, M * (M + 1) / 2, ell, sig, Rv);
 }
@@ -520,6 +507,15 @@ int hads_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9
 
 }  // namespace
 
+// the batched pieces the posterior-draw entry (nmgp_predsample_hadamard.hip) shares with the objective
+void nmgp_hads_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* sig, double* Rv, int batch) {
+    hads_prep(s, pars, indx, N, M, ell, sig, Rv, batch);
+}
+int nmgp_hads_cov_build(hipStream_t s, const double* x, const double* ell, const double* sig, const double* Rv, const double* pars,
+                        long long P, double* S, int ld, int N, int M, int batch, long long sstride) {
+    return hads_cov_build(s, x, ell, sig, Rv, pars, P, S, ld, N, M, batch, sstride);
+}
+
 // B chains of the resident Hadamard subject under the separable model: pars [B, P] -> out6 [B, 6] (the verbose tuples), grad [B, P]
 // = d NegLog / d pars or NULL, status [B] (0, a leading-minor index, NMGP_NUM_NAN; a failing chain has a NaN row, a zero gradient
 // row, and does not fail the call).  The workspace is the entry's own, evaluated in chunks of chains below NMGP_HAD_BATCH_SLAB_GB
@@ -628,7 +624,9 @@ extern "C" int nmgp_predict_hads(nmgp_ctx* c, const double* pars, const double h
         if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
         set_row(s, buf, ld, N, c->had_y, N, 1, 0, 0);
         NMGP_TRY(hads_crosscov_rows(s, c->d_x, ell, sig, Rv, Lvec, N, M, d_xs, d_star, s0, Sc, buf, ld, N + 1));
-        nmgp_potrf(c, buf, ld, N, 1 + E, 0, info);
+        // the substitution-based panel kernels, as every batched entry: their bits do not depend on the schedule the batch size
+        // selects, so this predictor is nmgp_predsample_hads with one draw and no noise, bit for bit
+        nmgp_potrf(c, buf, ld, N, 1 + E, 0, info, 1, 0, 0, 1);
         ps_rows_reduce(s, buf, ld, 0, N, N + 1, N, E, part, 1, d_mean, d_colsq, 0, (long long)s0 * M);
     }
     NMGP_LAUNCH(k_hads_predvar, dim3(cdiv((long long)S * M, 256)), dim3(256), 0, s, d_star, Lvec, d_colsq, S, M, dP + (P - 1), d_var);

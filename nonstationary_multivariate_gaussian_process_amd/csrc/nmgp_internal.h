@@ -298,6 +298,24 @@ int had_priors(nmgp_ctx* c, const double* hyper, PriorFactor** p0, PriorFactor**
 // op(L) X = R for the 1 + T prior columns of every chain (column 0 against p0, the others against p1)
 int had_prior_solve(nmgp_ctx* c, hipStream_t sp, rocblas_handle hb, bool trans, PriorFactor* p0, PriorFactor* p1, double* R, int N,
                     int T, int B);
+// separable Hadamard model (nmgp_hadamard_sep.hip): ell = exp(tilde_l), sig = exp(tilde_sigma), Rv[i] = row c_i of the chain's L for
+// `batch` parameter vectors [batch, P]; S = K_x o (R R^T) + sigma2 I (lower, matrix z at S + z * sstride)
+void nmgp_hads_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* sig, double* Rv, int batch);
+int nmgp_hads_cov_build(hipStream_t s, const double* x, const double* ell, const double* sig, const double* Rv, const double* pars,
+                        long long P, double* S, int ld, int N, int M, int batch, long long sstride);
+// kernels templated over the number of outputs M <= 8
+#define NMGP_HADS_SWITCH(M, CALL)               \
+    switch (M) {                                \
+        case 1: { constexpr int MM = 1; CALL; } break; \
+        case 2: { constexpr int MM = 2; CALL; } break; \
+        case 3: { constexpr int MM = 3; CALL; } break; \
+        case 4: { constexpr int MM = 4; CALL; } break; \
+        case 5: { constexpr int MM = 5; CALL; } break; \
+        case 6: { constexpr int MM = 6; CALL; } break; \
+        case 7: { constexpr int MM = 7; CALL; } break; \
+        case 8: { constexpr int MM = 8; CALL; } break; \
+        default: return NMGP_E_UNSUPPORTED;     \
+    }
 
 // ---- kernel launchers (nmgp_kernels.hip) -------------------------------------------------------
 
@@ -458,6 +476,11 @@ void two_col_rhs_b(hipStream_t s, const double* pars, long long P, double mu_a, 
 // zrow, sqs[..] = |row (R0 + e)|^2 over the n columns, e < E, in a fixed order; part: batch * 2 * E * ceil(n / 128) doubles
 void ps_rows_reduce(hipStream_t s, const double* A, int ld, long long bstride, int n, int R0, int zrow, int E, double* part,
                     int batch, double* dots, double* sqs, long long ostride, long long o0);
+// ---- nmgp_predsample_sep.hip ----
+// starred values of B draws (k_pss_star): star[h, s, c] = mu_c + W_c[s] . (curve_c of draw h - mu_c) + sqrt(cv_c[s]) z[h, s, c];
+// z == nullptr: the conditional means
+void pss_star(hipStream_t s, const double* W0, const double* W1, const double* cv0, const double* cv1, const double* pars, long long P,
+              const double* z, int N, int S, double mu_l, double mu_s, double* star, int B);
 // ---- nmgp_chol.hip ----
 // C -= A A^T on the lower trapezoid.  finfo / fistride / goff: the launch also factors the diagonal block in its tile (0, 0) where
 // its shape allows (returned); hook: per-launch profiling.  Defaults: neither.

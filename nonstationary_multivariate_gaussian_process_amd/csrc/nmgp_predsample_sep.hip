@@ -146,6 +146,11 @@ __global__ void k_pss_combine(const double* __restrict__ dots, const double* __r
     var[(size_t)h * S * M + k] = v;
 }
 
+void pss_star(hipStream_t s, const double* W0, const double* W1, const double* cv0, const double* cv1, const double* pars, long long P,
+              const double* z, int N, int S, double mu_l, double mu_s, double* star, int B) {
+    NMGP_LAUNCH(k_pss_star, dim3(S, 2, B), dim3(256), 0, s, W0, W1, cv0, cv1, pars, P, z, N, S, mu_l, mu_s, star);
+}
+
 }  // namespace nmgpk
 
 namespace {
@@ -243,8 +248,7 @@ int predsample_kron(nmgp_ctx* c, bool stationary, const double* pars, int H, con
             sep_prep_b(s, d_pars, P, c->d_Y, d_small, sp, N, M, d_ell, d_sig, yt, Bc);
             if (regress) {
                 if (z) HIP_TRY(c, hipMemcpyAsync(d_z, z + (size_t)h0 * S2, Bc * S2 * sizeof(double), hipMemcpyHostToDevice, s));
-                NMGP_LAUNCH(k_pss_star, dim3(S, 2, Bc), dim3(256), 0, s, W0, W1, cv0, cv1, d_pars, P, d_z, N, S, hyper[0], hyper[3],
-                            d_star);
+                pss_star(s, W0, W1, cv0, cv1, d_pars, P, d_z, N, S, hyper[0], hyper[3], d_star, Bc);
             } else {
                 HIP_TRY(c, hipMemcpyAsync(d_star, star_in + (size_t)h0 * S2, Bc * S2 * sizeof(double), hipMemcpyHostToDevice, s));
             }

@@ -1259,7 +1259,8 @@ def summarize_posterior_predictive(mean, var, y_samples, tilde_l_star, status, q
     one sampled y* per draw; tilde_l_star: [H, S]; status: [H] (0 = the draw's covariance factored).  Draws with non-zero status
     are left out and counted.  Returns a dict: ``mean`` [S, M] (mean of the per-draw means), ``var`` [S, M] by the law of total
     variance (mean of the per-draw variances + variance of the per-draw means), ``quantiles`` [len(quantiles), S, M] of the
-    sampled y*, ``tilde_l_star`` [H_used, S], ``status`` [H], ``n_used``, ``n_failed``."""
+    sampled y*, ``tilde_l_star`` [H_used, S], ``status`` [H], ``n_used``, ``n_failed``.  The moments may also be [H, S] (one
+    output per new input, the indexed form of the Hadamard model): every summary then loses its last axis."""
     mean, var, y_samples = np.asarray(mean, dtype=np.float64), np.asarray(var, dtype=np.float64), np.asarray(y_samples, dtype=np.float64)
     status = np.asarray(status)
     ok = status == 0
@@ -1318,6 +1319,35 @@ def posterior_predict_separable(x, Y, hyper_pars, samples, xs, draws=None, seed=
     zy = rng.standard_normal((S_.shape[0], xs.shape[0], Y.shape[1]))
     ctx.set_data(x, Y)
     mean, var, star, status = ctx.predsample_sep(S_, hyper, xs, z=z, kss_jitter=True)
+    out = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
+    out["tilde_sigma_star"] = star[:, :, 1][status == 0]
+    return out
+
+
+def posterior_predict_hadamard_sep(x, indx, y, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, ctx=None):
+    """Posterior-predictive band of the separable HADAMARD model (irregularly observed outputs) from :class:`BatchedHMCHadamardSep`'s
+    draws -- what the reference's scripts do, commented out, with ``pointwise_predsample_hadamard`` / ``test_predsample_hadamard``:
+    ``samples`` [iters, chains, 2N+T+1] or [H, 2N+T+1], ``xs`` [S] the new inputs; ``draws`` thins the history evenly to that many.
+    ``indx_star=None`` predicts all M outputs at every new input (moments [S, M]); ``indx_star`` [S] predicts output
+    ``indx_star[s]`` only at ``xs[s]`` (held-out pairs; moments [S]).  Per draw and new input tilde_l* and tilde_sigma* are
+    regressed and sampled and y* is sampled (``seed``: NumPy generator of all the normals); all draws and inputs go through one
+    batched device call (``Context.predsample_hads``).  Returns :func:`summarize_posterior_predictive`'s dict plus
+    ``tilde_sigma_star`` [H_used, S]."""
+    from . import _lib
+    ctx = ctx if ctx is not None else _lib.default_context()
+    x, y = np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(y, dtype=np.float64).reshape(-1)
+    indx = np.ascontiguousarray(np.asarray(indx).reshape(-1), dtype=np.int32)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1)
+    S_ = np.asarray(samples, dtype=np.float64)
+    S_ = S_.reshape(-1, S_.shape[-1])
+    if draws is not None and int(draws) < S_.shape[0]:
+        S_ = S_[np.unique(np.round(np.linspace(0, S_.shape[0] - 1, int(draws))).astype(int))]
+    hyper = np.array([float(hyper_pars[k]) for k in SEP_HYPER_KEYS])
+    ctx.had_set_data(x, indx, y)
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal((S_.shape[0], xs.shape[0], 2))
+    zy = rng.standard_normal((S_.shape[0], xs.shape[0]) + (() if indx_star is not None else (ctx.M,)))
+    mean, var, star, status = ctx.predsample_hads(S_, hyper, xs, indx_star=indx_star, z=z)
     out = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
     out["tilde_sigma_star"] = star[:, :, 1][status == 0]
     return out
