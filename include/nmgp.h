@@ -110,6 +110,31 @@ int nmgp_hads_covariance(nmgp_ctx* ctx, const double* pars, double* out);
 int nmgp_predict_hads(nmgp_ctx* ctx, const double* pars, const double hyper[9], const double* xs, int S, double* mean, double* var,
                       double* star);
 
+/* ---- Hadamard form of the stationary model (logpos.nlogpos_obj_hadamard_S / logpos_hadamard_S, logpos.py:662-716;
+ * prediction.point_ / pointwise_predmap_S_hadamard, prediction.py:1695-1740): the LMC baseline on the subject nmgp_had_set_data
+ * made resident (NMGP_E_STATE otherwise).  pars = [tilde_l, tilde_sigma, L_vec (T raw slots: no exp), tilde_sigma2_err], P = T + 3;
+ * hyper[5] = {mu_tilde_l, sigma_tilde_l, a, b, c} as for nmgp_logpos_sta.  With l = exp(tilde_l), s = exp(tilde_sigma), B_f = L L^T,
+ * u = x / l:  S[i, j] = B_f[c_i, c_j] (s^2 exp(-(u_i - u_j)^2 / 2) + 1e-6 d_ij) + sigma2_err d_ij.  No GP prior: neither the prior
+ * factors nor the prior stream are used.  The three entries may be interleaved with the nmgp_had_* / nmgp_hads_* ones. */
+/* B chains: out5 [B, 5] = (NegLog, loglik without the 2 pi term, log_prior_tilde_l, log_prior_L_vec, log_prior_sigma2_err: the
+ * UNNORMALISED inverse gamma; tilde_sigma has no prior; the prior entries are reported whatever `prior` is); grad [B, T + 3] =
+ * d NegLog / d pars, or NULL; status [B] and the failure semantics as for nmgp_hads_batch_eval.  Chunks of chains below
+ * NMGP_HAD_BATCH_SLAB_GB; no summation order depends on B. */
+int nmgp_hadst_batch_eval(nmgp_ctx* ctx, const double* pars /*[B,T+3]*/, int B, const double hyper[5], int prior,
+                          double* out5 /*[B,5]*/, double* grad /*[B,T+3] or NULL*/, int* status /*[B]*/);
+/* out [N, N]: the full symmetric covariance S of one parameter vector. */
+int nmgp_hadst_covariance(nmgp_ctx* ctx, const double* pars, double* out /*[N,N]*/);
+/* Prediction at the new inputs xs [S] under H parameter vectors: H = 1 is the MAP predictor, H > 1 a chain of posterior draws (the
+ * model has no latent curve to regress: a draw is just another parameter vector).  A chunk of draws (nmgp_ps_chunk with
+ * (N + 1 + E) ld doubles per draw) is ONE batched factorisation with y and the slice's E cross-covariance rows riding.
+ *   indx_star == NULL: all M outputs at every new input; mean, var: [H,S,M]; slices of max(1, N / M) inputs.
+ *   indx_star [S]    : output indx_star[s] only at xs[s]; mean, var: [H,S]; slices of N inputs.  A label outside [0, M): NMGP_E_SHAPE.
+ * var = B_f[m, m] (s^2 + 1e-6) - |L_S^-1 k_f|^2 + sigma2_err, a value <= 0 replaced by 1e-6.  status [H] or NULL as for
+ * nmgp_predsample_hads; the workspace is the posterior-draw entries' (a pending batch result stays valid).  H draws in one call give
+ * the bits of H single calls.  NMGP_E_SHAPE if one draw's factorisation buffer reaches 2^31 elements. */
+int nmgp_predict_hadst(nmgp_ctx* ctx, const double* pars /*[H,T+3]*/, int H, const double* xs /*[S]*/,
+                       const int* indx_star /*[S] or NULL*/, int S, double* mean, double* var, int* status /*[H] or NULL*/);
+
 /* ---- nonseparable ("SVC") objective:  logpos.nlogpos_obj_SVC / logpos_SVC, logpos.py:299-380 -- */
 /* hyper[8] = {mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L, a, b}.
  * out5 = {NegLog, loglik, log_prior_tilde_l, log_prior_uL_vecs, log_prior_sigma2_err} (the verbose tuple).

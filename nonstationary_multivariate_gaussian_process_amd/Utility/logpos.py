@@ -240,9 +240,10 @@ def deviance(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, Y, x):
 def __getattr__(name):
     """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py); the Hadamard objective
     of the nonseparable model from ``..hadamard`` with ``NMGP_HADAMARD=1`` in the environment, that of the separable model from
-    ``..hadamard_sep`` with ``NMGP_HADAMARD_SEP=1`` (opt-in, each read at every look-up)."""
-    from .. import hadamard, hadamard_sep
-    for mod in (hadamard, hadamard_sep):
+    ``..hadamard_sep`` with ``NMGP_HADAMARD_SEP=1``, that of the stationary model from ``..hadamard_sta`` with
+    ``NMGP_HADAMARD_STA=1`` (opt-in, each read at every look-up)."""
+    from .. import hadamard, hadamard_sep, hadamard_sta
+    for mod in (hadamard, hadamard_sep, hadamard_sta):
         if name in mod.LOGPOS_NAMES and mod.enabled():
             return getattr(mod, name)
     from . import _overlay

@@ -17,8 +17,11 @@ with ``NMGP_HADAMARD_SEP=1``.  The posterior-draw families of the Hadamard separ
 ``indexedpoint_`` / ``test_predsample_hadamard``, :461-707) and the MAP forms of its indexed predictor
 (``indexedpoint_predmap_hadamard`` / ``test_predmap_harmard``, :810-908, with ``test_predmap_hadamard`` as an alias) live in
 ``...predsample_hadamard`` and are served only with ``NMGP_PREDSAMPLE_HADAMARD=1``, a switch of its own: none of ``NMGP_HADAMARD``,
-``NMGP_HADAMARD_SEP`` and ``NMGP_PREDSAMPLE`` serves them.  The other Hadamard names (``indexedpoint_`` /
-``test_predmap_SVC_hadamard``, the stationary ``*_hadamard_S`` variants) keep resolving to the user's checkout.
+``NMGP_HADAMARD_SEP`` and ``NMGP_PREDSAMPLE`` serves them.  The MAP predictors of the Hadamard stationary model (``point_`` /
+``pointwise_predmap_S_hadamard``, :1695-1740) live in ``...hadamard_sta`` and are served only with ``NMGP_HADAMARD_STA=1``.  The other
+Hadamard names (``indexedpoint_`` / ``test_predmap_SVC_hadamard``, ``indexedpoint_predmap_S_hadamard`` / ``test_predmap_S_hadamard``)
+keep resolving to the user's checkout whatever the switches: their variance takes output 0's prior variance for every label
+(INTEGRATION.md); ``hadamard_sta.indexed_predict`` is the corrected stationary form.
 """
 import numpy as np
 import torch
@@ -121,8 +124,8 @@ def test_predmap_S(tilde_l, tilde_sigma, uL_vec, tilde_sigma2_err, Y, x, test_x,
 
 def __getattr__(name):
     """Names outside the mirrored path come from the user's reference checkout (Utility/_overlay.py)."""
-    from .. import hadamard, hadamard_sep, predsample, predsample_hadamard, predsample_sep
-    for mod in (hadamard, hadamard_sep):
+    from .. import hadamard, hadamard_sep, hadamard_sta, predsample, predsample_hadamard, predsample_sep
+    for mod in (hadamard, hadamard_sep, hadamard_sta):
         if name in mod.PREDICTION_NAMES and mod.enabled():
             return getattr(mod, name)
     if name in predsample_hadamard.NAMES and predsample_hadamard.enabled():

@@ -85,6 +85,9 @@ SIGNATURES = {
     "nmgp_hads_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_covariance": (I, [V, P, P]),
     "nmgp_predict_hads": (I, [V, P, P, P, I, P, P, P]),
+    "nmgp_hadst_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_hadst_covariance": (I, [V, P, P]),
+    "nmgp_predict_hadst": (I, [V, P, I, P, ctypes.POINTER(ctypes.c_int), I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_svc": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sep": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sta": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
@@ -797,6 +800,63 @@ class Context:
         self.check(self.lib.nmgp_predsample_hads(self.h, ptr(pars), H, ptr(hyper), ptr(xs), ip, S, ptr(za), ptr(sa), ptr(mean),
                                                  ptr(var), ptr(star_out), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return mean, var, star_out, status
+
+    # -- Hadamard form of the stationary model (the resident subject is had_set_data's) -------------
+    def hadst_batch_eval(self, pars, hyper, prior=True, want_grad=False):
+        """B parameter vectors [tilde_l, tilde_sigma, L_vec, tilde_sigma2_err] of the resident Hadamard subject in one launch
+        sequence: pars [B, T+3] (or one vector), hyper [5] = (mu_tilde_l, sigma_tilde_l, a, b, c) -> (out [B, 5], grad [B, T+3] or
+        None, status [B]: 0, a leading-minor index or NUM_NAN; a failing chain has a NaN row and a zero gradient row)."""
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        P_ = self.T + 3
+        if pars.ndim != 2 or pars.shape[1] != P_:
+            raise NmgpError("parameters must be [B, T+3 = %d], got %s" % (P_, pars.shape))
+        hyper = as_f64(hyper).reshape(-1)
+        if hyper.shape[0] != 5:
+            raise NmgpError("hyper must have 5 entries, got %d" % hyper.shape[0])
+        B = pars.shape[0]
+        out = np.empty((B, 5))
+        grad = np.empty((B, P_)) if want_grad else None
+        status = np.zeros(B, dtype=np.int32)
+        self.check(self.lib.nmgp_hadst_batch_eval(self.h, ptr(pars), B, ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
+                                                  status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out, grad, status
+
+    def hadst_covariance(self, pars):
+        pars = as_f64(pars).reshape(-1)
+        if pars.shape[0] != self.T + 3:
+            raise NmgpError("bad parameter vector length %d (T+3 = %d)" % (pars.shape[0], self.T + 3))
+        out = np.empty((self.N, self.N))
+        self.check(self.lib.nmgp_hadst_covariance(self.h, ptr(pars), ptr(out)))
+        return out
+
+    def predict_hadst(self, pars, xs, indx_star=None):
+        """Prediction of the stationary HADAMARD model at the new inputs xs [S] under the parameter vectors pars [H, T+3] (one
+        vector: the MAP predictor with H = 1; a chain of posterior draws otherwise).  indx_star=None: all M outputs at every input,
+        moments [H, S, M]; indx_star [S]: output indx_star[s] only at xs[s], moments [H, S].  Returns (mean, var, status [H]); a draw
+        with non-zero status has NaN rows."""
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        if pars.ndim != 2 or pars.shape[1] != self.T + 3:
+            raise NmgpError("parameters must be [H, T+3 = %d], got %s" % (self.T + 3, pars.shape))
+        xs = as_f64(xs).reshape(-1)
+        H, S = pars.shape[0], xs.shape[0]
+        ia = None
+        if indx_star is not None:
+            if hasattr(indx_star, "detach"):
+                indx_star = indx_star.detach().cpu().numpy()
+            ia = np.ascontiguousarray(np.asarray(indx_star).reshape(-1).astype(np.int32))
+            if ia.shape[0] != S:
+                raise NmgpError("indx_star must have one label per new input (S=%d), got %d" % (S, ia.shape[0]))
+        shape = (H, S, self.M) if ia is None else (H, S)
+        mean, var = np.empty(shape), np.empty(shape)
+        status = np.zeros(H, dtype=np.int32)
+        ip = None if ia is None else ia.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        self.check(self.lib.nmgp_predict_hadst(self.h, ptr(pars), H, ptr(xs), ip, S, ptr(mean), ptr(var),
+                                               status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return mean, var, status
 
     # -- measurement ----------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -1,0 +1,609 @@
+// Hadamard form of the stationary model (the LMC baseline): irregularly observed outputs, ONE cross-output matrix and a stationary
+// RBF kernel (logpos.py:662-716, prediction.py:1695-1740).
+//
+// The subject is the Hadamard one (nmgp_had_set_data: N single observations (x_i, c_i, y_i)).  The parameter vector is
+// [tilde_l, tilde_sigma, L_vec (T), tilde_sigma2_err], P = T + 3 (vec2pars_S).  L = vec2lowtriangle(L_vec) is taken as it is (no exp on
+// the diagonal slots), B_f = L L^T, r_i = row c_i of L.  With l = exp(tilde_l), s2 = exp(tilde_sigma)^2, u = x / l
+//   S[i, j] = B_f[c_i, c_j] (s2 exp(-d_ij / 2) + 1e-6 d_ij) + sigma2_err d_ij,   d_ij = u_i^2 + u_j^2 - 2 u_i u_j   (kernels.py:20-43)
+// one dense N x N SPD matrix per evaluation: the jitter is multiplied by B_f[c_i, c_i].  Priors: Normal(mu, sd) on tilde_l, Normal(0, c)
+// on every raw L_vec slot, the unnormalised inverse gamma on sigma2_err; none on tilde_sigma.  There is no GP prior: neither the cached
+// prior factors nor the prior stream are touched.  The factorisation with its riding rows, the triangular matrix-vector product, the
+// inverse SYRK and the trace terms are the library's; this file adds the kernels around them and the entries.  A draw of the posterior
+// is just another parameter vector (no latent curve to regress), so ONE predictor serves the MAP and a chain of draws.
+// Layout conventions of nmgp_hadamard.hip: a 64 x 64 tile of observations per 256-thread workgroup, lanes along i, the j side in LDS,
+// blockIdx.z = chain; fixed summation order and no atomics, so B chains in one launch give the bits of B launches.
+#include "nmgp_internal.h"
+
+#include <algorithm>
+
+using namespace nmgpk;
+
+namespace {
+
+inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
+
+// B_f[a, b] = <row a of L, row b of L> of the packed lower triangle Lvec
+template <int M>
+__device__ inline double hadst_bf(const double* __restrict__ Lvec, int a, int b) {
+    const int lo = a < b ? a : b;
+    double acc = 0.0;
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+        if (m <= lo) acc += Lvec[a * (a + 1) / 2 + m] * Lvec[b * (b + 1) / 2 + m];
+    return acc;
+}
+
+// The chain's scalars, once per workgroup: sp = {l, s2, sigma2_err}, sB = B_f [M, M]; and the j side of the tile: su = x_j / l, sc = c_j.
+// The caller synchronises.
+template <int M>
+__device__ inline void hadst_stage(const double* __restrict__ pars, long long P, const double* __restrict__ x,
+                                   const int* __restrict__ indx, int N, int j0, double* sp, double* sB, double* su, int* sc) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const int j = j0 + tid;
+        const double l = exp(pars[0]);
+        su[tid] = (j < N) ? x[j] / l : 0.0;
+        sc[tid] = (j < N) ? indx[j] : 0;
+        if (tid == 0) {
+            const double sg = exp(pars[1]);
+            sp[0] = l;
+            sp[1] = sg * sg;
+            sp[2] = exp(pars[P - 1]);
+        }
+    } else if (tid - 64 < M * M) {
+        const int k = tid - 64;
+        sB[k] = hadst_bf<M>(pars + 2, k / M, k % M);
+    }
+}
+
+// S[i, j] = B_f[c_i, c_j] (s2 exp(-d_ij / 2) + jitter d_ij) + sigma2_err d_ij, lower triangle, column-major with leading dimension ld
+template <int M>
+__global__ __launch_bounds__(256) void k_hadst_cov(const double* __restrict__ x, const int* __restrict__ indx,
+                                                    const double* __restrict__ pars, long long P, double* __restrict__ S, int ld,
+                                                    int N, long long sstride) {
+    constexpr int TJ = 64;
+    __shared__ double su[TJ], sB[M * M], sp[3];
+    __shared__ int sc[TJ];
+    const int I = blockIdx.x, J = blockIdx.y;
+    if (I < J) return;
+    pars += (size_t)blockIdx.z * P;
+    S += (size_t)blockIdx.z * sstride;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    hadst_stage<M>(pars, P, x, indx, N, j0, sp, sB, su, sc);
+    __syncthreads();
+    const int i = I * 64 + lane;
+    if (i >= N) return;
+    const double s2 = sp[1], s2e = sp[2];
+    const double ui = x[i] / sp[0];
+    const double ui2 = ui * ui;
+    const double* bi = sB + indx[i] * M;
+#pragma unroll 2
+    for (int jj = 0; jj < TJ / 4; ++jj) {
+        const int k = w * (TJ / 4) + jj;
+        const int j = j0 + k;
+        if (j >= N) break;
+        if (i < j) continue;
+        const double uj = su[k];
+        const double dist = (ui2 + uj * uj) - 2.0 * (ui * uj);          // kernels.py:20
+        double kv = exp(-0.5 * dist) * s2;                              // kernels.py:42
+        if (i == j) kv = NMGP_JITTER + kv;                              // kernels.py:35
+        double v = kv * bi[sc[k]];
+        if (i == j) v += s2e;
+        S[(size_t)j * ld + i] = v;
+    }
+}
+
+// Adjoint of the likelihood, one pass over the FULL symmetric -S^-1 (what the inverse SYRK leaves):
+//   G = 1/2 (alpha alpha^T - S^-1),  e_ij = s2 exp(-d_ij / 2)
+//   a_l[i]  = sum_j G_ij B_f[c_i, c_j] e_ij d_ij          (summed over i: d loglik / d tilde_l)
+//   a_s[i]  = sum_j G_ij B_f[c_i, c_j] e_ij               (twice its sum: d loglik / d tilde_sigma)
+//   w_i[m]  = sum_j G_ij (e_ij + jitter d_ij) r_j[m]      (twice its sum over {i : c_i = c}: d loglik / d L[c, m])
+// Each wave takes 16 j; the four waves' sums meet in LDS in a fixed order and leave part[t][J][i] (component t: 0 = a_l, 1 = a_s,
+// 2 + m = w[m]; component-major, so that the stores here and the loads of k_hadst_grad_final run along i).
+template <int M>
+__global__ __launch_bounds__(256) void k_hadst_adjoint(const double* __restrict__ x, const int* __restrict__ indx,
+                                                        const double* __restrict__ pars, long long P,
+                                                        const double* __restrict__ alpha, const double* __restrict__ Sneg, int ld,
+                                                        int N, double* __restrict__ part, long long pstride) {
+    constexpr int TJ = 64;
+    __shared__ double su[TJ], sB[M * M], sp[3], sR[TJ * M], sa[TJ];
+    __shared__ int sc[TJ];
+    __shared__ double red[2][4][64];
+    const int I = blockIdx.x, J = blockIdx.y, NJ = gridDim.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    const size_t Ns = (size_t)N;
+    {   // blockIdx.z = chain
+        const size_t z = blockIdx.z;
+        pars += z * (size_t)P;
+        alpha += z * Ns;
+        Sneg += z * (size_t)ld * Ns;
+        part += z * (size_t)pstride;
+    }
+    hadst_stage<M>(pars, P, x, indx, N, j0, sp, sB, su, sc);
+    if (tid < TJ) sa[tid] = (j0 + tid < N) ? alpha[j0 + tid] : 0.0;
+    for (int k = tid; k < TJ * M; k += 256) {           // r_j = row c_j of L, zero-padded to M
+        const int j = j0 + k / M, m = k % M;
+        const int cj = (j < N) ? indx[j] : 0;
+        sR[k] = (j < N && m <= cj) ? pars[2 + cj * (cj + 1) / 2 + m] : 0.0;
+    }
+    __syncthreads();
+    const int i = I * 64 + lane;
+    const bool iv = i < N;
+    const int ic = iv ? i : N - 1;
+    const double s2 = sp[1], ai = alpha[ic];
+    const double ui = x[ic] / sp[0];
+    const double ui2 = ui * ui;
+    const double* bi = sB + indx[ic] * M;
+    double acc[M + 2];
+#pragma unroll
+    for (int t = 0; t < M + 2; ++t) acc[t] = 0.0;
+    if (iv) {
+        for (int jj = 0; jj < TJ / 4; ++jj) {
+            const int k = w * (TJ / 4) + jj;
+            const int j = j0 + k;
+            if (j >= N) break;
+            const double uj = su[k];
+            const double dist = (ui2 + uj * uj) - 2.0 * (ui * uj);
+            const double e = exp(-0.5 * dist) * s2;
+            const double G = 0.5 * (ai * sa[k] + Sneg[(size_t)j * ld + i]);
+            const double ge = G * e;
+            const double gk = (i == j) ? G * (NMGP_JITTER + e) : ge;
+            const double gb = ge * bi[sc[k]];
+            acc[0] = fma(gb, dist, acc[0]);
+            acc[1] += gb;
+#pragma unroll
+            for (int m = 0; m < M; ++m) acc[2 + m] = fma(gk, sR[k * M + m], acc[2 + m]);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < M + 2; ++t) {
+        red[t & 1][w][lane] = acc[t];
+        __syncthreads();
+        if (w == 0 && iv)
+            part[((size_t)t * NJ + J) * Ns + i] =
+                (red[t & 1][0][lane] + red[t & 1][1][lane]) + (red[t & 1][2][lane] + red[t & 1][3][lane]);
+    }
+}
+
+// Final gradient: one workgroup per (output slot t = blockIdx.x, chain = blockIdx.y).  Thread k walks the observations k, k + 256, ...
+// in index order, adds each one's NJ partials in order (for an L slot (c, m): of the observations with label c only), then the fixed
+// tree over the 256 threads.  No order depends on the batch.  Slot T + 2 is sigma2_err d loglik / d sigma2_err = sigma2_err tr G with
+// tr = {sum alpha^2, trace S^-1} (k_trace_terms).  Priors: Normal(mu, sd) on tilde_l, Normal(0, c) on the L slots (d lp / d v =
+// -(v - mean) / var), the inverse gamma + Jacobian on tilde_sigma2_err (distributions.py:116-124); none on tilde_sigma.
+__global__ __launch_bounds__(256) void k_hadst_grad_final(const double* __restrict__ part, long long pstride, int NJ, int N, int M,
+                                                           int T, const int* __restrict__ indx, const double* __restrict__ pars,
+                                                           const double* __restrict__ tr, double mu_l, double var_l, double var_c,
+                                                           double a, double b, int prior, double* __restrict__ grad) {
+    __shared__ double sh[256];
+    const int t = blockIdx.x, P = T + 3;
+    part += (size_t)blockIdx.y * (size_t)pstride;
+    pars += (size_t)blockIdx.y * P;
+    tr += (size_t)blockIdx.y * 2;
+    grad += (size_t)blockIdx.y * P;
+    if (t == P - 1) {                      // (uniform over the workgroup)
+        if (threadIdx.x == 0) {
+            const double sigma2 = exp(pars[P - 1]);
+            double g = sigma2 * (0.5 * (tr[0] - tr[1]));
+            if (prior) g += (-a - 1.0) + b / sigma2 + 1.0;
+            grad[P - 1] = -g;
+        }
+        return;
+    }
+    int comp = t, c = -1;                  // component of the partial rows; label of an L slot
+    if (t >= 2) {
+        const int tl = t - 2;
+        c = 0;
+        while ((c + 1) * (c + 2) / 2 <= tl) ++c;
+        comp = 2 + (tl - c * (c + 1) / 2);
+    }
+    const double* pc = part + (size_t)comp * NJ * N;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        if (c >= 0 && indx[i] != c) continue;
+        double sacc = 0.0;
+        for (int J = 0; J < NJ; ++J) sacc += pc[(size_t)J * N + i];
+        acc += sacc;
+    }
+    acc = block_sum_256(acc, sh);
+    if (threadIdx.x == 0) {
+        double g = (t == 0) ? acc : 2.0 * acc;
+        if (prior && t == 0) g -= (pars[0] - mu_l) / var_l;
+        if (prior && t >= 2) g -= pars[t] / var_c;
+        grad[t] = -g;
+    }
+}
+
+// Scalar epilogue (logpos.py:692-716): Normal(mu, sd).log_prob with the float32-rounded mean, variance and log sd that torch uses for
+// Python-number arguments (computed by the host as normal_logprob_f32 of nmgp_eig.hip does); loglik drops the 2 pi term
+// (distributions.multivariate_normal_logpdf); the three prior entries are reported whether or not `prior` adds them.
+__global__ void k_hadst_finalize(const double* __restrict__ scal, const double* __restrict__ pars, int T, double mu_l, double var_l,
+                                 double log_sd_l, double var_c, double log_sd_c, double a, double b, int prior,
+                                 double* __restrict__ out5) {
+    if (threadIdx.x != 0) return;
+    const int P = T + 3;
+    scal += (size_t)blockIdx.x * 16;             // blockIdx.x = chain: [0] log det, [1] quadratic form, [8..12] the verbose tuple
+    out5 += (size_t)blockIdx.x * 16;
+    pars += (size_t)blockIdx.x * P;
+    const double LOGSQRT2PI = log(sqrt(2.0 * M_PI));
+    const double tse = pars[P - 1];
+    const double sigma2 = exp(tse);
+    const double loglik = -0.5 * scal[0] - 0.5 * scal[1];
+    const double r = pars[0] - mu_l;
+    const double lp_l = -(r * r) / (2.0 * var_l) - log_sd_l - LOGSQRT2PI;
+    double lp_L = 0.0;
+    for (int t = 0; t < T; ++t) {
+        const double v = pars[2 + t];
+        lp_L += -(v * v) / (2.0 * var_c) - log_sd_c - LOGSQRT2PI;
+    }
+    const double lp_s2 = (-a - 1.0) * log(sigma2) - b / sigma2;
+    double res = 0.0;
+    res += loglik;
+    if (prior) {
+        res += lp_l;
+        res += lp_L;
+        res += lp_s2;
+        res += tse;
+    }
+    out5[0] = -res;
+    out5[1] = loglik;
+    out5[2] = lp_l;
+    out5[3] = lp_L;
+    out5[4] = lp_s2;
+}
+
+// Cross-covariances k_f[i, e] = B_f[m, c_i] s2 exp(-d(x_i, x*_s) / 2) (prediction.py:1711-1715; no jitter) of the new inputs s0 .. of
+// draw h = blockIdx.z, written as riding rows R0 + e below the covariance: the factorisation turns each into (L_S^-1 k_f[:, e])^T.
+// Observation i = blockIdx.x; lanes along the riding-row index (contiguous in a column).
+//   istar == nullptr: e = (s - s0) M + m;  else e = s - s0, m = istar[s]
+template <int M>
+__global__ __launch_bounds__(256) void k_hadst_cross_rows(const double* __restrict__ x, const int* __restrict__ indx,
+                                                           const double* __restrict__ pars, long long P, int N,
+                                                           const double* __restrict__ xs, const int* __restrict__ istar, int s0,
+                                                           int E, double* __restrict__ A, int ld, long long bstride, int R0) {
+    __shared__ double sBc[M], sp[3];
+    const int i = blockIdx.x, h = blockIdx.z;
+    pars += (size_t)h * P;
+    if (threadIdx.x == 0) {
+        const double sg = exp(pars[1]);
+        sp[0] = exp(pars[0]);
+        sp[1] = sg * sg;
+    } else if (threadIdx.x - 64 < (unsigned)M) {
+        sBc[threadIdx.x - 64] = hadst_bf<M>(pars + 2, threadIdx.x - 64, indx[i]);     // B_f[m, c_i]
+    }
+    __syncthreads();
+    const int e = blockIdx.y * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int s = istar ? s0 + e : s0 + e / M;
+    const int mp = istar ? istar[s] : e % M;
+    const double ui = x[i] / sp[0], uj = xs[s] / sp[0];
+    const double dist = (ui * ui + uj * uj) - 2.0 * (ui * uj);
+    A[(size_t)h * bstride + (size_t)i * ld + R0 + e] = sBc[mp] * (exp(-0.5 * dist) * sp[1]);
+}
+
+// var = B_f[m, m] (jitter + s2) - |L_S^-1 k_f|^2 + sigma2_err, a value <= 0 replaced by settings.precision (prediction.py:1719-1726:
+// the prior term is B_f kron RBF_cov(x*), which carries the jitter).  Draw h = blockIdx.y; O = S M outputs per draw (k = s M + m), or
+// O = S in the indexed form (k = s, m = istar[s]).
+__global__ void k_hadst_predvar(const double* __restrict__ pars, long long P, const double* __restrict__ colsq,
+                                const int* __restrict__ istar, int S, int M, double* __restrict__ var) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, h = blockIdx.y;
+    const int O = istar ? S : S * M;
+    if (k >= O) return;
+    const int mp = istar ? istar[k] : k % M;
+    pars += (size_t)h * P;
+    double b = 0.0;
+    for (int r = 0; r <= mp; ++r) {
+        const double v = pars[2 + mp * (mp + 1) / 2 + r];
+        b += v * v;
+    }
+    const double sg = exp(pars[1]);
+    const double kss = NMGP_JITTER + sg * sg;
+    double v = (b * kss - colsq[(size_t)h * O + k]) + exp(pars[P - 1]);
+    if (v <= 0.0) v = NMGP_PRECISION;
+    var[(size_t)h * O + k] = v;
+}
+
+int hadst_cov_build(hipStream_t s, const double* x, const int* indx, const double* pars, long long P, double* S, int ld, int N, int M,
+                    int batch, long long sstride) {
+    const dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);
+    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadst_cov<MM>), grid, dim3(256), 0, s, x, indx, pars, P, S, ld, N, sstride));
+    return 0;
+}
+
+int hadst_adjoint(hipStream_t s, const double* x, const int* indx, const double* pars, long long P, const double* alpha,
+                  const double* Sneg, int ld, int N, int M, double* part, long long pstride, int batch) {
+    const dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);      // -S^-1 of chain z: ld x N doubles further on
+    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadst_adjoint<MM>), grid, dim3(256), 0, s, x, indx, pars, P, alpha, Sneg, ld, N, part, pstride));
+    return 0;
+}
+
+int hadst_cross_rows(hipStream_t s, const double* x, const int* indx, const double* pars, long long P, int N, int M, const double* xs,
+                     const int* istar, int s0, int E, double* A, int ld, long long bstride, int R0, int B) {
+    const dim3 grid(N, cdiv(E, 256), B);
+    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadst_cross_rows<MM>), grid, dim3(256), 0, s, x, indx, pars, P, N, xs, istar, s0, E, A, ld,
+                                    bstride, R0));
+    return 0;
+}
+
+// Normal(mean, sd) with Python-number arguments: torch rounds both to float32, squares and takes the logarithm there
+struct NormalF32 {
+    double mean, var, log_sd;
+    NormalF32(double m, double sd) {
+        const float m32 = (float)m, s32 = (float)sd;
+        mean = (double)m32;
+        var = (double)(s32 * s32);
+        log_sd = (double)std::log(s32);
+    }
+};
+
+// device workspace of a chunk of B chains, in doubles (every piece at an even offset)
+struct HadstLayout {
+    size_t o_P, o_z, o_scal, o_info, o_S;
+    size_t o_alpha = 0, o_Sneg = 0, o_part = 0, o_grad = 0, o_tr = 0;
+    size_t total = 0, part_per = 0;
+    int ld = 0, xpad = 0, xoff = 0;
+    long long bs = 0;
+};
+
+HadstLayout hadst_layout(int B, int N, int M, int T, bool want_grad) {
+    HadstLayout L;
+    const size_t P = (size_t)T + 3, Bs = B, NJ = (N + 63) / 64;
+    // rows: N (matrix) + 1 (y); with gradients + pad + N identity rows (-> L^-T)
+    L.xpad = (N + 1) & 1;
+    L.xoff = N + 1 + L.xpad;
+    L.ld = (int)nmgp_ld(want_grad ? (size_t)2 * N + 2 : (size_t)N + 1);
+    L.bs = (long long)L.ld * N;
+    // adjoint partial rows; before that pass the same buffer holds the block sums of alpha = L^-T z (tri_gemv_upper)
+    L.part_per = std::max((size_t)(M + 2) * NJ * N, (size_t)N * ((N + 255) / 256));
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off += (n + 1) & ~(size_t)1; return o; };
+    L.o_P = take(Bs * P); L.o_z = take(Bs * N); L.o_scal = take(Bs * 16); L.o_info = take(Bs);
+    L.o_S = take(Bs * (size_t)L.bs);
+    if (want_grad) {
+        L.o_alpha = take(Bs * N); L.o_Sneg = take(Bs * (size_t)N * N); L.o_part = take(Bs * L.part_per);
+        L.o_grad = take(Bs * P); L.o_tr = take(Bs * 2);
+    }
+    L.total = off;
+    return L;
+}
+
+// chains [0, B) of `pars` (already offset by the caller): value and gradient halves enqueued back to back, ONE synchronisation
+int hadst_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[5], int prior, double* out5, double* grad,
+                     int* status) {
+    const int N = c->N, M = c->M, T = c->T;
+    const size_t P = (size_t)T + 3;
+    const bool want_grad = grad != nullptr;
+    const NormalF32 nl(hyper[0], hyper[1]), nc(0.0, hyper[4]);
+    const double a = hyper[2], b = hyper[3];
+    hipStream_t s = c->stream;
+    const HadstLayout L = hadst_layout(B, N, M, T, want_grad);
+    double* slab;
+    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
+    double *dP = slab + L.o_P, *z = slab + L.o_z, *scal = slab + L.o_scal, *S = slab + L.o_S;
+    int* info = reinterpret_cast<int*>(slab + L.o_info);
+    const int ld = L.ld;
+    const long long bs = L.bs;
+    HIP_TRY(c, hipMemcpyAsync(dP, pars, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)B * sizeof(int), s));
+    {
+        NmgpStage sp(c, NMGP_STAGE_COV);
+        int r = hadst_cov_build(s, c->d_x, c->had_indx, dP, (long long)P, S, ld, N, M, B, bs);
+        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+    }
+    {
+        NmgpStage sp(c, NMGP_STAGE_CHOL);
+        set_row(s, S, ld, N, c->had_y, N, B, bs, 0);                // y rides along as row N (shared by the chains)
+        if (want_grad) identity_rows(s, S, ld, N + 1, N, L.xpad, B, bs);
+        nmgp_potrf(c, S, ld, N, want_grad ? 1 + L.xpad : 1, want_grad ? N : 0, info, B, bs, 1);
+        get_row(s, S, ld, N, z, N, B, bs, N);                       // z = L^-1 y
+    }
+    {
+        NmgpStage sp(c, NMGP_STAGE_REDUCE);
+        chol_logdet_quad(s, S, ld, N, z, scal, scal + 1, B, bs, 16);
+        NMGP_LAUNCH(k_hadst_finalize, dim3(B), dim3(64), 0, s, scal, dP, T, nl.mean, nl.var, nl.log_sd, nc.var, nc.log_sd, a, b, prior,
+                    scal + 8);
+    }
+    std::vector<double> hs((size_t)B * 16);
+    std::vector<int> hi(B);
+    HIP_TRY(c, hipMemcpyAsync(hs.data(), scal, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(hi.data(), info, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (want_grad) {
+        // enqueued behind the value half without waiting for it (a chain that failed produces garbage here, which the epilogue discards)
+        double *alpha = slab + L.o_alpha, *Sneg = slab + L.o_Sneg, *part = slab + L.o_part, *dg = slab + L.o_grad, *tr = slab + L.o_tr;
+        const int NJ = (N + 63) / 64;
+        {
+            NmgpStage sp(c, NMGP_STAGE_SOLVE);
+            tri_gemv_upper(s, S + L.xoff, ld, N, z, alpha, part, B, bs, (long long)L.part_per);   // alpha = L^-T z = X z
+        }
+        {
+            NmgpStage sp(c, NMGP_STAGE_INVERSE);
+            syrk_lower(s, S + L.xoff, ld, Sneg, N, N, N, N, B, bs, (long long)N * N, 2);         // -S^-1 = -X X^T, both triangles
+        }
+        {
+            NmgpStage sp(c, NMGP_STAGE_ADJOINT);
+            trace_terms(s, alpha, Sneg, N, N, tr, -1.0, B);
+            int r = hadst_adjoint(s, c->d_x, c->had_indx, dP, (long long)P, alpha, Sneg, N, N, M, part, (long long)L.part_per, B);
+            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+            NMGP_LAUNCH(k_hadst_grad_final, dim3((unsigned)P, B), dim3(256), 0, s, part, (long long)L.part_per, NJ, N, M, T, c->had_indx,
+                        dP, tr, nl.mean, nl.var, nc.var, a, b, prior, dg);
+        }
+        HIP_TRY(c, hipMemcpyAsync(grad, dg, (size_t)B * P * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));          // the one synchronisation of the evaluation
+    NMGP_TRY(nmgp_take_launch_error(c));
+    for (int z_ = 0; z_ < B; ++z_) {
+        int st = hi[z_];
+        double* o = out5 + (size_t)z_ * 5;
+        for (int k = 0; k < 5; ++k) o[k] = hs[(size_t)z_ * 16 + 8 + k];
+        // a parameter vector that is not finite has no leading minor to blame: NMGP_NUM_NAN whatever pivot met the NaN first
+        bool finite_in = true;
+        for (size_t k = 0; k < P && finite_in; ++k) finite_in = std::isfinite(pars[(size_t)z_ * P + k]);
+        if (!finite_in || (st == 0 && (!std::isfinite(o[0]) || !std::isfinite(o[1])))) st = NMGP_NUM_NAN;
+        if (st != 0) {
+            for (int k = 0; k < 5; ++k) o[k] = std::nan("");
+            if (want_grad) std::fill(grad + (size_t)z_ * P, grad + (size_t)(z_ + 1) * P, 0.0);
+        }
+        status[z_] = st;
+    }
+    return 0;
+}
+
+}  // namespace
+
+// B chains of the resident Hadamard subject under the stationary model: pars [B, T + 3] -> out5 [B, 5] (the verbose tuples), grad
+// [B, T + 3] = d NegLog / d pars or NULL, status [B] (0, a leading-minor index, NMGP_NUM_NAN; a failing chain has a NaN row, a zero
+// gradient row, and does not fail the call).  hyper = {mu_tilde_l, sigma_tilde_l, a, b, c}.  The workspace is the entry's own,
+// evaluated in chunks of chains below NMGP_HAD_BATCH_SLAB_GB (default 96).
+extern "C" int nmgp_hadst_batch_eval(nmgp_ctx* c, const double* pars, int B, const double hyper[5], int prior, double* out5,
+                                     double* grad, int* status) {
+    if (!c) return NMGP_E_NULL;
+    if (!pars || !hyper || !out5 || !status) return nmgp_fail(c, NMGP_E_NULL, "pars/hyper/out5/status must not be NULL");
+    if (B <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "B must be positive");
+    NMGP_TRY(require_had(c));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->N, M = c->M, T = c->T;
+    const size_t P = (size_t)T + 3;
+    const bool want_grad = grad != nullptr;
+    double cap_gb = 96.0;
+    if (const char* e = std::getenv("NMGP_HAD_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
+    const size_t per_chain = hadst_layout(1, N, M, T, want_grad).total * sizeof(double);
+    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
+    Bc = std::min(Bc, 65535);                      // the chain is a grid dimension
+    if (Bc < 1)
+        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the stationary Hadamard model at N = %d needs %.1f GB of device workspace, "
+                         "above the NMGP_HAD_BATCH_SLAB_GB cap of %.0f GB", N, per_chain / 1e9, cap_gb);
+    for (int b0 = 0; b0 < B; b0 += Bc) {
+        const int nb = std::min(Bc, B - b0);
+        NMGP_TRY(hadst_batch_core(c, pars + (size_t)b0 * P, nb, hyper, prior, out5 + (size_t)b0 * 5,
+                                  want_grad ? grad + (size_t)b0 * P : nullptr, status + b0));
+    }
+    c->last_kind = 0;
+    return 0;
+}
+
+// out: [N, N] row-major, the full symmetric S = K_x o B_f[c, c] + sigma2_err I
+extern "C" int nmgp_hadst_covariance(nmgp_ctx* c, const double* pars, double* out) {
+    if (!c) return NMGP_E_NULL;
+    if (!pars || !out) return nmgp_fail(c, NMGP_E_NULL, "pars/out must not be NULL");
+    NMGP_TRY(require_had(c));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->N, M = c->M, T = c->T;
+    const size_t P = (size_t)T + 3;
+    hipStream_t s = c->stream;
+    const int ld = (int)nmgp_ld((size_t)N);
+    auto ev = [](size_t n) { return (n + 1) & ~(size_t)1; };
+    double* w;
+    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, ev(P) + (size_t)ld * N, &w));
+    double *dP = w, *S = dP + ev(P);
+    HIP_TRY(c, hipMemcpyAsync(dP, pars, P * sizeof(double), hipMemcpyHostToDevice, s));
+    int r = hadst_cov_build(s, c->d_x, c->had_indx, dP, (long long)P, S, ld, N, M, 1, 0);
+    if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+    fill_lower_to_full(s, S, ld, N);
+    HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)N * sizeof(double), S, (size_t)ld * sizeof(double), (size_t)N * sizeof(double), (size_t)N,
+                                hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return nmgp_take_launch_error(c);
+}
+
+// Prediction at the new inputs xs [S] under H parameter vectors (H = 1: the MAP predictor; H > 1: posterior draws).  A chunk of B
+// draws is ONE batched factorisation of B matrices of order N with y and the slice's cross-covariance rows riding below each.
+//   indx_star == NULL: mean, var [H, S, M] (all outputs at every input), slices of max(1, N / M) inputs
+//   indx_star given:   mean, var [H, S] (output indx_star[s] at input s), slices of N inputs
+// status [H] or NULL as nmgp_hadst_batch_eval reports it; a failing draw has NaN rows and does not fail the call.
+extern "C" int nmgp_predict_hadst(nmgp_ctx* c, const double* pars, int H, const double* xs, const int* indx_star, int S, double* mean,
+                                  double* var, int* status) {
+    if (!c) return NMGP_E_NULL;
+    if (!pars || !xs || !mean || !var) return nmgp_fail(c, NMGP_E_NULL, "null argument");
+    if (H <= 0 || S <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "H and S must be positive (H=%d, S=%d)", H, S);
+    NMGP_TRY(require_had(c));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->N, M = c->M, T = c->T;
+    if (M > 8) return nmgp_fail(c, NMGP_E_UNSUPPORTED, "unsupported number of outputs M=%d", M);
+    const bool indexed = indx_star != nullptr;
+    if (indexed)
+        for (int k = 0; k < S; ++k)
+            if (indx_star[k] < 0 || indx_star[k] >= M)
+                return nmgp_fail(c, NMGP_E_SHAPE, "indx_star[%d] = %d is not an output label in [0, %d)", k, indx_star[k], M);
+    const long long P = (long long)T + 3;
+    hipStream_t s = c->stream;
+    // new inputs per factorisation: at most N riding cross-covariance rows
+    const int smax = indexed ? N : std::max(1, N / M), Sm = std::min(S, smax);
+    const int per = indexed ? 1 : M, Emax = Sm * per;
+    const int ld = (int)nmgp_ld((size_t)N + 1 + Emax);
+    const long long bs = (long long)ld * N;
+    if (bs >= 0x7fffffffLL)
+        return nmgp_fail(c, NMGP_E_SHAPE, "a matrix of order N = %d with %d riding rows exceeds the 2^31 elements the row kernels index",
+                         N, ld - N);
+    const int chunks = (N + 127) / 128;
+    const int B = nmgp_ps_chunk(H, (size_t)(N + 1 + Emax) * ld);
+    const size_t O = (size_t)S * per;
+    // one workspace, carved; its size depends on (N, M, S, B), not on H
+    size_t off = 0;
+    auto take = [&off](size_t nelem) {
+        const size_t o = off;
+        off += (nelem + 15) / 16 * 16;
+        return o;
+    };
+    const size_t o_xs = take(S), o_is = take(indexed ? ((size_t)S + 1) / 2 : 0), o_pars = take((size_t)B * P), o_mean = take(B * O),
+                 o_colsq = take(B * O), o_var = take(B * O), o_part = take((size_t)B * 2 * Emax * chunks),
+                 o_info = take(((size_t)B + 1) / 2), o_S = take((size_t)B * bs);
+    if (c->ps_cap < off) {
+        c->ps_cap = 0;
+        NMGP_TRY(nmgp_dev_alloc(c, &c->ps_buf, off));
+        c->ps_cap = off;
+    } else if (nmgp_poison()) {
+        HIP_TRY(c, hipMemsetAsync(c->ps_buf, 0xFF, off * sizeof(double), s));
+    }
+    double* w = c->ps_buf;
+    double *d_xs = w + o_xs, *d_pars = w + o_pars, *d_mean = w + o_mean, *d_colsq = w + o_colsq, *d_var = w + o_var, *part = w + o_part,
+           *Sb = w + o_S;
+    int* d_is = indexed ? reinterpret_cast<int*>(w + o_is) : nullptr;
+    int* d_info = reinterpret_cast<int*>(w + o_info);
+
+    HIP_TRY(c, hipMemcpyAsync(d_xs, xs, (size_t)S * sizeof(double), hipMemcpyHostToDevice, s));
+    if (indexed) HIP_TRY(c, hipMemcpyAsync(d_is, indx_star, (size_t)S * sizeof(int), hipMemcpyHostToDevice, s));
+    std::vector<int> hinfo(B);
+    for (int h0 = 0; h0 < H; h0 += B) {
+        const int Bc = std::min(B, H - h0);
+        HIP_TRY(c, hipMemcpyAsync(d_pars, pars + (size_t)h0 * P, (size_t)Bc * P * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemsetAsync(d_info, 0, (size_t)Bc * sizeof(int), s));
+        for (int s0 = 0; s0 < S; s0 += smax) {
+            const int Sc = std::min(smax, S - s0), E = Sc * per;
+            int r = hadst_cov_build(s, c->d_x, c->had_indx, d_pars, P, Sb, ld, N, M, Bc, bs);
+            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+            set_row(s, Sb, ld, N, c->had_y, N, Bc, bs, 0);                // y rides along as row N (shared by the draws)
+            NMGP_TRY(hadst_cross_rows(s, c->d_x, c->had_indx, d_pars, P, N, M, d_xs, d_is, s0, E, Sb, ld, bs, N + 1, Bc));
+            // the substitution-based panel kernels, as every batched predictor: their bits do not depend on the schedule the batch
+            // size selects, so H draws in one call give the bits of H single calls
+            nmgp_potrf(c, Sb, ld, N, 1 + E, 0, d_info, Bc, bs, 1, 1);
+            ps_rows_reduce(s, Sb, ld, bs, N, N + 1, N, E, part, Bc, d_mean, d_colsq, (long long)O, (long long)s0 * per);
+        }
+        NMGP_LAUNCH(k_hadst_predvar, dim3(cdiv((long long)O, 256), Bc), dim3(256), 0, s, d_pars, P, d_colsq, d_is, S, M, d_var);
+        double* hm = mean + (size_t)h0 * O;
+        double* hv = var + (size_t)h0 * O;
+        HIP_TRY(c, hipMemcpyAsync(hm, d_mean, Bc * O * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(hv, d_var, Bc * O * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(hinfo.data(), d_info, (size_t)Bc * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        NMGP_TRY(nmgp_take_launch_error(c));
+        for (int b = 0; b < Bc; ++b) {
+            int st = hinfo[b];
+            const double* pb = pars + (size_t)(h0 + b) * P;
+            bool finite_in = true;
+            for (long long k = 0; k < P && finite_in; ++k) finite_in = std::isfinite(pb[k]);
+            if (!finite_in) st = NMGP_NUM_NAN;
+            if (st == 0)
+                for (size_t k = 0; k < O; ++k)
+                    if (!std::isfinite(hm[b * O + k]) || !std::isfinite(hv[b * O + k])) {
+                        st = NMGP_NUM_NAN;
+                        break;
+                    }
+            if (st != 0)
+                for (size_t k = 0; k < O; ++k) hm[b * O + k] = hv[b * O + k] = std::nan("");
+            if (status) status[h0 + b] = st;
+        }
+    }
+    c->last_kind = 0;
+    return 0;
+}

@@ -1132,6 +1132,61 @@ class BatchedHMCHadamardSep(_HadamardSepSubject, LockStepHMC):
     potential_and_grad = BatchedHMCHadamard.potential_and_grad
 
 
+# ---- Hadamard form of the stationary model (the LMC baseline: T + 3 parameters, no GP prior) --------------------------------------
+STA_HYPER_KEYS = ("mu_tilde_l", "sigma_tilde_l", "a", "b", "c")
+
+
+class _HadamardStaSubject(_HadamardSubject):
+    """One Hadamard subject on a context under the stationary model: the batched objective of ``hadamard_sta.nlogpos_obj_hadamard_S``."""
+
+    HYPER_KEYS = STA_HYPER_KEYS
+
+    def _eval(self, P):
+        self.ctx.had_set_data(self.x, self.indx, self.y)       # (a no-op while this subject is the resident one)
+        return self.ctx.hadst_batch_eval(P, self.hyper, True, True)
+
+
+class HadamardStaMAP(_HadamardStaSubject, LockStepMAP):
+    """B restarts of the MAP loop on ``logpos.nlogpos_obj_hadamard_S`` in lock-step: host-side Adam (the arithmetic of
+    ``torch.optim.Adam``, row by row), every iteration ONE ``nmgp_hadst_batch_eval`` for all restarts.  ``init_pars`` [B, T+3]."""
+
+    def __init__(self, x, indx, y, hyper_pars, init_pars, lr=2e-1, ctx=None):
+        LockStepMAP.__init__(self, init_pars, lr=lr)
+        self._bind(x, indx, y, hyper_pars, ctx)
+
+    def value_and_grad(self, P):
+        return self._eval(P)
+
+
+class BatchedHMCHadamardSta(_HadamardStaSubject, LockStepHMC):
+    """B independent HMC chains of the stationary Hadamard model of one subject in lock-step: every leapfrog step evaluates
+    ``logpos.nlogpos_obj_hadamard_S`` and its gradient for all chains with one ``nmgp_hadst_batch_eval``.  The leapfrog update runs
+    on the host; identity, diagonal or dense mass matrix through the base class (with T + 3 parameters and no GP prior a dense mass
+    is all the metric the model needs).  Chain b reproduces a one-chain run started from the same state with seed ``seed + b``."""
+
+    def __init__(self, x, indx, y, hyper_pars, init_positions, step_size=1e-2, num_steps_in_leap=20, seed=None, ctx=None, M=None,
+                 Minv=None):
+        LockStepHMC.__init__(self, init_positions, step_size, num_steps_in_leap, seed, M, Minv)
+        if self.mass_kind >= 3:
+            raise NotImplementedError("the prior-factor metrics belong to the complete-data models")
+        self._bind(x, indx, y, hyper_pars, ctx)
+
+    potential_and_grad = BatchedHMCHadamard.potential_and_grad
+
+    # Under a dense mass the base class takes all chains' momenta through ONE matrix-matrix product, whose summation order depends
+    # on the number of rows B.  P = T + 3 is small: here every chain goes through its own matrix-vector product, so chain b keeps
+    # its bits whatever B is, under a dense mass too.
+    def draw_momenta(self):
+        if self.mass_kind != 2:
+            return LockStepHMC.draw_momenta(self)
+        return np.stack([self.Mchol @ r.standard_normal(self.P) for r in self.rngs])
+
+    def velocity(self, p):
+        if self.mass_kind != 2:
+            return LockStepHMC.velocity(self, p)
+        return np.stack([self.Minv @ row for row in p])
+
+
 # ---- the whole recipe behind one call ---------------------------------------------------------------------------------------------
 def _sample_recipe(polish, build_metric, make_sampler, pars0, chains, iters, warm, warm_step, windows, window_iters, step_size,
                    step_candidates, target_accept, progress, segment):
@@ -1351,3 +1406,28 @@ def posterior_predict_hadamard_sep(x, indx, y, hyper_pars, samples, xs, indx_sta
     out = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
     out["tilde_sigma_star"] = star[:, :, 1][status == 0]
     return out
+
+
+def posterior_predict_hadamard_sta(x, indx, y, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, ctx=None):
+    """Posterior-predictive band of the stationary HADAMARD model (irregularly observed outputs) from
+    :class:`BatchedHMCHadamardSta`'s draws: ``samples`` [iters, chains, T+3] or [H, T+3], ``xs`` [S] the new inputs; ``draws`` thins
+    the history evenly to that many.  ``indx_star=None`` predicts all M outputs at every new input (moments [S, M]); ``indx_star``
+    [S] predicts output ``indx_star[s]`` only at ``xs[s]`` (held-out pairs; moments [S]).  The model has no latent curve to regress:
+    a draw is a parameter vector, and only y* is sampled (``seed``: NumPy generator of its normals).  All draws and inputs go
+    through one batched device call (``Context.predict_hadst``); ``hyper_pars`` is accepted for symmetry with the siblings and not
+    used.  Returns :func:`summarize_posterior_predictive`'s dict, ``tilde_l_star`` being each used draw's constant tilde_l [H_used, S]."""
+    from . import _lib
+    ctx = ctx if ctx is not None else _lib.default_context()
+    x, y = np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(y, dtype=np.float64).reshape(-1)
+    indx = np.ascontiguousarray(np.asarray(indx).reshape(-1), dtype=np.int32)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1)
+    S_ = np.asarray(samples, dtype=np.float64)
+    S_ = S_.reshape(-1, S_.shape[-1])
+    if draws is not None and int(draws) < S_.shape[0]:
+        S_ = S_[np.unique(np.round(np.linspace(0, S_.shape[0] - 1, int(draws))).astype(int))]
+    ctx.had_set_data(x, indx, y)
+    rng = np.random.default_rng(seed)
+    zy = rng.standard_normal((S_.shape[0], xs.shape[0]) + (() if indx_star is not None else (ctx.M,)))
+    mean, var, status = ctx.predict_hadst(S_, xs, indx_star=indx_star)
+    tl = np.repeat(S_[:, :1], xs.shape[0], axis=1)
+    return summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, tl, status)

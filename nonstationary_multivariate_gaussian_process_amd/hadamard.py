@@ -14,8 +14,9 @@ must occur.  The parameter vector is ``[tilde_l (N) | L_vecs (N T) | tilde_sigma
 as it is (no exp on the diagonal slots).
 
 Not provided: ``indexedpoint_predmap_SVC_hadamard`` / ``test_predmap_SVC_hadamard`` (INTEGRATION.md says why), the
-``predsample_hadamard`` families and the stationary Hadamard objectives (``*_hadamard_S``).  The separable Hadamard model
-(``nlogpos_obj_hadamard``, ``point_predmap_hadamard``, ...) is served by ``hadamard_sep.py`` under its own opt-in.
+``predsample_hadamard`` families.  The separable Hadamard model (``nlogpos_obj_hadamard``, ``point_predmap_hadamard``, ...) is
+served by ``hadamard_sep.py``, the stationary one (``*_hadamard_S``, ``*_predmap_S_hadamard``) by ``hadamard_sta.py``, each under its
+own opt-in.
 
 The names are opt-in behind the reference's module names: with ``NMGP_HADAMARD=1`` in the environment ``Utility.logpos`` /
 ``Utility.prediction`` serve them; otherwise they keep resolving to the user's checkout.  Importing this module directly always

@@ -22,8 +22,9 @@ Quirks of the reference that are kept:
 ``M`` is inferred from ``indx`` as the reference does (the number of distinct labels), so the labels must be 0 .. M-1 and each
 must occur.  The reference forms S^-1 of the predictor through ``symeig``; here it is the blocked Cholesky with riding rows.
 
-Not provided: the stationary ``*_hadamard_S`` names.  ``indexedpoint_predmap_hadamard`` / ``test_predmap_hadamard`` and the
-``predsample_hadamard`` families live in ``predsample_hadamard.py`` behind a switch of their own.
+The stationary ``*_hadamard_S`` names live in ``hadamard_sta.py`` behind ``NMGP_HADAMARD_STA=1``.
+``indexedpoint_predmap_hadamard`` / ``test_predmap_hadamard`` and the ``predsample_hadamard`` families live in
+``predsample_hadamard.py`` behind a switch of their own.
 
 The names are opt-in behind the reference's module names: with ``NMGP_HADAMARD_SEP=1`` in the environment ``Utility.logpos`` /
 ``Utility.prediction`` serve them; otherwise they keep resolving to the user's checkout (``NMGP_HADAMARD=1`` alone does not serve
