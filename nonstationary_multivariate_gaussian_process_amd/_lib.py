@@ -679,28 +679,42 @@ class Context:
         """B parameter vectors of the resident Hadamard subject in one launch sequence: pars [B, N(1+T)+1] (or one vector) ->
         (out [B, 5], grad [B, P] or None, status [B]: 0, a leading-minor index or NUM_NAN; a failing chain has a NaN row and a
         zero gradient row)."""
+        return self._had_eval(self.lib.nmgp_had_batch_eval, pars, self.N * (1 + self.T) + 1, 5, hyper, None, "N(1+T)+1", prior,
+                              want_grad)
+
+    def _had_eval(self, fn, pars, P_, width, hyper, n_hyper, what, prior, want_grad):
+        """One batched evaluation entry of the three Hadamard models: pars [B, P_] (or one vector) -> (out [B, width], grad [B, P_]
+        or None, status [B]).  ``what`` spells P_ in the error text; n_hyper=None: the length of hyper is not checked."""
         pars = as_f64(pars)
         if pars.ndim == 1:
             pars = pars[None]
-        P_ = self.N * (1 + self.T) + 1
         if pars.ndim != 2 or pars.shape[1] != P_:
-            raise NmgpError("parameters must be [B, N(1+T)+1 = %d], got %s" % (P_, pars.shape))
+            raise NmgpError("parameters must be [B, %s = %d], got %s" % (what, P_, pars.shape))
         hyper = as_f64(hyper)
+        if n_hyper is not None:
+            hyper = hyper.reshape(-1)
+            if hyper.shape[0] != n_hyper:
+                raise NmgpError("hyper must have %d entries, got %d" % (n_hyper, hyper.shape[0]))
         B = pars.shape[0]
-        out = np.empty((B, 5))
+        out = np.empty((B, width))
         grad = np.empty((B, P_)) if want_grad else None
         status = np.zeros(B, dtype=np.int32)
-        self.check(self.lib.nmgp_had_batch_eval(self.h, ptr(pars), B, ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
-                                                status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        self.check(fn(self.h, ptr(pars), B, ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
+                      status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out, grad, status
 
-    def had_covariance(self, pars):
+    def _had_cov(self, fn, pars, P_, what):
+        """One covariance entry of the three Hadamard models: the full symmetric [N, N] of one parameter vector of length P_;
+        ``what`` is appended to the error text."""
         pars = as_f64(pars).reshape(-1)
-        if pars.shape[0] != self.N * (1 + self.T) + 1:
-            raise NmgpError("bad parameter vector length %d" % pars.shape[0])
+        if pars.shape[0] != P_:
+            raise NmgpError("bad parameter vector length %d%s" % (pars.shape[0], what))
         out = np.empty((self.N, self.N))
-        self.check(self.lib.nmgp_had_covariance(self.h, ptr(pars), ptr(out)))
+        self.check(fn(self.h, ptr(pars), ptr(out)))
         return out
+
+    def had_covariance(self, pars):
+        return self._had_cov(self.lib.nmgp_had_covariance, pars, self.N * (1 + self.T) + 1, "")
 
     def predict_had(self, pars, hyper, xs):
         """(mean [S, M], var [S, M], star [S, 1+T]) of the resident Hadamard subject at the new inputs xs."""
@@ -720,30 +734,10 @@ class Context:
         """B parameter vectors [tilde_l | tilde_sigma | L_vec | tilde_sigma2_err] of the resident Hadamard subject in one launch
         sequence: pars [B, 2N+T+1] (or one vector), hyper [9] -> (out [B, 6], grad [B, P] or None, status [B]: 0, a leading-minor
         index or NUM_NAN; a failing chain has a NaN row and a zero gradient row)."""
-        pars = as_f64(pars)
-        if pars.ndim == 1:
-            pars = pars[None]
-        P_ = self._hads_len()
-        if pars.ndim != 2 or pars.shape[1] != P_:
-            raise NmgpError("parameters must be [B, 2N+T+1 = %d], got %s" % (P_, pars.shape))
-        hyper = as_f64(hyper).reshape(-1)
-        if hyper.shape[0] != 9:
-            raise NmgpError("hyper must have 9 entries, got %d" % hyper.shape[0])
-        B = pars.shape[0]
-        out = np.empty((B, 6))
-        grad = np.empty((B, P_)) if want_grad else None
-        status = np.zeros(B, dtype=np.int32)
-        self.check(self.lib.nmgp_hads_batch_eval(self.h, ptr(pars), B, ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
-                                                 status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
-        return out, grad, status
+        return self._had_eval(self.lib.nmgp_hads_batch_eval, pars, self._hads_len(), 6, hyper, 9, "2N+T+1", prior, want_grad)
 
     def hads_covariance(self, pars):
-        pars = as_f64(pars).reshape(-1)
-        if pars.shape[0] != self._hads_len():
-            raise NmgpError("bad parameter vector length %d (2N+T+1 = %d)" % (pars.shape[0], self._hads_len()))
-        out = np.empty((self.N, self.N))
-        self.check(self.lib.nmgp_hads_covariance(self.h, ptr(pars), ptr(out)))
-        return out
+        return self._had_cov(self.lib.nmgp_hads_covariance, pars, self._hads_len(), " (2N+T+1 = %d)" % self._hads_len())
 
     def predict_hads(self, pars, hyper, xs):
         """(mean [S, M], var [S, M], star [S, 2] = tilde_l*, tilde_sigma*) of the resident Hadamard subject at the new inputs xs."""
@@ -806,30 +800,10 @@ class Context:
         """B parameter vectors [tilde_l, tilde_sigma, L_vec, tilde_sigma2_err] of the resident Hadamard subject in one launch
         sequence: pars [B, T+3] (or one vector), hyper [5] = (mu_tilde_l, sigma_tilde_l, a, b, c) -> (out [B, 5], grad [B, T+3] or
         None, status [B]: 0, a leading-minor index or NUM_NAN; a failing chain has a NaN row and a zero gradient row)."""
-        pars = as_f64(pars)
-        if pars.ndim == 1:
-            pars = pars[None]
-        P_ = self.T + 3
-        if pars.ndim != 2 or pars.shape[1] != P_:
-            raise NmgpError("parameters must be [B, T+3 = %d], got %s" % (P_, pars.shape))
-        hyper = as_f64(hyper).reshape(-1)
-        if hyper.shape[0] != 5:
-            raise NmgpError("hyper must have 5 entries, got %d" % hyper.shape[0])
-        B = pars.shape[0]
-        out = np.empty((B, 5))
-        grad = np.empty((B, P_)) if want_grad else None
-        status = np.zeros(B, dtype=np.int32)
-        self.check(self.lib.nmgp_hadst_batch_eval(self.h, ptr(pars), B, ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
-                                                  status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
-        return out, grad, status
+        return self._had_eval(self.lib.nmgp_hadst_batch_eval, pars, self.T + 3, 5, hyper, 5, "T+3", prior, want_grad)
 
     def hadst_covariance(self, pars):
-        pars = as_f64(pars).reshape(-1)
-        if pars.shape[0] != self.T + 3:
-            raise NmgpError("bad parameter vector length %d (T+3 = %d)" % (pars.shape[0], self.T + 3))
-        out = np.empty((self.N, self.N))
-        self.check(self.lib.nmgp_hadst_covariance(self.h, ptr(pars), ptr(out)))
-        return out
+        return self._had_cov(self.lib.nmgp_hadst_covariance, pars, self.T + 3, " (T+3 = %d)" % (self.T + 3))
 
     def predict_hadst(self, pars, xs, indx_star=None):
         """Prediction of the stationary HADAMARD model at the new inputs xs [S] under the parameter vectors pars [H, T+3] (one

@@ -3,7 +3,7 @@
 hipcc cross-compiles without a GPU.  The shared object is written next to the sources' package
 (in-tree, git-ignored) so that it travels with the repository snapshot.
 
-Provenance: the library carries the SHA-256 of everything it was built from -- the .hip sources, the two headers and
+Provenance: the library carries the SHA-256 of everything it was built from -- the .hip sources, the headers and
 the compiler flags (`tree_id()`) -- as `nmgp_build_id()`; `_lib.load()` refuses a shared object whose id differs from
 the tree beside it, `bench.py` prints the id in its JSON line, and rebuilds are decided by content hash (one `.sha`
 file per object), not by modification time.
@@ -24,7 +24,7 @@ SOURCES = ["nmgp_kernels.hip", "nmgp_kernels_eig.hip", "nmgp_kernels_sep.hip", "
            "nmgp_predsample.hip", "nmgp_predsample_sep.hip", "nmgp_hadamard.hip", "nmgp_hadamard_sep.hip",
            "nmgp_predsample_hadamard.hip", "nmgp_hadamard_sta.hip"]
 ID_SOURCE = "nmgp_build_id.hip"        # compiled last, with -DNMGP_BUILD_ID="<tree id>"
-HEADERS = [os.path.join(INCLUDE, "nmgp.h"), os.path.join(CSRC, "nmgp_internal.h")]
+HEADERS = [os.path.join(INCLUDE, "nmgp.h"), os.path.join(CSRC, "nmgp_internal.h"), os.path.join(CSRC, "nmgp_hadamard_common.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # flags that decide the generated code (part of the build id); the -I paths are added at compile time and are not
 # hashed: the same tree at another absolute path is the same build

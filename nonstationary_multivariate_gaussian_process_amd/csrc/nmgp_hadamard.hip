@@ -8,13 +8,12 @@
 // ONE dense N x N SPD matrix per evaluation: the SVC covariance restricted to the observed (output, input) pairs.  Everything
 // between the covariance build and the adjoint is the library's own: the blocked Cholesky with its riding rows (y, the rows of
 // L^-T, the cross-covariance rows of prediction), the triangular matrix-vector product, the inverse SYRK, the cached prior
-// factors.  This file adds the kernels around them (k_had_prep, k_had_cov, k_had_adjoint, k_had_grad_final,
-// k_had_crosscov_rows) and the entries.  There is no structured (Schur) value path: no per-location block to eliminate.
-//
-// Layout conventions of k_svc_cov / k_svc_adjoint: a 64 x 64 tile of observations per 256-thread workgroup, lanes along i (a wave
-// stores / loads 512 contiguous bytes of one column), the j side staged in LDS, blockIdx.z = chain; fixed summation order and no
-// atomics, so B chains in one launch give the bits of B launches.
-#include "nmgp_internal.h"
+// factors.  The schedule of a batched evaluation and the Gibbs covariance / adjoint kernels (k_gibbs_cov, k_gibbs_adjoint with AMP =
+// false: unit amplitude) are nmgp_hadamard_common.h's, shared with the other two Hadamard models.  This file adds the model's own
+// kernels (k_had_prep, k_had_grad_final, k_had_star, k_had_crosscov_rows, k_had_predvar), its hooks into that schedule
+// (HadNonsep), the MAP predictor and the three host helpers every Hadamard file calls (require_had, had_priors, had_prior_solve).
+// There is no structured (Schur) value path: no per-location block to eliminate.
+#include "nmgp_hadamard_common.h"
 
 #include <algorithm>
 
@@ -36,138 +35,6 @@ __global__ void k_had_prep(const double* __restrict__ pars, const int* __restric
     const int c = indx[i];
     const double* u = pars + N + (size_t)i * T + c * (c + 1) / 2;
     for (int m = 0; m < M; ++m) Rv[(size_t)i * M + m] = (m <= c) ? u[m] : 0.0;
-}
-
-// S[i, j] = (K0(i, j) + jitter d_ij) <r_i, r_j> + sigma2 d_ij, lower triangle, column-major with leading dimension ld
-template <int M>
-__global__ __launch_bounds__(256) void k_had_cov(const double* __restrict__ x, const double* __restrict__ ell,
-                                                  const double* __restrict__ Rv, const double* __restrict__ pars, long long P,
-                                                  double* __restrict__ S, int ld, int N, long long sstride) {
-    constexpr int TJ = 64;
-    __shared__ double sx[TJ], sl[TJ], sR[TJ * M];
-    const int I = blockIdx.x, J = blockIdx.y;
-    if (I < J) return;
-    ell += (size_t)blockIdx.z * N;
-    Rv += (size_t)blockIdx.z * N * M;
-    pars += (size_t)blockIdx.z * P;
-    S += (size_t)blockIdx.z * sstride;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j0 = J * TJ;
-    if (tid < TJ) {
-        const int j = j0 + tid;
-        sx[tid] = (j < N) ? x[j] : 0.0;
-        sl[tid] = (j < N) ? ell[j] : 1.0;
-    }
-    for (int k = tid; k < TJ * M; k += 256) {
-        const size_t g = (size_t)j0 * M + k;
-        sR[k] = (g < (size_t)N * M) ? Rv[g] : 0.0;
-    }
-    __syncthreads();
-    const int i = I * 64 + lane;
-    if (i >= N) return;
-    const double sigma2 = exp(pars[P - 1]);
-    const double xi = x[i], li = ell[i];
-    const double xi2 = xi * xi, li2 = li * li;
-    double ri[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)i * M + m];
-#pragma unroll 2
-    for (int jj = 0; jj < TJ / 4; ++jj) {
-        const int k = w * (TJ / 4) + jj;
-        const int j = j0 + k;
-        if (j >= N) break;
-        if (i < j) continue;
-        const double xj = sx[k], lj = sl[k];
-        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);   // kernels.py:20
-        const double A = li2 + lj * lj;                          // kernels.py:69
-        double kv = sqrt(2.0 * (li * lj) / A) * exp(-dist / A);  // kernels.py:70,72 (sigma == 1)
-        if (i == j) kv = NMGP_JITTER + kv;                       // kernels.py:64
-        double b = 0.0;
-#pragma unroll
-        for (int m = 0; m < M; ++m) b += ri[m] * sR[k * M + m];
-        double v = kv * b;
-        if (i == j) v += sigma2;
-        S[(size_t)j * ld + i] = v;
-    }
-}
-
-// Adjoint of the likelihood, one pass over the FULL symmetric -S^-1 (what the inverse SYRK leaves):
-//   G = 1/2 (alpha alpha^T - S^-1)
-//   d loglik / d r_i       = 2 sum_j G_ij K_x[i, j] r_j                       (j = i included)
-//   d loglik / d tilde_l_i = sum_{j != i} 2 G_ij K0[i, j] <r_i, r_j> (1/2 - l_i^2 / A + 2 l_i^2 d_ij / A^2),  A = l_i^2 + l_j^2
-// Each wave takes 16 j; the four waves' sums meet in LDS and leave part[J][i][0..M] (slot 0 = tilde_l, 1 + m = component m of r_i).
-template <int M>
-__global__ __launch_bounds__(256) void k_had_adjoint(const double* __restrict__ x, const double* __restrict__ ell,
-                                                      const double* __restrict__ Rv, const double* __restrict__ alpha,
-                                                      const double* __restrict__ Sneg, int ld, int N, double* __restrict__ part) {
-    constexpr int TJ = 64;
-    __shared__ double sx[TJ], sl[TJ], sR[TJ * M], sa[TJ];
-    __shared__ double red[2][4][64];
-    const int I = blockIdx.x, J = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j0 = J * TJ;
-    const size_t Ns = (size_t)N;
-    {   // blockIdx.z = chain
-        const size_t z = blockIdx.z;
-        ell += z * Ns;
-        Rv += z * Ns * M;
-        alpha += z * Ns;
-        Sneg += z * (size_t)ld * Ns;
-        part += z * (size_t)gridDim.y * Ns * (M + 1);
-    }
-    if (tid < TJ) {
-        const int j = j0 + tid;
-        sx[tid] = (j < N) ? x[j] : 0.0;
-        sl[tid] = (j < N) ? ell[j] : 1.0;
-        sa[tid] = (j < N) ? alpha[j] : 0.0;
-    }
-    for (int k = tid; k < TJ * M; k += 256) {
-        const size_t g = (size_t)j0 * M + k;
-        sR[k] = (g < Ns * M) ? Rv[g] : 0.0;
-    }
-    __syncthreads();
-    const int i = I * 64 + lane;
-    const bool iv = i < N;
-    const int ic = iv ? i : N - 1;
-    const double xi = x[ic], li = ell[ic], ai = alpha[ic];
-    const double xi2 = xi * xi, li2 = li * li;
-    double ri[M], acc[M + 1];
-#pragma unroll
-    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
-#pragma unroll
-    for (int t = 0; t <= M; ++t) acc[t] = 0.0;
-    if (iv) {
-        for (int jj = 0; jj < TJ / 4; ++jj) {
-            const int k = w * (TJ / 4) + jj;
-            const int j = j0 + k;
-            if (j >= N) break;
-            const double xj = sx[k], lj = sl[k];
-            const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
-            const double A = li2 + lj * lj;
-            const double k0 = sqrt(2.0 * (li * lj) / A) * exp(-dist / A);
-            const double kx = (i == j) ? (NMGP_JITTER + k0) : k0;
-            const double G = 0.5 * (ai * sa[k] + Sneg[(size_t)j * ld + i]);
-            const double gk = 2.0 * kx * G;
-            double dot = 0.0;
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                const double rj = sR[k * M + m];
-                acc[1 + m] = fma(gk, rj, acc[1 + m]);
-                dot = fma(ri[m], rj, dot);
-            }
-            if (i != j) {
-                const double dlogk = 0.5 - li2 / A + 2.0 * li2 * dist / (A * A);
-                acc[0] = fma(2.0 * (G * dot) * k0, dlogk, acc[0]);
-            }
-        }
-    }
-    double* o = part + ((size_t)J * Ns + ic) * (M + 1);
-#pragma unroll
-    for (int t = 0; t <= M; ++t) {
-        red[t & 1][w][lane] = acc[t];
-        __syncthreads();
-        if (w == 0 && iv) o[t] = (red[t & 1][0][lane] + red[t & 1][1][lane]) + (red[t & 1][2][lane] + red[t & 1][3][lane]);
-    }
 }
 
 // d NegLog / d pars: the J partials summed in order, the c_i + 1 components of d / d r_i scattered into row c_i's slots, the prior
@@ -275,35 +142,8 @@ __global__ void k_had_predvar(const double* __restrict__ star, const double* __r
     var[k] = v;
 }
 
-#define NMGP_HAD_SWITCH(M, CALL)                \
-    switch (M) {                                \
-        case 1: { constexpr int MM = 1; CALL; } break; \
-        case 2: { constexpr int MM = 2; CALL; } break; \
-        case 3: { constexpr int MM = 3; CALL; } break; \
-        case 4: { constexpr int MM = 4; CALL; } break; \
-        case 5: { constexpr int MM = 5; CALL; } break; \
-        case 6: { constexpr int MM = 6; CALL; } break; \
-        case 7: { constexpr int MM = 7; CALL; } break; \
-        case 8: { constexpr int MM = 8; CALL; } break; \
-        default: return NMGP_E_UNSUPPORTED;     \
-    }
-
 void had_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* Rv, int batch) {
     NMGP_LAUNCH(k_had_prep, dim3(cdiv(N, 256), batch), dim3(256), 0, s, pars, indx, N, M, M * (M + 1) / 2, ell, Rv);
-}
-
-int had_cov_build(hipStream_t s, const double* x, const double* ell, const double* Rv, const double* pars, long long P, double* S,
-                  int ld, int N, int M, int batch, long long sstride) {
-    const dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);
-    NMGP_HAD_SWITCH(M, NMGP_LAUNCH((k_had_cov<MM>), grid, dim3(256), 0, s, x, ell, Rv, pars, P, S, ld, N, sstride));
-    return 0;
-}
-
-int had_adjoint(hipStream_t s, const double* x, const double* ell, const double* Rv, const double* alpha, const double* Sneg,
-                int ld, int N, int M, double* part, int batch) {
-    const dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);      // -S^-1 of chain z: ld x N doubles further on
-    NMGP_HAD_SWITCH(M, NMGP_LAUNCH((k_had_adjoint<MM>), grid, dim3(256), 0, s, x, ell, Rv, alpha, Sneg, ld, N, part));
-    return 0;
 }
 
 void had_grad_final(hipStream_t s, const double* part, int NJ, int N, int M, const int* indx, const double* R2, int ldR,
@@ -315,13 +155,14 @@ void had_grad_final(hipStream_t s, const double* part, int NJ, int N, int M, con
 int had_crosscov_rows(hipStream_t s, const double* x, const double* ell, const double* Rv, int N, int M, const double* xs,
                       const double* star, int s0, int Sc, double* A, int ld, int R0) {
     const dim3 grid(N, cdiv((long long)Sc * M, 256));
-    NMGP_HAD_SWITCH(M, NMGP_LAUNCH((k_had_crosscov_rows<MM>), grid, dim3(256), 0, s, x, ell, Rv, N, xs, star, s0, Sc, A, ld, R0));
+    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_had_crosscov_rows<MM>), grid, dim3(256), 0, s, x, ell, Rv, N, xs, star, s0, Sc, A, ld, R0));
     return 0;
 }
 
 }  // namespace
 
-// (the next three are shared with nmgp_hadamard_sep.hip: declared in nmgp_internal.h)
+// The next three are declared in nmgp_internal.h: require_had guards every entry of the three Hadamard models and of
+// nmgp_predsample_hadamard.hip; had_priors / had_prior_solve serve the two models with GP priors (this one and the separable one).
 int require_had(nmgp_ctx* c) {
     if (!c->had || !c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_data must be called first (the resident subject is not a Hadamard one)");
     if (c->chol_algo != 1)
@@ -363,196 +204,63 @@ int had_prior_solve(nmgp_ctx* c, hipStream_t sp, rocblas_handle hb, bool trans, 
 
 namespace {
 
-// device workspace of a chunk of B chains, in doubles (every piece at an even offset)
-struct HadLayout {
-    size_t o_P, o_ell, o_Rv, o_z, o_R, o_q, o_scal, o_info, o_S;
-    size_t o_alpha = 0, o_R2 = 0, o_Sneg = 0, o_part = 0, o_grad = 0, o_tr = 0;
-    size_t total = 0, tri_part = 0;
-    int ld = 0, xpad = 0, xoff = 0;
-    long long bs = 0;
-};
-
-HadLayout had_layout(int B, int N, int M, int T, bool want_grad) {
-    HadLayout L;
-    const size_t P = (size_t)N * (1 + T) + 1, Bs = B, NJ = (N + 63) / 64;
-    // rows: N (matrix) + 1 (y); with gradients + pad + N identity rows (-> L^-T)
-    L.xpad = (N + 1) & 1;
-    L.xoff = N + 1 + L.xpad;
-    L.ld = (int)nmgp_ld(want_grad ? (size_t)2 * N + 2 : (size_t)N + 1);
-    L.bs = (long long)L.ld * N;
-    L.tri_part = (size_t)N * ((N + 255) / 256);
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 1) & ~(size_t)1; return o; };
-    L.o_P = take(Bs * P); L.o_ell = take(Bs * N); L.o_Rv = take(Bs * N * M); L.o_z = take(Bs * N);
-    L.o_R = take(Bs * N * (1 + T)); L.o_q = take(Bs * (1 + T)); L.o_scal = take(Bs * 16); L.o_info = take(Bs);
-    L.o_S = take(Bs * (size_t)L.bs);
-    if (want_grad) {
-        L.o_alpha = take(Bs * N); L.o_R2 = take(Bs * N * (1 + T)); L.o_Sneg = take(Bs * (size_t)N * N);
-        // adjoint partial rows; before that pass the same buffer holds the block sums of alpha = L^-T z (tri_gemv_upper)
-        L.o_part = take(Bs * std::max(NJ * (size_t)N * (M + 1), L.tri_part));
-        L.o_grad = take(Bs * P); L.o_tr = take(Bs * 2);
+// hooks of the nonseparable model into the shared schedule (nmgp_hadamard_common.h)
+struct HadNonsep {
+    static constexpr int WIDTH = 5;
+    static constexpr bool GP_PRIORS = true;
+    static constexpr const char* NOUN = "Hadamard";
+    static size_t P(int N, int T) { return (size_t)N * (1 + T) + 1; }
+    static size_t part_width(int M) { return M + 1; }
+    template <class Take>
+    static void extras(HadLayout& L, Take take, size_t Bs, size_t N, int M, int T, bool want_grad) {
+        L.o_ell = take(Bs * N); L.o_Rv = take(Bs * N * M); L.o_R = take(Bs * N * (1 + T)); L.o_q = take(Bs * (1 + T));
+        if (want_grad) L.o_R2 = take(Bs * N * (1 + T));
     }
-    L.total = off;
-    return L;
-}
-
-// chains [0, B) of `pars` (already offset by the caller): value and gradient halves enqueued back to back, ONE synchronisation
-int had_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[8], int prior, double* out5, double* grad, int* status) {
-    const int N = c->N, M = c->M, T = c->T;
-    const size_t P = (size_t)N * (1 + T) + 1;
-    const bool want_grad = grad != nullptr;
-    const double mu_l = hyper[0], mu_L = hyper[3], a = hyper[6], b = hyper[7];
-    hipStream_t s = c->stream;
-    PriorFactor *pl = nullptr, *pL = nullptr;
-    NMGP_TRY(had_priors(c, hyper, &pl, &pL));
-    const HadLayout L = had_layout(B, N, M, T, want_grad);
-    double* slab;
-    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
-    double *dP = slab + L.o_P, *ell = slab + L.o_ell, *Rv = slab + L.o_Rv, *z = slab + L.o_z, *R = slab + L.o_R, *q = slab + L.o_q;
-    double *scal = slab + L.o_scal, *S = slab + L.o_S;
-    int* info = reinterpret_cast<int*>(slab + L.o_info);
-    const int ld = L.ld;
-    const long long bs = L.bs;
-    HIP_TRY(c, hipMemcpyAsync(dP, pars, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)B * sizeof(int), s));
-    PriorStreamScope ps(c);          // fork now, enqueue the prior solves after the factorisation's launches (see svc_enqueue)
-    {
-        NmgpStage sp(c, NMGP_STAGE_COV);
-        had_prep(s, dP, c->had_indx, N, M, ell, Rv, B);
-        int r = had_cov_build(s, c->d_x, ell, Rv, dP, (long long)P, S, ld, N, M, B, bs);
-        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+    static int build_cov(const HadChunk& k) {
+        nmgp_ctx* c = k.c;
+        const int N = c->N, M = c->M;
+        double *dP = k.at(k.L.o_P), *ell = k.at(k.L.o_ell), *Rv = k.at(k.L.o_Rv);
+        had_prep(c->stream, dP, c->had_indx, N, M, ell, Rv, k.B);
+        return gibbs_cov_build<false>(c->stream, c->d_x, ell, nullptr, Rv, dP, (long long)P(N, c->T), k.at(k.L.o_S), k.L.ld, N, M, k.B,
+                                      k.L.bs);
     }
-    {
-        NmgpStage sp(c, NMGP_STAGE_CHOL);
-        set_row(s, S, ld, N, c->had_y, N, B, bs, 0);                // y rides along as row N (shared by the chains)
-        if (want_grad) identity_rows(s, S, ld, N + 1, N, L.xpad, B, bs);
-        nmgp_potrf(c, S, ld, N, want_grad ? 1 + L.xpad : 1, want_grad ? N : 0, info, B, bs, 1);
-        get_row(s, S, ld, N, z, N, B, bs, N);                       // z = L^-1 y
-    }
-    {
-        NmgpStage sp(c, NMGP_STAGE_REDUCE);
-        chol_logdet_quad(s, S, ld, N, z, scal, scal + 1, B, bs, 16);
-    }
-    {
-        NmgpStage sp(c, NMGP_STAGE_PRIOR, ps.sp, 0.0, 0.0);
-        svc_prior_rhs(ps.sp, dP, N, T, mu_l, mu_L, R, N, B);
-        NMGP_TRY(had_prior_solve(c, ps.sp, ps.hb, false, pl, pL, R, N, T, B));
-        col_sumsq(ps.sp, R, N, N, B * (1 + T), q);
-        if (want_grad && prior) {
-            double* R2 = slab + L.o_R2;
-            HIP_TRY(c, hipMemcpyAsync(R2, R, (size_t)B * N * (1 + T) * sizeof(double), hipMemcpyDeviceToDevice, ps.sp));
-            NMGP_TRY(had_prior_solve(c, ps.sp, ps.hb, true, pl, pL, R2, N, T, B));
-        }
-    }
-    ps.done();
-    ps.join();
-    {
+    static int value_epilogue(const HadChunk& k) {
+        nmgp_ctx* c = k.c;
+        const int N = c->N, T = c->T, B = k.B;
+        const double mu_l = k.hyper[0], mu_L = k.hyper[3], a = k.hyper[6], b = k.hyper[7];
+        double *dP = k.at(k.L.o_P), *scal = k.at(k.L.o_scal);
+        NMGP_TRY(had_gp_prior_terms(k, 1 + T, [&](hipStream_t sp, double* R) { svc_prior_rhs(sp, dP, N, T, mu_l, mu_L, R, N, B); }));
         NmgpStage sp(c, NMGP_STAGE_REDUCE);
         // (ig_const = 0: the Hadamard objective uses the UNNORMALISED inverse-gamma density, logpos.py:650 / distributions.py:116-124,
         // where logpos_SVC uses the normalised one)
-        svc_finalize(s, scal, scal + 1, q, pl->logdet, pL->logdet, dP, (long long)P, N, T, a, b, 0.0, prior, scal + 8, B, 16, 0, 1);
+        svc_finalize(c->stream, scal, scal + 1, k.at(k.L.o_q), k.p0->logdet, k.p1->logdet, dP, (long long)P(N, T), N, T, a, b, 0.0,
+                     k.prior, scal + 8, B, 16, 0, 1);
+        return 0;
     }
-    std::vector<double> hs((size_t)B * 16);
-    std::vector<int> hi(B);
-    HIP_TRY(c, hipMemcpyAsync(hs.data(), scal, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(hi.data(), info, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (want_grad) {
-        // enqueued behind the value half without waiting for it (a chain that failed produces garbage here, which the epilogue discards)
-        double *alpha = slab + L.o_alpha, *R2 = slab + L.o_R2, *Sneg = slab + L.o_Sneg, *part = slab + L.o_part;
-        double *dg = slab + L.o_grad, *tr = slab + L.o_tr;
-        const long long pstride = (long long)std::max((size_t)((N + 63) / 64) * N * (M + 1), L.tri_part);
-        {
-            NmgpStage sp(c, NMGP_STAGE_SOLVE);
-            tri_gemv_upper(s, S + L.xoff, ld, N, z, alpha, part, B, bs, pstride);                 // alpha = L^-T z = X z
-        }
-        {
-            NmgpStage sp(c, NMGP_STAGE_INVERSE);
-            syrk_lower(s, S + L.xoff, ld, Sneg, N, N, N, N, B, bs, (long long)N * N, 2);         // -S^-1 = -X X^T, both triangles
-        }
-        {
-            NmgpStage sp(c, NMGP_STAGE_ADJOINT);
-            trace_terms(s, alpha, Sneg, N, N, tr, -1.0, B);
-            // (the adjoint's partial rows are (N + 63) / 64 * N * (M + 1) per chain, contiguous: the stride of part inside the kernel)
-            int r = had_adjoint(s, c->d_x, ell, Rv, alpha, Sneg, N, N, M, part, B);
-            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-            had_grad_final(s, part, (N + 63) / 64, N, M, c->had_indx, R2, N, dP, tr, a, b, prior, dg, B);
-        }
-        HIP_TRY(c, hipMemcpyAsync(grad, dg, (size_t)B * P * sizeof(double), hipMemcpyDeviceToHost, s));
+    static int adjoint_grad(const HadChunk& k) {
+        nmgp_ctx* c = k.c;
+        const int N = c->N, M = c->M;
+        double* part = k.at(k.L.o_part);
+        // (the adjoint's partial rows are (N + 63) / 64 * N * (M + 1) per chain, contiguous: the stride of part inside the kernel)
+        NMGP_TRY(gibbs_adjoint<false>(c->stream, c->d_x, k.at(k.L.o_ell), nullptr, k.at(k.L.o_Rv), k.at(k.L.o_alpha), k.at(k.L.o_Sneg), N,
+                                      N, M, part, k.B));
+        had_grad_final(c->stream, part, (N + 63) / 64, N, M, c->had_indx, k.at(k.L.o_R2), N, k.at(k.L.o_P), k.at(k.L.o_tr), k.hyper[6],
+                       k.hyper[7], k.prior, k.at(k.L.o_grad), k.B);
+        return 0;
     }
-    HIP_TRY(c, hipStreamSynchronize(s));          // the one synchronisation of the evaluation
-    NMGP_TRY(nmgp_take_launch_error(c));
-    for (int z_ = 0; z_ < B; ++z_) {
-        int st = hi[z_];
-        double* o = out5 + (size_t)z_ * 5;
-        for (int k = 0; k < 5; ++k) o[k] = hs[(size_t)z_ * 16 + 8 + k];
-        // a parameter vector that is not finite has no leading minor to blame: NMGP_NUM_NAN whatever pivot met the NaN first
-        bool finite_in = true;
-        for (size_t k = 0; k < P && finite_in; ++k) finite_in = std::isfinite(pars[(size_t)z_ * P + k]);
-        if (!finite_in || (st == 0 && (!std::isfinite(o[0]) || !std::isfinite(o[1])))) st = NMGP_NUM_NAN;
-        if (st != 0) {
-            for (int k = 0; k < 5; ++k) o[k] = std::nan("");
-            if (want_grad) std::fill(grad + (size_t)z_ * P, grad + (size_t)(z_ + 1) * P, 0.0);
-        }
-        status[z_] = st;
-    }
-    return 0;
-}
+};
 
 }  // namespace
 
 // B chains of the resident Hadamard subject: pars [B, P] -> out5 [B, 5] (the verbose tuples), grad [B, P] = d NegLog / d pars or
-// NULL, status [B] (0, a leading-minor index, NMGP_NUM_NAN; a failing chain has a NaN row, a zero gradient row, and does not fail
-// the call).  The workspace is the entry's own, evaluated in chunks of chains below NMGP_HAD_BATCH_SLAB_GB (default 96).
+// NULL, status [B]; see had_batch_eval
 extern "C" int nmgp_had_batch_eval(nmgp_ctx* c, const double* pars, int B, const double hyper[8], int prior, double* out5,
                                    double* grad, int* status) {
-    if (!c) return NMGP_E_NULL;
-    if (!pars || !hyper || !out5 || !status) return nmgp_fail(c, NMGP_E_NULL, "pars/hyper/out5/status must not be NULL");
-    if (B <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "B must be positive");
-    NMGP_TRY(require_had(c));
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->N, M = c->M, T = c->T;
-    const size_t P = (size_t)N * (1 + T) + 1;
-    const bool want_grad = grad != nullptr;
-    double cap_gb = 96.0;
-    if (const char* e = std::getenv("NMGP_HAD_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
-    const size_t per_chain = had_layout(1, N, M, T, want_grad).total * sizeof(double);
-    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
-    Bc = std::min(Bc, 65535);                      // the chain is a grid dimension
-    if (Bc < 1)
-        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the Hadamard model at N = %d needs %.1f GB of device workspace, above the "
-                         "NMGP_HAD_BATCH_SLAB_GB cap of %.0f GB", N, per_chain / 1e9, cap_gb);
-    for (int b0 = 0; b0 < B; b0 += Bc) {
-        const int nb = std::min(Bc, B - b0);
-        NMGP_TRY(had_batch_core(c, pars + (size_t)b0 * P, nb, hyper, prior, out5 + (size_t)b0 * 5,
-                                want_grad ? grad + (size_t)b0 * P : nullptr, status + b0));
-    }
-    c->last_kind = 0;
-    return 0;
+    return had_batch_eval<HadNonsep>(c, pars, B, hyper, prior, out5, grad, status);
 }
 
 // out: [N, N] row-major, the full symmetric S = K_x o (R R^T) + sigma2 I
-extern "C" int nmgp_had_covariance(nmgp_ctx* c, const double* pars, double* out) {
-    if (!c) return NMGP_E_NULL;
-    if (!pars || !out) return nmgp_fail(c, NMGP_E_NULL, "pars/out must not be NULL");
-    NMGP_TRY(require_had(c));
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->N, M = c->M, T = c->T;
-    const size_t P = (size_t)N * (1 + T) + 1;
-    hipStream_t s = c->stream;
-    const int ld = (int)nmgp_ld((size_t)N);
-    double* w;
-    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, P + 1 + (size_t)N * (1 + M) + 2 + (size_t)ld * N, &w));
-    double *dP = w, *ell = dP + ((P + 1) & ~(size_t)1), *Rv = ell + N, *S = Rv + (((size_t)N * M + 1) & ~(size_t)1);
-    HIP_TRY(c, hipMemcpyAsync(dP, pars, P * sizeof(double), hipMemcpyHostToDevice, s));
-    had_prep(s, dP, c->had_indx, N, M, ell, Rv, 1);
-    int r = had_cov_build(s, c->d_x, ell, Rv, dP, (long long)P, S, ld, N, M, 1, 0);
-    if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-    fill_lower_to_full(s, S, ld, N);
-    HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)N * sizeof(double), S, (size_t)ld * sizeof(double), (size_t)N * sizeof(double), (size_t)N,
-                                hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return nmgp_take_launch_error(c);
-}
+extern "C" int nmgp_had_covariance(nmgp_ctx* c, const double* pars, double* out) { return had_covariance<HadNonsep>(c, pars, out); }
 
 // MAP prediction of all M outputs at the new inputs xs [S]: the starred values by GP regression under the two priors, then ONE
 // factorisation per slice of grid points with y and the slice's S_c M cross-covariance vectors riding below the matrix.
@@ -595,12 +303,12 @@ extern "C" int nmgp_predict_had(nmgp_ctx* c, const double* pars, const double hy
     HIP_TRY(c, hipMemcpyAsync(d_xs, xs, (size_t)S * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemsetAsync(info, 0, sizeof(int), s));
     NMGP_TRY(nmgp_ps_project(c, pl, d_xs, S, W0, cv));
-    if (pl != pL) NMGP_TRY(nmgp_ps_project(c, pL, d_xs, S, W1, cv + S));
+    if (pl != pL) NMGP_TRY(nmgp_ps_project(c, pL, d_xs, S, W1, cv + ev(S)));
     NMGP_LAUNCH(k_had_star, dim3(S, 1 + T), dim3(256), 0, s, W0, pl != pL ? W1 : W0, dP, N, T, hyper[0], hyper[3], d_star);
     had_prep(s, dP, c->had_indx, N, M, ell, Rv, 1);
     for (int s0 = 0; s0 < S; s0 += smax) {
         const int Sc = std::min(smax, S - s0), E = Sc * M;
-        int r = had_cov_build(s, c->d_x, ell, Rv, dP, (long long)P, buf, ld, N, M, 1, 0);
+        int r = gibbs_cov_build<false>(s, c->d_x, ell, nullptr, Rv, dP, (long long)P, buf, ld, N, M, 1, 0);
         if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
         set_row(s, buf, ld, N, c->had_y, N, 1, 0, 0);
         NMGP_TRY(had_crosscov_rows(s, c->d_x, ell, Rv, N, M, d_xs, d_star, s0, Sc, buf, ld, N + 1));

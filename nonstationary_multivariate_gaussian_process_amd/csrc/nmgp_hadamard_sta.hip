@@ -8,11 +8,12 @@
 // one dense N x N SPD matrix per evaluation: the jitter is multiplied by B_f[c_i, c_i].  Priors: Normal(mu, sd) on tilde_l, Normal(0, c)
 // on every raw L_vec slot, the unnormalised inverse gamma on sigma2_err; none on tilde_sigma.  There is no GP prior: neither the cached
 // prior factors nor the prior stream are touched.  The factorisation with its riding rows, the triangular matrix-vector product, the
-// inverse SYRK and the trace terms are the library's; this file adds the kernels around them and the entries.  A draw of the posterior
-// is just another parameter vector (no latent curve to regress), so ONE predictor serves the MAP and a chain of draws.
-// Layout conventions of nmgp_hadamard.hip: a 64 x 64 tile of observations per 256-thread workgroup, lanes along i, the j side in LDS,
-// blockIdx.z = chain; fixed summation order and no atomics, so B chains in one launch give the bits of B launches.
-#include "nmgp_internal.h"
+// inverse SYRK and the trace terms are the library's, and the schedule of a batched evaluation is nmgp_hadamard_common.h's, shared
+// with the other two Hadamard models; this file adds the model's kernels, its hooks into that schedule (HadSta) and the predictor.
+// A draw of the posterior is just another parameter vector (no latent curve to regress), so ONE predictor serves the MAP and a
+// chain of draws.  Layout conventions of the Gibbs kernels: a 64 x 64 tile of observations per 256-thread workgroup, lanes along i,
+// the j side in LDS, blockIdx.z = chain; fixed summation order and no atomics, so B chains in one launch give the bits of B launches.
+#include "nmgp_hadamard_common.h"
 
 #include <algorithm>
 
@@ -337,174 +338,52 @@ struct NormalF32 {
     }
 };
 
-// device workspace of a chunk of B chains, in doubles (every piece at an even offset)
-struct HadstLayout {
-    size_t o_P, o_z, o_scal, o_info, o_S;
-    size_t o_alpha = 0, o_Sneg = 0, o_part = 0, o_grad = 0, o_tr = 0;
-    size_t total = 0, part_per = 0;
-    int ld = 0, xpad = 0, xoff = 0;
-    long long bs = 0;
+// hooks of the stationary model into the shared schedule (nmgp_hadamard_common.h); hyper = {mu_tilde_l, sigma_tilde_l, a, b, c}
+struct HadSta {
+    static constexpr int WIDTH = 5;
+    static constexpr bool GP_PRIORS = false;
+    static constexpr const char* NOUN = "stationary Hadamard";
+    static size_t P(int, int T) { return (size_t)T + 3; }
+    static size_t part_width(int M) { return M + 2; }
+    template <class Take>
+    static void extras(HadLayout&, Take, size_t, size_t, int, int, bool) {}
+    static int build_cov(const HadChunk& k) {
+        nmgp_ctx* c = k.c;
+        return hadst_cov_build(c->stream, c->d_x, c->had_indx, k.at(k.L.o_P), (long long)P(c->N, c->T), k.at(k.L.o_S), k.L.ld, c->N, c->M,
+                               k.B, k.L.bs);
+    }
+    static int value_epilogue(const HadChunk& k) {
+        nmgp_ctx* c = k.c;
+        const NormalF32 nl(k.hyper[0], k.hyper[1]), nc(0.0, k.hyper[4]);
+        double* scal = k.at(k.L.o_scal);
+        NMGP_LAUNCH(k_hadst_finalize, dim3(k.B), dim3(64), 0, c->stream, scal, k.at(k.L.o_P), c->T, nl.mean, nl.var, nl.log_sd, nc.var,
+                    nc.log_sd, k.hyper[2], k.hyper[3], k.prior, scal + 8);
+        return 0;
+    }
+    static int adjoint_grad(const HadChunk& k) {
+        nmgp_ctx* c = k.c;
+        const int N = c->N, M = c->M, T = c->T;
+        const long long P_ = (long long)P(N, T), pstride = (long long)k.L.part_per;
+        const NormalF32 nl(k.hyper[0], k.hyper[1]), nc(0.0, k.hyper[4]);
+        double *dP = k.at(k.L.o_P), *part = k.at(k.L.o_part);
+        NMGP_TRY(hadst_adjoint(c->stream, c->d_x, c->had_indx, dP, P_, k.at(k.L.o_alpha), k.at(k.L.o_Sneg), N, N, M, part, pstride, k.B));
+        NMGP_LAUNCH(k_hadst_grad_final, dim3((unsigned)P_, k.B), dim3(256), 0, c->stream, part, pstride, (N + 63) / 64, N, M, T,
+                    c->had_indx, dP, k.at(k.L.o_tr), nl.mean, nl.var, nc.var, k.hyper[2], k.hyper[3], k.prior, k.at(k.L.o_grad));
+        return 0;
+    }
 };
-
-HadstLayout hadst_layout(int B, int N, int M, int T, bool want_grad) {
-    HadstLayout L;
-    const size_t P = (size_t)T + 3, Bs = B, NJ = (N + 63) / 64;
-    // rows: N (matrix) + 1 (y); with gradients + pad + N identity rows (-> L^-T)
-    L.xpad = (N + 1) & 1;
-    L.xoff = N + 1 + L.xpad;
-    L.ld = (int)nmgp_ld(want_grad ? (size_t)2 * N + 2 : (size_t)N + 1);
-    L.bs = (long long)L.ld * N;
-    // adjoint partial rows; before that pass the same buffer holds the block sums of alpha = L^-T z (tri_gemv_upper)
-    L.part_per = std::max((size_t)(M + 2) * NJ * N, (size_t)N * ((N + 255) / 256));
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 1) & ~(size_t)1; return o; };
-    L.o_P = take(Bs * P); L.o_z = take(Bs * N); L.o_scal = take(Bs * 16); L.o_info = take(Bs);
-    L.o_S = take(Bs * (size_t)L.bs);
-    if (want_grad) {
-        L.o_alpha = take(Bs * N); L.o_Sneg = take(Bs * (size_t)N * N); L.o_part = take(Bs * L.part_per);
-        L.o_grad = take(Bs * P); L.o_tr = take(Bs * 2);
-    }
-    L.total = off;
-    return L;
-}
-
-// chains [0, B) of `pars` (already offset by the caller): value and gradient halves enqueued back to back, ONE synchronisation
-int hadst_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[5], int prior, double* out5, double* grad,
-                     int* status) {
-    const int N = c->N, M = c->M, T = c->T;
-    const size_t P = (size_t)T + 3;
-    const bool want_grad = grad != nullptr;
-    const NormalF32 nl(hyper[0], hyper[1]), nc(0.0, hyper[4]);
-    const double a = hyper[2], b = hyper[3];
-    hipStream_t s = c->stream;
-    const HadstLayout L = hadst_layout(B, N, M, T, want_grad);
-    double* slab;
-    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
-    double *dP = slab + L.o_P, *z = slab + L.o_z, *scal = slab + L.o_scal, *S = slab + L.o_S;
-    int* info = reinterpret_cast<int*>(slab + L.o_info);
-    const int ld = L.ld;
-    const long long bs = L.bs;
-    HIP_TRY(c, hipMemcpyAsync(dP, pars, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)B * sizeof(int), s));
-    {
-        NmgpStage sp(c, NMGP_STAGE_COV);
-        int r = hadst_cov_build(s, c->d_x, c->had_indx, dP, (long long)P, S, ld, N, M, B, bs);
-        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-    }
-    {
-        NmgpStage sp(c, NMGP_STAGE_CHOL);
-        set_row(s, S, ld, N, c->had_y, N, B, bs, 0);                // y rides along as row N (shared by the chains)
-        if (want_grad) identity_rows(s, S, ld, N + 1, N, L.xpad, B, bs);
-        nmgp_potrf(c, S, ld, N, want_grad ? 1 + L.xpad : 1, want_grad ? N : 0, info, B, bs, 1);
-        get_row(s, S, ld, N, z, N, B, bs, N);                       // z = L^-1 y
-    }
-    {
-        NmgpStage sp(c, NMGP_STAGE_REDUCE);
-        chol_logdet_quad(s, S, ld, N, z, scal, scal + 1, B, bs, 16);
-        NMGP_LAUNCH(k_hadst_finalize, dim3(B), dim3(64), 0, s, scal, dP, T, nl.mean, nl.var, nl.log_sd, nc.var, nc.log_sd, a, b, prior,
-                    scal + 8);
-    }
-    std::vector<double> hs((size_t)B * 16);
-    std::vector<int> hi(B);
-    HIP_TRY(c, hipMemcpyAsync(hs.data(), scal, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(hi.data(), info, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (want_grad) {
-        // enqueued behind the value half without waiting for it (a chain that failed produces garbage here, which the epilogue discards)
-        double *alpha = slab + L.o_alpha, *Sneg = slab + L.o_Sneg, *part = slab + L.o_part, *dg = slab + L.o_grad, *tr = slab + L.o_tr;
-        const int NJ = (N + 63) / 64;
-        {
-            NmgpStage sp(c, NMGP_STAGE_SOLVE);
-            tri_gemv_upper(s, S + L.xoff, ld, N, z, alpha, part, B, bs, (long long)L.part_per);   // alpha = L^-T z = X z
-        }
-        {
-            NmgpStage sp(c, NMGP_STAGE_INVERSE);
-            syrk_lower(s, S + L.xoff, ld, Sneg, N, N, N, N, B, bs, (long long)N * N, 2);         // -S^-1 = -X X^T, both triangles
-        }
-        {
-            NmgpStage sp(c, NMGP_STAGE_ADJOINT);
-            trace_terms(s, alpha, Sneg, N, N, tr, -1.0, B);
-            int r = hadst_adjoint(s, c->d_x, c->had_indx, dP, (long long)P, alpha, Sneg, N, N, M, part, (long long)L.part_per, B);
-            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-            NMGP_LAUNCH(k_hadst_grad_final, dim3((unsigned)P, B), dim3(256), 0, s, part, (long long)L.part_per, NJ, N, M, T, c->had_indx,
-                        dP, tr, nl.mean, nl.var, nc.var, a, b, prior, dg);
-        }
-        HIP_TRY(c, hipMemcpyAsync(grad, dg, (size_t)B * P * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(c, hipStreamSynchronize(s));          // the one synchronisation of the evaluation
-    NMGP_TRY(nmgp_take_launch_error(c));
-    for (int z_ = 0; z_ < B; ++z_) {
-        int st = hi[z_];
-        double* o = out5 + (size_t)z_ * 5;
-        for (int k = 0; k < 5; ++k) o[k] = hs[(size_t)z_ * 16 + 8 + k];
-        // a parameter vector that is not finite has no leading minor to blame: NMGP_NUM_NAN whatever pivot met the NaN first
-        bool finite_in = true;
-        for (size_t k = 0; k < P && finite_in; ++k) finite_in = std::isfinite(pars[(size_t)z_ * P + k]);
-        if (!finite_in || (st == 0 && (!std::isfinite(o[0]) || !std::isfinite(o[1])))) st = NMGP_NUM_NAN;
-        if (st != 0) {
-            for (int k = 0; k < 5; ++k) o[k] = std::nan("");
-            if (want_grad) std::fill(grad + (size_t)z_ * P, grad + (size_t)(z_ + 1) * P, 0.0);
-        }
-        status[z_] = st;
-    }
-    return 0;
-}
 
 }  // namespace
 
 // B chains of the resident Hadamard subject under the stationary model: pars [B, T + 3] -> out5 [B, 5] (the verbose tuples), grad
-// [B, T + 3] = d NegLog / d pars or NULL, status [B] (0, a leading-minor index, NMGP_NUM_NAN; a failing chain has a NaN row, a zero
-// gradient row, and does not fail the call).  hyper = {mu_tilde_l, sigma_tilde_l, a, b, c}.  The workspace is the entry's own,
-// evaluated in chunks of chains below NMGP_HAD_BATCH_SLAB_GB (default 96).
+// [B, T + 3] = d NegLog / d pars or NULL, status [B]; see had_batch_eval.  hyper = {mu_tilde_l, sigma_tilde_l, a, b, c}.
 extern "C" int nmgp_hadst_batch_eval(nmgp_ctx* c, const double* pars, int B, const double hyper[5], int prior, double* out5,
                                      double* grad, int* status) {
-    if (!c) return NMGP_E_NULL;
-    if (!pars || !hyper || !out5 || !status) return nmgp_fail(c, NMGP_E_NULL, "pars/hyper/out5/status must not be NULL");
-    if (B <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "B must be positive");
-    NMGP_TRY(require_had(c));
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->N, M = c->M, T = c->T;
-    const size_t P = (size_t)T + 3;
-    const bool want_grad = grad != nullptr;
-    double cap_gb = 96.0;
-    if (const char* e = std::getenv("NMGP_HAD_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
-    const size_t per_chain = hadst_layout(1, N, M, T, want_grad).total * sizeof(double);
-    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
-    Bc = std::min(Bc, 65535);                      // the chain is a grid dimension
-    if (Bc < 1)
-        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the stationary Hadamard model at N = %d needs %.1f GB of device workspace, "
-                         "above the NMGP_HAD_BATCH_SLAB_GB cap of %.0f GB", N, per_chain / 1e9, cap_gb);
-    for (int b0 = 0; b0 < B; b0 += Bc) {
-        const int nb = std::min(Bc, B - b0);
-        NMGP_TRY(hadst_batch_core(c, pars + (size_t)b0 * P, nb, hyper, prior, out5 + (size_t)b0 * 5,
-                                  want_grad ? grad + (size_t)b0 * P : nullptr, status + b0));
-    }
-    c->last_kind = 0;
-    return 0;
+    return had_batch_eval<HadSta>(c, pars, B, hyper, prior, out5, grad, status);
 }
 
 // out: [N, N] row-major, the full symmetric S = K_x o B_f[c, c] + sigma2_err I
-extern "C" int nmgp_hadst_covariance(nmgp_ctx* c, const double* pars, double* out) {
-    if (!c) return NMGP_E_NULL;
-    if (!pars || !out) return nmgp_fail(c, NMGP_E_NULL, "pars/out must not be NULL");
-    NMGP_TRY(require_had(c));
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->N, M = c->M, T = c->T;
-    const size_t P = (size_t)T + 3;
-    hipStream_t s = c->stream;
-    const int ld = (int)nmgp_ld((size_t)N);
-    auto ev = [](size_t n) { return (n + 1) & ~(size_t)1; };
-    double* w;
-    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, ev(P) + (size_t)ld * N, &w));
-    double *dP = w, *S = dP + ev(P);
-    HIP_TRY(c, hipMemcpyAsync(dP, pars, P * sizeof(double), hipMemcpyHostToDevice, s));
-    int r = hadst_cov_build(s, c->d_x, c->had_indx, dP, (long long)P, S, ld, N, M, 1, 0);
-    if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-    fill_lower_to_full(s, S, ld, N);
-    HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)N * sizeof(double), S, (size_t)ld * sizeof(double), (size_t)N * sizeof(double), (size_t)N,
-                                hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return nmgp_take_launch_error(c);
-}
+extern "C" int nmgp_hadst_covariance(nmgp_ctx* c, const double* pars, double* out) { return had_covariance<HadSta>(c, pars, out); }
 
 // Prediction at the new inputs xs [S] under H parameter vectors (H = 1: the MAP predictor; H > 1: posterior draws).  A chunk of B
 // draws is ONE batched factorisation of B matrices of order N with y and the slice's cross-covariance rows riding below each.

@@ -288,12 +288,14 @@ int nmgp_ps_chunk(int H, size_t per_draw_doubles);
 // if B is not finite
 void nmgp_small_eig(const double* uL, int M, double* wB, double* VB, double* Bdiag);
 
-// ---- pieces shared by the two Hadamard models (nmgp_hadamard.hip, nmgp_hadamard_sep.hip) ----
+// ---- pieces shared by the Hadamard models (nmgp_hadamard.hip, nmgp_hadamard_sep.hip, nmgp_hadamard_sta.hip and the posterior-draw
+// entry nmgp_predsample_hadamard.hip); the schedule of a batched evaluation and the Gibbs kernels are in nmgp_hadamard_common.h ----
 // scratch slots of the context (nmgp_eig.hip numbers them; a Hadamard entry never runs inside one of that file)
 enum { HSL_SMALL = 13, HSL_SLAB = 14, HSL_PRED = 15 };
-// NMGP_E_STATE unless a Hadamard subject is resident, NMGP_E_UNSUPPORTED off the custom factorisation (riding rows)
+// NMGP_E_STATE unless a Hadamard subject is resident, NMGP_E_UNSUPPORTED off the custom factorisation (riding rows); every entry
+// of the three models calls it (defined in nmgp_hadamard.hip, as the next two)
 int require_had(nmgp_ctx* c);
-// the two cached prior factors of hyper[1..2] and hyper[4..5]
+// the two cached prior factors of hyper[1..2] and hyper[4..5] (the two models with GP priors: nonseparable and separable)
 int had_priors(nmgp_ctx* c, const double* hyper, PriorFactor** p0, PriorFactor** p1);
 // op(L) X = R for the 1 + T prior columns of every chain (column 0 against p0, the others against p1)
 int had_prior_solve(nmgp_ctx* c, hipStream_t sp, rocblas_handle hb, bool trans, PriorFactor* p0, PriorFactor* p1, double* R, int N,

@@ -65,24 +65,49 @@ def generate_K_index_SVC_hadamard0(L_f_list, indexes):
     return torch.mm(L, L.t())
 
 
-class _HadamardObjective(torch.autograd.Function):
-    """Value + gradient of the Hadamard objective from one C-ABI call: forward(flags, hyper, x, indx, y, tilde_l, L_vecs,
-    tilde_sigma2_err) -> (res, loglik, lp_tilde_l, lp_L_vecs, lp_sigma2_err), ``res`` the log posterior (NOT negated), the rest
-    non-differentiable.  The gradient is computed in the forward call whenever a parameter requires grad and autograd is
-    recording at the call site (see ``Utility.logpos._FusedObjective``)."""
+def _bands(mean, var):
+    """[mu - 1.96 s, mu, mu + 1.96 s] stacked on axis 1 ([S, 3, M]) as a double tensor."""
+    sd = np.sqrt(var)
+    pct = np.stack([mean - 1.96 * sd, mean, mean + 1.96 * sd], axis=1)
+    return torch.from_numpy(np.ascontiguousarray(pct)).type(torch.DoubleTensor)
 
-    @staticmethod
+
+def _backward(fctx, gres, *unused):
+    """The backward of every Hadamard objective: scatter d NegLog / d pars over the parameter pieces."""
+    g = fctx.grad_np
+    outs = [None] * 5          # the parameter pieces follow five non-tensor arguments
+    if g is None:
+        return tuple(outs + [None] * len(fctx.shapes))
+    scale = -float(gres)          # grad_np is for NegLog = -res
+    k = 0
+    for shp in fctx.shapes:
+        if shp is None:
+            outs.append(None)
+            k += 1
+            continue
+        cnt = int(np.prod(shp)) if len(shp) else 1
+        outs.append(torch.from_numpy(g[k:k + cnt] * scale).type(torch.DoubleTensor).reshape(shp))
+        k += cnt
+    return tuple(outs)
+
+
+def _objective(module, name, eval_method, what, doc):
+    """The ``torch.autograd.Function`` of one Hadamard model: value + gradient from one C-ABI call, ``eval_method`` of
+    ``_lib.Context``; ``what`` is the reference function its error speaks of, ``module`` the module that binds the class (its ``__module__``).  forward(flags, hyper, x, indx, y, *parameter pieces)
+    -> (res, loglik, the model's prior terms ...), ``res`` the log posterior (NOT negated), the rest non-differentiable.  The
+    gradient is computed in the forward call whenever a parameter requires grad and autograd is recording at the call site (see
+    ``Utility.logpos._FusedObjective``)."""
+
     def forward(fctx, flags, hyper, x, indx, y, *pieces):
         prior, grad_mode = flags
         c = _lib.default_context()
         c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
         flat = np.concatenate([_np(p).reshape(-1) for p in pieces])
         want_grad = bool(grad_mode) and any(isinstance(p, torch.Tensor) and p.requires_grad for p in pieces)
-        out, grad, status = c.had_batch_eval(flat[None], hyper, prior, want_grad)
+        out, grad, status = getattr(c, eval_method)(flat[None], hyper, prior, want_grad)
         if status[0] != 0:
-            # torch.inverse raises on a singular covariance (reference logpos.py:623)
-            raise RuntimeError("nlogpos_obj_hadamard_SVC: the covariance is not positive definite or not finite (status %d)"
-                               % int(status[0]))
+            # torch.inverse raises on a singular covariance (reference logpos.py:528 / 623 / 690)
+            raise RuntimeError("%s: the covariance is not positive definite or not finite (status %d)" % (what, int(status[0])))
         fctx.shapes = [tuple(p.shape) if isinstance(p, torch.Tensor) else None for p in pieces]
         fctx.grad_np = grad[0] if want_grad else None          # d NegLog / d pars
         res = [torch.tensor(-float(out[0, 0]), dtype=torch.float64)]
@@ -90,23 +115,14 @@ class _HadamardObjective(torch.autograd.Function):
         fctx.mark_non_differentiable(*res[1:])
         return tuple(res)
 
-    @staticmethod
-    def backward(fctx, gres, *unused):
-        g = fctx.grad_np
-        outs = [None] * 5
-        if g is None:
-            return tuple(outs + [None] * len(fctx.shapes))
-        scale = -float(gres)          # grad_np is for NegLog = -res
-        k = 0
-        for shp in fctx.shapes:
-            if shp is None:
-                outs.append(None)
-                k += 1
-                continue
-            cnt = int(np.prod(shp)) if len(shp) else 1
-            outs.append(torch.from_numpy(g[k:k + cnt] * scale).type(torch.DoubleTensor).reshape(shp))
-            k += cnt
-        return tuple(outs)
+    return type(name, (torch.autograd.Function,),
+                {"forward": staticmethod(forward), "backward": staticmethod(_backward), "__doc__": doc, "__module__": module})
+
+
+_HadamardObjective = _objective(
+    __name__, "_HadamardObjective", "had_batch_eval", "nlogpos_obj_hadamard_SVC",
+    "Nonseparable model: forward(flags, hyper, x, indx, y, tilde_l, L_vecs, tilde_sigma2_err) -> (res, loglik, lp_tilde_l, "
+    "lp_L_vecs, lp_sigma2_err).")
 
 
 def nlogpos_obj_hadamard_SVC(pars, x, indx, y, mu_tilde_l=0., alpha_tilde_l=1., beta_tilde_l=1., mu_L=0., alpha_L=1., beta_L=1.,
@@ -143,9 +159,7 @@ def _predict(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, xs, mu_tilde_l, alph
     hyper = [_f(mu_tilde_l), _f(alpha_tilde_l), _f(beta_tilde_l), _f(mu_L), _f(alpha_L), _f(beta_L), 1.0, 1.0]
     pars = np.concatenate([_np(tilde_l).reshape(-1), _np(L_vecs).reshape(-1), _np(tilde_sigma2_err).reshape(-1)])
     mean, var, _ = c.predict_had(pars, hyper, _np(xs).reshape(-1))
-    sd = np.sqrt(var)
-    pct = np.stack([mean - 1.96 * sd, mean, mean + 1.96 * sd], axis=1)          # [S, 3, M]
-    return torch.from_numpy(np.ascontiguousarray(pct)).type(torch.DoubleTensor)
+    return _bands(mean, var)
 
 
 def point_predmap_SVC_hadamard(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, x_star, mu_tilde_l, alpha_tilde_l, beta_tilde_l,

@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .hadamard import _HadamardObjective, _as_tensor, _f, _labels, _np
+from .hadamard import _as_tensor, _bands, _f, _labels, _np, _objective
 
 LOGPOS_NAMES = ("nlogpos_obj_hadamard", "logpos_hadamard")
 PREDICTION_NAMES = ("point_predmap_hadamard", "pointwise_predmap_hadmard", "pointwise_predmap_hadamard")
@@ -47,33 +47,10 @@ def enabled():
     return os.environ.get("NMGP_HADAMARD_SEP", "") not in ("", "0")
 
 
-class _HadamardSepObjective(torch.autograd.Function):
-    """Value + gradient of the separable Hadamard objective from one C-ABI call: forward(flags, hyper, x, indx, y, tilde_l,
-    tilde_sigma, L_vec, tilde_sigma2_err) -> (res, loglik, lp_tilde_l, lp_tilde_sigma, lp_L_vec, lp_sigma2_err), ``res`` the log
-    posterior (NOT negated), the rest non-differentiable.  The gradient is computed in the forward call whenever a parameter
-    requires grad and autograd is recording at the call site."""
-
-    @staticmethod
-    def forward(fctx, flags, hyper, x, indx, y, *pieces):
-        prior, grad_mode = flags
-        c = _lib.default_context()
-        c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
-        flat = np.concatenate([_np(p).reshape(-1) for p in pieces])
-        want_grad = bool(grad_mode) and any(isinstance(p, torch.Tensor) and p.requires_grad for p in pieces)
-        out, grad, status = c.hads_batch_eval(flat[None], hyper, prior, want_grad)
-        if status[0] != 0:
-            # torch.inverse raises on a singular covariance (reference logpos.py:528)
-            raise RuntimeError("nlogpos_obj_hadamard: the covariance is not positive definite or not finite (status %d)"
-                               % int(status[0]))
-        fctx.shapes = [tuple(p.shape) if isinstance(p, torch.Tensor) else None for p in pieces]
-        fctx.grad_np = grad[0] if want_grad else None          # d NegLog / d pars
-        res = [torch.tensor(-float(out[0, 0]), dtype=torch.float64)]
-        res += [torch.tensor(float(v), dtype=torch.float64) for v in out[0, 1:]]
-        fctx.mark_non_differentiable(*res[1:])
-        return tuple(res)
-
-    # the parameter pieces follow five non-tensor arguments, as in hadamard._HadamardObjective: one scatter serves both
-    backward = staticmethod(_HadamardObjective.backward)
+_HadamardSepObjective = _objective(
+    __name__, "_HadamardSepObjective", "hads_batch_eval", "nlogpos_obj_hadamard",
+    "Separable model: forward(flags, hyper, x, indx, y, tilde_l, tilde_sigma, L_vec, tilde_sigma2_err) -> (res, loglik, "
+    "lp_tilde_l, lp_tilde_sigma, lp_L_vec, lp_sigma2_err).")
 
 
 def nlogpos_obj_hadamard(pars, x, indx, y, mu_tilde_l=0., alpha_tilde_l=1., beta_tilde_l=1., mu_tilde_sigma=0., alpha_tilde_sigma=1.,
@@ -115,9 +92,7 @@ def _predict(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, xs, mu_t
     pars = np.concatenate([_np(tilde_l).reshape(-1), _np(tilde_sigma).reshape(-1), _np(L_vec).reshape(-1),
                            _np(tilde_sigma2_err).reshape(-1)])
     mean, var, _ = c.predict_hads(pars, hyper, _np(xs).reshape(-1))
-    sd = np.sqrt(var)
-    pct = np.stack([mean - 1.96 * sd, mean, mean + 1.96 * sd], axis=1)          # [S, 3, M]
-    return torch.from_numpy(np.ascontiguousarray(pct)).type(torch.DoubleTensor)
+    return _bands(mean, var)
 
 
 def point_predmap_hadamard(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, x_star, mu_tilde_l, alpha_tilde_l, beta_tilde_l,

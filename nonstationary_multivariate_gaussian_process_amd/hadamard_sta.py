@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .hadamard import _HadamardObjective, _as_tensor, _f, _labels, _np
+from .hadamard import _as_tensor, _bands, _f, _labels, _np, _objective
 
 LOGPOS_NAMES = ("nlogpos_obj_hadamard_S", "logpos_hadamard_S")
 PREDICTION_NAMES = ("point_predmap_S_hadamard", "pointwise_predmap_S_hadamard")
@@ -50,33 +50,10 @@ def enabled():
     return os.environ.get("NMGP_HADAMARD_STA", "") not in ("", "0")
 
 
-class _HadamardStaObjective(torch.autograd.Function):
-    """Value + gradient of the stationary Hadamard objective from one C-ABI call: forward(flags, hyper, x, indx, y, tilde_l,
-    tilde_sigma, L_vec, tilde_sigma2_err) -> (res, loglik, lp_tilde_l, lp_L_vec, lp_sigma2_err), ``res`` the log posterior (NOT
-    negated), the rest non-differentiable.  The gradient is computed in the forward call whenever a parameter requires grad and
-    autograd is recording at the call site."""
-
-    @staticmethod
-    def forward(fctx, flags, hyper, x, indx, y, *pieces):
-        prior, grad_mode = flags
-        c = _lib.default_context()
-        c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
-        flat = np.concatenate([_np(p).reshape(-1) for p in pieces])
-        want_grad = bool(grad_mode) and any(isinstance(p, torch.Tensor) and p.requires_grad for p in pieces)
-        out, grad, status = c.hadst_batch_eval(flat[None], hyper, prior, want_grad)
-        if status[0] != 0:
-            # torch.inverse raises on a singular covariance (reference logpos.py:690)
-            raise RuntimeError("nlogpos_obj_hadamard_S: the covariance is not positive definite or not finite (status %d)"
-                               % int(status[0]))
-        fctx.shapes = [tuple(p.shape) if isinstance(p, torch.Tensor) else None for p in pieces]
-        fctx.grad_np = grad[0] if want_grad else None          # d NegLog / d pars
-        res = [torch.tensor(-float(out[0, 0]), dtype=torch.float64)]
-        res += [torch.tensor(float(v), dtype=torch.float64) for v in out[0, 1:]]
-        fctx.mark_non_differentiable(*res[1:])
-        return tuple(res)
-
-    # the parameter pieces follow five non-tensor arguments, as in hadamard._HadamardObjective: one scatter serves both
-    backward = staticmethod(_HadamardObjective.backward)
+_HadamardStaObjective = _objective(
+    __name__, "_HadamardStaObjective", "hadst_batch_eval", "nlogpos_obj_hadamard_S",
+    "Stationary model: forward(flags, hyper, x, indx, y, tilde_l, tilde_sigma, L_vec, tilde_sigma2_err) -> (res, loglik, "
+    "lp_tilde_l, lp_L_vec, lp_sigma2_err).")
 
 
 def nlogpos_obj_hadamard_S(pars, x, indx, y, mu_tilde_l, sigma_tilde_l, a=1, b=1, c=10, verbose=False, Prior=True):
@@ -118,10 +95,7 @@ def _moments(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, xs, indx
 
 
 def _predict(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, xs):
-    mean, var = _moments(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, xs)
-    sd = np.sqrt(var)
-    pct = np.stack([mean - 1.96 * sd, mean, mean + 1.96 * sd], axis=1)          # [S, 3, M]
-    return torch.from_numpy(np.ascontiguousarray(pct)).type(torch.DoubleTensor)
+    return _bands(*_moments(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, xs))
 
 
 def point_predmap_S_hadamard(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, x_star, *args, **kwargs):

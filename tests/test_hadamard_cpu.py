@@ -304,5 +304,7 @@ def test_abi_declares_and_binds_the_four_entries():
         assert n in _lib.SIGNATURES and ("int %s(" % n) in header, n
         assert hasattr(_lib.Context, n[len("nmgp_"):] if n != "nmgp_predict_had" else "predict_had")
     assert "nmgp_hadamard.hip" in build.SOURCES
+    # the shared schedule and kernels: a header outside HEADERS is outside the build id, and a stale library would load
+    assert "nmgp_hadamard_common.h" in [os.path.basename(h) for h in build.HEADERS]
     from nonstationary_multivariate_gaussian_process_amd import drivers
     assert issubclass(drivers.HadamardMAP, drivers.LockStepMAP) and issubclass(drivers.BatchedHMCHadamard, drivers.LockStepHMC)
