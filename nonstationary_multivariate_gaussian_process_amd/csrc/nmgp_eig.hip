@@ -1298,7 +1298,10 @@ static int chol_predict(nmgp_ctx* c, EigWork& w, double sigma2, int mode, const 
         sep_blocks(s, c->d_K, w.wB, w.sig2, N, M, Sbuf, ld, bs);
         set_row(s, Sbuf, ld, N, yt, N, M, bs, N);
         cols_to_rows(s, KX + (size_t)s0 * N, N, Sc, Sbuf, ld, N + 1, M, bs);
-        nmgp_potrf(c, Sbuf, ld, N, 1 + Sc, 0, info, M, bs, 1);
+        // precise = 1 (substitution-based panel kernels): a block wB[p] K + sigma2 I of a smooth K under a large wB[p] has diagonal
+        // blocks of condition number ~1e5, and the solves through their inverted 16 x 16 blocks left the variance -- the small
+        // difference B_mm kss - |L^-1 k|^2 -- 6e-8 away from the dense references at M = 8 (tests/test_gpu_prediction_sweep.py)
+        nmgp_potrf(c, Sbuf, ld, N, 1 + Sc, 0, info, M, bs, 1, 1);
         for (int p = 0; p < M; ++p)
             pred_rows_reduce(s, Sbuf + (size_t)p * bs, ld, N, N + 1, N, Sc, part, dots + (size_t)p * S + s0, sqs + (size_t)p * S + s0);
     }

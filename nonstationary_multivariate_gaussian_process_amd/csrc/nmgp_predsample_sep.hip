@@ -267,7 +267,7 @@ int predsample_kron(nmgp_ctx* c, bool stationary, const double* pars, int H, con
                             ld, bs, N + 1);
             }
             set_row(s, Sb, ld, N, yt, N, BM, bs, N);
-            nmgp_potrf(c, Sb, ld, N, 1 + Sc, 0, d_info, BM, bs, 1);
+            nmgp_potrf(c, Sb, ld, N, 1 + Sc, 0, d_info, BM, bs, 1, 1);          // precise = 1, as chol_predict (nmgp_eig.hip) and why
             ps_rows_reduce(s, Sb, ld, bs, N, N + 1, N, Sc, part, BM, dots, sqs, (long long)S, (long long)s0);
         }
         NMGP_LAUNCH(k_pss_combine, dim3(cdiv((long long)SMo, 256), Bc), dim3(256), 0, s, dots, sqs, d_small, d_star, S, M,

@@ -183,9 +183,31 @@ def gen_n512(only):
     assert os.path.getsize(os.path.join(HERE, name + ".npz")) < 1 << 20
 
 
+SMALL = ((8, 1), (12, 2), (10, 8))             # (N, M) away from M = 3: one output, an even M, the largest instantiation
+SMALL_XS = np.array([0.02, 0.37, 0.613, 0.99])
+
+
+def gen_small(only):
+    """predsample_N8_M1, predsample_N12_M2, predsample_N10_M8: both families at H = n_sample = 3, S = 4 (a few kB each)."""
+    for N, M in SMALL:
+        name = "predsample_N%d_M%d" % (N, M)
+        if only and not name.startswith(only):
+            continue
+        T = M * (M + 1) // 2
+        x, Y = sim.rngfree_inputs(N, M)
+        h = sim.HYPER_SVC
+        draws = smooth_draws(sim.rngfree_pars_svc(N, M), x, N, T, 3)
+        out = dict(x=x, Y=Y, xs=SMALL_XS, hyper=G.hyper_vec(h, G.SVC_KEYS), draws=draws)
+        out.update(gen_family_predsample(x, Y, draws, SMALL_XS, h, seed=500 + M))
+        out.update(gen_family_sampling(x, Y, draws[0], SMALL_XS, h, n_sample=3, seed=600 + M))
+        G.save(name, **out)
+        assert os.path.getsize(os.path.join(HERE, name + ".npz")) < 50000
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     gen_n64(a.only)
     gen_n512(a.only)
+    gen_small(a.only)

@@ -22,7 +22,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import make_golden as G  # noqa: E402
-from make_golden_predsample import PRECISION, condvar, recorded  # noqa: E402
+from make_golden_predsample import PRECISION, SMALL, SMALL_XS, condvar, recorded  # noqa: E402
 
 sim, prediction, logpos, t = G.sim, G.prediction, G.logpos, G.t
 HYPER_NAMES = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_tilde_sigma", "alpha_tilde_sigma", "beta_tilde_sigma")
@@ -188,9 +188,28 @@ def gen_n512(only):
     finish(name, out)
 
 
+def gen_small(only):
+    """predsample_sep_N8_M1, predsample_sep_N12_M2, predsample_sep_N10_M8: the three families at H = n_sample = 3, S = 4."""
+    for N, M in SMALL:
+        name = "predsample_sep_N%d_M%d" % (N, M)
+        if only and not name.startswith(only):
+            continue
+        T = M * (M + 1) // 2
+        x, Y = sim.rngfree_inputs(N, M)
+        h = sim.HYPER_SEP
+        draws = sep_draws(sim.rngfree_pars_sep(N, M), x, N, T, 3)
+        out = dict(x=x, Y=Y, xs=SMALL_XS, hyper=G.hyper_vec(h, G.SEP_KEYS), draws=draws)
+        out.update(gen_family_predsample(x, Y, draws, SMALL_XS, h, seed=700 + M))
+        out.update(gen_family_sampling(x, Y, draws[0], SMALL_XS, h, n_sample=3, seed=800 + M))
+        out.update(gen_family_stationary(x, Y, sta_draws(sim.rngfree_pars_sta(M), T, 3), SMALL_XS, seed=900 + M))
+        G.save(name, **out)
+        assert os.path.getsize(os.path.join(HERE, name + ".npz")) < 50000
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     gen_n64(a.only)
     gen_n512(a.only)
+    gen_small(a.only)
