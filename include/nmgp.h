@@ -279,6 +279,25 @@ int nmgp_logpos_sta(nmgp_ctx* ctx, const double* pars, const double hyper[5], in
 int nmgp_sep_batch_eval(nmgp_ctx* ctx, const double* pars, int B, const double hyper[9], int prior, double* out6, double* grad,
                         int* status);
 
+/* The separable model for MANY SUBJECTS per launch sequence (the cohort loop of Separable_model_mpiKAISER.py, one process per subject
+ * and chain there): x [S, N], Y [S, N, M] row-major, N and M those of nmgp_set_data.  While the set is active nmgp_sep_batch_eval
+ * requires B == S * chains_per_subject (NMGP_E_SHAPE otherwise) and batch element b = s * chains_per_subject + k is chain k of
+ * subject s: it reads x[s], Y[s] and that subject's GP-prior factors (one pair per subject, one batched factorisation on first use,
+ * cached per (alpha, beta) with the set; a subject whose prior covariance is not positive definite fails the evaluation with its
+ * index in the message).  Outputs, gradient layout and status are those of nmgp_sep_batch_eval.  The prior terms are solved by
+ * substitution against the subject's factors (NMGP_PRIOR_SOLVE=rocblas, and N > 3500: one library trsm per subject), so they agree
+ * with the resident path to rounding; the likelihood and its gradient agree to the bit.  Chunks (NMGP_SEP_BATCH_SLAB_GB) are whole
+ * subjects, or parts of one subject when chains_per_subject exceeds a chunk.  A chain that fails numerically -- and every chain when
+ * B == 1, under NMGP_SEP=eig or beyond the block kernel's N -- is evaluated through nmgp_logpos_sep ON ITS OWN SUBJECT; the
+ * resident subject and its cached prior factors are back in place when the call returns.
+ * NMGP_E_STATE without a complete-data resident subject, NMGP_E_NULL for a NULL x or Y, NMGP_E_SHAPE for S < 1 or
+ * chains_per_subject < 1.  A second call replaces the set.  The set lives until nmgp_sep_batch_clear_subjects, nmgp_set_data or
+ * nmgp_had_set_data, each of which frees it with its prior factors; without a set nmgp_sep_batch_eval evaluates the resident
+ * subject exactly as before.  No other entry looks at the set: nmgp_logpos_sep, nmgp_sep_prior_apply and the predictors keep using
+ * the resident subject. */
+int nmgp_sep_batch_set_subjects_chains(nmgp_ctx* ctx, const double* x, const double* Y, int S, int chains_per_subject);
+int nmgp_sep_batch_clear_subjects(nmgp_ctx* ctx);
+
 /* ---- primitives (host buffers in / out) ----------------------------------------------------- */
 /* kernels.pairwise_distances, kernels.py:5-21.  x1: [n1,d], x2: [n2,d] or NULL (=x1). out: [n1,n2]. */
 int nmgp_pairwise_distances(nmgp_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int d,

@@ -65,6 +65,8 @@ SIGNATURES = {
     "nmgp_logpos_sep": (I, [V, P, P, I, P, P]),
     "nmgp_logpos_sta": (I, [V, P, P, I, P, P]),
     "nmgp_sep_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_sep_batch_set_subjects_chains": (I, [V, P, P, I, I]),
+    "nmgp_sep_batch_clear_subjects": (I, [V]),
     "nmgp_pairwise_distances": (I, [V, P, I, P, I, I, P]),
     "nmgp_rbf_cov": (I, [V, P, I, P, I, I, D, D, P]),
     "nmgp_nonstat_rbf_cov": (I, [V, P, P, P, I, P, P, P, I, I, P]),
@@ -210,6 +212,7 @@ class Context:
             raise NmgpError("Y must be [N, M] with N == len(x); got Y%s x%s" % (Y.shape, x.shape))
         key = ("complete", x.shape, Y.shape, hash(x.tobytes()), hash(Y.tobytes()))
         if key == self._data_key:
+            self.sep_batch_clear_subjects()      # (the upload, which would drop a separable subject set, is skipped)
             return
         self.check(self.lib.nmgp_set_data(self.h, ptr(x), ptr(Y), Y.shape[0], Y.shape[1]))
         self.N, self.M = Y.shape
@@ -453,6 +456,21 @@ class Context:
                                                 status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out, grad, status
 
+    def sep_batch_set_subjects(self, xs, Ys, chains_per_subject=1):
+        """S subjects of the separable model for ``sep_batch_eval``: xs [S, N], Ys [S, N, M] (N, M of ``set_data``).  While the set is
+        active ``sep_batch_eval`` takes pars [S * chains_per_subject, 2N+T+1], row s * chains_per_subject + k being chain k of subject
+        s.  ``sep_batch_clear_subjects``, ``set_data`` and ``had_set_data`` end it; every other entry keeps using the resident
+        subject."""
+        xs, Ys = as_f64(xs), as_f64(Ys)
+        if xs.ndim != 2 or Ys.ndim != 3 or Ys.shape[0] != xs.shape[0]:
+            raise NmgpError("subjects must be xs [S, N], Ys [S, N, M]; got %s, %s" % (xs.shape, Ys.shape))
+        if self.N and (xs.shape[1] != self.N or Ys.shape[1:] != (self.N, self.M)):
+            raise NmgpError("subjects must be xs [S, N=%d], Ys [S, N, M=%d]; got %s, %s" % (self.N, self.M, xs.shape, Ys.shape))
+        self.check(self.lib.nmgp_sep_batch_set_subjects_chains(self.h, ptr(xs), ptr(Ys), xs.shape[0], int(chains_per_subject)))
+
+    def sep_batch_clear_subjects(self):
+        self.check(self.lib.nmgp_sep_batch_clear_subjects(self.h))
+
     def logpos_sta(self, pars, hyper, prior=True, want_grad=False):
         pars = as_f64(pars).reshape(-1)
         P_ = self.T + 3
@@ -667,6 +685,7 @@ class Context:
         M = int(np.unique(indx).shape[0]) if M is None else int(M)
         key = ("hadamard", M, x.shape, hash(x.tobytes()), hash(indx.tobytes()), hash(y.tobytes()))
         if key == self._data_key:
+            self.sep_batch_clear_subjects()
             return
         self._data_key = None            # whatever was resident is gone even if the call fails
         self.check(self.lib.nmgp_had_set_data(self.h, ptr(x), indx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ptr(y),

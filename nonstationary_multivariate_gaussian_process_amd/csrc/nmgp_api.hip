@@ -158,7 +158,21 @@ static void free_priors(nmgp_ctx* c) {
     c->priors.clear();
 }
 
+void nmgp_sep_subjects_free(nmgp_ctx* c) {
+    if (c->ss_x) hipFree(c->ss_x);
+    if (c->ss_Y) hipFree(c->ss_Y);
+    c->ss_x = c->ss_Y = nullptr;
+    for (auto& pf : c->ss_priors) {
+        if (pf.L) hipFree(pf.L);
+        if (pf.logdet) hipFree(pf.logdet);
+    }
+    c->ss_priors.clear();
+    c->ss_S = 0;
+    c->ss_cps = 1;
+}
+
 static void free_subject(nmgp_ctx* c) {
+    nmgp_sep_subjects_free(c);
     double** ptrs[] = {&c->d_x, &c->d_Y, &c->d_y, &c->d_pars, &c->d_grad, &c->d_ell, &c->d_sig, &c->d_Lv,
                        &c->d_S, &c->d_Sinv, &c->d_z, &c->d_alpha, &c->d_R, &c->d_R2, &c->d_part, &c->d_K, &c->d_K2,
                        &c->d_w, &c->d_E};
@@ -854,9 +868,11 @@ extern "C" int nmgp_svc_batch_set_subjects_chains(nmgp_ctx* c, const double* x, 
     return 0;
 }
 
-// per-subject Cholesky factors of RBF(x_b; alpha, beta) + jitter I for the whole batch (one batched factorisation)
-static int get_batch_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor** out) {
-    for (auto& p : c->b_priors)
+// per-subject Cholesky factors of RBF(xs[s]; alpha, beta) + jitter I for S subjects (one batched factorisation), cached in `cache`:
+// the nonseparable multi-subject batch (b_x, b_priors) and the separable subject set (ss_x, ss_priors)
+int nmgp_get_batch_prior(nmgp_ctx* c, const double* xs, int S, std::vector<PriorFactor>& cache, double alpha, double beta,
+                         PriorFactor** out) {
+    for (auto& p : cache)
         if (p.alpha == alpha && p.beta == beta) {
             *out = &p;
             return 0;
@@ -864,7 +880,7 @@ static int get_batch_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor**
     PriorFactor pf;
     pf.alpha = alpha;
     pf.beta = beta;
-    const size_t N = c->N, B = (size_t)c->batch / c->b_cps;      // one factor per SUBJECT
+    const size_t N = c->N, B = (size_t)S;      // one factor per SUBJECT
     pf.ld = (int)(((N + 15) / 16) * 16);
     NMGP_TRY(nmgp_dev_alloc(c, &pf.L, B * (size_t)pf.ld * N));
     if (nmgp_dev_alloc(c, &pf.logdet, B) != 0) {
@@ -874,26 +890,33 @@ static int get_batch_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor**
     int* info;
     HIP_TRY(c, hipMalloc((void**)&info, B * sizeof(int)));
     hipMemsetAsync(info, 0, B * sizeof(int), c->stream);
-    rbf_cov_sym(c->stream, c->b_x, c->N, alpha, beta, pf.L, pf.ld, false, (int)B);
+    rbf_cov_sym(c->stream, xs, c->N, alpha, beta, pf.L, pf.ld, false, (int)B);
     nmgp_potrf(c, pf.L, pf.ld, c->N, 0, 0, info, (int)B, (long long)pf.ld * N, 1, 1);
     half_logdet(c->stream, pf.L, pf.ld, c->N, pf.logdet, (int)B);
     std::vector<int> hi(B);
     hipMemcpyAsync(hi.data(), info, B * sizeof(int), hipMemcpyDeviceToHost, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
     hipFree(info);
-    int bad = 0;
+    int bad = 0, who = -1;
     for (size_t b = 0; b < B; ++b)
-        if (hi[b] != 0 && bad == 0) bad = hi[b];
+        if (hi[b] != 0 && bad == 0) {
+            bad = hi[b];
+            who = (int)b;
+        }
     if (e != hipSuccess || bad != 0) {
         hipFree(pf.L);
         hipFree(pf.logdet);
         if (e != hipSuccess) return nmgp_fail(c, NMGP_E_HIP, "batched prior factorisation failed (%s)", hipGetErrorString(e));
-        return nmgp_fail(c, bad, "GP prior covariance RBF(alpha=%g, beta=%g)+jitter of a subject is not positive definite "
-                         "(leading minor %d)", alpha, beta, bad);
+        return nmgp_fail(c, bad, "GP prior covariance RBF(alpha=%g, beta=%g)+jitter of subject %d is not positive definite "
+                         "(leading minor %d)", alpha, beta, who, bad);
     }
-    c->b_priors.push_back(pf);
-    *out = &c->b_priors.back();
+    cache.push_back(pf);
+    *out = &cache.back();
     return 0;
+}
+
+static int get_batch_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor** out) {
+    return nmgp_get_batch_prior(c, c->b_x, c->batch / c->b_cps, c->b_priors, alpha, beta, out);
 }
 
 static int batch_grad_alloc(nmgp_ctx* c) {

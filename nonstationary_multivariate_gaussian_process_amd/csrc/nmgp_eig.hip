@@ -611,10 +611,53 @@ SepBatchLayout sep_batch_layout(int B, int N, int M, int T, bool want_grad) {
     return L;
 }
 
+// GP-prior solves of a chunk of a subject set: R holds the chunk's 2 B columns [tilde_l | tilde_sigma] per chain; chain b solves against
+// the factors of subject s0 + b / cps.  By substitution (k_prior_trsv: column 0 of a chain against L0, column 1 against L1 -- both
+// branches pl == ps and pl != ps); under NMGP_PRIOR_SOLVE=rocblas, and beyond the substitution kernel's N, one library trsm per subject.
+// r2 != nullptr: also Sigma_prior^-1 r (the gradient of the prior terms).
+int sep_subjects_prior_solve(nmgp_ctx* c, rocblas_handle hb, hipStream_t sp, PriorFactor* pl, PriorFactor* ps, int s0, int nsub, int cps,
+                             double* R, int B, double* r2) {
+    const int N = c->N;
+    const double one = 1.0;
+    const rocblas_stride sl = (rocblas_stride)pl->ld * N, ss = (rocblas_stride)ps->ld * N;
+    const double *Ll = pl->L + (size_t)s0 * sl, *Ls = ps->L + (size_t)s0 * ss;
+    const bool subst = !c->prior_rocblas && N <= 3500;
+    for (int pass = 0; pass < (r2 ? 2 : 1); ++pass) {
+        double* Rp = pass == 0 ? R : r2;
+        if (pass == 1) HIP_TRY(c, hipMemcpyAsync(r2, R, (size_t)N * 2 * B * sizeof(double), hipMemcpyDeviceToDevice, sp));
+        if (subst) {
+            prior_trsv(sp, pass == 1, Ll, pl->ld, sl, Ls, ps->ld, ss, Rp, N, 2, B, cps);
+            continue;
+        }
+        const rocblas_operation op = pass == 0 ? rocblas_operation_none : rocblas_operation_transpose;
+        for (int sj = 0; sj < nsub; ++sj) {
+            const int b0 = sj * cps, nb = std::min(cps, B - b0);          // the subject's chains: consecutive, 2 columns each
+            double* Rs = Rp + (size_t)2 * b0 * N;
+            if (pl == ps) {
+                BLAS_TRY(c, rocblas_dtrsm(hb, rocblas_side_left, rocblas_fill_lower, op, rocblas_diagonal_non_unit, N, 2 * nb, &one,
+                                          Ll + (size_t)sj * sl, pl->ld, Rs, N));
+            } else {
+                BLAS_TRY(c, rocblas_dtrsm_strided_batched(hb, rocblas_side_left, rocblas_fill_lower, op, rocblas_diagonal_non_unit, N, 1,
+                                                          &one, Ll + (size_t)sj * sl, pl->ld, 0, Rs, N, (rocblas_stride)2 * N, nb));
+                BLAS_TRY(c, rocblas_dtrsm_strided_batched(hb, rocblas_side_left, rocblas_fill_lower, op, rocblas_diagonal_non_unit, N, 1,
+                                                          &one, Ls + (size_t)sj * ss, ps->ld, 0, Rs + N, N, (rocblas_stride)2 * N, nb));
+            }
+        }
+    }
+    return 0;
+}
+
+// The subjects of a chunk of chains (nmgp_sep_batch_set_subjects_chains): chain b of the chunk reads x / Y of subject s0 + b / cps and
+// solves against that subject's prior factors.  A chunk is a whole number of subjects (cps = chains per subject) or lies within one
+// subject (cps = the chunk's size), so no kernel needs a chain offset.  nsub == 0: no set, every chain reads the resident subject.
+struct SepChunkSubjects {
+    int s0 = 0, nsub = 0, cps = 1;
+};
+
 // chains [0, B) of `pars` (already offset by the caller): everything enqueued, one synchronisation, host epilogue.  bad[b] = 1 marks a
 // chain whose blocks failed numerically (its out6 / grad rows are then unspecified: the caller re-evaluates it one by one).
 int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9], int prior, double* out6, double* grad, int* status,
-                   std::vector<char>& bad) {
+                   std::vector<char>& bad, const SepChunkSubjects& sub) {
     const int N = c->N, M = c->M, T = c->T;
     const size_t P = (size_t)2 * N + T + 1;
     const bool want_grad = grad != nullptr;
@@ -622,9 +665,21 @@ int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9]
     const double a = hyper[6], bb = hyper[7], cc = hyper[8];
     hipStream_t s = c->stream;
     PriorFactor *pl = nullptr, *ps = nullptr;
-    NMGP_TRY(nmgp_get_prior(c, al_l, be_l, &pl));
-    NMGP_TRY(nmgp_get_prior(c, al_s, be_s, &ps));
-    NMGP_TRY(nmgp_get_prior(c, al_l, be_l, &pl));           // (re-resolved: the second call may have grown the cache)
+    const bool multi = sub.nsub > 0;
+    if (multi) {
+        NMGP_TRY(nmgp_get_batch_prior(c, c->ss_x, c->ss_S, c->ss_priors, al_l, be_l, &pl));
+        NMGP_TRY(nmgp_get_batch_prior(c, c->ss_x, c->ss_S, c->ss_priors, al_s, be_s, &ps));
+        NMGP_TRY(nmgp_get_batch_prior(c, c->ss_x, c->ss_S, c->ss_priors, al_l, be_l, &pl));
+    } else {
+        NMGP_TRY(nmgp_get_prior(c, al_l, be_l, &pl));
+        NMGP_TRY(nmgp_get_prior(c, al_s, be_s, &ps));
+        NMGP_TRY(nmgp_get_prior(c, al_l, be_l, &pl));           // (re-resolved: the second call may have grown the cache)
+    }
+    // inputs of the chunk's first subject; strides 0 without a set (every chain reads the resident subject)
+    const long long xstride = multi ? N : 0, ystride = multi ? (long long)N * M : 0;
+    const double* xs = multi ? c->ss_x + (size_t)sub.s0 * N : c->d_x;
+    const double* Ys = multi ? c->ss_Y + (size_t)sub.s0 * N * M : c->d_Y;
+    const int cps = multi ? sub.cps : 1, nsub = multi ? sub.nsub : 1;
     const int BM = B * M;
     const SepBatchLayout L = sep_batch_layout(B, N, M, T, want_grad);
     const int xpad = (N + 1) & 1, xoff = N + 1 + xpad;
@@ -659,8 +714,8 @@ int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9]
     PriorStreamScope pscope(c);
     {
         NmgpStage sp(c, NMGP_STAGE_COV);
-        sep_prep_b(s, dP, (long long)P, c->d_Y, d_small, sp_, N, M, d_ell, d_sig, yt, B);
-        sep_blocks_b(s, c->d_x, d_ell, d_sig, d_small, sp_, N, M, S, ld, bs, want_grad ? dK : nullptr, B);
+        sep_prep_b(s, dP, (long long)P, Ys, d_small, sp_, N, M, d_ell, d_sig, yt, B, ystride, cps);
+        sep_blocks_b(s, xs, d_ell, d_sig, d_small, sp_, N, M, S, ld, bs, want_grad ? dK : nullptr, B, xstride, cps);
     }
     {
         NmgpStage sp(c, NMGP_STAGE_CHOL);
@@ -678,7 +733,9 @@ int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9]
         NmgpStage sp(c, NMGP_STAGE_PRIOR, pscope.sp, 0.0, 0.0);
         two_col_rhs_b(pscope.sp, dP, (long long)P, mu_l, mu_s, N, R, B);
         double* r2 = (want_grad && prior) ? R2 : nullptr;
-        if (pl == ps) {
+        if (multi) {
+            NMGP_TRY(sep_subjects_prior_solve(c, pscope.hb, pscope.sp, pl, ps, sub.s0, nsub, cps, R, B, r2));
+        } else if (pl == ps) {
             NMGP_TRY(prior_solve(c, pscope.hb, pscope.sp, pl, R, 2 * B, r2));
         } else {
             for (int b = 0; b < B; ++b) {
@@ -692,12 +749,13 @@ int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9]
     pscope.join();
     std::vector<double> hr((size_t)BM * 4), hq((size_t)2 * B);
     std::vector<int> hi(BM);
-    double hl[2];
+    std::vector<double> hl((size_t)2 * nsub);        // half log-determinants of the prior factors: [tilde_l | tilde_sigma] x subject
+    const size_t ld0 = multi ? (size_t)sub.s0 : 0;
     HIP_TRY(c, hipMemcpyAsync(hr.data(), red, hr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(hi.data(), info, (size_t)BM * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(hq.data(), dq, hq.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&hl[0], pl->logdet, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&hl[1], ps->logdet, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(hl.data(), pl->logdet + ld0, (size_t)nsub * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(hl.data() + nsub, ps->logdet + ld0, (size_t)nsub * sizeof(double), hipMemcpyDeviceToHost, s));
     // ---- gradient half: enqueued behind the value half without waiting for it (a chain that failed produces garbage here, which the
     // epilogue discards) ----
     std::vector<double> hx, hg, hR2, htr;
@@ -714,7 +772,7 @@ int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9]
             // traces, <S^-1, K>, the weighted sum C and the M x M quadratic forms alpha_p^T K alpha_q: ONE pass over -S^-1 and K_x
             sep_reduce_b(s, Cneg, dK, alpha, d_small, sp_, N, M, G, C, trs, Xi, B);
             fill_lower_to_full(s, C, N, N, B);
-            sep_adjoint_b(s, c->d_x, d_ell, d_sig, alpha, d_small, sp_, M, C, N, part, d_g, B);
+            sep_adjoint_b(s, xs, d_ell, d_sig, alpha, d_small, sp_, M, C, N, part, d_g, B, xstride, cps);
         }
         hx.assign((size_t)B * G * M * (M + 1) / 2, 0.0);
         hg.assign((size_t)B * 2 * N, 0.0);
@@ -737,8 +795,9 @@ int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9]
         }
         if (!std::isfinite(ll)) bad[b] = 1;
         const double* pb = pars + (size_t)b * P;
-        const double lp_l = -0.5 * (N * LOG2PI + hq[(size_t)2 * b]) - hl[0];
-        const double lp_s = -0.5 * (N * LOG2PI + hq[(size_t)2 * b + 1]) - hl[1];
+        const int sb = multi ? b / cps : 0;           // the chain's subject within the chunk (the resident one without a set)
+        const double lp_l = -0.5 * (N * LOG2PI + hq[(size_t)2 * b]) - hl[sb];
+        const double lp_s = -0.5 * (N * LOG2PI + hq[(size_t)2 * b + 1]) - hl[(size_t)nsub + sb];
         double lp_uL = 0.0;
         std::vector<double> g_uL_prior(T, 0.0);
         for (int t = 0; t < T; ++t) lp_uL += normal_logprob_f32(pb[2 * N + t], 0.0, cc, &g_uL_prior[t]);
@@ -796,7 +855,97 @@ int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9]
     return 0;
 }
 
+// One chain of a subject set through the single-chain entry (a chain that failed numerically, B == 1, NMGP_SEP=eig, N beyond the block
+// kernel's offsets): subject s becomes the resident one for the evaluation -- its x / Y are the set's device copies, d_y their
+// output-major transpose, the prior cache an empty one that nmgp_logpos_sep fills for this subject -- and the originally resident
+// subject comes back, with its cached prior factors, when the guard goes (whatever the evaluations returned).
+struct SepResidentSwap {
+    nmgp_ctx* c;
+    double *x0, *Y0, *y0, *ytmp = nullptr;
+    std::vector<PriorFactor> priors0;
+    int cur = -1;
+    explicit SepResidentSwap(nmgp_ctx* ctx) : c(ctx), x0(ctx->d_x), Y0(ctx->d_Y), y0(ctx->d_y) {}
+    void drop_priors() {
+        for (auto& p : c->priors) {
+            if (p.L) hipFree(p.L);
+            if (p.logdet) hipFree(p.logdet);
+        }
+        c->priors.clear();
+    }
+    int to(int subj) {
+        if (subj == cur) return 0;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (cur < 0) {
+            NMGP_TRY(nmgp_dev_alloc(c, &ytmp, (size_t)c->n));      // (first: nothing is swapped yet if it fails)
+            c->priors.swap(priors0);
+        } else {
+            drop_priors();
+        }
+        cur = subj;
+        c->d_x = c->ss_x + (size_t)subj * c->N;
+        c->d_Y = c->ss_Y + (size_t)subj * c->n;
+        c->d_y = ytmp;
+        transpose_y(c->stream, c->d_Y, c->N, c->M, c->d_y);
+        return 0;
+    }
+    ~SepResidentSwap() {
+        if (cur < 0) return;
+        hipStreamSynchronize(c->stream);
+        drop_priors();
+        c->priors.swap(priors0);
+        c->d_x = x0;
+        c->d_Y = Y0;
+        c->d_y = y0;
+        if (ytmp) hipFree(ytmp);
+    }
+};
+
 }  // namespace
+
+// ---- separable model, many subjects: x [S, N], Y [S, N, M] row-major; batch element b = s * chains_per_subject + k of
+// nmgp_sep_batch_eval is chain k of subject s.  One pair of GP-prior factors per SUBJECT, built on first use by one batched
+// factorisation and cached per (alpha, beta) with the set.  The set lives until nmgp_sep_batch_clear_subjects, nmgp_set_data or
+// nmgp_had_set_data; no other entry looks at it.
+extern "C" int nmgp_sep_batch_set_subjects_chains(nmgp_ctx* c, const double* x, const double* Y, int S, int chains_per_subject) {
+    if (!c) return NMGP_E_NULL;
+    if (!nmgp_complete_subject(c))
+        return nmgp_fail(c, NMGP_E_STATE, "nmgp_sep_batch_set_subjects_chains: nmgp_set_data must be called first (it fixes N and M)");
+    if (!x || !Y) return nmgp_fail(c, NMGP_E_NULL, "nmgp_sep_batch_set_subjects_chains: x and Y must not be NULL");
+    if (S < 1 || chains_per_subject < 1)
+        return nmgp_fail(c, NMGP_E_SHAPE, "nmgp_sep_batch_set_subjects_chains: S = %d and chains_per_subject = %d must be positive", S,
+                         chains_per_subject);
+    if ((long long)S * chains_per_subject > 0x7fffffffLL)
+        return nmgp_fail(c, NMGP_E_SHAPE, "nmgp_sep_batch_set_subjects_chains: S * chains_per_subject = %lld does not fit a batch size",
+                         (long long)S * chains_per_subject);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    nmgp_sep_subjects_free(c);
+    const size_t N = c->N, n = c->n;
+    NMGP_TRY(nmgp_dev_alloc(c, &c->ss_x, (size_t)S * N));
+    if (nmgp_dev_alloc(c, &c->ss_Y, (size_t)S * n) != 0) {
+        nmgp_sep_subjects_free(c);
+        return NMGP_E_NOMEM;
+    }
+    hipError_t e = hipMemcpyAsync(c->ss_x, x, (size_t)S * N * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->ss_Y, Y, (size_t)S * n * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);          // (the host buffers may be temporaries)
+    if (e != hipSuccess) {
+        nmgp_sep_subjects_free(c);
+        return nmgp_fail(c, NMGP_E_HIP, "nmgp_sep_batch_set_subjects_chains: upload failed (%s)", hipGetErrorString(e));
+    }
+    c->ss_S = S;
+    c->ss_cps = chains_per_subject;
+    return 0;
+}
+
+extern "C" int nmgp_sep_batch_clear_subjects(nmgp_ctx* c) {
+    if (!c) return NMGP_E_NULL;
+    if (c->ss_S <= 0) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    nmgp_sep_subjects_free(c);
+    return 0;
+}
 
 extern "C" int nmgp_sep_batch_eval(nmgp_ctx* c, const double* pars, int B, const double hyper[9], int prior, double* out6,
                                    double* grad, int* status) {
@@ -808,7 +957,14 @@ extern "C" int nmgp_sep_batch_eval(nmgp_ctx* c, const double* pars, int B, const
     const int N = c->N, M = c->M, T = c->T;
     const size_t P = (size_t)2 * N + T + 1;
     const bool want_grad = grad != nullptr;
+    const bool multi = c->ss_S > 0;                 // a subject set is active: chain b belongs to subject b / cps
+    const int cps = multi ? c->ss_cps : 1;
+    if (multi && (long long)B != (long long)c->ss_S * cps)
+        return nmgp_fail(c, NMGP_E_SHAPE, "nmgp_sep_batch_eval: B = %d, but the subject set holds %d subjects x %d chains = %lld", B,
+                         c->ss_S, cps, (long long)c->ss_S * cps);
+    SepResidentSwap swap(c);
     auto one_by_one = [&](int b) -> int {
+        if (multi) NMGP_TRY(swap.to(b / cps));
         int rc = nmgp_logpos_sep(c, pars + (size_t)b * P, hyper, prior, out6 + (size_t)b * 6, want_grad ? grad + (size_t)b * P : nullptr);
         if (rc < 0) return rc;
         if (rc > 0) {
@@ -838,12 +994,29 @@ extern "C" int nmgp_sep_batch_eval(nmgp_ctx* c, const double* pars, int B, const
         return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the separable model at N = %d, D = %d needs %.1f GB of device workspace, above the "
                          "NMGP_SEP_BATCH_SLAB_GB cap of %.0f GB", N, M, per_chain / 1e9, cap_gb);
     std::vector<char> bad(B, 0);
-    for (int b0 = 0; b0 < B; b0 += Bc) {
-        const int nb = std::min(Bc, B - b0);
+    // With a subject set a chunk is a whole number of subjects (cps fits in a chunk: the chunk size is rounded down to a multiple of
+    // it) or a part of ONE subject (the subject's chains are split, and no chunk crosses into the next subject).
+    const bool split = multi && cps > Bc;
+    if (multi && !split) Bc = (Bc / cps) * cps;
+    for (int b0 = 0; b0 < B;) {
+        int nb = std::min(Bc, B - b0);
+        SepChunkSubjects sub;
+        if (multi) {
+            sub.s0 = b0 / cps;
+            if (split) {
+                nb = std::min(nb, (sub.s0 + 1) * cps - b0);
+                sub.nsub = 1;
+                sub.cps = nb;
+            } else {
+                sub.nsub = nb / cps;
+                sub.cps = cps;
+            }
+        }
         std::vector<char> badc(nb, 0);
         NMGP_TRY(sep_batch_core(c, pars + (size_t)b0 * P, nb, hyper, prior, out6 + (size_t)b0 * 6, want_grad ? grad + (size_t)b0 * P : nullptr,
-                                status + b0, badc));
+                                status + b0, badc, sub));
         for (int k = 0; k < nb; ++k) bad[b0 + k] = badc[k];
+        b0 += nb;
     }
     // chains that failed numerically: the single-chain entry, with the reference's jitter retries
     for (int b = 0; b < B; ++b)

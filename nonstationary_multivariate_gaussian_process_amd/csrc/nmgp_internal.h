@@ -168,6 +168,12 @@ struct nmgp_ctx {
     // posterior-draw prediction (nmgp_predsample.hip): ONE workspace for a chunk of draws, its own (no batch buffer is touched)
     double* ps_buf = nullptr;
     size_t ps_cap = 0;          // elements
+    // separable multi-subject set (nmgp_sep_batch_set_subjects_chains): while ss_S > 0, batch element b of nmgp_sep_batch_eval is chain
+    // b % ss_cps of subject b / ss_cps.  No other entry looks at it; nmgp_sep_subjects_free drops it with its prior factors
+    int ss_S = 0, ss_cps = 1;
+    double* ss_x = nullptr;     // [S, N]
+    double* ss_Y = nullptr;     // [S, N, M] row-major (k_sep_prep_b rotates it per chain)
+    std::vector<PriorFactor> ss_priors;  // L: [S] x (ld x N), logdet: [S]
     int last_sep_attempts = 0;  // jitter retries the last separable / stationary evaluation needed (0 = the exact covariance)
     bool last_want_grad = false;
     int last_kind = 0;          // 1 svc
@@ -192,6 +198,11 @@ inline bool nmgp_complete_subject(const nmgp_ctx* c) { return c->d_x != nullptr 
 int nmgp_dev_alloc(nmgp_ctx* c, double** p, size_t nelem);
 int nmgp_scratch_get(nmgp_ctx* c, int slot, size_t nelem, double** out);
 int nmgp_get_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor** out);
+// per-subject Cholesky factors of RBF(xs[s]; alpha, beta) + jitter I for the S subjects of xs [S, N] by ONE batched factorisation,
+// cached in `cache` (the nonseparable multi-subject batch and the separable subject set each own one)
+int nmgp_get_batch_prior(nmgp_ctx* c, const double* xs, int S, std::vector<PriorFactor>& cache, double alpha, double beta,
+                         PriorFactor** out);
+void nmgp_sep_subjects_free(nmgp_ctx* c);      // drops the separable subject set (no-op without one)
 int nmgp_ensure_S(nmgp_ctx* c);
 size_t nmgp_ld(size_t rows);      // leading dimension of a factorisation buffer with `rows` rows
 // Cholesky of the n x n lower triangle (custom gfx950 factorisation or rocSOLVER, per ctx->chol_algo); `extra` rows
@@ -464,14 +475,15 @@ void sep_blocks(hipStream_t s, const double* K, const double* wB, const double* 
 int sep_traces(hipStream_t s, const double* Cneg, const double* K, const double* alpha, int N, int M, double* out);
 void weighted_sum_lower(hipStream_t s, const double* Cneg, const double* wB, int N, int M, double* C);
 // ---- nmgp_kernels_sep.hip: the separable objective's pieces with the chain as a grid dimension (nmgp_sep_batch_eval) ----
+// x / Y of chain b: those of subject b / cps at xstride / ystride doubles per subject (stride 0: every chain reads the same subject)
 void sep_prep_b(hipStream_t s, const double* pars, long long P, const double* Y, const double* small, int small_per, int N, int M,
-                double* ell, double* sig, double* yt, int B);
+                double* ell, double* sig, double* yt, int B, long long ystride = 0, int cps = 1);
 void sep_blocks_b(hipStream_t s, const double* x, const double* ell, const double* sig, const double* small, int small_per, int N, int M,
-                  double* S, int ldo, long long bstride, double* Kout, int B);
+                  double* S, int ldo, long long bstride, double* Kout, int B, long long xstride = 0, int cps = 1);
 void sep_reduce_b(hipStream_t s, const double* Cneg, const double* K, const double* alpha, const double* small, int small_per, int N,
                   int M, int G, double* C, double* out, double* xi, int B);
 void sep_adjoint_b(hipStream_t s, const double* x, const double* ell, const double* sig, const double* U, const double* small,
-                   int small_per, int M, const double* C, int N, double* part, double* g, int B);
+                   int small_per, int M, const double* C, int N, double* part, double* g, int B, long long xstride = 0, int cps = 1);
 void two_col_rhs_b(hipStream_t s, const double* pars, long long P, double mu_a, double mu_b, int N, double* R, int B);
 // ---- nmgp_predsample.hip ----
 // after a factorisation with riding rows, for each of `batch` matrices (stride bstride): dots[z ostride + o0 + e] = row (R0 + e) . row

@@ -39,9 +39,11 @@ __device__ inline double block_sum_s(double v, double* sh /*[16]*/) {
 // yt[(b M + p) N + i] = sum_m Y[i, m] VB_b[m, p]   (small[b]: wB [M] | VB row-major [M, M] | sigma2 | pad)
 __global__ __launch_bounds__(256) void k_sep_prep_b(const double* __restrict__ pars, long long P, const double* __restrict__ Y,
                                                      const double* __restrict__ small, int small_per, int N, int M,
-                                                     double* __restrict__ ell, double* __restrict__ sig, double* __restrict__ yt) {
+                                                     double* __restrict__ ell, double* __restrict__ sig, double* __restrict__ yt,
+                                                     long long ystride, int cps) {
     const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (i >= N) return;
+    Y += (size_t)(b / cps) * ystride;                  // the chain's subject (stride 0: the resident one)
     const double* pb = pars + (size_t)b * P;
     ell[(size_t)b * N + i] = exp(pb[i]);
     sig[(size_t)b * N + i] = exp(pb[N + i]);
@@ -54,8 +56,9 @@ __global__ __launch_bounds__(256) void k_sep_prep_b(const double* __restrict__ p
 }
 
 void sep_prep_b(hipStream_t s, const double* pars, long long P, const double* Y, const double* small, int small_per, int N, int M,
-                double* ell, double* sig, double* yt, int B) {
-    NMGP_LAUNCH(k_sep_prep_b, dim3(cdiv_s(N, 256), B), dim3(256), 0, s, pars, P, Y, small, small_per, N, M, ell, sig, yt);
+                double* ell, double* sig, double* yt, int B, long long ystride, int cps) {
+    NMGP_LAUNCH(k_sep_prep_b, dim3(cdiv_s(N, 256), B), dim3(256), 0, s, pars, P, Y, small, small_per, N, M, ell, sig, yt, ystride,
+                cps < 1 ? 1 : cps);
 }
 
 // Lower triangles of the M blocks of chain b = blockIdx.z, and of K_x,b itself when Kout != nullptr (kernels.py:46-73 with the
@@ -67,10 +70,11 @@ template <int M>
 __global__ __launch_bounds__(256) void k_sep_blocks_b(const double* __restrict__ x, const double* __restrict__ ell,
                                                        const double* __restrict__ sig, const double* __restrict__ small,
                                                        int small_per, int N, double* __restrict__ S, int ldo, long long bstride,
-                                                       double* __restrict__ Kout) {
+                                                       double* __restrict__ Kout, long long xstride, int cps) {
     constexpr int TJ = 64;
     __shared__ double sx[TJ], sl[TJ], ss[TJ];
     const int b = blockIdx.z;
+    x += (size_t)(b / cps) * xstride;                  // the chain's subject (stride 0: the resident one)
     // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (each with its own L2), so workgroup g of the launch
     // takes tile t = (g mod 8) * per + g / 8 of the lower-triangular tile list, enumerated column by column (J, then I = J ..):
     // the tiles ONE XCD works on at a time are vertical neighbours -- the adjacent 512-byte segments of the same 64 columns --
@@ -153,10 +157,11 @@ template <int M>
 __global__ __launch_bounds__(256) void k_sep_blocks_b4(const double* __restrict__ x, const double* __restrict__ ell,
                                                         const double* __restrict__ sig, const double* __restrict__ small,
                                                         int small_per, int N, double* __restrict__ S, int ldo, long long bstride,
-                                                        double* __restrict__ Kout) {
+                                                        double* __restrict__ Kout, long long xstride, int cps) {
     constexpr int TJ = 32, TI = 128;
     __shared__ double sx[TJ], sl[TJ], ss[TJ];
     const int b = blockIdx.z;
+    x += (size_t)(b / cps) * xstride;
     const int NI = (N + TI - 1) / TI, NJ = (N + TJ - 1) / TJ;
     // lower-triangular tile list, column by column: column J holds the row tiles I = J / 4 .. NI - 1
     int ntl = 0;
@@ -233,7 +238,7 @@ __global__ __launch_bounds__(256) void k_sep_blocks_b4(const double* __restrict_
 
 template <int M>
 static void launch_sep_blocks_b(hipStream_t s, const double* x, const double* ell, const double* sig, const double* small, int small_per,
-                                int N, double* S, int ldo, long long bstride, double* Kout, int B) {
+                                int N, double* S, int ldo, long long bstride, double* Kout, int B, long long xstride, int cps) {
     // 128 x 32 tiles with 1 KB stores for even N, 64 x 64 tiles otherwise; both in the XCD-aware order (measured for 16 chains of
     // N = 4096, D = 5: 64 x 64 tiles in grid order 2.43 ms, in the XCD-aware order 1.69 ms, 128 x 32 tiles 1.49 ms)
     if ((N & 1) == 0) {
@@ -241,24 +246,26 @@ static void launch_sep_blocks_b(hipStream_t s, const double* x, const double* el
         int ntl = 0;
         for (int J = 0; J < NJ; ++J) ntl += NI - J / 4;
         NMGP_LAUNCH((k_sep_blocks_b4<M>), dim3(8 * ((ntl + 7) / 8), 1, B), dim3(256), 0, s, x, ell, sig, small, small_per, N, S, ldo, bstride,
-                    Kout);
+                    Kout, xstride, cps);
     } else {
         const int NI = cdiv_s(N, 64), ntl = NI * (NI + 1) / 2, per = (ntl + 7) / 8;
-        NMGP_LAUNCH((k_sep_blocks_b<M>), dim3(8 * per, 1, B), dim3(256), 0, s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout);
+        NMGP_LAUNCH((k_sep_blocks_b<M>), dim3(8 * per, 1, B), dim3(256), 0, s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout,
+                    xstride, cps);
     }
 }
 
 void sep_blocks_b(hipStream_t s, const double* x, const double* ell, const double* sig, const double* small, int small_per, int N, int M,
-                  double* S, int ldo, long long bstride, double* Kout, int B) {
+                  double* S, int ldo, long long bstride, double* Kout, int B, long long xstride, int cps) {
+    if (cps < 1) cps = 1;
     switch (M) {
-        case 1: launch_sep_blocks_b<1>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B); break;
-        case 2: launch_sep_blocks_b<2>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B); break;
-        case 3: launch_sep_blocks_b<3>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B); break;
-        case 4: launch_sep_blocks_b<4>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B); break;
-        case 5: launch_sep_blocks_b<5>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B); break;
-        case 6: launch_sep_blocks_b<6>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B); break;
-        case 7: launch_sep_blocks_b<7>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B); break;
-        default: launch_sep_blocks_b<8>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B); break;      // (M <= NMGP_MAX_OUTPUTS)
+        case 1: launch_sep_blocks_b<1>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B, xstride, cps); break;
+        case 2: launch_sep_blocks_b<2>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B, xstride, cps); break;
+        case 3: launch_sep_blocks_b<3>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B, xstride, cps); break;
+        case 4: launch_sep_blocks_b<4>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B, xstride, cps); break;
+        case 5: launch_sep_blocks_b<5>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B, xstride, cps); break;
+        case 6: launch_sep_blocks_b<6>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B, xstride, cps); break;
+        case 7: launch_sep_blocks_b<7>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B, xstride, cps); break;
+        default: launch_sep_blocks_b<8>(s, x, ell, sig, small, small_per, N, S, ldo, bstride, Kout, B, xstride, cps); break;      // (M <= NMGP_MAX_OUTPUTS)
     }
 }
 
@@ -379,11 +386,13 @@ void sep_reduce_b(hipStream_t s, const double* Cneg, const double* K, const doub
 __global__ __launch_bounds__(256) void k_sep_adjoint_b(const double* __restrict__ x, const double* __restrict__ ell,
                                                         const double* __restrict__ sig, const double* __restrict__ U,
                                                         const double* __restrict__ small, int small_per, int M,
-                                                        const double* __restrict__ C, int N, double* __restrict__ part, int NJ) {
+                                                        const double* __restrict__ C, int N, double* __restrict__ part, int NJ,
+                                                        long long xstride, int cps) {
     constexpr int TJ = 64;
     __shared__ double sx[TJ], sl[TJ], ss[TJ], sU[TJ * NMGP_MAX_OUTPUTS];
     __shared__ double red[2][4][64];
     const int I = blockIdx.x, J = blockIdx.y, b = blockIdx.z;
+    x += (size_t)(b / cps) * xstride;                  // the chain's subject (stride 0: the resident one)
     ell += (size_t)b * N;
     sig += (size_t)b * N;
     U += (size_t)b * M * N;
@@ -459,9 +468,10 @@ __global__ void k_sep_grad_sum_b(const double* __restrict__ part, int NJ, int N,
 }
 
 void sep_adjoint_b(hipStream_t s, const double* x, const double* ell, const double* sig, const double* U, const double* small,
-                   int small_per, int M, const double* C, int N, double* part, double* g, int B) {
+                   int small_per, int M, const double* C, int N, double* part, double* g, int B, long long xstride, int cps) {
     const int NJ = cdiv_s(N, 64);
-    NMGP_LAUNCH(k_sep_adjoint_b, dim3(cdiv_s(N, 64), NJ, B), dim3(256), 0, s, x, ell, sig, U, small, small_per, M, C, N, part, NJ);
+    NMGP_LAUNCH(k_sep_adjoint_b, dim3(cdiv_s(N, 64), NJ, B), dim3(256), 0, s, x, ell, sig, U, small, small_per, M, C, N, part, NJ,
+                xstride, cps < 1 ? 1 : cps);
     NMGP_LAUNCH(k_sep_grad_sum_b, dim3(cdiv_s(N, 256), B), dim3(256), 0, s, part, NJ, N, g);
 }
 

@@ -222,6 +222,35 @@ class BatchedMAP(LockStepMAP):
         return self.sync_pars().copy(), hist, alive
 
 
+class BatchedMAPSeparable(LockStepMAP):
+    """The MAP loop of ``Separable_model_mpiKAISER.py`` for ALL subjects of a rank at once: S subjects of the same size (own x, Y, own
+    GP-prior factors) form one subject set on the GPU (``nmgp_sep_batch_set_subjects_chains``) and every Adam iteration is ONE
+    ``nmgp_sep_batch_eval`` -- the subjects' S * k * M blocks as one batch of the blocked Cholesky.  Host-side Adam, row by row the
+    arithmetic of :func:`map_separable`.  ``xs`` [S, N], ``Ys`` [S, N, M], ``init_pars`` [S * chains_per_subject, 2N+T+1]: row
+    s * chains_per_subject + k is restart k of subject s."""
+
+    def __init__(self, xs, Ys, hyper_pars, init_pars, lr=2e-1, ctx=None, chains_per_subject=1):
+        from . import _lib
+        super().__init__(init_pars, lr=lr)
+        xs = np.ascontiguousarray(xs, dtype=np.float64)
+        Ys = np.ascontiguousarray(Ys, dtype=np.float64)
+        k = int(chains_per_subject)
+        if xs.ndim != 2 or Ys.ndim != 3 or k < 1 or self.P.shape[0] != xs.shape[0] * k:
+            raise ValueError("xs [S, N], Ys [S, N, M] and init_pars [S * chains_per_subject, P] do not fit: %s, %s, %s, k = %d"
+                             % (xs.shape, Ys.shape, self.P.shape, k))
+        self.ctx = ctx if ctx is not None else _lib.default_context()
+        self.hyper = np.array([float(hyper_pars[key]) for key in SEP_HYPER_KEYS])
+        self.prior = True
+        self.ctx.set_data(xs[0], Ys[0])
+        self.ctx.sep_batch_set_subjects(xs, Ys, k)
+
+    def value_and_grad(self, P):
+        """out [B, 6], grad [B, P] and a status that is 0 for every valid evaluation: jitter retries (status > 0) count as valid, a
+        numerical failure (status < 0) marks the row dead for :func:`valid_rows`."""
+        out, grad, status = self.ctx.sep_batch_eval(P, self.hyper, self.prior, True)
+        return out, grad, np.where(status < 0, status, 0)
+
+
 class HMCSampler:
     """Hamiltonian Monte Carlo with a (optionally dense) constant mass matrix.
 
@@ -972,7 +1001,9 @@ class BatchedHMCSeparable(LockStepHMC):
     ``Separable_model_mpiKAISER.py:281`` for B chains at once; chain b reproduces ``HMCSampler(potential_func=logpos.nlogpos_obj,
     ...)`` started from the same state with the same random stream.  The leapfrog update runs on the host (P = 2N + T + 1).
     ``M=`` a :class:`SeparablePriorMetric` (from :func:`separable_prior_metric`) selects the whitened-momentum loop -- the metric
-    under which this model's chains mix; ``step_jitter`` as in :class:`BatchedHMC`."""
+    under which this model's chains mix; ``step_jitter`` as in :class:`BatchedHMC`.
+    SEVERAL SUBJECTS: ``x`` [S, N] with ``Y`` [S, N, M] puts B / S consecutive chains on each subject (``nmgp_sep_batch_set_subjects_
+    chains``: chain b belongs to subject b // (B / S)); identity, diagonal or dense mass only -- a prior metric belongs to one subject."""
 
     KEYS = SEP_HYPER_KEYS
 
@@ -984,7 +1015,20 @@ class BatchedHMCSeparable(LockStepHMC):
         self.jitter_rng = np.random.default_rng(None if seed is None else 7919 * (seed + 1))
         self.ctx = ctx if ctx is not None else _lib.default_context()
         self.hyper = np.array([float(hyper_pars[k]) for k in self.KEYS])
-        self.ctx.set_data(np.asarray(x, dtype=np.float64), np.asarray(Y, dtype=np.float64))
+        x, Y = np.asarray(x, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+        if x.ndim == 2:
+            S = x.shape[0]
+            if Y.ndim != 3 or Y.shape[0] != S:
+                raise ValueError("x [S, N] needs Y [S, N, M]; got %s, %s" % (x.shape, Y.shape))
+            if self.B % S:
+                raise ValueError("the number of chains %d is not a multiple of the number of subjects %d" % (self.B, S))
+            if self.mass_kind == 4:
+                raise ValueError("a SeparablePriorMetric belongs to ONE subject's prior factors: with several subjects use the identity, "
+                                 "a diagonal or a dense mass matrix (no per-subject prior metric yet)")
+            self.ctx.set_data(x[0], Y[0])
+            self.ctx.sep_batch_set_subjects(x, Y, self.B // S)
+        else:
+            self.ctx.set_data(x, Y)
 
     def potential_and_grad(self, q):
         """U [B] and dU/dq [B, P]; a chain whose covariance stays numerically singular after the jitter retries gets U = inf."""
