@@ -419,6 +419,31 @@ int nmgp_predsample_sta(nmgp_ctx* ctx, const double* pars /*[H,T+3]*/, int H, co
 int nmgp_predsample_hads(nmgp_ctx* ctx, const double* pars /*[H,2N+T+1]*/, int H, const double hyper[9], const double* xs /*[S]*/,
                          const int* indx_star /*[S] or NULL*/, int S, const double* z, const double* star_in, double* mean,
                          double* var, double* star_out, int* status);
+/* The same for the NONSEPARABLE Hadamard model: posterior-draw and held-out prediction.  The reference has no posterior-draw form
+ * for this model, and its indexed MAP predictor (prediction.indexedpoint_ / test_predmap_SVC_hadamard, prediction.py:1480-1561)
+ * reports the variance of output 0 whatever the label; this entry is the corrected predictor for one draw and the posterior-draw
+ * form for H.  H parameter vectors of the subject nmgp_had_set_data made resident (NMGP_E_STATE otherwise; pars and hyper as for
+ * nmgp_had_batch_eval), S new inputs.  A chunk of B draws is ONE batched factorisation of B matrices of order N with y and the
+ * cross-covariance rows of the draw's own starred values riding.
+ *   indx_star == NULL: all M outputs at every new input; mean, var: [H,S,M]; slices of max(1, N / M) grid points.
+ *   indx_star [S]    : output indx_star[s] only at xs[s] (held-out pairs); mean, var: [H,S]; slices of N points.  A label outside
+ *                      [0, M) is NMGP_E_SHAPE.
+ * z, star_in, star_out: [H,S,1+T]: slot 0 tilde_l* (before exp), slot 1 + t slot t of L* (taken as it is: no exp, as everywhere in
+ * this model).  Each is the GP regression of the draw's own curve under its prior (tilde_l: hyper[0..2]; the T columns of L_vecs:
+ * hyper[3..5]) + sqrt(cv) z with ONE conditional variance per prior, cv = (alpha^2 + 1e-6) - proj . k, serving all T slots (the
+ * rules of nmgp_predsample_svc); z == NULL gives the conditional means; with star_in the regression is skipped and z must be NULL
+ * (NMGP_E_STATE).  Riding row: k_f[i] = g(i, s) <row indx[i] of the draw's L_i, row m of L*_s>, g the Gibbs cross term without
+ * jitter with l* = exp(tilde_l*).  mean = (L_S^-1 k_f)^T (L_S^-1 y); var = (1 + 1e-6) (L* L*^T)_mm - |L_S^-1 k_f|^2 + sigma2_err; a
+ * conditional variance < 0 and a predictive variance <= 0 are replaced by 1e-6.  status [H] (or NULL), the failure semantics, the
+ * chunking (8 (N + 1 + E) ld bytes per draw) and the workspace as for nmgp_predsample_hads (a pending nmgp_had_batch_eval result
+ * stays valid).  H draws in one call give the bits of H single-draw calls, whatever the chunking and whichever slice a grid point
+ * falls in.  One draw with z == NULL and indx_star == NULL is nmgp_predict_had's predictor: the same starred values bit for bit, mean
+ * and variance to rounding (this entry factors with the substitution-based panel kernels, that one with the default ones).
+ * NMGP_E_UNSUPPORTED for M > 8; NMGP_E_SHAPE if one draw's factorisation buffer reaches 2^31 elements. */
+int nmgp_predsample_had(nmgp_ctx* ctx, const double* pars /*[H,N(1+T)+1]*/, int H, const double hyper[8], const double* xs /*[S]*/,
+                        const int* indx_star /*[S] or NULL*/, int S, const double* z /*[H,S,1+T] or NULL*/,
+                        const double* star_in /*[H,S,1+T] or NULL*/, double* mean, double* var,
+                        double* star_out /*[H,S,1+T] or NULL*/, int* status /*[H] or NULL*/);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Per-stage HIP-event timing on the context's stream (bench.py roofline figures).  Stages: */

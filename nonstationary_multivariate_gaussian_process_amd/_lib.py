@@ -94,6 +94,7 @@ SIGNATURES = {
     "nmgp_predsample_sep": (I, [V, P, I, P, P, I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_sta": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_hads": (I, [V, P, I, P, P, ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_predsample_had": (I, [V, P, I, P, P, ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_profile_enable": (I, [V, I]),
     "nmgp_profile_read": (I, [V, P, c_ll_p]),
     "nmgp_profile_reset": (I, [V]),
@@ -744,6 +745,51 @@ class Context:
         mean, var, star = np.empty((S, self.M)), np.empty((S, self.M)), np.empty((S, 1 + self.T))
         self.check(self.lib.nmgp_predict_had(self.h, ptr(pars), ptr(hyper), ptr(xs), S, ptr(mean), ptr(var), ptr(star)))
         return mean, var, star
+
+    def predsample_had(self, pars_hist, hyper, xs, indx_star=None, z=None, star=None):
+        """Posterior-draw and held-out prediction of the nonseparable HADAMARD model: pars_hist [H, N(1+T)+1] of the resident
+        Hadamard subject at the new inputs xs [S].  indx_star=None: all M outputs at every input, moments [H, S, M]; indx_star [S]:
+        output indx_star[s] only at xs[s] (held-out pairs), moments [H, S].  z [H, S, 1+T]: standard normals of the latent regression
+        of (tilde_l*, the T raw slots of L*) (None: the conditional means); star [H, S, 1+T]: starred values to use instead of
+        regressing (z must then be None).  Returns (mean, var, star [H, S, 1+T], status [H]); a draw with non-zero status has NaN
+        rows."""
+        pars = as_f64(pars_hist)
+        if pars.ndim == 1:
+            pars = pars[None]
+        P_, W = self.N * (1 + self.T) + 1, 1 + self.T
+        if pars.ndim != 2 or pars.shape[1] != P_:
+            raise NmgpError("draws must be [H, N(1+T)+1 = %d], got %s" % (P_, pars.shape))
+        hyper, xs = as_f64(hyper).reshape(-1), as_f64(xs).reshape(-1)
+        if hyper.shape[0] != 8:
+            raise NmgpError("hyper must have 8 entries, got %d" % hyper.shape[0])
+        H, S = pars.shape[0], xs.shape[0]
+        ia = None
+        if indx_star is not None:
+            if hasattr(indx_star, "detach"):
+                indx_star = indx_star.detach().cpu().numpy()
+            ia = np.ascontiguousarray(np.asarray(indx_star).reshape(-1).astype(np.int32))
+            if ia.shape[0] != S:
+                raise NmgpError("indx_star must have one label per new input (S=%d), got %d" % (S, ia.shape[0]))
+        if z is not None and star is not None:
+            raise NmgpError("star= replaces the regression: z must be None")
+        za = sa = None
+        for name, a in (("z", z), ("star", star)):
+            if a is not None:
+                a = as_f64(a)
+                if a.shape != (H, S, W):
+                    raise NmgpError("%s must be [H=%d, S=%d, 1+T=%d], got %s" % (name, H, S, W, a.shape))
+                if name == "z":
+                    za = a
+                else:
+                    sa = a
+        shape = (H, S, self.M) if ia is None else (H, S)
+        mean, var = np.empty(shape), np.empty(shape)
+        star_out = np.empty((H, S, W))
+        status = np.zeros(H, dtype=np.int32)
+        ip = None if ia is None else ia.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        self.check(self.lib.nmgp_predsample_had(self.h, ptr(pars), H, ptr(hyper), ptr(xs), ip, S, ptr(za), ptr(sa), ptr(mean),
+                                                ptr(var), ptr(star_out), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return mean, var, star_out, status
 
     # -- Hadamard form of the separable model (the resident subject is had_set_data's) -------------
     def _hads_len(self):

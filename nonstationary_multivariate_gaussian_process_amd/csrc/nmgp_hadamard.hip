@@ -142,10 +142,6 @@ __global__ void k_had_predvar(const double* __restrict__ star, const double* __r
     var[k] = v;
 }
 
-void had_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* Rv, int batch) {
-    NMGP_LAUNCH(k_had_prep, dim3(cdiv(N, 256), batch), dim3(256), 0, s, pars, indx, N, M, M * (M + 1) / 2, ell, Rv);
-}
-
 void had_grad_final(hipStream_t s, const double* part, int NJ, int N, int M, const int* indx, const double* R2, int ldR,
                     const double* pars, const double* tr, double a, double b, int prior, double* grad, int batch) {
     NMGP_LAUNCH(k_had_grad_final, dim3(cdiv(N, 256), batch), dim3(256), 0, s, part, NJ, N, M, M * (M + 1) / 2, indx, R2, ldR, pars, tr,
@@ -161,13 +157,18 @@ int had_crosscov_rows(hipStream_t s, const double* x, const double* ell, const d
 
 }  // namespace
 
-// The next three are declared in nmgp_internal.h: require_had guards every entry of the three Hadamard models and of
-// nmgp_predsample_hadamard.hip; had_priors / had_prior_solve serve the two models with GP priors (this one and the separable one).
+// The next four are declared in nmgp_internal.h: require_had guards every entry of the three Hadamard models and of the two
+// posterior-draw files; had_priors / had_prior_solve serve the two models with GP priors (this one and the separable one); had_prep
+// unpacks this model's parameter vectors, here and in nmgp_predsample_had.hip.
 int require_had(nmgp_ctx* c) {
     if (!c->had || !c->d_x) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_data must be called first (the resident subject is not a Hadamard one)");
     if (c->chol_algo != 1)
         return nmgp_fail(c, NMGP_E_UNSUPPORTED, "the Hadamard entries run on the custom factorisation only (riding rows)");
     return 0;
+}
+
+void had_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* Rv, int batch) {
+    NMGP_LAUNCH(k_had_prep, dim3(cdiv(N, 256), batch), dim3(256), 0, s, pars, indx, N, M, M * (M + 1) / 2, ell, Rv);
 }
 
 // the two cached prior factors (the cache is a vector: the second look-up may move its elements, so the first is re-resolved)

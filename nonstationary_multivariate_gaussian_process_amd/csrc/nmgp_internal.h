@@ -300,7 +300,7 @@ int nmgp_ps_chunk(int H, size_t per_draw_doubles);
 void nmgp_small_eig(const double* uL, int M, double* wB, double* VB, double* Bdiag);
 
 // ---- pieces shared by the Hadamard models (nmgp_hadamard.hip, nmgp_hadamard_sep.hip, nmgp_hadamard_sta.hip and the posterior-draw
-// entry nmgp_predsample_hadamard.hip); the schedule of a batched evaluation and the Gibbs kernels are in nmgp_hadamard_common.h ----
+// entries nmgp_predsample_hadamard.hip, nmgp_predsample_had.hip); the schedule of a batched evaluation and the Gibbs kernels are in nmgp_hadamard_common.h ----
 // scratch slots of the context (nmgp_eig.hip numbers them; a Hadamard entry never runs inside one of that file)
 enum { HSL_SMALL = 13, HSL_SLAB = 14, HSL_PRED = 15 };
 // NMGP_E_STATE unless a Hadamard subject is resident, NMGP_E_UNSUPPORTED off the custom factorisation (riding rows); every entry
@@ -311,6 +311,9 @@ int had_priors(nmgp_ctx* c, const double* hyper, PriorFactor** p0, PriorFactor**
 // op(L) X = R for the 1 + T prior columns of every chain (column 0 against p0, the others against p1)
 int had_prior_solve(nmgp_ctx* c, hipStream_t sp, rocblas_handle hb, bool trans, PriorFactor* p0, PriorFactor* p1, double* R, int N,
                     int T, int B);
+// nonseparable Hadamard model (nmgp_hadamard.hip): ell = exp(tilde_l), Rv[i] = row c_i of observation i's own L_i (raw slots,
+// zero-padded to M) for `batch` parameter vectors [batch, N(1+T)+1]; also the per-draw unpacking of nmgp_predsample_had.hip
+void had_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* Rv, int batch);
 // separable Hadamard model (nmgp_hadamard_sep.hip): ell = exp(tilde_l), sig = exp(tilde_sigma), Rv[i] = row c_i of the chain's L for
 // `batch` parameter vectors [batch, P]; S = K_x o (R R^T) + sigma2 I (lower, matrix z at S + z * sstride)
 void nmgp_hads_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* sig, double* Rv, int batch);

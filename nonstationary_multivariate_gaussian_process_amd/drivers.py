@@ -1452,6 +1452,50 @@ def posterior_predict_hadamard_sep(x, indx, y, hyper_pars, samples, xs, indx_sta
     return out
 
 
+def posterior_predict_hadamard(x, indx, y, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, ctx=None):
+    """Posterior-predictive band of the nonseparable HADAMARD model (irregularly observed outputs) from :class:`BatchedHMCHadamard`'s
+    draws: ``samples`` [iters, chains, N(1+T)+1] or [H, N(1+T)+1], ``xs`` [S] the new inputs; ``draws`` thins the history evenly to
+    that many.  ``indx_star=None`` predicts all M outputs at every new input (moments [S, M]); ``indx_star`` [S] predicts output
+    ``indx_star[s]`` only at ``xs[s]`` (held-out pairs; moments [S]).  Per draw and new input tilde_l* and the T slots of L* are
+    regressed and sampled and y* is sampled (``seed``: NumPy generator of all the normals); all draws and inputs go through one
+    batched device call (``Context.predsample_had``).  Returns :func:`summarize_posterior_predictive`'s dict plus ``L_star``
+    [H_used, S, T] and ``corr_quantiles`` [3, S, M, M]: the 2.5 / 50 / 97.5 % quantiles over the used draws of cov2cor(L* L*^T), the
+    time-varying cross-output correlation at the new inputs (what the reference's ``Post_Process`` scripts report)."""
+    from . import _lib
+    ctx = ctx if ctx is not None else _lib.default_context()
+    x, y = np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(y, dtype=np.float64).reshape(-1)
+    indx = np.ascontiguousarray(np.asarray(indx).reshape(-1), dtype=np.int32)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1)
+    S_ = np.asarray(samples, dtype=np.float64)
+    S_ = S_.reshape(-1, S_.shape[-1])
+    if draws is not None and int(draws) < S_.shape[0]:
+        S_ = S_[np.unique(np.round(np.linspace(0, S_.shape[0] - 1, int(draws))).astype(int))]
+    hyper = np.array([float(hyper_pars[k]) for k in SVC_HYPER_KEYS])
+    ctx.had_set_data(x, indx, y)
+    M = ctx.M
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal((S_.shape[0], xs.shape[0], 1 + M * (M + 1) // 2))
+    zy = rng.standard_normal((S_.shape[0], xs.shape[0]) + (() if indx_star is not None else (M,)))
+    mean, var, star, status = ctx.predsample_had(S_, hyper, xs, indx_star=indx_star, z=z)
+    out = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
+    out["L_star"] = star[:, :, 1:][status == 0]
+    out["corr_quantiles"] = correlation_quantiles(out["L_star"], M)
+    return out
+
+
+def correlation_quantiles(L_star, M, quantiles=(2.5, 50.0, 97.5)):
+    """[len(quantiles), S, M, M]: quantiles over the draws of cov2cor(L* L*^T), L* the lower triangle packed row by row in
+    ``L_star`` [H, S, T] (the slots as they are).  Pure NumPy."""
+    L_star = np.asarray(L_star, dtype=np.float64)
+    H, S = L_star.shape[:2]
+    L = np.zeros((H, S, M, M))
+    r, c = np.tril_indices(M)
+    L[:, :, r, c] = L_star
+    B = L @ np.swapaxes(L, -1, -2)
+    d = np.sqrt(np.einsum("hsmm->hsm", B))
+    return np.percentile(B / (d[..., :, None] * d[..., None, :]), list(quantiles), axis=0)
+
+
 def posterior_predict_hadamard_sta(x, indx, y, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, ctx=None):
     """Posterior-predictive band of the stationary HADAMARD model (irregularly observed outputs) from
     :class:`BatchedHMCHadamardSta`'s draws: ``samples`` [iters, chains, T+3] or [H, T+3], ``xs`` [S] the new inputs; ``draws`` thins

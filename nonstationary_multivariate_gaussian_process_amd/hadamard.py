@@ -13,8 +13,18 @@ measurements where each output has its own time stamps), instead of a complete `
 must occur.  The parameter vector is ``[tilde_l (N) | L_vecs (N T) | tilde_sigma2_err]``; ``L_vecs`` enters ``vec2lowtriangle``
 as it is (no exp on the diagonal slots).
 
-Not provided: ``indexedpoint_predmap_SVC_hadamard`` / ``test_predmap_SVC_hadamard`` (INTEGRATION.md says why), the
-``predsample_hadamard`` families.  The separable Hadamard model (``nlogpos_obj_hadamard``, ``point_predmap_hadamard``, ...) is
+Under this package's OWN names (the reference has none for them, so nothing is installed behind its module names):
+
+* ``point_`` / ``pointwise_`` / ``indexedpoint_`` / ``test_predsample_SVC_hadamard``: sampled y from a HISTORY of posterior draws
+  ``(tilde_l_hist [H, N], L_vecs_hist [H, N T], tilde_sigma2_err_hist [H])``, with the argument order of the reference's separable
+  family (``prediction.py:461-707``) minus ``tilde_sigma_hist``: all M outputs at a new input / on a grid (``[H, M]`` /
+  ``[S, H, M]``), or one labelled output per held-out pair (``[H]`` / ``[S_test, H]``).  All points of all draws go through ONE
+  device call (``nmgp_predsample_had``);
+* ``indexed_predict``: mean and variance of ONE labelled output per held-out input from one parameter vector -- the corrected
+  form of the reference's ``test_predmap_SVC_hadamard``.
+
+Not provided: ``indexedpoint_predmap_SVC_hadamard`` / ``test_predmap_SVC_hadamard`` themselves (their variance is output 0's for
+every label; INTEGRATION.md says why).  The separable Hadamard model (``nlogpos_obj_hadamard``, ``point_predmap_hadamard``, ...) is
 served by ``hadamard_sep.py``, the stationary one (``*_hadamard_S``, ``*_predmap_S_hadamard``) by ``hadamard_sta.py``, each under its
 own opt-in.
 
@@ -179,3 +189,97 @@ def pointwise_predmap_SVC_hadamard(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y
             raise TypeError("point_predmap_SVC_hadamard() missing required argument: %r" % k)
         vals.append(kwargs[k])
     return _predict(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, grids, *vals)
+
+
+# ---- posterior-draw and held-out prediction: this package's own names (nmgp_predsample_had) --------------------------------------
+def _hyper8(mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L):
+    return np.array([_f(mu_tilde_l), _f(alpha_tilde_l), _f(beta_tilde_l), _f(mu_L), _f(alpha_L), _f(beta_L), 1.0, 1.0])
+
+
+def _history(tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist):
+    hs = [_np(tilde_l_hist), _np(L_vecs_hist), _np(tilde_sigma2_err_hist).reshape(-1)]
+    H = min(len(h) for h in hs)                            # the histories are zipped, as the reference's separable family does
+    return np.concatenate([hs[0][:H].reshape(H, -1), hs[1][:H].reshape(H, -1), hs[2][:H, None]], axis=1)
+
+
+def _std_normals(shape, z, name):
+    if z is None:
+        return np.random.standard_normal(shape)
+    z = _np(z)
+    if z.shape != tuple(shape):
+        raise ValueError("%s must have shape %s (new input, draw, numbers consumed), got %s" % (name, tuple(shape), z.shape))
+    return z
+
+
+def _predsample(hist, x, indx, y, xs, indx_star, hyper, z, zy):
+    """Sampled y point-major: [S, H, M], or [S, H] with indx_star; ONE call of the device entry."""
+    pars = _history(*hist)
+    xs = _np(xs).reshape(-1)
+    S, H = xs.shape[0], pars.shape[0]
+    c = _lib.default_context()
+    c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
+    M = int(np.unique(_labels(indx)).shape[0])
+    T = M * (M + 1) // 2
+    zl = _std_normals((S, H, 1 + T), z, "z")
+    zy = _std_normals((S, H, M) if indx_star is None else (S, H), zy, "zy")
+    mean, var, _, _ = c.predsample_had(pars, hyper, xs, indx_star=indx_star, z=np.ascontiguousarray(zl.transpose(1, 0, 2)))
+    axes = (1, 0, 2) if indx_star is None else (1, 0)
+    ys = mean.transpose(axes) + np.sqrt(var.transpose(axes)) * zy
+    return torch.from_numpy(np.ascontiguousarray(ys))
+
+
+def point_predsample_SVC_hadamard(tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist, x, indx, y, x_star, mu_tilde_l, alpha_tilde_l,
+                                  beta_tilde_l, mu_L, alpha_L, beta_L, z=None, zy=None):
+    """Sampled y of all M outputs at x_star, one row per draw: 2d tensor [H, M].  z [1, H, 1+T]: the standard normals of the latent
+    regression (tilde_l*, the T slots of L*), zy [1, H, M]: those of y; both default to NumPy's global generator.  A draw whose
+    covariance does not factor has a NaN row."""
+    return _predsample((tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist), x, indx, y, _np(x_star).reshape(1), None,
+                       _hyper8(mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L), z, zy)[0]
+
+
+def pointwise_predsample_SVC_hadamard(tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist, x, indx, y, grids, mu_tilde_l, alpha_tilde_l,
+                                      beta_tilde_l, mu_L, alpha_L, beta_L, z=None, zy=None):
+    """Sampled y on a grid: 3d tensor [S, H, M]; all grid points of all draws go through one device call.  z [S, H, 1+T],
+    zy [S, H, M]."""
+    return _predsample((tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist), x, indx, y, grids, None,
+                       _hyper8(mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L), z, zy)
+
+
+def indexedpoint_predsample_SVC_hadamard(tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist, x, indx, y, x_star, indx_star, mu_tilde_l,
+                                         alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L, z=None, zy=None):
+    """Sampled y of output indx_star at x_star, one value per draw: 1d tensor [H].  z [1, H, 1+T], zy [1, H]."""
+    return _predsample((tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist), x, indx, y, _np(x_star).reshape(1),
+                       _labels(indx_star).reshape(1), _hyper8(mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L), z,
+                       zy)[0]
+
+
+def test_predsample_SVC_hadamard(tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist, x, indx, y, x_test, indx_test, mu_tilde_l,
+                                 alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L, z=None, zy=None):
+    """Sampled y at the held-out pairs (x_test[s], indx_test[s]): 2d tensor [S_test, H]; all pairs of all draws go through one device
+    call.  z [S_test, H, 1+T], zy [S_test, H]."""
+    return _predsample((tilde_l_hist, L_vecs_hist, tilde_sigma2_err_hist), x, indx, y, x_test, _labels(indx_test),
+                       _hyper8(mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L), z, zy)
+
+
+test_predsample_SVC_hadamard.__test__ = False           # a predictor of held-out ("test") pairs, not a pytest test
+
+
+def indexed_predict(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, x_test, indx_test, **hyper):
+    """(mean [S], var [S]) of output ``indx_test[s]`` at ``x_test[s]`` from ONE parameter vector (no noise: the conditional means
+    of the starred values), the variance with ``(L* L*^T)[c*, c*]``; ``hyper``: the six GP-prior hyper-parameters by keyword
+    (mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L).  The reference's ``test_predmap_SVC_hadamard``
+    (prediction.py:1549-1561) returns the same mean, and this variance at the label-0 points only (see the module docstring)."""
+    names = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_L", "beta_L")
+    missing = [k for k in names if k not in hyper]
+    if missing:
+        raise TypeError("indexed_predict() missing required keyword arguments: %s" % ", ".join(missing))
+    c = _lib.default_context()
+    c.had_set_data(_np(x).reshape(-1), _labels(indx), _np(y).reshape(-1))
+    pars = np.concatenate([_np(tilde_l).reshape(-1), _np(L_vecs).reshape(-1), _np(tilde_sigma2_err).reshape(-1)])[None]
+    mean, var, _, status = c.predsample_had(pars, _hyper8(*[hyper[k] for k in names]), _np(x_test).reshape(-1),
+                                            indx_star=_labels(indx_test))
+    if status[0] != 0:
+        # torch.cholesky raises on a covariance that is not positive definite (reference prediction.py:1538)
+        raise RuntimeError("indexed_predict: the covariance is not positive definite or not finite (status %d)" % int(status[0]))
+    return (torch.from_numpy(np.ascontiguousarray(mean[0])).type(torch.DoubleTensor),
+            torch.from_numpy(np.ascontiguousarray(var[0])).type(torch.DoubleTensor))
