@@ -293,10 +293,32 @@ int nmgp_sep_batch_eval(nmgp_ctx* ctx, const double* pars, int B, const double h
  * NMGP_E_STATE without a complete-data resident subject, NMGP_E_NULL for a NULL x or Y, NMGP_E_SHAPE for S < 1 or
  * chains_per_subject < 1.  A second call replaces the set.  The set lives until nmgp_sep_batch_clear_subjects, nmgp_set_data or
  * nmgp_had_set_data, each of which frees it with its prior factors; without a set nmgp_sep_batch_eval evaluates the resident
- * subject exactly as before.  No other entry looks at the set: nmgp_logpos_sep, nmgp_sep_prior_apply and the predictors keep using
- * the resident subject. */
+ * subject exactly as before.  nmgp_sta_batch_eval (below) reads the set's x and Y in the same way; no other entry looks at the set:
+ * nmgp_logpos_sep, nmgp_logpos_sta, nmgp_sep_prior_apply and the predictors keep using the resident subject. */
 int nmgp_sep_batch_set_subjects_chains(nmgp_ctx* ctx, const double* x, const double* Y, int S, int chains_per_subject);
 int nmgp_sep_batch_clear_subjects(nmgp_ctx* ctx);
+
+/* B chains of the STATIONARY (LMC) model per launch sequence: Sigma = B kron K_rbf + sigma2 I, the baseline of
+ * Stationary_model.py, Stationary_model_mpisim.py (one process per chain there) and Stationary_model_mpiKAISER.py (one per subject);
+ * objective of logpos.py:383-462 per chain.  pars [B, T+3] = [tilde_l, tilde_sigma, uL_vec (T), tilde_sigma2_err]; hyper, out5 [B, 5]
+ * and the prior terms (reported whatever `prior` is) as nmgp_logpos_sta; grad [B, T+3] or NULL; status [B] as nmgp_sep_batch_eval:
+ * 0 = exact covariance, k in 1..3 = the chain needed k jitter retries (re-evaluated through nmgp_logpos_sta), negative = -(numerical
+ * failure code) if it failed even so (its out5 row is NaN, its gradient row zero); the other chains keep their bits.
+ * Chain b's M blocks wB_b[p] K_b + sigma2_b I (in B_b's eigenbasis) are written straight from (x, exp(tilde_l), exp(tilde_sigma))
+ * with the Gibbs build's element expression -- K itself is never stored -- and join ONE batch of the blocked Cholesky on its
+ * substitution-based (`precise`) panel kernels, so that a chain's bits depend neither on B nor on its neighbours; B = 1 runs the same
+ * kernels.  The gradient is ONE pass over the M blocks -S_p^-1 (K_ij and d_ij recomputed) that leaves partial sums per column
+ * group, added by the host in index order.  One host synchronisation per chunk.  Device workspace per chain: M (2N + 2) N doubles
+ * for the factorisation with gradients (N + 1 without) + M N^2 (-S^-1): 2.02 GB at N = 4096, D = 5 (the separable entry: 2.29 GB),
+ * 0.67 GB without gradients.  Chunks: below NMGP_SEP_BATCH_SLAB_GB, at most 65,535 / M chains and at most NMGP_STA_BATCH_MAX chains
+ * (environment, read at call time, unset = no limit); NMGP_E_SHAPE if a single chain does not fit.
+ * While a set of nmgp_sep_batch_set_subjects_chains is active, chain b reads x and Y of subject b / chains_per_subject and
+ * B == S * chains_per_subject is required (NMGP_E_SHAPE); chunks are whole subjects or parts of one.  Nothing per subject is cached:
+ * the model has no GP priors.  Without a set every chain reads the resident subject.  NMGP_E_STATE without a complete-data resident
+ * subject (a Hadamard subject included: the context stays usable), NMGP_E_NULL for a NULL pars / hyper / out5 / status,
+ * NMGP_E_SHAPE for B < 1.  NMGP_SEP=eig and N > 11,584 evaluate chain by chain through nmgp_logpos_sta. */
+int nmgp_sta_batch_eval(nmgp_ctx* ctx, const double* pars, int B, const double hyper[5], int prior, double* out5, double* grad,
+                        int* status);
 
 /* ---- primitives (host buffers in / out) ----------------------------------------------------- */
 /* kernels.pairwise_distances, kernels.py:5-21.  x1: [n1,d], x2: [n2,d] or NULL (=x1). out: [n1,n2]. */

@@ -67,6 +67,7 @@ SIGNATURES = {
     "nmgp_sep_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_sep_batch_set_subjects_chains": (I, [V, P, P, I, I]),
     "nmgp_sep_batch_clear_subjects": (I, [V]),
+    "nmgp_sta_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_pairwise_distances": (I, [V, P, I, P, I, I, P]),
     "nmgp_rbf_cov": (I, [V, P, I, P, I, I, D, D, P]),
     "nmgp_nonstat_rbf_cov": (I, [V, P, P, P, I, P, P, P, I, I, P]),
@@ -482,6 +483,37 @@ class Context:
         grad = np.empty(P_) if want_grad else None
         self.check(self.lib.nmgp_logpos_sta(self.h, ptr(pars), ptr(hyper), int(bool(prior)), ptr(out), ptr(grad)))
         return out, grad
+
+    def sta_batch_eval(self, pars, hyper, prior=True, want_grad=False):
+        """B chains of the stationary (LMC) model in one launch sequence: pars [B, T+3] (or one vector [T+3]) -> (out [B, 5] as
+        ``logpos_sta``, grad [B, T+3] or None, status [B]: 0 exact, 1..3 jitter retries needed, negative = numerical failure even so
+        (row NaN, gradient row zero)).  A chain's bits do not depend on B.  While a subject set is active (``sta_batch_set_subjects``)
+        row s * chains_per_subject + k is chain k of subject s."""
+        pars = as_f64(pars)
+        P_ = self.T + 3
+        if pars.ndim == 1:
+            pars = pars.reshape(1, -1)
+        if pars.ndim != 2 or pars.shape[1] != P_:
+            raise NmgpError("parameters must be [B, T+3 = %d], got %s" % (P_, pars.shape))
+        hyper = as_f64(hyper)
+        if hyper.size != 5:
+            raise NmgpError("the stationary model takes 5 hyper-parameters, got %d" % hyper.size)
+        B = pars.shape[0]
+        out = np.empty((B, 5))
+        grad = np.empty((B, P_)) if want_grad else None
+        status = np.zeros(B, dtype=np.int32)
+        self.check(self.lib.nmgp_sta_batch_eval(self.h, ptr(pars), B, ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
+                                                status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out, grad, status
+
+    def sta_batch_set_subjects(self, xs, Ys, chains_per_subject=1):
+        """Alias of ``sep_batch_set_subjects``: the stationary and the separable batched entries share ONE subject set (xs [S, N],
+        Ys [S, N, M]); the stationary model has no GP priors, so nothing per subject is factored for it."""
+        self.sep_batch_set_subjects(xs, Ys, chains_per_subject)
+
+    def sta_batch_clear_subjects(self):
+        """Alias of ``sep_batch_clear_subjects``."""
+        self.sep_batch_clear_subjects()
 
     # -- primitives -----------------------------------------------------------------------------
     def pairwise_distances(self, x1, x2=None):

@@ -654,6 +654,33 @@ struct SepChunkSubjects {
     int s0 = 0, nsub = 0, cps = 1;
 };
 
+// core(b0, nb, sub) for every chunk of at most Bc chains of a batch of B (nmgp_sep_batch_eval, nmgp_sta_batch_eval).  With a subject
+// set a chunk is a whole number of subjects (cps fits in a chunk: the chunk size is rounded down to a multiple of it) or a part of ONE
+// subject (the subject's chains are split, and no chunk crosses into the next subject).
+template <class Core>
+int sep_for_each_chunk(int B, int Bc, bool multi, int cps, Core&& core) {
+    const bool split = multi && cps > Bc;
+    if (multi && !split) Bc = (Bc / cps) * cps;
+    for (int b0 = 0; b0 < B;) {
+        int nb = std::min(Bc, B - b0);
+        SepChunkSubjects sub;
+        if (multi) {
+            sub.s0 = b0 / cps;
+            if (split) {
+                nb = std::min(nb, (sub.s0 + 1) * cps - b0);
+                sub.nsub = 1;
+                sub.cps = nb;
+            } else {
+                sub.nsub = nb / cps;
+                sub.cps = cps;
+            }
+        }
+        NMGP_TRY(core(b0, nb, sub));
+        b0 += nb;
+    }
+    return 0;
+}
+
 // chains [0, B) of `pars` (already offset by the caller): everything enqueued, one synchronisation, host epilogue.  bad[b] = 1 marks a
 // chain whose blocks failed numerically (its out6 / grad rows are then unspecified: the caller re-evaluates it one by one).
 int sep_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[9], int prior, double* out6, double* grad, int* status,
@@ -905,7 +932,8 @@ struct SepResidentSwap {
 // ---- separable model, many subjects: x [S, N], Y [S, N, M] row-major; batch element b = s * chains_per_subject + k of
 // nmgp_sep_batch_eval is chain k of subject s.  One pair of GP-prior factors per SUBJECT, built on first use by one batched
 // factorisation and cached per (alpha, beta) with the set.  The set lives until nmgp_sep_batch_clear_subjects, nmgp_set_data or
-// nmgp_had_set_data; no other entry looks at it.
+// nmgp_had_set_data; nmgp_sta_batch_eval reads its x / Y too (the stationary model has no GP priors, so none of its factors), no
+// other entry looks at it.
 extern "C" int nmgp_sep_batch_set_subjects_chains(nmgp_ctx* c, const double* x, const double* Y, int S, int chains_per_subject) {
     if (!c) return NMGP_E_NULL;
     if (!nmgp_complete_subject(c))
@@ -994,30 +1022,13 @@ extern "C" int nmgp_sep_batch_eval(nmgp_ctx* c, const double* pars, int B, const
         return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the separable model at N = %d, D = %d needs %.1f GB of device workspace, above the "
                          "NMGP_SEP_BATCH_SLAB_GB cap of %.0f GB", N, M, per_chain / 1e9, cap_gb);
     std::vector<char> bad(B, 0);
-    // With a subject set a chunk is a whole number of subjects (cps fits in a chunk: the chunk size is rounded down to a multiple of
-    // it) or a part of ONE subject (the subject's chains are split, and no chunk crosses into the next subject).
-    const bool split = multi && cps > Bc;
-    if (multi && !split) Bc = (Bc / cps) * cps;
-    for (int b0 = 0; b0 < B;) {
-        int nb = std::min(Bc, B - b0);
-        SepChunkSubjects sub;
-        if (multi) {
-            sub.s0 = b0 / cps;
-            if (split) {
-                nb = std::min(nb, (sub.s0 + 1) * cps - b0);
-                sub.nsub = 1;
-                sub.cps = nb;
-            } else {
-                sub.nsub = nb / cps;
-                sub.cps = cps;
-            }
-        }
+    NMGP_TRY(sep_for_each_chunk(B, Bc, multi, cps, [&](int b0, int nb, const SepChunkSubjects& sub) -> int {
         std::vector<char> badc(nb, 0);
         NMGP_TRY(sep_batch_core(c, pars + (size_t)b0 * P, nb, hyper, prior, out6 + (size_t)b0 * 6, want_grad ? grad + (size_t)b0 * P : nullptr,
                                 status + b0, badc, sub));
         for (int k = 0; k < nb; ++k) bad[b0 + k] = badc[k];
-        b0 += nb;
-    }
+        return 0;
+    }));
     // chains that failed numerically: the single-chain entry, with the reference's jitter retries
     for (int b = 0; b < B; ++b)
         if (bad[b]) NMGP_TRY(one_by_one(b));
@@ -1096,6 +1107,288 @@ extern "C" int nmgp_logpos_sta(nmgp_ctx* c, const double* pars, const double hyp
     }
     NMGP_TRY(nmgp_take_launch_error(c));
     if (!std::isfinite(out5[1])) return nmgp_fail(c, NMGP_NUM_NAN, "non-finite stationary likelihood (%g)", out5[1]);
+    return 0;
+}
+
+// =================================================================================================
+// stationary objective, B chains per launch sequence
+// =================================================================================================
+// The baseline model's chains (one process each in the reference: Stationary_model_mpisim.py, one per subject in
+// Stationary_model_mpiKAISER.py) as ONE batch of the blocked Cholesky, on nmgp_sep_batch_eval's schedule: chain b contributes its M
+// blocks S_bp = wB_b[p] K_b + sigma2_b I, the B M matrices of order N go through one factorisation, one triangular matrix-vector
+// product and one inverse SYRK, value and gradient halves are enqueued back to back and there is ONE synchronisation per chunk of
+// chains.  What the constant curves change (nmgp_kernels_sta.hip): the blocks are written from (x, l_b, s_b) and K is never stored;
+// the adjoint is ONE pass over the M blocks -S_bp^-1 that leaves, per column group, the T + 3 gradient's ingredients
+//   d ll / d tilde_l     = 1/2 sum_p wB_p (alpha_p^T (K o D) alpha_p - <S_p^-1, K o D>) / l^2
+//   d ll / d tilde_sigma = sum_p wB_p (alpha_p^T K' alpha_p - <S_p^-1, K'>),   K' = K - 1e-6 I
+//   d ll / dB, d ll / d sigma2 as in sep_batch_core
+// -- no N x N weighted sum, no per-location adjoint, no K_x read back.  The factorisation runs the substitution-based (`precise`)
+// panel kernels, whose bits do not depend on the schedule the batch size selects: a chain's result does not depend on its
+// neighbours, and B = 1 runs the same kernels.  A chain that fails numerically is re-evaluated through nmgp_logpos_sta (the
+// reference's jitter retries); NMGP_SEP=eig and N beyond the block kernel's offsets evaluate chain by chain.
+namespace {
+
+struct StaBatchLayout {
+    size_t o_small = 0, o_yt = 0, o_z = 0, o_alpha = 0, o_red = 0, o_info = 0, o_S = 0;
+    size_t o_Cneg = 0, o_part = 0, o_Xi = 0, o_tr = 0;            // with gradients only
+    size_t total = 0, small_per = 0, tri_part = 0;
+    int ld = 0;
+    long long bs = 0;
+};
+
+StaBatchLayout sta_batch_layout(int B, int N, int M, bool want_grad) {
+    StaBatchLayout L;
+    const size_t NN = (size_t)N * N, BM = (size_t)B * M;
+    L.ld = want_grad ? (int)((((size_t)2 * N + 2 + 15) / 16) * 16) : (int)((((size_t)N + 1 + 15) / 16) * 16);
+    L.bs = (long long)L.ld * N;
+    L.small_per = NMGP_STA_SMALL((size_t)M);
+    L.tri_part = (size_t)N * ((N + 255) / 256);
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off += (n + 1) & ~(size_t)1; return o; };
+    L.o_small = take((size_t)B * L.small_per); L.o_yt = take(BM * N); L.o_z = take(BM * N);
+    L.o_alpha = take(BM * N); L.o_red = take(BM * 4); L.o_info = take(BM);
+    L.o_S = take(BM * (size_t)L.bs);
+    if (want_grad) {
+        L.o_Cneg = take(BM * NN);
+        L.o_part = take(BM * L.tri_part);                         // block sums of alpha = L^-T z
+        L.o_Xi = take((size_t)B * NMGP_SEP_TR_G * M * (M + 1) / 2);
+        L.o_tr = take(BM * NMGP_SEP_TR_G * 5);
+    }
+    L.total = off;
+    return L;
+}
+
+// chains [0, B) of `pars` (already offset by the caller): everything enqueued, one synchronisation, host epilogue.  bad[b] = 1 marks a
+// chain whose blocks failed numerically (its out5 / grad rows are then unspecified: the caller re-evaluates it one by one).
+int sta_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[5], int prior, double* out5, double* grad, int* status,
+                   std::vector<char>& bad, const SepChunkSubjects& sub) {
+    const int N = c->N, M = c->M, T = c->T;
+    const size_t P = (size_t)T + 3;
+    const bool want_grad = grad != nullptr;
+    const double mu_l = hyper[0], sd_l = hyper[1], a = hyper[2], bb = hyper[3], cc = hyper[4];
+    hipStream_t s = c->stream;
+    const bool multi = sub.nsub > 0;
+    // inputs of the chunk's first subject; strides 0 without a set (every chain reads the resident subject)
+    const long long xstride = multi ? N : 0, ystride = multi ? (long long)N * M : 0;
+    const double* xs = multi ? c->ss_x + (size_t)sub.s0 * N : c->d_x;
+    const double* Ys = multi ? c->ss_Y + (size_t)sub.s0 * N * M : c->d_Y;
+    const int cps = multi ? sub.cps : 1;
+    const int BM = B * M;
+    const StaBatchLayout L = sta_batch_layout(B, N, M, want_grad);
+    const int xpad = (N + 1) & 1, xoff = N + 1 + xpad;
+    const int ld = L.ld;
+    const long long bs = L.bs;
+    const size_t NN = (size_t)N * N;
+    const int sp_ = (int)L.small_per;
+    const int G = NMGP_SEP_TR_G;
+    double* slab;
+    NMGP_TRY(nmgp_scratch_get(c, SL_BIG, L.total, &slab));      // (the single-chain path's slot: the two never run at the same time)
+    double *d_small = slab + L.o_small, *yt = slab + L.o_yt, *z = slab + L.o_z, *alpha = slab + L.o_alpha, *red = slab + L.o_red;
+    int* info = reinterpret_cast<int*>(slab + L.o_info);
+    double* S = slab + L.o_S;
+    // ---- host: B = L L^T and its eigendecomposition, per chain (M x M: known before the first launch) ----
+    std::vector<EigWork> w(B);
+    std::vector<double> hsmall((size_t)B * L.small_per, 0.0), sig2(B), tse(B), ell(B);
+    for (int b = 0; b < B; ++b) {
+        const double* pb = pars + (size_t)b * P;
+        tse[b] = pb[P - 1];
+        sig2[b] = std::exp(tse[b]);
+        ell[b] = std::exp(pb[0]);
+        build_B(pb + 2, M, true, w[b].h_L, w[b].h_B);
+        jacobi_eigh(M, w[b].h_B.data(), w[b].h_wB, w[b].h_VB);
+        double* h = hsmall.data() + (size_t)b * L.small_per;
+        for (int p = 0; p < M; ++p) h[p] = w[b].h_wB[p];
+        for (int k = 0; k < M * M; ++k) h[M + k] = w[b].h_VB[k];
+        h[M + (size_t)M * M] = sig2[b];
+        h[M + (size_t)M * M + 1] = ell[b];
+        h[M + (size_t)M * M + 2] = std::exp(pb[1]);
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_small, hsmall.data(), hsmall.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)BM * sizeof(int), s));
+    {
+        NmgpStage sp(c, NMGP_STAGE_COV);
+        sta_prep_b(s, Ys, d_small, sp_, N, M, yt, B, ystride, cps);
+        int r = sta_blocks_b(s, xs, d_small, sp_, N, M, S, ld, bs, B, xstride, cps);
+        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+    }
+    {
+        NmgpStage sp(c, NMGP_STAGE_CHOL);
+        set_row(s, S, ld, N, yt, N, BM, bs, N);
+        if (want_grad) identity_rows(s, S, ld, N + 1, N, xpad, BM, bs);
+        nmgp_potrf(c, S, ld, N, want_grad ? 1 + xpad : 1, want_grad ? N : 0, info, BM, bs, 1, 1);      // precise panels
+        get_row(s, S, ld, N, z, N, BM, bs, N);
+    }
+    {
+        NmgpStage sp(c, NMGP_STAGE_REDUCE);
+        chol_logdet_quad(s, S, ld, N, z, red, red + 1, BM, bs, 4);
+    }
+    std::vector<double> hr((size_t)BM * 4);
+    std::vector<int> hi(BM);
+    HIP_TRY(c, hipMemcpyAsync(hr.data(), red, hr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(hi.data(), info, (size_t)BM * sizeof(int), hipMemcpyDeviceToHost, s));
+    // ---- gradient half: enqueued behind the value half without waiting for it (a chain that failed produces garbage here, which the
+    // epilogue discards) ----
+    const int NX = M * (M + 1) / 2;
+    std::vector<double> hx, htr;
+    if (want_grad) {
+        double *Cneg = slab + L.o_Cneg, *part = slab + L.o_part, *Xi = slab + L.o_Xi, *trs = slab + L.o_tr;
+        {
+            NmgpStage sp(c, NMGP_STAGE_INVERSE);
+            tri_gemv_upper(s, S + xoff, ld, N, z, alpha, part, BM, bs, (long long)L.tri_part);
+            syrk_lower(s, S + xoff, ld, Cneg, N, N, N, N, BM, bs, (long long)NN, 1);              // -S_bp^-1
+        }
+        {
+            NmgpStage sp(c, NMGP_STAGE_ADJOINT);
+            int r = sta_reduce_b(s, Cneg, xs, alpha, d_small, sp_, N, M, G, trs, Xi, B, xstride, cps);
+            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+        }
+        hx.assign((size_t)B * G * NX, 0.0);
+        htr.assign((size_t)BM * G * 5, 0.0);
+        HIP_TRY(c, hipMemcpyAsync(hx.data(), Xi, hx.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(htr.data(), trs, htr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));          // the one synchronisation of the chunk
+    NMGP_TRY(nmgp_take_launch_error(c));
+    // ---- host epilogue ----
+    for (int b = 0; b < B; ++b) {
+        bad[b] = 0;
+        double ll = 0.0;
+        for (int p = 0; p < M; ++p) {
+            if (hi[(size_t)b * M + p] != 0) bad[b] = 1;
+            ll += -0.5 * hr[((size_t)b * M + p) * 4] - 0.5 * hr[((size_t)b * M + p) * 4 + 1];
+        }
+        if (!std::isfinite(ll)) bad[b] = 1;
+        const double* pb = pars + (size_t)b * P;
+        // the prior terms of nmgp_logpos_sta (logpos.py:445-458), reported whatever `prior` is
+        double dl = 0.0, lp_uL = 0.0;
+        std::vector<double> g_uL_prior(T, 0.0);
+        const double lp_l = normal_logprob_f32(pb[0], mu_l, sd_l, &dl);
+        for (int t = 0; t < T; ++t) lp_uL += normal_logprob_f32(pb[2 + t], 0.0, cc, &g_uL_prior[t]);
+        const double lp_s2 = (-a - 1.0) * std::log(sig2[b]) - bb / sig2[b] + a * std::log(bb) - std::lgamma(a);
+        double res = 0.0;
+        res += ll;
+        if (prior) { res += lp_l; res += lp_uL; res += lp_s2; res += tse[b]; }
+        double* o = out5 + (size_t)b * 5;
+        o[0] = -res; o[1] = ll; o[2] = lp_l; o[3] = lp_uL; o[4] = lp_s2;
+        status[b] = 0;
+        if (!want_grad || bad[b]) continue;
+        // the G partials of every sum, in index order
+        std::vector<double> tr(M, 0.0), tk(M, 0.0), tkd(M, 0.0), aa(M, 0.0), akd(M, 0.0);
+        const double* tb = htr.data() + (size_t)b * M * G * 5;
+        for (int p = 0; p < M; ++p)
+            for (int g = 0; g < G; ++g) {
+                const double* q = tb + ((size_t)p * G + g) * 5;
+                tr[p] += q[0]; tk[p] += q[1]; tkd[p] += q[2]; aa[p] += q[3]; akd[p] += q[4];
+            }
+        std::vector<double> Xs((size_t)M * M), dB((size_t)M * M, 0.0), g_uL, aKa((size_t)M * M, 0.0);
+        {
+            const double* hxb = hx.data() + (size_t)b * G * NX;
+            int e = 0;
+            for (int p = 0; p < M; ++p)
+                for (int q = p; q < M; ++q, ++e) {
+                    double acc = 0.0;
+                    for (int g = 0; g < G; ++g) acc += hxb[(size_t)g * NX + e];
+                    aKa[(size_t)p * M + q] = aKa[(size_t)q * M + p] = acc;
+                }
+        }
+        // the two scalar curves: every location moves together
+        double gtl = 0.0, gts = 0.0;
+        for (int p = 0; p < M; ++p) {
+            const double wp = w[b].h_wB[p];
+            gtl += wp * (akd[p] - tkd[p]);
+            gts += wp * ((aKa[(size_t)p * M + p] - NMGP_JITTER * aa[p]) - (tk[p] - NMGP_JITTER * tr[p]));
+        }
+        gtl = 0.5 * gtl / (ell[b] * ell[b]);
+        // d loglik / dB = V_B Xi V_B^T,  Xi[p,p'] = 1/2 (alpha_p^T K alpha_p' - d_pp' <S_p^-1, K>)
+        for (int p = 0; p < M; ++p)
+            for (int q = 0; q < M; ++q) Xs[(size_t)p * M + q] = 0.5 * (aKa[(size_t)q * M + p] - (p == q ? tk[p] : 0.0));
+        for (int i = 0; i < M; ++i)
+            for (int j = 0; j < M; ++j) {
+                double acc = 0.0;
+                for (int p = 0; p < M; ++p)
+                    for (int q = 0; q < M; ++q) acc += w[b].h_VB[(size_t)i * M + p] * Xs[(size_t)p * M + q] * w[b].h_VB[(size_t)j * M + q];
+                dB[(size_t)i * M + j] = acc;
+            }
+        double ds = 0.0;
+        for (int p = 0; p < M; ++p) ds += 0.5 * (aa[p] - tr[p]);
+        dB_to_guL(dB, w[b].h_L, M, g_uL);
+        double* gb = grad + (size_t)b * P;
+        if (prior) gtl += dl;
+        gb[0] = -gtl;
+        gb[1] = -gts;
+        for (int t = 0; t < T; ++t) gb[2 + t] = -(g_uL[t] + (prior ? g_uL_prior[t] : 0.0));
+        double ge = sig2[b] * ds;
+        if (prior) ge += (-a - 1.0) + bb / sig2[b] + 1.0;
+        gb[P - 1] = -ge;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int nmgp_sta_batch_eval(nmgp_ctx* c, const double* pars, int B, const double hyper[5], int prior, double* out5, double* grad,
+                                   int* status) {
+    if (!c) return NMGP_E_NULL;
+    if (!pars || !hyper || !out5 || !status) return nmgp_fail(c, NMGP_E_NULL, "pars/hyper/out5/status must not be NULL");
+    if (B <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "B must be positive");
+    NMGP_TRY(require_data(c));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->N, M = c->M, T = c->T;
+    const size_t P = (size_t)T + 3;
+    const bool want_grad = grad != nullptr;
+    const bool multi = c->ss_S > 0;                 // a subject set is active: chain b belongs to subject b / cps
+    const int cps = multi ? c->ss_cps : 1;
+    if (multi && (long long)B != (long long)c->ss_S * cps)
+        return nmgp_fail(c, NMGP_E_SHAPE, "nmgp_sta_batch_eval: B = %d, but the subject set holds %d subjects x %d chains = %lld", B,
+                         c->ss_S, cps, (long long)c->ss_S * cps);
+    SepResidentSwap swap(c);
+    auto one_by_one = [&](int b) -> int {
+        if (multi) NMGP_TRY(swap.to(b / cps));
+        int rc = nmgp_logpos_sta(c, pars + (size_t)b * P, hyper, prior, out5 + (size_t)b * 5, want_grad ? grad + (size_t)b * P : nullptr);
+        if (rc < 0) return rc;
+        if (rc > 0) {
+            for (int k = 0; k < 5; ++k) out5[(size_t)b * 5 + k] = std::nan("");
+            if (want_grad) for (size_t k = 0; k < P; ++k) grad[(size_t)b * P + k] = 0.0;
+            status[b] = -rc;                  // (negative: a leading-minor index must not read as a retry count)
+        } else {
+            status[b] = c->last_sep_attempts;
+        }
+        return 0;
+    };
+    // (the block kernels address a block with 32-bit byte offsets, as the separable entry's: N <= 11,584 -- beyond that, and for the
+    // eigen formulation, the chains are evaluated one by one)
+    const bool blocks_fit = (long long)(2 * (long long)N + 18) * N * 8 < 0x7fffffffLL;
+    if (c->sep_algo != 1 || !blocks_fit) {
+        for (int b = 0; b < B; ++b) NMGP_TRY(one_by_one(b));
+        return 0;
+    }
+    // chunk of chains: the device slab below the cap, the chain x block index within the grid's limit, NMGP_STA_BATCH_MAX chains
+    double cap_gb = 96.0;
+    if (const char* e = std::getenv("NMGP_SEP_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
+    const size_t per_chain = sta_batch_layout(1, N, M, want_grad).total * sizeof(double);
+    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
+    Bc = std::min(Bc, 65535 / std::max(M, 1));
+    if (Bc < 1)
+        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the stationary model at N = %d, D = %d needs %.1f GB of device workspace, above the "
+                         "NMGP_SEP_BATCH_SLAB_GB cap of %.0f GB", N, M, per_chain / 1e9, cap_gb);
+    if (const char* e = std::getenv("NMGP_STA_BATCH_MAX")) {
+        const int cap = std::atoi(e);
+        if (cap >= 1) Bc = std::min(Bc, cap);
+    }
+    std::vector<char> bad(B, 0);
+    NMGP_TRY(sep_for_each_chunk(B, Bc, multi, cps, [&](int b0, int nb, const SepChunkSubjects& sub) -> int {
+        std::vector<char> badc(nb, 0);
+        NMGP_TRY(sta_batch_core(c, pars + (size_t)b0 * P, nb, hyper, prior, out5 + (size_t)b0 * 5, want_grad ? grad + (size_t)b0 * P : nullptr,
+                                status + b0, badc, sub));
+        for (int k = 0; k < nb; ++k) bad[b0 + k] = badc[k];
+        return 0;
+    }));
+    // chains that failed numerically: the single-chain entry, with the reference's jitter retries
+    for (int b = 0; b < B; ++b)
+        if (bad[b]) NMGP_TRY(one_by_one(b));
+    c->last_sep_attempts = 0;
+    for (int b = 0; b < B; ++b)
+        if (status[b] > c->last_sep_attempts) c->last_sep_attempts = status[b];
     return 0;
 }
 

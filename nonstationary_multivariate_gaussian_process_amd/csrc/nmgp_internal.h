@@ -168,8 +168,9 @@ struct nmgp_ctx {
     // posterior-draw prediction (nmgp_predsample.hip): ONE workspace for a chunk of draws, its own (no batch buffer is touched)
     double* ps_buf = nullptr;
     size_t ps_cap = 0;          // elements
-    // separable multi-subject set (nmgp_sep_batch_set_subjects_chains): while ss_S > 0, batch element b of nmgp_sep_batch_eval is chain
-    // b % ss_cps of subject b / ss_cps.  No other entry looks at it; nmgp_sep_subjects_free drops it with its prior factors
+    // separable multi-subject set (nmgp_sep_batch_set_subjects_chains): while ss_S > 0, batch element b of nmgp_sep_batch_eval and of
+    // nmgp_sta_batch_eval is chain b % ss_cps of subject b / ss_cps.  No other entry looks at it; nmgp_sep_subjects_free drops it with
+    // its prior factors
     int ss_S = 0, ss_cps = 1;
     double* ss_x = nullptr;     // [S, N]
     double* ss_Y = nullptr;     // [S, N, M] row-major (k_sep_prep_b rotates it per chain)
@@ -488,6 +489,17 @@ void sep_reduce_b(hipStream_t s, const double* Cneg, const double* K, const doub
 void sep_adjoint_b(hipStream_t s, const double* x, const double* ell, const double* sig, const double* U, const double* small,
                    int small_per, int M, const double* C, int N, double* part, double* g, int B, long long xstride = 0, int cps = 1);
 void two_col_rhs_b(hipStream_t s, const double* pars, long long P, double mu_a, double mu_b, int N, double* R, int B);
+// ---- nmgp_kernels_sta.hip: the stationary objective's pieces with the chain as a grid dimension (nmgp_sta_batch_eval) ----
+// small[b]: wB [M] | VB row-major [M, M] | sigma2 | l = exp(tilde_l) | s = exp(tilde_sigma) | pad
+#define NMGP_STA_SMALL(M) ((M) + (M) * (M) + 4)
+void sta_prep_b(hipStream_t s, const double* Y, const double* small, int small_per, int N, int M, double* yt, int B,
+                long long ystride = 0, int cps = 1);
+// NMGP_E_UNSUPPORTED for M outside 1 .. 8 (as sta_reduce_b)
+int sta_blocks_b(hipStream_t s, const double* x, const double* small, int small_per, int N, int M, double* S, int ldo, long long bstride,
+                 int B, long long xstride = 0, int cps = 1);
+// out: B * M * G * 5 doubles, xi: B * G * M (M + 1) / 2 doubles (partial sums per column group, see k_sta_reduce_b); G a multiple of 8
+int sta_reduce_b(hipStream_t s, const double* Cneg, const double* x, const double* alpha, const double* small, int small_per, int N, int M,
+                 int G, double* out, double* xi, int B, long long xstride = 0, int cps = 1);
 // ---- nmgp_predsample.hip ----
 // after a factorisation with riding rows, for each of `batch` matrices (stride bstride): dots[z ostride + o0 + e] = row (R0 + e) . row
 // zrow, sqs[..] = |row (R0 + e)|^2 over the n columns, e < E, in a fixed order; part: batch * 2 * E * ceil(n / 128) doubles

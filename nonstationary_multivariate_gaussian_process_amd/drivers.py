@@ -1231,6 +1231,98 @@ class BatchedHMCHadamardSta(_HadamardStaSubject, LockStepHMC):
         return np.stack([self.Minv @ row for row in p])
 
 
+# ---- stationary (LMC) model, complete data: the baseline ----------------------------------------------------------------------------
+class BatchedMAPStationary(LockStepMAP):
+    """The MAP loop of ``Stationary_model_mpiKAISER.py`` (:func:`map_stationary` per subject) for ALL subjects of a rank, or B restarts
+    of one subject, at once: every Adam iteration is ONE ``nmgp_sta_batch_eval`` -- the rows' B * M blocks as one batch of the blocked
+    Cholesky.  Host-side Adam, row by row the arithmetic of :func:`map_stationary`.  ``xs`` [N] with ``Ys`` [N, M]: ``init_pars``
+    [B, T+3] are B restarts of that subject.  ``xs`` [S, N] with ``Ys`` [S, N, M]: ``init_pars`` [S * chains_per_subject, T+3], row
+    s * chains_per_subject + k being restart k of subject s (the subject set of ``nmgp_sep_batch_set_subjects_chains``).
+    ``fix_tilde_sigma`` (default) zeroes column 1 of the gradient before Adam's update: the reference keeps ``tilde_sigma`` out of
+    its optimiser ("fixed for correlation"), so ``pars[:, 1]`` stays at its initial value, bit for bit."""
+
+    def __init__(self, xs, Ys, hyper_pars, init_pars, lr=1e-1, ctx=None, chains_per_subject=1, fix_tilde_sigma=True):
+        from . import _lib
+        super().__init__(init_pars, lr=lr)
+        xs = np.ascontiguousarray(xs, dtype=np.float64)
+        Ys = np.ascontiguousarray(Ys, dtype=np.float64)
+        k = int(chains_per_subject)
+        if xs.ndim == 1:
+            if Ys.ndim != 2 or Ys.shape[0] != xs.shape[0] or k != 1:
+                raise ValueError("xs [N] needs Ys [N, M] and chains_per_subject = 1 (the rows of init_pars are the restarts): %s, %s, k = %d"
+                                 % (xs.shape, Ys.shape, k))
+            M = Ys.shape[1]
+        else:
+            if xs.ndim != 2 or Ys.ndim != 3 or Ys.shape[:2] != xs.shape or k < 1 or self.P.shape[0] != xs.shape[0] * k:
+                raise ValueError("xs [S, N], Ys [S, N, M] and init_pars [S * chains_per_subject, P] do not fit: %s, %s, %s, k = %d"
+                                 % (xs.shape, Ys.shape, self.P.shape, k))
+            M = Ys.shape[2]
+        if self.P.shape[1] != M * (M + 1) // 2 + 3:
+            raise ValueError("init_pars must be [B, T+3 = %d] for M = %d outputs, got %s" % (M * (M + 1) // 2 + 3, M, self.P.shape))
+        self.ctx = ctx if ctx is not None else _lib.default_context()
+        self.hyper = np.array([float(hyper_pars[key]) for key in STA_HYPER_KEYS])
+        self.prior = True
+        self.fix_tilde_sigma = bool(fix_tilde_sigma)
+        if xs.ndim == 1:
+            self.ctx.set_data(xs, Ys)
+        else:
+            self.ctx.set_data(xs[0], Ys[0])
+            self.ctx.sta_batch_set_subjects(xs, Ys, k)
+
+    def value_and_grad(self, P):
+        """out [B, 5], grad [B, T+3] and a status that is 0 for every valid evaluation: jitter retries (status > 0) count as valid, a
+        numerical failure (status < 0) marks the row dead for :func:`valid_rows`."""
+        out, grad, status = self.ctx.sta_batch_eval(P, self.hyper, self.prior, True)
+        if self.fix_tilde_sigma:
+            grad[:, 1] = 0.0
+        return out, grad, np.where(status < 0, status, 0)
+
+
+class BatchedHMCStationary(LockStepHMC):
+    """B independent HMC chains of the stationary (LMC) model in lock-step: every leapfrog step evaluates ``logpos.nlogpos_obj_S``
+    and its gradient for all chains with one ``nmgp_sta_batch_eval``.  The sampler call of ``Stationary_model.py`` for B chains at
+    once; the leapfrog update runs on the host (P = T + 3).  Identity, diagonal or dense mass matrix; the prior-factor metrics belong
+    to the models with GP priors and are refused.  Chain b reproduces a one-chain run started from the same state with seed
+    ``seed + b``, bit for bit, under a dense mass too (per-chain matrix-vector products, as :class:`BatchedHMCHadamardSta`).
+    SEVERAL SUBJECTS: ``x`` [S, N] with ``Y`` [S, N, M] puts B / S consecutive chains on each subject (chain b belongs to subject
+    b // (B / S)), as :class:`BatchedHMCSeparable`."""
+
+    def __init__(self, x, Y, hyper_pars, init_positions, step_size=1e-2, num_steps_in_leap=20, seed=None, ctx=None, M=None, Minv=None):
+        from . import _lib
+        super().__init__(init_positions, step_size, num_steps_in_leap, seed, M, Minv)
+        if self.mass_kind >= 3:
+            raise NotImplementedError("the prior-factor metrics belong to the models with GP priors: the stationary model takes the "
+                                      "identity, a diagonal or a dense mass matrix")
+        self.ctx = ctx if ctx is not None else _lib.default_context()
+        self.hyper = np.array([float(hyper_pars[k]) for k in STA_HYPER_KEYS])
+        x, Y = np.asarray(x, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+        Mo = Y.shape[-1]
+        if self.P != Mo * (Mo + 1) // 2 + 3:
+            raise ValueError("init_positions must be [B, T+3 = %d] for M = %d outputs, got %s" % (Mo * (Mo + 1) // 2 + 3, Mo, self.q.shape))
+        if x.ndim == 2:
+            S = x.shape[0]
+            if Y.ndim != 3 or Y.shape[0] != S:
+                raise ValueError("x [S, N] needs Y [S, N, M]; got %s, %s" % (x.shape, Y.shape))
+            if self.B % S:
+                raise ValueError("the number of chains %d is not a multiple of the number of subjects %d" % (self.B, S))
+            self.ctx.set_data(x[0], Y[0])
+            self.ctx.sta_batch_set_subjects(x, Y, self.B // S)
+        else:
+            self.ctx.set_data(x, Y)
+
+    def potential_and_grad(self, q):
+        """U [B] and dU/dq [B, P]; a chain whose covariance stays numerically singular after the jitter retries gets U = inf."""
+        out, g, status = self.ctx.sta_batch_eval(q, self.hyper, True, True)
+        U = out[:, 0].copy()
+        bad = (status < 0) | ~np.isfinite(U)
+        U[bad] = np.inf
+        g[bad] = 0.0
+        return U, g
+
+    draw_momenta = BatchedHMCHadamardSta.draw_momenta
+    velocity = BatchedHMCHadamardSta.velocity
+
+
 # ---- the whole recipe behind one call ---------------------------------------------------------------------------------------------
 def _sample_recipe(polish, build_metric, make_sampler, pars0, chains, iters, warm, warm_step, windows, window_iters, step_size,
                    step_candidates, target_accept, progress, segment):
@@ -1421,6 +1513,30 @@ def posterior_predict_separable(x, Y, hyper_pars, samples, xs, draws=None, seed=
     out = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
     out["tilde_sigma_star"] = star[:, :, 1][status == 0]
     return out
+
+
+def posterior_predict_stationary(x, Y, hyper_pars, samples, xs, draws=None, seed=0, ctx=None):
+    """Posterior-predictive band of the STATIONARY (LMC) model from :class:`BatchedHMCStationary`'s draws: ``samples``
+    [iters, chains, T+3] or [H, T+3], ``xs`` [S] the new inputs; ``draws`` thins the history evenly to that many.  The model has no
+    latent curve to regress: a draw is a parameter vector, and only y* is sampled (``seed``: NumPy generator of its normals).  All
+    draws and inputs go through one batched device call (``Context.predsample_sta``); ``hyper_pars`` is accepted for symmetry with
+    the siblings and not used.  Returns :func:`summarize_posterior_predictive`'s dict -- the shape of
+    :func:`posterior_predict_separable`'s without ``tilde_sigma_star`` --, ``tilde_l_star`` being each used draw's constant tilde_l
+    [H_used, S]."""
+    from . import _lib
+    ctx = ctx if ctx is not None else _lib.default_context()
+    x, Y = np.asarray(x, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1)
+    S_ = np.asarray(samples, dtype=np.float64)
+    S_ = S_.reshape(-1, S_.shape[-1])
+    if draws is not None and int(draws) < S_.shape[0]:
+        S_ = S_[np.unique(np.round(np.linspace(0, S_.shape[0] - 1, int(draws))).astype(int))]
+    rng = np.random.default_rng(seed)
+    zy = rng.standard_normal((S_.shape[0], xs.shape[0], Y.shape[1]))
+    ctx.set_data(x, Y)
+    mean, var, status = ctx.predsample_sta(S_, xs)
+    tl = np.repeat(S_[:, :1], xs.shape[0], axis=1)
+    return summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, tl, status)
 
 
 def posterior_predict_hadamard_sep(x, indx, y, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, ctx=None):
