@@ -2119,6 +2119,241 @@ __global__ __launch_bounds__(512, OCC) void k_panel_step(double* __restrict__ Ab
 #undef PS_STAMP
 }
 
+// ---------------------------------------------------------------------------------------------
+// LEFT-LOOKING steps of a 256-column node of the throughput schedule (two 128-column leaves, column blocks 0 .. 3 at c0 + 64 i).
+// The K = 128 update between the two leaves (6 passes over the rows' column blocks: read blocks 0 and 1, read and write blocks
+// 2 and 3) is folded into the catch-up of the right leaf's two launches, the way MODE 0 / 2 of k_panel_step fold a K = 64 one:
+//   launch            catch-up (solve role)        critical workgroup (block row k + 1)          passes
+//   k_panel_step<1>   -                            D11, as before                                2
+//   <1, true>         block 1 with block 0         D22 = C22 - X20 X20^T - X21 X21^T, factored   3
+//   <2, true>         block 2 with blocks 0, 1     D33 = C33 - X30 X30^T - X31 X31^T - X32 X32^T 4
+//   <3, false>        block 3 with blocks 0, 1, 2  -                                             5
+// 14 passes and 4 launches per node instead of 16 and 5.  Every C entry receives the products it received before, in ascending k
+// through the same MFMA k-groups (the update kernels start from -C and store -acc, or negate the j side: exact either way), so
+// the factor is bit-identical; only the store and reload between the K = 128 update and the K = 64 catch-up are gone.
+// NP = previous column blocks [ck - 64 NP, ck) applied to block k = [ck, ck + 64) before its solve, one after the other: one
+// 64-column block of operands in LDS and one of the rows' X in registers at a time, so that with the rows' own block at most
+// TWO 64-column row blocks are live per thread.  FACT: workgroup 0 (block row k + 1, waves 0..3) also brings its diagonal block
+// up to date with the NP blocks and with block k and factors it (potf2b_core_mfma); its X blocks reach the MFMA's other side
+// through LDS (Xs, aliasing the operands), and its diagonal block is loaded only when the first X block has gone there.
+// No workgroup waits for another: every operand is final since the previous launch.
+// Rows of L^-T (gradient evaluations, the A phase of the structured value path): rows t_fresh0 <= row < t_fresh1 (absolute) have
+// entered since the node began; nobody has written their block k, which starts from zero and is not loaded.  What the
+// catch-up reads of such rows left of their own block is either written by an earlier launch of the node or inside the seeded band
+// (k_xtri_seed: three blocks left of the row's own; <3, false> reaches exactly that far).
+// ---------------------------------------------------------------------------------------------
+template <int NP, bool FACT, int OCC>
+__global__ __launch_bounds__(512, OCC) void k_leaf_step(double* __restrict__ Ab, int lda, int ck, int m_act, long long bstride,
+                                                       int* __restrict__ info, int istride, int T, int nbatch, int t_fresh0,
+                                                       int t_fresh1) {
+    constexpr int kOpsC = 2560;                                         // doubles; after opsT
+    constexpr int kSmem = kOpsC + (FACT ? 64 * PS_XLD : 4096);
+    static_assert(64 * PS_XLD >= 4096, "Xs aliases (and covers) the catch-up operands");
+    static_assert(!FACT || sizeof(Potf2Lds) <= kSmem * sizeof(double), "the factorisation's LDS aliases the step's");
+    static_assert(64 * NP <= 64 * NMGP_XTRI_SEED_BLOCKS, "the catch-up of a row of L^-T would read left of the seeded band");
+    __shared__ __attribute__((aligned(32))) double smem[kSmem];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    // role-major workgroup ids, as in k_panel_step: workgroup 0 of every matrix first
+    const int bx = (int)blockIdx.x / nbatch, by = (int)blockIdx.x - bx * nbatch;
+    double* A = Ab + (size_t)by * bstride;
+    v4d* opsT = reinterpret_cast<v4d*>(smem);                    // [10][64 lanes], as in k_trsm_64h
+    v4d* opsC = reinterpret_cast<v4d*>(smem + kOpsC);            // [4 q][4 sg][64 lanes]: -L[ck + 16 q + i][4 (4 sg + kk) + l4]
+    double* Xs = smem + kOpsC;                                   // [64][PS_XLD]: workgroup 0's X[k+1, .] (FACT)
+    const bool wg0 = bx == 0;                                    // block row k + 1, waves 0..3; waves 4..7 only keep the barriers
+    const bool isC = wg0 && w < 4;
+    const int row = wg0 ? ck + 64 + 16 * w + l15 : ck + 128 + 128 * (bx - 1) + 16 * w + l15;
+    const bool rv = row < m_act && !(wg0 && w >= 4);
+    const int rowc = row < m_act ? row : (m_act - 1);            // clamped: loads stay in bounds, results are masked
+    const bool tload = rv && !(row >= t_fresh0 && row < t_fresh1);
+    // addresses = a uniform column pointer + ONE lane offset per access pattern (32 bits): no 64-bit address registers per load
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const unsigned vrow = (unsigned)(l4 * lda + rowc), vops = (unsigned)(l4 * lda + l15);
+    auto colp = [&](int col) { return A + (size_t)col * lda; };
+    double oc[8], ot[5];
+    v4d Xp[4], Tk[4];
+    auto load_ops = [&](int p) {                                 // -L[block k, previous block p]
+        const int cb = ck - 64 * (NP - p);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) oc[j] = -(colp(cb + 4 * (wu + 8 * (j & 1))) + ck + 16 * (j >> 1))[vops];
+    };
+    auto store_ops = [&]() {                                     // element j: q = j >> 1, sx = w + 8 (j & 1), lane
+#pragma unroll
+        for (int j = 0; j < 8; ++j) smem[kOpsC + (((j >> 1) * 4 + (j & 1) * 2 + (wu >> 2)) * 64 + lane) * 4 + (wu & 3)] = oc[j];
+    };
+    auto load_x = [&](int p) {                                   // the rows' X in previous block p
+        const int cb = ck - 64 * (NP - p);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) Xp[q] = v4d{0.0, 0.0, 0.0, 0.0};
+        if (rv) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Xp[q][r] = colp(cb + 16 * q + 4 * r)[vrow];
+        }
+    };
+    // (1) operands of the first catch-up and of the solve, through registers into LDS; the row loads are issued behind them (the
+    // operand registers are free again, see k_panel_step<2>)
+    load_ops(0);
+    {
+        const double* L = A + (size_t)ck * lda + ck;              // diagonal block k (factor + inverted 16x16 blocks)
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const int idx = tid + 512 * j;                        // 0 .. 2559
+            const int blk = idx >> 8, kk = (idx >> 6) & 3, l = idx & 63;
+            const int rr = l & 15, kc = 4 * kk + (l >> 4);
+            double v;
+            if (blk < 6) {
+                const int q = blk == 0 ? 1 : (blk < 3 ? 2 : 3);
+                const int pp = blk == 0 ? 0 : (blk < 3 ? blk - 1 : blk - 3);
+                v = -L[(size_t)(16 * pp + kc) * lda + 16 * q + rr];
+            } else {
+                const int q = blk - 6;                   // inv(L_qq)[rr][kc] (kc < rr) sits at row 16 q + kc, column 16 q + rr
+                if (kc < rr) v = L[(size_t)(16 * q + rr) * lda + 16 * q + kc];
+                else if (kc == rr) v = 1.0 / L[(size_t)(16 * q + rr) * lda + 16 * q + rr];
+                else v = 0.0;
+            }
+            ot[j] = v;
+        }
+    }
+    store_ops();
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int idx = tid + 512 * j;
+        const int blk = idx >> 8, kk = (idx >> 6) & 3, l = idx & 63;
+        smem[(blk * 64 + l) * 4 + kk] = ot[j];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) Tk[q] = v4d{0.0, 0.0, 0.0, 0.0};
+    if (tload) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Tk[q][r] = colp(ck + 16 * q + 4 * r)[vrow];
+    }
+    load_x(0);
+    __syncthreads();
+    // (2) catch-up, previous block by previous block in ascending k:  T_q -= X[rows, p] L[block k, p]^T
+    // (the next block's loads are issued behind the barrier: hoisted above the MFMAs they would want a third row block)
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        if (!wg0 || isC) {
+#pragma unroll
+            for (int sg = 0; sg < 4; ++sg)
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const double a = reinterpret_cast<const double*>(&opsC[(q * 4 + sg) * 64 + lane])[kk];
+                        Tk[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Xp[sg][kk], Tk[q], 0, 0, 0);
+                    }
+        }
+        if (p + 1 < NP) {
+            __syncthreads();                                      // every wave is done with the operands of block p
+            load_ops(p + 1);
+            if constexpr (OCC > 4) {                              // 16 operand registers + two row blocks do not fit 80 VGPRs:
+                store_ops();                                      // the operands go to LDS before the row loads are issued
+                __builtin_amdgcn_sched_barrier(0);
+                load_x(p + 1);
+            } else {
+                load_x(p + 1);
+                store_ops();
+            }
+            __syncthreads();
+        }
+    }
+    // (3) solve against the diagonal block (right-looking over the four 16-column blocks, see k_trsm_64h)
+#pragma unroll
+    for (int pp = 0; pp < 4; ++pp) {
+        const v4d ai = opsT[(6 + pp) * 64 + lane];
+        v4d x0 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) x0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[kk], Tk[pp][kk], x0, 0, 0, 0);
+        Tk[pp] = x0;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int q = pp + 1; q < 4; ++q) {
+                const double a = reinterpret_cast<const double*>(&opsT[((q == 1 ? 0 : (q == 2 ? 1 : 3)) + pp) * 64 + lane])[kk];
+                Tk[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Tk[pp][kk], Tk[q], 0, 0, 0);
+            }
+    }
+    if (rv) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) colp(ck + 16 * q + 4 * r)[vrow] = Tk[q][r];
+    }
+    if constexpr (FACT) {
+        if (!wg0) return;
+        // (4) workgroup 0: U = C[k+1, k+1] - sum_p X[k+1, p] X[k+1, p]^T (the previous blocks of its own rows come back from
+        // memory into Xs, 64 x 64 at a time: both MFMA operands from LDS) - X[k+1, k] X[k+1, k]^T (the solve's result); factor it
+        v4d Un[4];
+        if (isC) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Un[q][r] = colp(ck + 64 + 16 * q + 4 * r)[vrow];
+        }
+#pragma unroll 1
+        for (int p = 0; p < NP; ++p) {
+            const int cb = ck - 64 * (NP - p);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) oc[j] = colp(cb + wu + 8 * j)[ck + 64 + lane];
+            __syncthreads();                                      // every wave is done with what the area held
+#pragma unroll
+            for (int j = 0; j < 8; ++j) Xs[lane * PS_XLD + wu + 8 * j] = oc[j];
+            __syncthreads();
+            if (isC) {
+#pragma unroll
+                for (int sg = 0; sg < 4; ++sg)
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) {
+                        const double b = Xs[(16 * w + l15) * PS_XLD + 16 * sg + 4 * kk + l4];              // own row
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const double a = -Xs[(16 * q + l15) * PS_XLD + 16 * sg + 4 * kk + l4];
+                            Un[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, Un[q], 0, 0, 0);
+                        }
+                    }
+            }
+        }
+        __syncthreads();                                          // every wave is done with the previous block in Xs
+        if (isC) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Xs[(16 * w + l15) * PS_XLD + 16 * q + 4 * r + l4] = Tk[q][r];
+        }
+        __syncthreads();
+        if (isC) {
+#pragma unroll
+            for (int sg = 0; sg < 4; ++sg)
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const double a = -Xs[(16 * q + l15) * PS_XLD + 16 * sg + 4 * kk + l4];
+                        Un[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Tk[sg][kk], Un[q], 0, 0, 0);
+                    }
+        }
+        Potf2Lds& P = *reinterpret_cast<Potf2Lds*>(smem);        // aliases the operand area: dead after the next barrier
+        __syncthreads();
+        if (isC) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int rr = 16 * w + l15, cc = 16 * q + 4 * r + l4;
+                    P.S[cc * PB_LD + rr] = (cc <= rr) ? Un[q][r] : 0.0;
+                }
+        }
+        __syncthreads();
+        potf2b_core_mfma(P, info + (size_t)by * istride, ck + 64);
+        potf2b_store(A + (size_t)(ck + 64) * lda + (ck + 64), lda, 64, P, tid, 512);
+    }
+}
+
 // A[row, j] = v[j]  (the extra row carrying the right-hand side)
 // vstride = 0 broadcasts one vector to every matrix of the batch (all chains of a subject share y)
 // (cps: consecutive groups of cps matrices share one vector -- the chains of a subject in a multi-subject batch)
@@ -2232,6 +2467,36 @@ struct Factorisation {
         }
     }
 
+    // columns [c0, c0 + 256) of the throughput schedule: two 128-column leaves with the K = 128 update between them folded into
+    // the right leaf's catch-up (k_leaf_step has the table)
+    void leaf256(int c0) {
+        if (!take_block_done()) potf2_64(s, at(c0, c0), lda, 64, info, c0, batch, bs, is, precise);   // the first diagonal block
+        // rows of L^-T that have entered since the node began: their column blocks 2 and 3 start from zero (the removed update's
+        // "fresh" rows and, for block 3, those that enter with block 2)
+        const int f0 = xtri > 0 ? n + extra + c0 : kNoTriRows;
+        for (int k = 0; k < 4; ++k) {
+            const int ck = c0 + 64 * k;
+            const int m_act = active_rows(ck + 64);
+            const int rows = m_act - (ck + 64);
+            if (rows <= 0) continue;                     // last block of the matrix and nothing below it
+            const int T = 1 + (rows > 64 ? cdiv_c(rows - 64, 128) : 0);     // workgroup 0: block row k + 1 alone
+            const dim3 grid((unsigned)(T * batch));
+            if (k == 0)
+                NMGP_LAUNCH((k_panel_step<1, 4>), grid, dim3(512), 0, s, A, lda, ck, 0, 1, m_act, c0 + 128, bs, info, is, T, 0, 0, 0, 0, batch,
+                            0, f0, xtri > 0 ? n + extra - 64 * NMGP_XTRI_SEED_BLOCKS : kNoTriRows,
+                            stamps ? stamps + (size_t)(ck / 64) * 16 : nullptr);
+            else if (k == 1)
+                NMGP_LAUNCH((k_leaf_step<1, true, 4>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, kNoTriRows,
+                            kNoTriRows);
+            else if (k == 2)
+                NMGP_LAUNCH((k_leaf_step<2, true, 4>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, f0,
+                            xtri > 0 ? f0 + 128 : kNoTriRows);
+            else
+                NMGP_LAUNCH((k_leaf_step<3, false, 6>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, f0,
+                            xtri > 0 ? f0 + 192 : kNoTriRows);
+        }
+    }
+
     // right-looking 64-wide steps (each step updates the rest of the panel with K = 64)
     void panel_rl(int c0, int w) {
         for (int j0 = c0; j0 < c0 + w; j0 += 64) {
@@ -2246,12 +2511,17 @@ struct Factorisation {
     enum Leaf {
         kBlockSolve,     // base = 64: diagonal block + solve
         kFusedSteps,     // pieces of `base` columns run as fused steps
-        kLeaf128         // the throughput schedule, base = 128: 128-column pieces take the two leaf launches (k_panel_step<1>,
-    };                   // <2>), a 64-column remainder the plain diagonal block + solve
+        kLeaf128         // the throughput schedule, base = 128: a 256-column node runs left-looking (leaf256: four launches, no
+    };                   // update between its leaves), any other 128-column piece takes the two leaf launches (k_panel_step<1>,
+                         // <2>), a 64-column remainder the plain diagonal block + solve
     void panel_halving(int c0, int w, int base, Leaf leaf) {
         if (w <= base) {
             if (leaf == kBlockSolve || (leaf == kLeaf128 && w != 128)) block_solve(c0, w);
             else fused_steps(c0, w, leaf == kLeaf128);
+            return;
+        }
+        if (leaf == kLeaf128 && w == 256) {                      // left 128, right 128: no update launch between them
+            leaf256(c0);
             return;
         }
         int h = ((w / 2 + 63) / 64) * 64;                       // left width: a multiple of 64, at least half
@@ -2274,6 +2544,10 @@ struct Factorisation {
     //    of LDS) = three rounds, 72 us, bound by that traffic.  So the panel is halved recursively (one K = w/2 update per level,
     //    ordinary update kernel with the next diagonal block fused) until the pieces are `base` wide, and only those run as
     //    fused steps: base = 128 keeps recursive halving's 768 passes with 11 launches per 512 columns instead of 23.
+    //  * the throughput schedule (kLeaf128) halves down to 256-column nodes.  A node as leaf, K = 128 update, leaf cost 2 + 3 + 6 +
+    //    2 + 3 = 16 passes (one pass = one read or write of a 64-column block of all active rows) in 5 launches; leaf256 runs it
+    //    left-looking in 2 + 3 + 4 + 5 = 14 passes and 4 launches (k_leaf_step): the K = 128 launch, HBM-bound at one tile column,
+    //    is gone.  Nodes of width 192 (left 128, right 64) keep the K = 128 update and the plain block solve.
     void panel(int c0, int w) {
         const Switches& sw = switches();
         // the matrix-core panel kernels: whole 64-column blocks, 16-byte loads, diagonal blocks with inverted 16x16 blocks
@@ -2380,7 +2654,8 @@ void potrf_lower(hipStream_t s, hipStream_t s2, hipEvent_t* ev, double* A, int l
 // (syrk_tile_fast & co.: fresh0; k_panel_step: un_fresh, u_tri).  Everything further left is never touched.
 // reach of the readers left of a row's own 64-column block: update tiles skip leading zero k-panels per 128-row TILE in pairs of
 // 16-column panels (SY_BM + 2 SY_BK - 2 columns left of the diagonal at most), the inverse SYRK starts at the tile's first row
-// (SY_BM - 1), k_panel_step's u_tri = n + extra - 192 assumes exactly three seeded blocks
+// (SY_BM - 1), k_panel_step's u_tri = n + extra - 192 assumes exactly three seeded blocks, k_leaf_step<3>'s catch-up of a row that
+// enters with a node's last block reads the node's first block: three blocks left of the row's own (asserted in the kernel)
 static_assert(SY_BM + 2 * SY_BK - 2 <= 64 * NMGP_XTRI_SEED_BLOCKS, "update tiles of L^-T rows would read left of the seeded band");
 static_assert(NMGP_XTRI_SEED_BLOCKS == 3, "k_panel_step (u_tri) and k_xtri_seed's grid (4 column blocks per row block) assume three seeded blocks");
 __global__ __launch_bounds__(256) void k_xtri_seed(double* __restrict__ A, int lda, int row0, int n, int pad,
