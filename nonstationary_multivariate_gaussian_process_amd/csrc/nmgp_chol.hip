@@ -164,11 +164,19 @@ __device__ __forceinline__ void syrk_fused_first_block(double* lds, const v4d (&
 
 // ---- epilogue of k_syrk_schur (the structured value path's inverse SYRK; the algebra is above k_svc_schur_a in nmgp_kernels.hip) ----
 // The expressions, in their order, of the separate kernel this replaced: bit-identical results under -ffp-contract=off.  After the
-// k-loop's last barrier the operand buffers hold one 32 x 33 patch per wave (-A^-1 on a 32-row half of the wave's sub-tile) and,
-// for M <= 4, a table of the tile's 128 column and 128 row locations: g_c[b] = sigma2 L_c[b,0] / L_c00^2 (b = 1..M-1), 1 / L_c00^2,
-// x_c and ell_c (larger M compute / load them where they are used).  k_syrk_schur's LDS: SY_SCHUR_SMEM doubles (two workgroups per CU).
+// k-loop's last barrier the operand buffers hold one patch per wave and a table of the tile's locations.  Two forms:
+//   * full tiles at M <= 3 (svc_schur_subtile, every tile of the headline): a 64 x 17 patch (-A^-1 on 16 columns of the wave's
+//     sub-tile), one lane per row, one column of Sigma' over 64 rows per store (512-byte runs at a uniform pointer + lane), and a
+//     table of the 128 COLUMN locations that also holds L_c (svc_schur_ctable), read as LDS broadcasts;
+//   * partial tiles and M >= 4 (svc_schur_patch): a 32 x 33 patch (a 32-row half of the sub-tile), 32 lanes x 2 columns per store
+//     (256-byte runs) and, for M <= 4, a table of the 128 column and 128 row locations: g_c[b] = sigma2 L_c[b,0] / L_c00^2
+//     (b = 1..M-1), 1 / L_c00^2, x_c and ell_c (larger M compute / load them where they are used).
+// Per element the FP64 exp, sqrt and two divisions of K_x plus the entries' products are ~125 vector instructions that share the
+// SIMD's FP64 pipe with the MFMAs, in a launch that already moves 35 GB at 4.3 TB/s: the epilogue is cheapest when it runs beside
+// the OTHER workgroup's k-loop (see the tile order of k_syrk_schur in syrk_tile_body; DESIGN Appendix B has the measurements).
+// k_syrk_schur's LDS: SY_SCHUR_SMEM doubles (two workgroups per CU).
 #define SY_SMEM (4 * SY_BK * SY_LD)
-#define SCHUR_PATCH (32 * 33)
+#define SCHUR_PATCH (64 * 17)
 #define SY_SCHUR_SMEM (8 * SCHUR_PATCH + 6 * 256)
 static_assert(SY_SCHUR_SMEM >= SY_SMEM && SY_SCHUR_SMEM * 8 * 2 <= 160 * 1024, "Schur epilogue LDS");
 
@@ -309,6 +317,102 @@ __device__ __forceinline__ void svc_schur_yrow(const SchurEpi& e, int i) {
     const double r = vi - (sigma2 * il2) * e.u[i];
 #pragma unroll
     for (int a = 1; a < M; ++a) e.S[((size_t)(a - 1) * Ns + i) * e.ld + n1] = e.y[(size_t)a * Ns + i] - Li[a * (a + 1) / 2] * r;
+}
+
+// ---- the epilogue of a FULL tile at M <= 3 (syrk_tile_fast): the same entries from the same expressions as svc_schur_patch, in a
+// store shape of one column of Sigma' per instruction ----
+// The tile's 128 column locations: g_c[1..M-1], 1 / L_c00^2, x_c, ell_c as in svc_schur_gtable, then L_c's T entries.  (The row
+// locations are the lanes' own: registers.)  Workgroup-uniform call after the k-loop's last barrier; ends on a barrier.
+constexpr int svc_cstride(int M) { return svc_gstride(M) + M * (M + 1) / 2; }
+static_assert(128 * svc_cstride(3) <= 6 * 256, "column table of the full-tile Schur epilogue");
+
+template <int M>
+__device__ __forceinline__ void svc_schur_ctable(const SchurEpi& e, double* lds, int col0, int tid, double sigma2) {
+    constexpr int T = M * (M + 1) / 2, GS = svc_gstride(M), CS = svc_cstride(M);
+    double* ct = lds + 8 * SCHUR_PATCH;
+    if (tid < 128) {
+        const int loc = col0 + tid;
+        const double* Lc = e.Lv + (size_t)loc * T;
+        const double l00 = Lc[0];
+#pragma unroll
+        for (int b = 1; b < M; ++b) ct[tid * CS + b - 1] = sigma2 * Lc[b * (b + 1) / 2] / (l00 * l00);
+        ct[tid * CS + M - 1] = 1.0 / (l00 * l00);
+        ct[tid * CS + M] = e.x[loc];
+        ct[tid * CS + M + 1] = e.ell[loc];
+#pragma unroll
+        for (int t = 0; t < T; ++t) ct[tid * CS + GS + t] = Lc[t];
+    }
+    __syncthreads();
+}
+
+// One wave's 64 x 32 sub-tile of -A^-1 (acc, the layout of syrk_tile_fast; rows i0.., columns j0.., all inside the matrix), 16
+// columns at a time through its 64 x 17 patch P.  Pass 1, one lane per ROW: column c of the chunk is wave-uniform -- its table
+// entry comes as LDS broadcasts, the lane's own location stays in registers for the whole sub-tile -- and every store instruction
+// writes one column of a Sigma' block over 64 rows, 512 contiguous bytes at a uniform pointer + lane.  At M = 3 the element's
+// mirrored entry (2,j),(1,i) replaces it in P, and pass 2 (16 lanes along j, four columns i per instruction) copies those out.
+template <int M>
+__device__ __forceinline__ void svc_schur_subtile(const SchurEpi& e, double* P, const double* ct, const v4d (&acc)[2][2][2], int i0,
+                                                  int j0, int col0, int lane, double sigma2) {
+    static_assert(M == 2 || M == 3, "larger M: svc_schur_patch");
+    constexpr int T = M * (M + 1) / 2, GS = svc_gstride(M), CS = svc_cstride(M);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const size_t Ns = (size_t)e.N, ld = (size_t)e.ld;
+    const int r = i0 + lane;
+    double Lr[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) Lr[t] = e.Lv[(size_t)r * T + t];
+    const double xr = e.x[r], lr = e.ell[r];
+    const double xr2 = xr * xr, lr2 = lr * lr;
+    const double l00 = Lr[0];
+    const double il2 = 1.0 / (l00 * l00);
+    const double gr1 = sigma2 * Lr[1] / (l00 * l00);            // g_r[1], the table's expression
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int jh = j0 + 16 * h;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int sx = 0; sx < 2; ++sx)
+#pragma unroll
+                for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+                    for (int r2 = 0; r2 < 2; ++r2)
+                        P[(32 * p + 2 * l15 + sx) * 17 + 2 * (l4 + 4 * r2) + tj] = -acc[p][sx][tj][2 * h + r2];
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll 2
+        for (int jl = 0; jl < 16; ++jl) {
+            const int c = jh + jl;
+            if (c > r) continue;
+            const double* cc = ct + (c - col0) * CS;
+            const double* Lc = cc + GS;
+            const double xc = cc[M], lc = cc[M + 1];
+            const double dist = (xr2 + xc * xc) - 2.0 * (xr * xc);
+            const double Aa = lr2 + lc * lc;
+            double kv = sqrt(2.0 * (lr * lc) / Aa) * exp(-dist / Aa);
+            if (r == c) kv = NMGP_JITTER + kv;
+            const double nai = P[lane * 17 + jl];
+            double* colp = e.S + ((size_t)c * ld + (size_t)i0);          // (uniform) column c of block (1, 1), the sub-tile's first row
+#pragma unroll
+            for (int a = 1; a < M; ++a)
+#pragma unroll
+                for (int b = 1; b <= a; ++b)
+                    (colp + ((size_t)(b - 1) * Ns * ld + (size_t)(a - 1) * Ns))[lane] =
+                        svc_schur_value<M>(sigma2, a, b, r == c, Lr, il2, Lc, kv, nai, cc[b - 1]);
+            // the mirrored entry: row location c (its 1 / L_c00^2 from the table), column location r (g_r[1])
+            if (M == 3 && c < r) P[lane * 17 + jl] = svc_schur_value<M>(sigma2, 2, 1, false, Lc, cc[M - 1], Lr, kv, nai, gr1);
+        }
+        if (M == 3) {
+            __builtin_amdgcn_wave_barrier();
+            const int jl = lane & 15, ii = lane >> 4;
+            double* mp = e.S + ((size_t)i0 * ld + Ns + (size_t)jh);      // (uniform) row (2, jh) of column (1, i0)
+#pragma unroll 4
+            for (int q = 0; q < 16; ++q) {
+                const int il = 4 * q + ii;
+                if (i0 + il > jh + jl) (mp + (size_t)(4 * q) * ld)[ii * e.ld + jl] = P[il * 17 + jl];
+            }
+        }
+    }
 }
 
 // SM > 0: k_syrk_schur (M = SM outputs, se = the chain's epilogue arguments): the tile goes into Sigma' instead of C
@@ -473,7 +577,18 @@ __device__ __forceinline__ void syrk_tile_fast(const double* __restrict__ A, int
         __syncthreads();
     }
     if constexpr (SM > 0) {
-        // the k-loop ended on a barrier: each wave moves its sub-tile, 32 rows at a time, through its patch into Sigma'
+        // the k-loop ended on a barrier: each wave moves its sub-tile through its patch into Sigma'
+        if constexpr (SM <= 3) {
+            const double sigma2 = exp(se->tse[0]);
+            svc_schur_ctable<SM>(*se, sA0, col0, tid, sigma2);
+            if (active)
+                svc_schur_subtile<SM>(*se, sA0 + w * SCHUR_PATCH, sA0 + 8 * SCHUR_PATCH, acc,
+                                      __builtin_amdgcn_readfirstlane(row0 + wi * 64), __builtin_amdgcn_readfirstlane(col0 + wj * 32),
+                                      col0, lane, sigma2);
+            if (diag && wj == 0) svc_schur_yrow<SM>(*se, row0 + wi * 64 + lane);
+            return;
+        }
+        // (M >= 4: 32 rows at a time)
         svc_schur_gtable<SM>(*se, sA0, row0, col0, tid);
         if (active) {
             double* P = sA0 + w * SCHUR_PATCH;
@@ -610,6 +725,12 @@ __device__ __forceinline__ void syrk_tile_body(const double* __restrict__ A, int
             bz = (int)(g / tiles_pm);
             if (bz >= nbatch) return;                                        // padding workgroup
             idx = (int)(g - (long long)bz * tiles_pm);
+            // k_syrk_schur: odd chains walk their tile list backwards (shortest tiles first).  Workgroups t and t + 256 share a CU
+            // and would otherwise hold tiles of the same length two chains apart: they leave the k-loop together, and their vector
+            // epilogues run with no k-loop beside them and no epilogue beside the k-loops.  With tiles of different length on a CU
+            // one workgroup's epilogue falls into the other's k-loop: 8.45 -> 8.12 ms at 128 chains of N = 2048 (DESIGN Appendix
+            // B).  The last chains keep longest-first for the launch's tail.  The tiles are independent: same bits in any order.
+            if (SM > 0 && (bz & 1) && bz + 8 < nbatch) idx = tiles_pm - 1 - idx;
         }
         const int gx = (mrows + SY_BM - 1) / SY_BM, gy = (ncols + SY_BM - 1) / SY_BM;
         if (rowmajor) {
