@@ -92,6 +92,28 @@ int nmgp_had_covariance(nmgp_ctx* ctx, const double* pars, double* out);
 int nmgp_predict_had(nmgp_ctx* ctx, const double* pars, const double hyper[8], const double* xs, int S, double* mean, double* var,
                      double* star);
 
+/* A cohort of S Hadamard subjects of RAGGED size per launch sequence.  Every subject is padded to the set's Nmax with decoupled
+ * unit observations (row / column of the identity in the covariance and in both GP-prior covariances, y = 0): the padded part of
+ * every factor is the identity, and log det, the quadratic form, the prior terms and their log-determinants gain exact zeros.
+ *   x, indx, y [S, Nmax] row-major: only the first nobs[s] entries of row s are read (the rest may hold anything).
+ * NMGP_E_SHAPE unless S >= 1, 1 <= M <= 8, 1 <= Nmax <= 3500 (every GP-prior solve of the set is by substitution),
+ * M <= nobs[s] <= Nmax, every real label in [0, M) and every label occurring in every subject.  The set is independent of the
+ * resident subject: it needs none, survives nmgp_set_data / nmgp_had_set_data, carries its own Nmax and M, and no other entry
+ * sees it.  It ends with nmgp_had_clear_subjects, a second nmgp_had_set_subjects, or the context; its per-subject GP-prior factors
+ * (one batched factorisation per (alpha, beta)) are cached with it. */
+int nmgp_had_set_subjects(nmgp_ctx* ctx, const double* x, const int* indx, const double* y, const int* nobs, int S, int Nmax, int M);
+int nmgp_had_clear_subjects(nmgp_ctx* ctx);
+/* B = S * chains_per_subject rows (NMGP_E_SHAPE otherwise); row s * chains_per_subject + k is chain k of subject s.
+ * pars [B, Pmax], Pmax = Nmax (1 + T) + 1, the PADDED layout [tilde_l (Nmax) | L_vecs (Nmax * T) | tilde_sigma2_err]: subject s's
+ * vector of length nobs[s] (1 + T) + 1 occupies the first nobs[s] entries (nobs[s] * T for L_vecs) of each block and the last slot.
+ * Padded slots are never read (a NaN there changes nothing, and the NMGP_NUM_NAN test covers the real slots only); their gradient is
+ * +0.0.  out5 [B, 5], grad [B, Pmax] or NULL and status [B] as for nmgp_had_batch_eval; a status k > 0 is a leading minor inside
+ * the subject's own nobs[s].  Chunks under NMGP_HAD_BATCH_SLAB_GB are whole subjects or parts of one subject's chains; one
+ * synchronisation per chunk; a chain's bits depend neither on the chunking nor on the other subjects of the set.
+ * NMGP_E_STATE without a set, NMGP_E_UNSUPPORTED under NMGP_CHOL=rocsolver. */
+int nmgp_had_subjects_eval(nmgp_ctx* ctx, const double* pars, int B, int chains_per_subject, const double hyper[8], int prior,
+                           double* out5, double* grad, int* status);
+
 /* ---- Hadamard form of the separable model: one cross-output matrix shared by all observations ----
  * logpos.nlogpos_obj_hadamard / logpos_hadamard (logpos.py:465-563), prediction.point_predmap_hadamard / pointwise_predmap_hadmard
  * (prediction.py:710-808).  The subject is the one nmgp_had_set_data made resident (NMGP_E_STATE otherwise).

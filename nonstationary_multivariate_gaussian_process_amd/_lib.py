@@ -85,6 +85,9 @@ SIGNATURES = {
     "nmgp_had_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_had_covariance": (I, [V, P, P]),
     "nmgp_predict_had": (I, [V, P, P, P, I, P, P, P]),
+    "nmgp_had_set_subjects": (I, [V, P, ctypes.POINTER(ctypes.c_int), P, ctypes.POINTER(ctypes.c_int), I, I, I]),
+    "nmgp_had_clear_subjects": (I, [V]),
+    "nmgp_had_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_covariance": (I, [V, P, P]),
     "nmgp_predict_hads": (I, [V, P, P, P, I, P, P, P]),
@@ -185,6 +188,7 @@ class Context:
             raise NmgpError("nmgp_ctx_create(device=%d) -> %d: %s" % (self.device, rc, msg))
         self.N = self.M = self.T = 0
         self._data_key = None
+        self._cohort = None              # (S, Nmax, M) of the Hadamard cohort, while one is set
 
     def close(self):
         if getattr(self, "h", None):
@@ -767,6 +771,82 @@ class Context:
 
     def had_covariance(self, pars):
         return self._had_cov(self.lib.nmgp_had_covariance, pars, self.N * (1 + self.T) + 1, "")
+
+    # -- a cohort of ragged Hadamard subjects (independent of the resident subject) -----------------
+    def had_set_subjects(self, xs, indxs, ys, M=None, Nmax=None):
+        """S Hadamard subjects of ragged size for ``had_subjects_eval``: lists of per-subject arrays ``xs[s]``, ``indxs[s]``,
+        ``ys[s]`` of length ``nobs[s]``.  ``M`` defaults to the number of distinct labels, which must be the same for all subjects;
+        ``Nmax`` (the order every subject is padded to) defaults to ``max(nobs)``.  The set needs no resident subject, survives
+        ``set_data`` / ``had_set_data``, and ends with ``had_clear_subjects``, the next ``had_set_subjects`` or the context."""
+        xs = [as_f64(v).reshape(-1) for v in xs]
+        ys = [as_f64(v).reshape(-1) for v in ys]
+        labs = []
+        for v in indxs:
+            if hasattr(v, "detach"):
+                v = v.detach().cpu().numpy()
+            labs.append(np.asarray(v).reshape(-1).astype(np.int32))
+        S = len(xs)
+        if S < 1 or len(ys) != S or len(labs) != S:
+            raise NmgpError("xs, indxs and ys must be lists of one positive length; got %d, %d, %d" % (S, len(labs), len(ys)))
+        nobs = np.array([v.shape[0] for v in xs], dtype=np.int32)
+        for s in range(S):
+            if not (xs[s].shape == ys[s].shape == labs[s].shape):
+                raise NmgpError("subject %d: x, indx and y must have one length; got x%s indx%s y%s"
+                                % (s, xs[s].shape, labs[s].shape, ys[s].shape))
+        if M is None:
+            counts = sorted({int(np.unique(v).shape[0]) for v in labs})
+            if len(counts) != 1:
+                raise NmgpError("the subjects have different numbers of distinct labels %s: pass M" % counts)
+            M = counts[0]
+        M = int(M)
+        Nmax = int(nobs.max()) if Nmax is None else int(Nmax)
+        if nobs.max() > Nmax:
+            raise NmgpError("a subject has %d observations, more than Nmax = %d" % (int(nobs.max()), Nmax))
+        x2, y2 = np.zeros((S, max(Nmax, 1))), np.zeros((S, max(Nmax, 1)))
+        i2 = np.zeros((S, max(Nmax, 1)), dtype=np.int32)
+        for s in range(S):
+            x2[s, :nobs[s]], y2[s, :nobs[s]], i2[s, :nobs[s]] = xs[s], ys[s], labs[s]
+        self.had_set_subjects_padded(x2, i2, y2, nobs, M)
+
+    def had_set_subjects_padded(self, x, indx, y, nobs, M):
+        """The C entry as it is: x, indx (int32), y [S, Nmax] of which only the first nobs[s] entries of row s are read."""
+        x, y = as_f64(x), as_f64(y)
+        indx = np.ascontiguousarray(np.asarray(indx), dtype=np.int32)
+        nobs = np.ascontiguousarray(np.asarray(nobs).reshape(-1), dtype=np.int32)
+        if x.ndim != 2 or x.shape != y.shape or x.shape != indx.shape or nobs.shape[0] != x.shape[0]:
+            raise NmgpError("x, indx, y must be [S, Nmax] and nobs [S]; got %s, %s, %s, %s" % (x.shape, indx.shape, y.shape, nobs.shape))
+        ip = ctypes.POINTER(ctypes.c_int)
+        # (a refused call leaves the previous set, and the shape recorded for it, in place)
+        self.check(self.lib.nmgp_had_set_subjects(self.h, ptr(x), indx.ctypes.data_as(ip), ptr(y), nobs.ctypes.data_as(ip),
+                                                  x.shape[0], x.shape[1], int(M)))
+        self._cohort = (x.shape[0], x.shape[1], int(M))
+
+    def had_clear_subjects(self):
+        self.check(self.lib.nmgp_had_clear_subjects(self.h))
+        self._cohort = None
+
+    def had_subjects_eval(self, pars, hyper, prior=True, want_grad=False, chains_per_subject=1):
+        """B = S * chains_per_subject chains of the cohort in one launch sequence: pars [B, Pmax = Nmax(1+T)+1] in the padded layout
+        (``hadamard.cohort_pack``), row s * chains_per_subject + k being chain k of subject s -> (out [B, 5], grad [B, Pmax] or None
+        with +0.0 in the padded slots, status [B] as ``had_batch_eval``).  Padded parameter slots are never read."""
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        cohort = getattr(self, "_cohort", None)
+        if cohort is not None:
+            P_ = cohort[1] * (1 + cohort[2] * (cohort[2] + 1) // 2) + 1
+            if pars.ndim != 2 or pars.shape[1] != P_:
+                raise NmgpError("parameters must be [B, Nmax(1+T)+1 = %d], got %s" % (P_, pars.shape))
+        elif pars.ndim != 2:
+            raise NmgpError("parameters must be [B, Pmax], got %s" % (pars.shape,))
+        hyper = as_f64(hyper)
+        B, P_ = pars.shape
+        out = np.empty((B, 5))
+        grad = np.empty((B, P_)) if want_grad else None
+        status = np.zeros(B, dtype=np.int32)
+        self.check(self.lib.nmgp_had_subjects_eval(self.h, ptr(pars), B, int(chains_per_subject), ptr(hyper), int(bool(prior)),
+                                                   ptr(out), ptr(grad), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out, grad, status
 
     def predict_had(self, pars, hyper, xs):
         """(mean [S, M], var [S, M], star [S, 1+T]) of the resident Hadamard subject at the new inputs xs."""

@@ -308,6 +308,7 @@ extern "C" int nmgp_ctx_destroy(nmgp_ctx* c) {
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     free_subject(c);
+    nmgp_had_subjects_free(c);
     for (auto& b : c->scratch)
         if (b.p) hipFree(b.p);
     for (auto& t : c->timers) {

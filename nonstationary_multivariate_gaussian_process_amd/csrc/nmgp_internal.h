@@ -175,6 +175,16 @@ struct nmgp_ctx {
     double* ss_x = nullptr;     // [S, N]
     double* ss_Y = nullptr;     // [S, N, M] row-major (k_sep_prep_b rotates it per chain)
     std::vector<PriorFactor> ss_priors;  // L: [S] x (ld x N), logdet: [S]
+    // Hadamard cohort (nmgp_had_set_subjects, nmgp_hadamard_cohort.hip): hc_S ragged subjects padded to hc_Nmax.  Independent of the
+    // resident subject (N / M / T above are not touched); only nmgp_had_subjects_eval looks at it; nmgp_had_subjects_free drops it
+    // with its prior factors
+    int hc_S = 0, hc_Nmax = 0, hc_M = 0, hc_T = 0;
+    double* hc_x = nullptr;     // [S, Nmax] (zeros in the padded slots)
+    double* hc_y = nullptr;     // [S, Nmax] (zeros in the padded slots)
+    int* hc_indx = nullptr;     // [S, Nmax] (zeros in the padded slots)
+    int* hc_nobs = nullptr;     // [S] device table of the subjects' sizes: every mask comes from it
+    std::vector<int> hc_nobs_h; // the same on the host
+    std::vector<PriorFactor> hc_priors;  // L: [S] x (ld x Nmax) masked RBF + jitter, logdet: [S]
     int last_sep_attempts = 0;  // jitter retries the last separable / stationary evaluation needed (0 = the exact covariance)
     bool last_want_grad = false;
     int last_kind = 0;          // 1 svc
@@ -204,6 +214,7 @@ int nmgp_get_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor** out);
 int nmgp_get_batch_prior(nmgp_ctx* c, const double* xs, int S, std::vector<PriorFactor>& cache, double alpha, double beta,
                          PriorFactor** out);
 void nmgp_sep_subjects_free(nmgp_ctx* c);      // drops the separable subject set (no-op without one)
+void nmgp_had_subjects_free(nmgp_ctx* c);      // drops the Hadamard cohort (no-op without one; nmgp_hadamard_cohort.hip)
 int nmgp_ensure_S(nmgp_ctx* c);
 size_t nmgp_ld(size_t rows);      // leading dimension of a factorisation buffer with `rows` rows
 // Cholesky of the n x n lower triangle (custom gfx950 factorisation or rocSOLVER, per ctx->chol_algo); `extra` rows

@@ -1114,6 +1114,74 @@ class HadamardMAP(_HadamardSubject, LockStepMAP):
         return self._eval(P)
 
 
+class HadamardCohortMAP:
+    """The MAP loop of :class:`HadamardMAP` for a cohort of subjects of RAGGED size: ``subjects`` is a list of ``(x, indx, y)``,
+    ``init_pars`` a list of ``[k, P_s]`` (k = ``chains_per_subject`` restarts of subject s, ``P_s = N_s (1 + T) + 1``).  The subjects
+    are split into buckets of similar size (``hadamard.cohort_buckets(nobs, max_flop_waste)``); every bucket is one subject set
+    (``nmgp_had_set_subjects``, padded to the bucket's largest subject) on a ``Context`` of its own, held for the whole run, and
+    every Adam iteration makes ONE ``nmgp_had_subjects_eval`` per bucket, followed by :class:`LockStepMAP`'s update on the padded
+    rows -- padded slots have zero gradient and therefore never move.  ``ctxs``: one context per bucket (default: new ones)."""
+
+    def __init__(self, subjects, hyper_pars, init_pars, lr=2e-1, chains_per_subject=1, max_flop_waste=0.5, ctxs=None):
+        from . import _lib, hadamard
+        k = int(chains_per_subject)
+        subjects = [(np.ascontiguousarray(x, dtype=np.float64).reshape(-1), np.asarray(indx).reshape(-1).astype(np.int32),
+                     np.ascontiguousarray(y, dtype=np.float64).reshape(-1)) for x, indx, y in subjects]
+        if k < 1 or len(subjects) < 1 or len(init_pars) != len(subjects):
+            raise ValueError("subjects and init_pars must be lists of one positive length, chains_per_subject >= 1")
+        self.nobs = [s[0].shape[0] for s in subjects]
+        Ms = sorted({int(np.unique(s[1]).shape[0]) for s in subjects})
+        if len(Ms) != 1:
+            raise ValueError("the subjects have different numbers of distinct labels: %s" % Ms)
+        self.M, self.k = Ms[0], k
+        self.hyper = np.array([float(hyper_pars[key]) for key in SVC_HYPER_KEYS])
+        self.buckets = hadamard.cohort_buckets(self.nobs, max_flop_waste)
+        if ctxs is not None and len(ctxs) != len(self.buckets):
+            raise ValueError("%d contexts for %d buckets" % (len(ctxs), len(self.buckets)))
+        self._own_ctxs = ctxs is None
+        self.ctxs = list(ctxs) if ctxs is not None else [_lib.Context() for _ in self.buckets]
+        self.maps = []
+        for ctx, idx in zip(self.ctxs, self.buckets):
+            ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=self.M)
+            m = LockStepMAP(hadamard.cohort_pack([init_pars[s] for s in idx], [self.nobs[s] for s in idx], self.M), lr=lr)
+            if m.P.shape[0] != len(idx) * k:
+                raise ValueError("init_pars must hold chains_per_subject = %d vectors per subject" % k)
+            m.value_and_grad = (lambda P, ctx=ctx: ctx.had_subjects_eval(P, self.hyper, True, True, k))
+            self.maps.append(m)
+
+    def close(self):
+        """Drops the sets; closes the contexts this object created itself."""
+        for ctx in self.ctxs:
+            if self._own_ctxs:
+                ctx.close()
+            elif ctx.h:
+                ctx.had_clear_subjects()
+        self.ctxs = []
+
+    def _rows(self, idx):
+        """columns of the caller's [.., S k] order that a bucket's rows fill"""
+        return (np.asarray(idx)[:, None] * self.k + np.arange(self.k)[None, :]).reshape(-1)
+
+    def run(self, N_opt, callback=None):
+        """Returns (list of per-subject pars [k, P_s], target_value_hist [N_opt, S k] = -NegLog per iteration, alive [S k]), rows and
+        columns in the caller's subject order."""
+        from . import hadamard
+        B = len(self.nobs) * self.k
+        hist = np.zeros((N_opt, B))
+        for i in range(N_opt):
+            for m, idx in zip(self.maps, self.buckets):
+                neglog, _ = m.step()
+                hist[i, self._rows(idx)] = -neglog
+            if callback is not None:
+                callback(i, hist[i])
+        pars, alive = [None] * len(self.nobs), np.zeros(B, dtype=bool)
+        for m, idx in zip(self.maps, self.buckets):
+            alive[self._rows(idx)] = m.alive
+            for s, p in zip(idx, hadamard.cohort_unpack(m.P, [self.nobs[s] for s in idx], self.M, self.k)):
+                pars[int(s)] = p
+        return pars, hist, alive
+
+
 class BatchedHMCHadamard(_HadamardSubject, LockStepHMC):
     """B independent HMC chains of the Hadamard nonseparable model of one subject in lock-step: every leapfrog step evaluates
     ``logpos.nlogpos_obj_hadamard_SVC`` and its gradient for all chains with one ``nmgp_had_batch_eval``.  The leapfrog update

@@ -21,7 +21,10 @@ Under this package's OWN names (the reference has none for them, so nothing is i
   ``[S, H, M]``), or one labelled output per held-out pair (``[H]`` / ``[S_test, H]``).  All points of all draws go through ONE
   device call (``nmgp_predsample_had``);
 * ``indexed_predict``: mean and variance of ONE labelled output per held-out input from one parameter vector -- the corrected
-  form of the reference's ``test_predmap_SVC_hadamard``.
+  form of the reference's ``test_predmap_SVC_hadamard``;
+* ``cohort_pack`` / ``cohort_unpack`` / ``cohort_buckets``: host helpers of the cohort entry (``Context.had_set_subjects`` /
+  ``had_subjects_eval``: S subjects of ragged size, padded to one order, S x k chains per launch sequence) -- the padded parameter
+  layout and the grouping of subjects of similar size; ``drivers.HadamardCohortMAP`` is the MAP loop on top of them.
 
 Not provided: ``indexedpoint_predmap_SVC_hadamard`` / ``test_predmap_SVC_hadamard`` themselves (their variance is output 0's for
 every label; INTEGRATION.md says why).  The separable Hadamard model (``nlogpos_obj_hadamard``, ``point_predmap_hadamard``, ...) is
@@ -283,3 +286,79 @@ def indexed_predict(tilde_l, L_vecs, tilde_sigma2_err, x, indx, y, x_test, indx_
         raise RuntimeError("indexed_predict: the covariance is not positive definite or not finite (status %d)" % int(status[0]))
     return (torch.from_numpy(np.ascontiguousarray(mean[0])).type(torch.DoubleTensor),
             torch.from_numpy(np.ascontiguousarray(var[0])).type(torch.DoubleTensor))
+
+
+# ---- a cohort of ragged subjects: the padded parameter layout of nmgp_had_subjects_eval and the host-side bucketing ------------------
+def _cohort_T(M):
+    return int(M) * (int(M) + 1) // 2
+
+
+def cohort_pack(vectors, nobs, M, Nmax=None, fill=0.0):
+    """Reference-layout vectors of S ragged subjects -> the padded layout of ``Context.had_subjects_eval``.  ``vectors[s]`` is
+    ``[k, P_s]`` (or ``[P_s]``: k = 1), ``P_s = nobs[s] (1 + T) + 1``, the same k for every subject; the result is
+    ``[S k, Pmax = Nmax (1 + T) + 1]`` with row ``s k + j`` = vector j of subject s: its ``tilde_l`` in the first ``nobs[s]`` slots of
+    the first block, its ``L_vecs`` in the first ``nobs[s] T`` slots of the second, ``tilde_sigma2_err`` in the last slot, ``fill``
+    in every padded slot (the device never reads those).  Parameters and gradients alike."""
+    nobs = [int(n) for n in nobs]
+    T = _cohort_T(M)
+    Nmax = max(nobs) if Nmax is None else int(Nmax)
+    if len(vectors) != len(nobs) or max(nobs) > Nmax:
+        raise ValueError("%d vectors for %d subjects, or a subject larger than Nmax = %d" % (len(vectors), len(nobs), Nmax))
+    vs = [np.atleast_2d(_np(v)) for v in vectors]
+    k = vs[0].shape[0]
+    out = np.full((len(nobs) * k, Nmax * (1 + T) + 1), float(fill))
+    for s, (v, n) in enumerate(zip(vs, nobs)):
+        if v.shape != (k, n * (1 + T) + 1):
+            raise ValueError("subject %d: expected [%d, nobs (1 + T) + 1 = %d], got %s" % (s, k, n * (1 + T) + 1, v.shape))
+        rows = out[s * k:(s + 1) * k]
+        rows[:, :n] = v[:, :n]
+        rows[:, Nmax:Nmax + n * T] = v[:, n:n + n * T]
+        rows[:, -1] = v[:, -1]
+    return out
+
+
+def cohort_unpack(P, nobs, M, chains_per_subject=1):
+    """The inverse of :func:`cohort_pack`: ``[S k, Pmax]`` -> a list of S arrays ``[k, P_s]`` (copies)."""
+    P = np.atleast_2d(_np(P))
+    nobs = [int(n) for n in nobs]
+    T, k = _cohort_T(M), int(chains_per_subject)
+    Nmax, rem = divmod(P.shape[1] - 1, 1 + T)
+    if rem or P.shape[0] != len(nobs) * k or max(nobs) > Nmax:
+        raise ValueError("P %s does not fit %d subjects x %d chains of at most Nmax (1 + T) + 1 slots, T = %d" % (P.shape, len(nobs), k, T))
+    out = []
+    for s, n in enumerate(nobs):
+        rows = P[s * k:(s + 1) * k]
+        out.append(np.concatenate([rows[:, :n], rows[:, Nmax:Nmax + n * T], rows[:, -1:]], axis=1))
+    return out
+
+
+def cohort_buckets(nobs, max_flop_waste=0.5):
+    """A deterministic partition of ``range(S)`` into sets for ``had_set_subjects``: a set of ``count`` subjects padded to its
+    ``Nmax`` factors ``count * Nmax^3`` where the subjects need ``sum N_s^3``.  Subjects are sorted by size, descending (ties by
+    index); a bucket opens at the largest remaining subject and takes the following ones while
+    ``count * Nmax^3 <= (1 + max_flop_waste) * sum N_s^3`` holds.  ``max_flop_waste = 0`` gives buckets of equal sizes only.
+    Returns a list of index arrays (each in that sorted order).
+
+    The default 0.5 was not chosen from a measurement: fewer, larger batches amortise launch latency, padding costs flop, and where
+    the two balance is unmeasured beyond the two points in the README (16 subjects of 512 .. 1024 observations: one set was faster
+    than these buckets with one chain per subject, the buckets were faster with eight chains and gradients).
+    ``tools/hadamard_cohort_bench.py`` reports one set against these buckets together with the flop ratio
+    ``S Nmax^3 / sum N_s^3``, the figure a default should later be chosen from."""
+    nobs = [int(n) for n in nobs]
+    w = float(max_flop_waste)
+    if w < 0.0 or any(n < 1 for n in nobs):
+        raise ValueError("max_flop_waste must be >= 0 and every nobs positive")
+    order = sorted(range(len(nobs)), key=lambda s: (-nobs[s], s))
+    buckets, cur, nmax3, need = [], [], 0, 0
+    for s in order:
+        n3 = nobs[s] ** 3                              # (Python integers; both sides below are exact in double up to 2^53)
+        if cur and (len(cur) + 1) * nmax3 <= (1.0 + w) * (need + n3):
+            cur.append(s)
+            need += n3
+            continue
+        if cur:
+            buckets.append(np.array(cur, dtype=np.int64))
+        cur, nmax3, need = [s], n3, n3
+    if cur:
+        buckets.append(np.array(cur, dtype=np.int64))
+    return buckets
