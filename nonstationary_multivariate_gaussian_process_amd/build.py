@@ -24,7 +24,8 @@ SOURCES = ["nmgp_kernels.hip", "nmgp_kernels_eig.hip", "nmgp_kernels_sep.hip", "
            "nmgp_predsample.hip", "nmgp_predsample_sep.hip", "nmgp_hadamard.hip", "nmgp_hadamard_sep.hip",
            "nmgp_predsample_hadamard.hip", "nmgp_hadamard_sta.hip", "nmgp_predsample_had.hip", "nmgp_hadamard_cohort.hip"]
 ID_SOURCE = "nmgp_build_id.hip"        # compiled last, with -DNMGP_BUILD_ID="<tree id>"
-HEADERS = [os.path.join(INCLUDE, "nmgp.h"), os.path.join(CSRC, "nmgp_internal.h"), os.path.join(CSRC, "nmgp_hadamard_common.h")]
+HEADERS = [os.path.join(INCLUDE, "nmgp.h"), os.path.join(CSRC, "nmgp_internal.h"), os.path.join(CSRC, "nmgp_hadamard_common.h"),
+           os.path.join(CSRC, "nmgp_predsample_common.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # flags that decide the generated code (part of the build id); the -I paths are added at compile time and are not
 # hashed: the same tree at another absolute path is the same build

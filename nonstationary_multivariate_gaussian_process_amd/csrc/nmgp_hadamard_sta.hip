@@ -9,11 +9,13 @@
 // on every raw L_vec slot, the unnormalised inverse gamma on sigma2_err; none on tilde_sigma.  There is no GP prior: neither the cached
 // prior factors nor the prior stream are touched.  The factorisation with its riding rows, the triangular matrix-vector product, the
 // inverse SYRK and the trace terms are the library's, and the schedule of a batched evaluation is nmgp_hadamard_common.h's, shared
-// with the other two Hadamard models; this file adds the model's kernels, its hooks into that schedule (HadSta) and the predictor.
+// with the other two Hadamard models; this file adds the model's kernels and its hooks into that schedule (HadSta) and into the
+// prediction schedule of nmgp_predsample_common.h (PsHadSt).
 // A draw of the posterior is just another parameter vector (no latent curve to regress), so ONE predictor serves the MAP and a
 // chain of draws.  Layout conventions of the Gibbs kernels: a 64 x 64 tile of observations per 256-thread workgroup, lanes along i,
 // the j side in LDS, blockIdx.z = chain; fixed summation order and no atomics, so B chains in one launch give the bits of B launches.
 #include "nmgp_hadamard_common.h"
+#include "nmgp_predsample_common.h"
 
 #include <algorithm>
 
@@ -319,14 +321,6 @@ int hadst_adjoint(hipStream_t s, const double* x, const int* indx, const double*
     return 0;
 }
 
-int hadst_cross_rows(hipStream_t s, const double* x, const int* indx, const double* pars, long long P, int N, int M, const double* xs,
-                     const int* istar, int s0, int E, double* A, int ld, long long bstride, int R0, int B) {
-    const dim3 grid(N, cdiv(E, 256), B);
-    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadst_cross_rows<MM>), grid, dim3(256), 0, s, x, indx, pars, P, N, xs, istar, s0, E, A, ld,
-                                    bstride, R0));
-    return 0;
-}
-
 // Normal(mean, sd) with Python-number arguments: torch rounds both to float32, squares and takes the logarithm there
 struct NormalF32 {
     double mean, var, log_sd;
@@ -373,6 +367,31 @@ struct HadSta {
     }
 };
 
+// hooks of the stationary model into the shared prediction schedule (nmgp_predsample_common.h): no per-location parameters, so
+// nothing to unpack, no latent regression and no workspace of its own
+struct PsHadSt : PsHadamard {
+    static size_t P(int, int T) { return (size_t)T + 3; }
+    static int star_width(int) { return 0; }
+    template <class Take>
+    static void extras(PsCall&, Take, size_t) {}
+    static int prep(const PsCall&) { return 0; }
+    static int star(const PsCall&) { return 0; }
+    static int build_cov(const PsCall& k) {
+        return hadst_cov_build(k.c->stream, k.c->d_x, k.c->had_indx, k.pars, k.P, k.Sb, k.ld, k.N, k.M, k.Bc, k.bs);
+    }
+    static int cross_rows(const PsCall& k) {
+        const dim3 grid(k.N, cdiv(k.E, 256), k.Bc);
+        NMGP_HADS_SWITCH(k.M, NMGP_LAUNCH((k_hadst_cross_rows<MM>), grid, dim3(256), 0, k.c->stream, k.c->d_x, k.c->had_indx, k.pars, k.P,
+                                          k.N, k.xs, k.is, k.s0, k.E, k.Sb, k.ld, k.bs, k.N + 1));
+        return 0;
+    }
+    static int finish(const PsCall& k) {
+        const long long O = (long long)k.S * k.per;
+        NMGP_LAUNCH(k_hadst_predvar, dim3(cdiv(O, 256), k.Bc), dim3(256), 0, k.c->stream, k.pars, k.P, k.sqs, k.is, k.S, k.M, k.var);
+        return 0;
+    }
+};
+
 }  // namespace
 
 // B chains of the resident Hadamard subject under the stationary model: pars [B, T + 3] -> out5 [B, 5] (the verbose tuples), grad
@@ -392,97 +411,6 @@ extern "C" int nmgp_hadst_covariance(nmgp_ctx* c, const double* pars, double* ou
 // status [H] or NULL as nmgp_hadst_batch_eval reports it; a failing draw has NaN rows and does not fail the call.
 extern "C" int nmgp_predict_hadst(nmgp_ctx* c, const double* pars, int H, const double* xs, const int* indx_star, int S, double* mean,
                                   double* var, int* status) {
-    if (!c) return NMGP_E_NULL;
-    if (!pars || !xs || !mean || !var) return nmgp_fail(c, NMGP_E_NULL, "null argument");
-    if (H <= 0 || S <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "H and S must be positive (H=%d, S=%d)", H, S);
-    NMGP_TRY(require_had(c));
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->N, M = c->M, T = c->T;
-    if (M > 8) return nmgp_fail(c, NMGP_E_UNSUPPORTED, "unsupported number of outputs M=%d", M);
-    const bool indexed = indx_star != nullptr;
-    if (indexed)
-        for (int k = 0; k < S; ++k)
-            if (indx_star[k] < 0 || indx_star[k] >= M)
-                return nmgp_fail(c, NMGP_E_SHAPE, "indx_star[%d] = %d is not an output label in [0, %d)", k, indx_star[k], M);
-    const long long P = (long long)T + 3;
-    hipStream_t s = c->stream;
-    // new inputs per factorisation: at most N riding cross-covariance rows
-    const int smax = indexed ? N : std::max(1, N / M), Sm = std::min(S, smax);
-    const int per = indexed ? 1 : M, Emax = Sm * per;
-    const int ld = (int)nmgp_ld((size_t)N + 1 + Emax);
-    const long long bs = (long long)ld * N;
-    if (bs >= 0x7fffffffLL)
-        return nmgp_fail(c, NMGP_E_SHAPE, "a matrix of order N = %d with %d riding rows exceeds the 2^31 elements the row kernels index",
-                         N, ld - N);
-    const int chunks = (N + 127) / 128;
-    const int B = nmgp_ps_chunk(H, (size_t)(N + 1 + Emax) * ld);
-    const size_t O = (size_t)S * per;
-    // one workspace, carved; its size depends on (N, M, S, B), not on H
-    size_t off = 0;
-    auto take = [&off](size_t nelem) {
-        const size_t o = off;
-        off += (nelem + 15) / 16 * 16;
-        return o;
-    };
-    const size_t o_xs = take(S), o_is = take(indexed ? ((size_t)S + 1) / 2 : 0), o_pars = take((size_t)B * P), o_mean = take(B * O),
-                 o_colsq = take(B * O), o_var = take(B * O), o_part = take((size_t)B * 2 * Emax * chunks),
-                 o_info = take(((size_t)B + 1) / 2), o_S = take((size_t)B * bs);
-    if (c->ps_cap < off) {
-        c->ps_cap = 0;
-        NMGP_TRY(nmgp_dev_alloc(c, &c->ps_buf, off));
-        c->ps_cap = off;
-    } else if (nmgp_poison()) {
-        HIP_TRY(c, hipMemsetAsync(c->ps_buf, 0xFF, off * sizeof(double), s));
-    }
-    double* w = c->ps_buf;
-    double *d_xs = w + o_xs, *d_pars = w + o_pars, *d_mean = w + o_mean, *d_colsq = w + o_colsq, *d_var = w + o_var, *part = w + o_part,
-           *Sb = w + o_S;
-    int* d_is = indexed ? reinterpret_cast<int*>(w + o_is) : nullptr;
-    int* d_info = reinterpret_cast<int*>(w + o_info);
-
-    HIP_TRY(c, hipMemcpyAsync(d_xs, xs, (size_t)S * sizeof(double), hipMemcpyHostToDevice, s));
-    if (indexed) HIP_TRY(c, hipMemcpyAsync(d_is, indx_star, (size_t)S * sizeof(int), hipMemcpyHostToDevice, s));
-    std::vector<int> hinfo(B);
-    for (int h0 = 0; h0 < H; h0 += B) {
-        const int Bc = std::min(B, H - h0);
-        HIP_TRY(c, hipMemcpyAsync(d_pars, pars + (size_t)h0 * P, (size_t)Bc * P * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemsetAsync(d_info, 0, (size_t)Bc * sizeof(int), s));
-        for (int s0 = 0; s0 < S; s0 += smax) {
-            const int Sc = std::min(smax, S - s0), E = Sc * per;
-            int r = hadst_cov_build(s, c->d_x, c->had_indx, d_pars, P, Sb, ld, N, M, Bc, bs);
-            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-            set_row(s, Sb, ld, N, c->had_y, N, Bc, bs, 0);                // y rides along as row N (shared by the draws)
-            NMGP_TRY(hadst_cross_rows(s, c->d_x, c->had_indx, d_pars, P, N, M, d_xs, d_is, s0, E, Sb, ld, bs, N + 1, Bc));
-            // the substitution-based panel kernels, as every batched predictor: their bits do not depend on the schedule the batch
-            // size selects, so H draws in one call give the bits of H single calls
-            nmgp_potrf(c, Sb, ld, N, 1 + E, 0, d_info, Bc, bs, 1, 1);
-            ps_rows_reduce(s, Sb, ld, bs, N, N + 1, N, E, part, Bc, d_mean, d_colsq, (long long)O, (long long)s0 * per);
-        }
-        NMGP_LAUNCH(k_hadst_predvar, dim3(cdiv((long long)O, 256), Bc), dim3(256), 0, s, d_pars, P, d_colsq, d_is, S, M, d_var);
-        double* hm = mean + (size_t)h0 * O;
-        double* hv = var + (size_t)h0 * O;
-        HIP_TRY(c, hipMemcpyAsync(hm, d_mean, Bc * O * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(hv, d_var, Bc * O * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(hinfo.data(), d_info, (size_t)Bc * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        NMGP_TRY(nmgp_take_launch_error(c));
-        for (int b = 0; b < Bc; ++b) {
-            int st = hinfo[b];
-            const double* pb = pars + (size_t)(h0 + b) * P;
-            bool finite_in = true;
-            for (long long k = 0; k < P && finite_in; ++k) finite_in = std::isfinite(pb[k]);
-            if (!finite_in) st = NMGP_NUM_NAN;
-            if (st == 0)
-                for (size_t k = 0; k < O; ++k)
-                    if (!std::isfinite(hm[b * O + k]) || !std::isfinite(hv[b * O + k])) {
-                        st = NMGP_NUM_NAN;
-                        break;
-                    }
-            if (st != 0)
-                for (size_t k = 0; k < O; ++k) hm[b * O + k] = hv[b * O + k] = std::nan("");
-            if (status) status[h0 + b] = st;
-        }
-    }
-    c->last_kind = 0;
-    return 0;
+    return ps_predict<PsHadSt>(c, pars, H, nullptr, xs, indx_star, S, 0, nullptr, nullptr, mean, var, nullptr, status);
 }
+

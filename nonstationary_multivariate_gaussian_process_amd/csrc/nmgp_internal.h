@@ -301,7 +301,7 @@ struct PriorStreamScope {
     }
 };
 
-// ---- pieces shared by the posterior-draw entries (nmgp_predsample.hip, nmgp_predsample_sep.hip) ----
+// ---- pieces shared by the posterior-draw entries; their one host schedule (ps_predict) is in nmgp_predsample_common.h ----
 // W = Sigma_prior^-1 K*(xs) ([S, N] row-major, substitution solve) and the clipped conditional variances cv [S] of one GP prior
 int nmgp_ps_project(nmgp_ctx* c, PriorFactor* pf, const double* d_xs, int S, double* W, double* cv);
 // draws per chunk for factorisation buffers of `per_draw_doubles` per draw (NMGP_PREDSAMPLE_SLAB_GB / NMGP_PREDSAMPLE_CHUNK)
@@ -318,7 +318,8 @@ enum { HSL_SMALL = 13, HSL_SLAB = 14, HSL_PRED = 15 };
 // NMGP_E_STATE unless a Hadamard subject is resident, NMGP_E_UNSUPPORTED off the custom factorisation (riding rows); every entry
 // of the three models calls it (defined in nmgp_hadamard.hip, as the next two)
 int require_had(nmgp_ctx* c);
-// the two cached prior factors of hyper[1..2] and hyper[4..5] (the two models with GP priors: nonseparable and separable)
+// the two cached prior factors of hyper[1..2] and hyper[4..5], the first re-resolved after the second look-up (which may grow the
+// cache); every model with GP priors lays its hyper out so, and the evaluations and ps_predict all resolve them here
 int had_priors(nmgp_ctx* c, const double* hyper, PriorFactor** p0, PriorFactor** p1);
 // op(L) X = R for the 1 + T prior columns of every chain (column 0 against p0, the others against p1)
 int had_prior_solve(nmgp_ctx* c, hipStream_t sp, rocblas_handle hb, bool trans, PriorFactor* p0, PriorFactor* p1, double* R, int N,

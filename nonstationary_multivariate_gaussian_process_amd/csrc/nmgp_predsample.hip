@@ -11,7 +11,7 @@
 // Every kernel below is per-draw independent with a fixed summation order: a batch of B draws gives the bits of B single calls.
 #include <algorithm>
 
-#include "nmgp_internal.h"
+#include "nmgp_predsample_common.h"
 
 using namespace nmgpk;
 
@@ -232,118 +232,73 @@ int nmgp_ps_chunk(int H, size_t per_draw_doubles) {
     return std::max(1, std::min(B, std::min(H, 65535)));
 }
 
+namespace {
+
+// hooks of the nonseparable model into the shared schedule (nmgp_predsample_common.h); one matrix of order n = N M per draw, M riding
+// rows per new input; flags = constrained
+struct PsSvc {
+    static size_t P(int N, int T) { return (size_t)N * (1 + T) + 1; }
+    static int star_width(int T) { return 1 + T; }
+    static int order(int N, int M) { return N * M; }
+    static int mats(int) { return 1; }
+    static int rows(int M, bool) { return M; }
+    static int smax(int N, int, bool) { return N; }      // up to n riding cross-covariance rows (x_test = x is one slice)
+    // the panel kernels of the evaluations: what this entry has run since it exists and what its golden files were checked against
+    static constexpr int PRECISE = 0;
+    static constexpr bool NAN_PARS = false;              // a NaN parameter is reported as the pivot that met it
+    // the call leaves batched evaluations and a begun trajectory alone
+    static constexpr bool RESETS_KIND = false;
+    static int require(nmgp_ctx* c) {
+        if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
+        if (c->chol_algo != 1)
+            return nmgp_fail(c, NMGP_E_UNSUPPORTED, "posterior-draw prediction runs on the custom factorisation only (riding rows)");
+        return 0;
+    }
+    static int size_guard(const PsCall&) { return 0; }   // none: this entry has never had one
+    static size_t chunk_doubles(const PsCall& k) { return (size_t)k.bs; }
+    static const double* y_rows(const PsCall& k, long long& stride) {
+        stride = 0;                  // shared by the draws
+        return k.c->d_y;
+    }
+    template <class Take>
+    static void extras(PsCall& k, Take take, size_t B) {
+        k.o_ell = take(B * k.N);
+        k.o_Lv = take(B * k.N * k.T);
+    }
+    static void host_prep(PsCall&) {}
+    static int prep(const PsCall& k) {
+        svc_prep(k.c->stream, k.pars, k.N, k.M, k.at(k.o_ell), k.at(k.o_Lv), k.Bc);
+        return 0;
+    }
+    static int star(const PsCall& k) {
+        hipStream_t s = k.c->stream;
+        // k_ps_star takes ONE cv [2, S]; where the two prior factors coincide the schedule fills its first half only
+        if (k.cv1 == k.cv0)
+            NMGP_LAUNCH(k_ps_condvar, dim3(k.S), dim3(256), 0, s, k.W1, k.c->d_x, k.N, k.xs, k.hyper[4], k.hyper[5], k.cv0 + k.S);
+        NMGP_LAUNCH(k_ps_star, dim3(k.S, 1 + k.T, k.Bc), dim3(256), 0, s, k.W0, k.W1, k.cv0, k.pars, k.at(k.o_Lv), k.z, k.N, k.M, k.T,
+                    k.S, k.hyper[0], k.hyper[3], k.flags ? 1 : 0, k.star);
+        return 0;
+    }
+    static int build_cov(const PsCall& k) {
+        return svc_cov_build(k.c->stream, k.c->d_x, k.at(k.o_ell), k.at(k.o_Lv), k.pars + (k.P - 1), k.Sb, k.ld, k.N, k.M, false, k.Bc,
+                             k.bs, 0, 1);
+    }
+    static int cross_rows(const PsCall& k) {
+        NMGP_LAUNCH(k_ps_crosscov_rows, dim3(k.N, cdiv(k.E, 256), k.Bc), dim3(256), 0, k.c->stream, k.c->d_x, k.at(k.o_ell),
+                    k.at(k.o_Lv), k.N, k.M, k.T, k.xs, k.star, k.S, k.s0, k.Sc, k.Sb, k.ld, k.bs, k.n + 1);
+        return 0;
+    }
+    static int finish(const PsCall& k) {
+        NMGP_LAUNCH(k_ps_predvar, dim3(cdiv((long long)k.S * k.M, 256), k.Bc), dim3(256), 0, k.c->stream, k.star, k.sqs, k.S, k.M, k.T,
+                    k.pars, k.P, k.var);
+        return 0;
+    }
+};
+
+}  // namespace
+
 extern "C" int nmgp_predsample_svc(nmgp_ctx* c, const double* pars, int H, const double hyper[8], const double* xs, int S,
                                    int constrained, const double* z, const double* star_in, double* mean, double* var,
                                    double* star_out, int* status) {
-    if (!c) return NMGP_E_NULL;
-    if (!pars || !hyper || !xs || !mean || !var) return nmgp_fail(c, NMGP_E_NULL, "null argument");
-    if (H <= 0 || S <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "H and S must be positive (H=%d, S=%d)", H, S);
-    if (z && star_in) return nmgp_fail(c, NMGP_E_STATE, "with star_in given the regression is skipped: z must be NULL");
-    if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
-    if (c->chol_algo != 1)
-        return nmgp_fail(c, NMGP_E_UNSUPPORTED, "posterior-draw prediction runs on the custom factorisation only (riding rows)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->N, M = c->M, T = c->T, n = c->n;
-    const long long P = c->P_svc;
-    hipStream_t s = c->stream;
-    const double mu_l = hyper[0], al_l = hyper[1], be_l = hyper[2], mu_L = hyper[3], al_L = hyper[4], be_L = hyper[5];
-    // grid points per factorisation: up to n riding cross-covariance rows (x_test = x is one slice)
-    const int smax = std::max(1, n / M), Sm = std::min(S, smax), Emax = Sm * M;
-    const int ld = (int)nmgp_ld((size_t)n + 1 + Emax);
-    const long long bs = (long long)ld * n;
-    const int chunks = (n + 127) / 128;
-    const int B = nmgp_ps_chunk(H, (size_t)bs);
-    const size_t SC = (size_t)S * (1 + T), SMo = (size_t)S * M;
-
-    // one workspace, carved; its size depends on (N, M, S, B), not on H
-    const bool regress = star_in == nullptr;
-    PriorFactor *pl = nullptr, *pL = nullptr;
-    if (regress) {
-        // (the factor cache is a vector: the second look-up may grow it and move its elements, so the first pointer is re-resolved)
-        NMGP_TRY(nmgp_get_prior(c, al_l, be_l, &pl));
-        NMGP_TRY(nmgp_get_prior(c, al_L, be_L, &pL));
-        NMGP_TRY(nmgp_get_prior(c, al_l, be_l, &pl));
-    }
-    const bool same = pl == pL;
-    size_t off = 0;
-    auto take = [&off](size_t nelem) {
-        const size_t o = off;
-        off += (nelem + 15) / 16 * 16;
-        return o;
-    };
-    const size_t o_xs = take(S), o_W0 = take(regress ? (size_t)N * S : 0), o_W1 = take(regress && !same ? (size_t)N * S : 0),
-                 o_cv = take(2 * (size_t)S), o_pars = take((size_t)B * P), o_ell = take((size_t)B * N),
-                 o_Lv = take((size_t)B * N * T), o_star = take(B * SC), o_z = take(z ? B * SC : 0), o_mean = take(B * SMo),
-                 o_colsq = take(B * SMo), o_var = take(B * SMo), o_part = take((size_t)B * 2 * Emax * chunks),
-                 o_info = take(((size_t)B + 1) / 2), o_S = take((size_t)B * bs);
-    if (c->ps_cap < off) {
-        c->ps_cap = 0;
-        NMGP_TRY(nmgp_dev_alloc(c, &c->ps_buf, off));
-        c->ps_cap = off;
-    } else if (nmgp_poison()) {
-        HIP_TRY(c, hipMemsetAsync(c->ps_buf, 0xFF, off * sizeof(double), s));
-    }
-    double* w = c->ps_buf;
-    double *d_xs = w + o_xs, *W0 = w + o_W0, *W1 = same ? W0 : w + o_W1, *cv = w + o_cv, *d_pars = w + o_pars, *d_ell = w + o_ell,
-           *d_Lv = w + o_Lv, *d_star = w + o_star, *d_z = z ? w + o_z : nullptr, *d_mean = w + o_mean, *d_colsq = w + o_colsq,
-           *d_var = w + o_var, *part = w + o_part, *Sb = w + o_S;
-    int* d_info = reinterpret_cast<int*>(w + o_info);
-
-    HIP_TRY(c, hipMemcpyAsync(d_xs, xs, (size_t)S * sizeof(double), hipMemcpyHostToDevice, s));
-    if (regress) {
-        NMGP_TRY(project_rows(c, pl, d_xs, S, W0));
-        NMGP_LAUNCH(k_ps_condvar, dim3(S), dim3(256), 0, s, W0, c->d_x, N, d_xs, al_l, be_l, cv);
-        if (!same) NMGP_TRY(project_rows(c, pL, d_xs, S, W1));
-        NMGP_LAUNCH(k_ps_condvar, dim3(S), dim3(256), 0, s, W1, c->d_x, N, d_xs, al_L, be_L, cv + S);
-    }
-    std::vector<int> hinfo(B);
-    for (int h0 = 0; h0 < H; h0 += B) {
-        const int Bc = std::min(B, H - h0);
-        HIP_TRY(c, hipMemcpyAsync(d_pars, pars + (size_t)h0 * P, (size_t)Bc * P * sizeof(double), hipMemcpyHostToDevice, s));
-        svc_prep(s, d_pars, N, M, d_ell, d_Lv, Bc);
-        if (regress) {
-            if (z) HIP_TRY(c, hipMemcpyAsync(d_z, z + (size_t)h0 * SC, Bc * SC * sizeof(double), hipMemcpyHostToDevice, s));
-            NMGP_LAUNCH(k_ps_star, dim3(S, 1 + T, Bc), dim3(256), 0, s, W0, W1, cv, d_pars, d_Lv, d_z, N, M, T, S, mu_l, mu_L,
-                        constrained ? 1 : 0, d_star);
-        } else {
-            HIP_TRY(c, hipMemcpyAsync(d_star, star_in + (size_t)h0 * SC, Bc * SC * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-        HIP_TRY(c, hipMemsetAsync(d_info, 0, (size_t)Bc * sizeof(int), s));
-        for (int s0 = 0; s0 < S; s0 += smax) {
-            const int Sc = std::min(smax, S - s0), E = Sc * M;
-            int r = svc_cov_build(s, c->d_x, d_ell, d_Lv, d_pars + (P - 1), Sb, ld, N, M, false, Bc, bs, 0, 1);
-            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-            set_row(s, Sb, ld, n, c->d_y, n, Bc, bs, 0, 1);
-            NMGP_LAUNCH(k_ps_crosscov_rows, dim3(N, cdiv(E, 256), Bc), dim3(256), 0, s, c->d_x, d_ell, d_Lv, N, M, T, d_xs, d_star,
-                        S, s0, Sc, Sb, ld, bs, n + 1);
-            nmgp_potrf(c, Sb, ld, n, 1 + E, 0, d_info, Bc, bs, 1);
-            NMGP_LAUNCH(k_ps_rows_part, dim3(cdiv(E, 64), chunks, Bc), dim3(256), 0, s, Sb, ld, bs, n, n + 1, n, E, part);
-            NMGP_LAUNCH(k_ps_rows_sum, dim3(cdiv(E, 256), Bc), dim3(256), 0, s, part, chunks, E, d_mean, d_colsq, (long long)SMo,
-                        (long long)s0 * M);
-        }
-        NMGP_LAUNCH(k_ps_predvar, dim3(cdiv((long long)SMo, 256), Bc), dim3(256), 0, s, d_star, d_colsq, S, M, T, d_pars, P, d_var);
-        double* hm = mean + (size_t)h0 * SMo;
-        double* hv = var + (size_t)h0 * SMo;
-        HIP_TRY(c, hipMemcpyAsync(hm, d_mean, Bc * SMo * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(hv, d_var, Bc * SMo * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (star_out)
-            HIP_TRY(c, hipMemcpyAsync(star_out + (size_t)h0 * SC, d_star, Bc * SC * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(hinfo.data(), d_info, (size_t)Bc * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        NMGP_TRY(nmgp_take_launch_error(c));
-        // per-draw status as nmgp_svc_batch_fetch reports it: a failing draw yields NaN rows, not a failed call
-        for (int b = 0; b < Bc; ++b) {
-            int st = hinfo[b];
-            if (st == 0)
-                for (size_t k = 0; k < SMo; ++k)
-                    if (!std::isfinite(hm[b * SMo + k]) || !std::isfinite(hv[b * SMo + k])) {
-                        st = NMGP_NUM_NAN;
-                        break;
-                    }
-            if (st != 0)
-                for (size_t k = 0; k < SMo; ++k) hm[b * SMo + k] = hv[b * SMo + k] = std::nan("");
-            if (status) status[h0 + b] = st;
-        }
-    }
-    return 0;
+    return ps_predict<PsSvc>(c, pars, H, hyper, xs, nullptr, S, constrained, z, star_in, mean, var, star_out, status);
 }

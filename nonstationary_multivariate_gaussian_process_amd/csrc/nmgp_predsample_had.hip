@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "nmgp_hadamard_common.h"
+#include "nmgp_predsample_common.h"
 
 using namespace nmgpk;
 
@@ -94,142 +95,47 @@ __global__ __launch_bounds__(256) void k_psn_predvar(const double* __restrict__ 
     var[(size_t)h * O + k] = v;
 }
 
-int psn_cross_rows(hipStream_t s, const double* x, const double* ell, const double* Rv, int N, int M, const double* xs,
-                   const double* star, const int* istar, int S, int s0, int E, double* A, int ld, long long bstride, int R0, int B) {
-    const dim3 grid(N, cdiv(E, 256), B);
-    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_psn_cross_rows<MM>), grid, dim3(256), 0, s, x, ell, Rv, N, xs, star, istar, S, s0, E, A, ld,
-                                    bstride, R0));
-    return 0;
-}
+// hooks of the nonseparable Hadamard model into the shared schedule (nmgp_predsample_common.h)
+struct PsHad : PsHadamard {
+    static size_t P(int N, int T) { return (size_t)N * (1 + T) + 1; }
+    static int star_width(int T) { return 1 + T; }
+    template <class Take>
+    static void extras(PsCall& k, Take take, size_t B) {
+        k.o_ell = take(B * k.N);
+        k.o_Rv = take(B * k.N * k.M);
+    }
+    static int prep(const PsCall& k) {
+        had_prep(k.c->stream, k.pars, k.c->had_indx, k.N, k.M, k.at(k.o_ell), k.at(k.o_Rv), k.Bc);
+        return 0;
+    }
+    static int star(const PsCall& k) {
+        NMGP_LAUNCH(k_psn_star, dim3(k.S, 1 + k.T, k.Bc), dim3(256), 0, k.c->stream, k.W0, k.W1, k.cv0, k.cv1, k.pars, k.P, k.z, k.N, k.T,
+                    k.S, k.hyper[0], k.hyper[3], k.star);
+        return 0;
+    }
+    static int build_cov(const PsCall& k) {
+        return gibbs_cov_build<false>(k.c->stream, k.c->d_x, k.at(k.o_ell), nullptr, k.at(k.o_Rv), k.pars, k.P, k.Sb, k.ld, k.N, k.M, k.Bc,
+                                      k.bs);
+    }
+    static int cross_rows(const PsCall& k) {
+        const dim3 grid(k.N, cdiv(k.E, 256), k.Bc);
+        NMGP_HADS_SWITCH(k.M, NMGP_LAUNCH((k_psn_cross_rows<MM>), grid, dim3(256), 0, k.c->stream, k.c->d_x, k.at(k.o_ell), k.at(k.o_Rv),
+                                          k.N, k.xs, k.star, k.is, k.S, k.s0, k.E, k.Sb, k.ld, k.bs, k.N + 1));
+        return 0;
+    }
+    static int finish(const PsCall& k) {
+        const long long O = (long long)k.S * k.per;
+        NMGP_LAUNCH(k_psn_predvar, dim3(cdiv(O, 256), k.Bc), dim3(256), 0, k.c->stream, k.star, k.pars, k.P, k.sqs, k.is, k.S, k.M, k.T,
+                    k.var);
+        return 0;
+    }
+};
 
 }  // namespace
 
 extern "C" int nmgp_predsample_had(nmgp_ctx* c, const double* pars, int H, const double hyper[8], const double* xs,
                                    const int* indx_star, int S, const double* z, const double* star_in, double* mean, double* var,
                                    double* star_out, int* status) {
-    if (!c) return NMGP_E_NULL;
-    if (!pars || !hyper || !xs || !mean || !var) return nmgp_fail(c, NMGP_E_NULL, "null argument");
-    if (H <= 0 || S <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "H and S must be positive (H=%d, S=%d)", H, S);
-    if (z && star_in) return nmgp_fail(c, NMGP_E_STATE, "with star_in given the regression is skipped: z must be NULL");
-    NMGP_TRY(require_had(c));
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->N, M = c->M, T = c->T;
-    if (M > 8) return nmgp_fail(c, NMGP_E_UNSUPPORTED, "unsupported number of outputs M=%d", M);
-    const bool indexed = indx_star != nullptr;
-    if (indexed)
-        for (int k = 0; k < S; ++k)
-            if (indx_star[k] < 0 || indx_star[k] >= M)
-                return nmgp_fail(c, NMGP_E_SHAPE, "indx_star[%d] = %d is not an output label in [0, %d)", k, indx_star[k], M);
-    const long long P = (long long)N * (1 + T) + 1;
-    hipStream_t s = c->stream;
-    // grid points per factorisation: at most N riding cross-covariance rows (nmgp_predict_had's slices in the full form)
-    const int smax = indexed ? N : std::max(1, N / M), Sm = std::min(S, smax);
-    const int per = indexed ? 1 : M, Emax = Sm * per;
-    const int ld = (int)nmgp_ld((size_t)N + 1 + Emax);
-    const long long bs = (long long)ld * N;
-    if (bs >= 0x7fffffffLL)
-        return nmgp_fail(c, NMGP_E_SHAPE, "a matrix of order N = %d with %d riding rows exceeds the 2^31 elements the row kernels index",
-                         N, ld - N);
-    const int chunks = (N + 127) / 128;
-    const int B = nmgp_ps_chunk(H, (size_t)(N + 1 + Emax) * ld);
-    const size_t SW = (size_t)S * (1 + T), O = (size_t)S * per;
-
-    const bool regress = star_in == nullptr;
-    PriorFactor *pl = nullptr, *pL = nullptr;
-    if (regress) NMGP_TRY(had_priors(c, hyper, &pl, &pL));
-    const bool same = pl == pL;
-    // one workspace, carved; its size depends on (N, M, S, B), not on H
-    size_t off = 0;
-    auto take = [&off](size_t nelem) {
-        const size_t o = off;
-        off += (nelem + 15) / 16 * 16;
-        return o;
-    };
-    const size_t o_xs = take(S), o_is = take(indexed ? ((size_t)S + 1) / 2 : 0), o_W0 = take(regress ? (size_t)N * S : 0),
-                 o_W1 = take(regress && !same ? (size_t)N * S : 0), o_cv = take(regress ? (size_t)2 * S : 0),
-                 o_pars = take((size_t)B * P), o_ell = take((size_t)B * N), o_Rv = take((size_t)B * N * M), o_star = take(B * SW),
-                 o_z = take(z ? B * SW : 0), o_mean = take(B * O), o_colsq = take(B * O), o_var = take(B * O),
-                 o_part = take((size_t)B * 2 * Emax * chunks), o_info = take(((size_t)B + 1) / 2), o_S = take((size_t)B * bs);
-    if (c->ps_cap < off) {
-        c->ps_cap = 0;
-        NMGP_TRY(nmgp_dev_alloc(c, &c->ps_buf, off));
-        c->ps_cap = off;
-    } else if (nmgp_poison()) {
-        HIP_TRY(c, hipMemsetAsync(c->ps_buf, 0xFF, off * sizeof(double), s));
-    }
-    double* w = c->ps_buf;
-    double *d_xs = w + o_xs, *W0 = w + o_W0, *W1 = same ? W0 : w + o_W1, *cv0 = w + o_cv, *cv1 = same ? cv0 : cv0 + S,
-           *d_pars = w + o_pars, *d_ell = w + o_ell, *d_Rv = w + o_Rv, *d_star = w + o_star, *d_z = z ? w + o_z : nullptr,
-           *d_mean = w + o_mean, *d_colsq = w + o_colsq, *d_var = w + o_var, *part = w + o_part, *Sb = w + o_S;
-    int* d_is = indexed ? reinterpret_cast<int*>(w + o_is) : nullptr;
-    int* d_info = reinterpret_cast<int*>(w + o_info);
-
-    HIP_TRY(c, hipMemcpyAsync(d_xs, xs, (size_t)S * sizeof(double), hipMemcpyHostToDevice, s));
-    if (indexed) HIP_TRY(c, hipMemcpyAsync(d_is, indx_star, (size_t)S * sizeof(int), hipMemcpyHostToDevice, s));
-    if (regress) {   // once per call per distinct prior factor, not per draw
-        NmgpStage sp(c, NMGP_STAGE_PRIOR);
-        NMGP_TRY(nmgp_ps_project(c, pl, d_xs, S, W0, cv0));
-        if (!same) NMGP_TRY(nmgp_ps_project(c, pL, d_xs, S, W1, cv1));
-    }
-    std::vector<int> hinfo(B);
-    for (int h0 = 0; h0 < H; h0 += B) {
-        const int Bc = std::min(B, H - h0);
-        HIP_TRY(c, hipMemcpyAsync(d_pars, pars + (size_t)h0 * P, (size_t)Bc * P * sizeof(double), hipMemcpyHostToDevice, s));
-        had_prep(s, d_pars, c->had_indx, N, M, d_ell, d_Rv, Bc);
-        if (regress) {
-            if (z) HIP_TRY(c, hipMemcpyAsync(d_z, z + (size_t)h0 * SW, Bc * SW * sizeof(double), hipMemcpyHostToDevice, s));
-            NmgpStage sp(c, NMGP_STAGE_PRIOR);
-            NMGP_LAUNCH(k_psn_star, dim3(S, 1 + T, Bc), dim3(256), 0, s, W0, W1, cv0, cv1, d_pars, P, d_z, N, T, S, hyper[0], hyper[3],
-                        d_star);
-        } else {
-            HIP_TRY(c, hipMemcpyAsync(d_star, star_in + (size_t)h0 * SW, Bc * SW * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-        HIP_TRY(c, hipMemsetAsync(d_info, 0, (size_t)Bc * sizeof(int), s));
-        for (int s0 = 0; s0 < S; s0 += smax) {
-            const int Sc = std::min(smax, S - s0), E = Sc * per;
-            {
-                NmgpStage sp(c, NMGP_STAGE_COV);
-                int r = gibbs_cov_build<false>(s, c->d_x, d_ell, nullptr, d_Rv, d_pars, P, Sb, ld, N, M, Bc, bs);
-                if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-                set_row(s, Sb, ld, N, c->had_y, N, Bc, bs, 0);            // y rides along as row N (shared by the draws)
-                NMGP_TRY(psn_cross_rows(s, c->d_x, d_ell, d_Rv, N, M, d_xs, d_star, d_is, S, s0, E, Sb, ld, bs, N + 1, Bc));
-            }
-            {
-                NmgpStage sp(c, NMGP_STAGE_CHOL);
-                nmgp_potrf(c, Sb, ld, N, 1 + E, 0, d_info, Bc, bs, 1, 1);
-            }
-            NmgpStage sp(c, NMGP_STAGE_REDUCE);
-            ps_rows_reduce(s, Sb, ld, bs, N, N + 1, N, E, part, Bc, d_mean, d_colsq, (long long)O, (long long)s0 * per);
-        }
-        NMGP_LAUNCH(k_psn_predvar, dim3(cdiv((long long)O, 256), Bc), dim3(256), 0, s, d_star, d_pars, P, d_colsq, d_is, S, M, T,
-                    d_var);
-        double* hm = mean + (size_t)h0 * O;
-        double* hv = var + (size_t)h0 * O;
-        HIP_TRY(c, hipMemcpyAsync(hm, d_mean, Bc * O * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(hv, d_var, Bc * O * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (star_out) HIP_TRY(c, hipMemcpyAsync(star_out + (size_t)h0 * SW, d_star, Bc * SW * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(hinfo.data(), d_info, (size_t)Bc * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));          // the one synchronisation of the chunk
-        NMGP_TRY(nmgp_take_launch_error(c));
-        // per-draw status as nmgp_predsample_hads reports it: a failing draw yields NaN rows, not a failed call; a parameter vector
-        // that is not finite has no leading minor to blame
-        for (int b = 0; b < Bc; ++b) {
-            int st = hinfo[b];
-            const double* pb = pars + (size_t)(h0 + b) * P;
-            bool finite_in = true;
-            for (long long k = 0; k < P && finite_in; ++k) finite_in = std::isfinite(pb[k]);
-            if (!finite_in) st = NMGP_NUM_NAN;
-            if (st == 0)
-                for (size_t k = 0; k < O; ++k)
-                    if (!std::isfinite(hm[b * O + k]) || !std::isfinite(hv[b * O + k])) {
-                        st = NMGP_NUM_NAN;
-                        break;
-                    }
-            if (st != 0)
-                for (size_t k = 0; k < O; ++k) hm[b * O + k] = hv[b * O + k] = std::nan("");
-            if (status) status[h0 + b] = st;
-        }
-    }
-    c->last_kind = 0;
-    return 0;
+    return ps_predict<PsHad>(c, pars, H, hyper, xs, indx_star, S, 0, z, star_in, mean, var, star_out, status);
 }
+

@@ -13,7 +13,7 @@
 // Every kernel below is per-draw independent with a fixed summation order: a batch of B draws gives the bits of B single calls.
 #include <algorithm>
 
-#include "nmgp_internal.h"
+#include "nmgp_predsample_common.h"
 
 using namespace nmgpk;
 
@@ -157,159 +157,113 @@ namespace {
 
 inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
-// both entries: stationary = the model without per-location parameters and without a latent regression
-int predsample_kron(nmgp_ctx* c, bool stationary, const double* pars, int H, const double* hyper, const double* xs, int S,
-                    int kss_jitter, const double* z, const double* star_in, double* mean, double* var, double* star_out,
-                    int* status) {
-    if (!pars || !xs || !mean || !var || (!stationary && !hyper)) return nmgp_fail(c, NMGP_E_NULL, "null argument");
-    if (H <= 0 || S <= 0) return nmgp_fail(c, NMGP_E_SHAPE, "H and S must be positive (H=%d, S=%d)", H, S);
-    if (z && star_in) return nmgp_fail(c, NMGP_E_STATE, "with star_in given the regression is skipped: z must be NULL");
-    if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
-    if (c->chol_algo != 1 || c->sep_algo != 1)
-        return nmgp_fail(c, NMGP_E_UNSUPPORTED, "posterior-draw prediction runs on the custom factorisation of the M blocks only "
-                                                "(riding rows): not under NMGP_CHOL=rocsolver or NMGP_SEP=eig");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->N, M = c->M, T = c->T;
-    const long long P = stationary ? T + 3 : 2LL * N + T + 1;
-    hipStream_t s = c->stream;
-    // grid points per factorisation: up to N - 2 riding cross-covariance rows besides the data row (as chol_predict)
-    const int smax = std::max(1, N - 2), Sm = std::min(S, smax);
-    const int ld = (int)nmgp_ld((size_t)N + 1 + Sm);
-    const long long bs = (long long)ld * N;
-    // (sep_blocks_b addresses a block with 32-bit byte offsets)
-    if (8LL * ld * N >= 0x7fffffffLL)
-        return nmgp_fail(c, NMGP_E_SHAPE, "a block of order N = %d with %d riding rows exceeds the 2 GiB the block build addresses", N,
-                         ld - N);
-    const int chunks = (N + 127) / 128;
-    const int B = nmgp_ps_chunk(H, (size_t)M * bs);
-    const int sp = pss_small_per(M);
-    const size_t S2 = (size_t)S * 2, SMo = (size_t)S * M;
-
-    const bool regress = !stationary && star_in == nullptr;
-    PriorFactor *pl = nullptr, *pg = nullptr;
-    if (regress) {
-        // (the factor cache is a vector: the second look-up may grow it and move its elements, so the first pointer is re-resolved)
-        NMGP_TRY(nmgp_get_prior(c, hyper[1], hyper[2], &pl));
-        NMGP_TRY(nmgp_get_prior(c, hyper[4], hyper[5], &pg));
-        NMGP_TRY(nmgp_get_prior(c, hyper[1], hyper[2], &pl));
+// hooks of the two Kronecker models into the shared schedule (nmgp_predsample_common.h): M matrices of order N per draw, one riding
+// row per new input below every one of them.  stationary = the model without per-location parameters and without a latent
+// regression; flags = kss_jitter (separable only)
+template <bool stationary>
+struct PsKron {
+    static size_t P(int N, int T) { return stationary ? (size_t)T + 3 : 2 * (size_t)N + T + 1; }
+    static int star_width(int) { return stationary ? 0 : 2; }
+    static int order(int N, int) { return N; }
+    static int mats(int M) { return M; }
+    static int rows(int, bool) { return 1; }
+    // up to N - 2 riding cross-covariance rows besides the data row (as chol_predict)
+    static int smax(int N, int, bool) { return std::max(1, N - 2); }
+    static constexpr int PRECISE = 1;                    // as chol_predict (nmgp_eig.hip) and why
+    static constexpr bool NAN_PARS = false;              // a NaN parameter is reported as whatever the factorisations met
+    // the call leaves batched evaluations and a begun trajectory alone
+    static constexpr bool RESETS_KIND = false;
+    static int require(nmgp_ctx* c) {
+        if (!nmgp_complete_subject(c)) return nmgp_fail(c, NMGP_E_STATE, "nmgp_set_data must be called first");
+        if (c->chol_algo != 1 || c->sep_algo != 1)
+            return nmgp_fail(c, NMGP_E_UNSUPPORTED, "posterior-draw prediction runs on the custom factorisation of the M blocks only "
+                                                    "(riding rows): not under NMGP_CHOL=rocsolver or NMGP_SEP=eig");
+        return 0;
     }
-    const bool same = pl == pg;
-    // one workspace, carved; its size depends on (N, M, S, B), not on H
-    size_t off = 0;
-    auto take = [&off](size_t nelem) {
-        const size_t o = off;
-        off += (nelem + 15) / 16 * 16;
-        return o;
-    };
-    const size_t o_xs = take(S), o_W0 = take(regress ? (size_t)N * S : 0), o_W1 = take(regress && !same ? (size_t)N * S : 0),
-                 o_cv = take(regress ? S2 : 0), o_pars = take((size_t)B * P), o_small = take((size_t)B * sp),
-                 o_ell = take(stationary ? 0 : (size_t)B * N), o_sig = take(stationary ? 0 : (size_t)B * N),
-                 o_yt = take((size_t)B * M * N), o_star = take(stationary ? 0 : B * S2), o_z = take(z ? B * S2 : 0),
-                 o_dots = take((size_t)B * M * S), o_sqs = take((size_t)B * M * S), o_mean = take(B * SMo), o_var = take(B * SMo),
-                 o_part = take((size_t)B * M * 2 * Sm * chunks), o_info = take(((size_t)B * M + 1) / 2), o_S = take((size_t)B * M * bs);
-    if (c->ps_cap < off) {
-        c->ps_cap = 0;
-        NMGP_TRY(nmgp_dev_alloc(c, &c->ps_buf, off));
-        c->ps_cap = off;
-    } else if (nmgp_poison()) {
-        HIP_TRY(c, hipMemsetAsync(c->ps_buf, 0xFF, off * sizeof(double), s));
+    static int size_guard(const PsCall& k) {             // (sep_blocks_b addresses a block with 32-bit byte offsets)
+        if (8LL * k.ld * k.N >= 0x7fffffffLL)
+            return nmgp_fail(k.c, NMGP_E_SHAPE, "a block of order N = %d with %d riding rows exceeds the 2 GiB the block build addresses",
+                             k.N, k.ld - k.N);
+        return 0;
     }
-    double* w = c->ps_buf;
-    double *d_xs = w + o_xs, *W0 = w + o_W0, *W1 = same ? W0 : w + o_W1, *cv0 = w + o_cv, *cv1 = same ? cv0 : cv0 + S,
-           *d_pars = w + o_pars, *d_small = w + o_small, *d_ell = w + o_ell, *d_sig = w + o_sig, *yt = w + o_yt, *d_star = w + o_star,
-           *d_z = z ? w + o_z : nullptr, *dots = w + o_dots, *sqs = w + o_sqs, *d_mean = w + o_mean, *d_var = w + o_var,
-           *part = w + o_part, *Sb = w + o_S;
-    int* d_info = reinterpret_cast<int*>(w + o_info);
-
-    HIP_TRY(c, hipMemcpyAsync(d_xs, xs, (size_t)S * sizeof(double), hipMemcpyHostToDevice, s));
-    if (regress) {
-        NMGP_TRY(nmgp_ps_project(c, pl, d_xs, S, W0, cv0));
-        if (!same) NMGP_TRY(nmgp_ps_project(c, pg, d_xs, S, W1, cv1));
+    static size_t chunk_doubles(const PsCall& k) { return (size_t)k.M * k.bs; }
+    static const double* y_rows(const PsCall& k, long long& stride) {
+        stride = k.N;                // every block has its own rotated data row
+        return k.at(k.o_yt);
     }
-    std::vector<int> hinfo((size_t)B * M);
-    std::vector<double> hsmall((size_t)B * sp);
-    for (int h0 = 0; h0 < H; h0 += B) {
-        const int Bc = std::min(B, H - h0), BM = Bc * M;
-        // host: B = L L^T and its eigenpairs per draw (M x M: known before the first launch)
-        for (int b = 0; b < Bc; ++b) {
-            const double* pb = pars + (size_t)(h0 + b) * P;
-            double* hs = hsmall.data() + (size_t)b * sp;
+    template <class Take>
+    static void extras(PsCall& k, Take take, size_t B) {
+        k.o_small = take(B * pss_small_per(k.M));
+        k.o_ell = take(stationary ? 0 : B * k.N);
+        k.o_sig = take(stationary ? 0 : B * k.N);
+        k.o_yt = take(B * k.M * k.N);
+        k.host.resize(B * pss_small_per(k.M));
+    }
+    // host: B = L L^T and its eigenpairs per draw (M x M: known before the first launch)
+    static void host_prep(PsCall& k) {
+        const int N = k.N, M = k.M, sp = pss_small_per(M);
+        for (int b = 0; b < k.Bc; ++b) {
+            const double* pb = k.hpars + (size_t)b * k.P;
+            double* hs = k.host.data() + (size_t)b * sp;
             nmgp_small_eig(pb + (stationary ? 2 : 2 * (size_t)N), M, hs, hs + M, hs + pss_o_bd(M));
-            hs[pss_o_s2(M)] = std::exp(pb[P - 1]);
+            hs[pss_o_s2(M)] = std::exp(pb[k.P - 1]);
             hs[pss_o_s2(M) + 1] = 0.0;
             hs[pss_o_l0(M)] = stationary ? std::exp(pb[0]) : 1.0;
             hs[pss_o_l0(M) + 1] = stationary ? std::exp(pb[1]) : 1.0;
         }
-        HIP_TRY(c, hipMemcpyAsync(d_pars, pars + (size_t)h0 * P, (size_t)Bc * P * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_small, hsmall.data(), (size_t)Bc * sp * sizeof(double), hipMemcpyHostToDevice, s));
-        if (stationary) {
-            NMGP_LAUNCH(k_pss_rotate_y, dim3(cdiv(N, 256), Bc), dim3(256), 0, s, c->d_Y, d_small, N, M, yt);
-        } else {
-            sep_prep_b(s, d_pars, P, c->d_Y, d_small, sp, N, M, d_ell, d_sig, yt, Bc);
-            if (regress) {
-                if (z) HIP_TRY(c, hipMemcpyAsync(d_z, z + (size_t)h0 * S2, Bc * S2 * sizeof(double), hipMemcpyHostToDevice, s));
-                pss_star(s, W0, W1, cv0, cv1, d_pars, P, d_z, N, S, hyper[0], hyper[3], d_star, Bc);
-            } else {
-                HIP_TRY(c, hipMemcpyAsync(d_star, star_in + (size_t)h0 * S2, Bc * S2 * sizeof(double), hipMemcpyHostToDevice, s));
-            }
-        }
-        HIP_TRY(c, hipMemsetAsync(d_info, 0, (size_t)BM * sizeof(int), s));
-        for (int s0 = 0; s0 < S; s0 += smax) {
-            const int Sc = std::min(smax, S - s0);
-            const dim3 gx(N, cdiv(Sc, 256), Bc);
-            if (stationary) {
-                NMGP_LAUNCH(k_pss_sta_blocks, dim3(cdiv(N, 256), N, Bc), dim3(256), 0, s, c->d_x, d_small, N, M, Sb, ld, bs);
-                NMGP_LAUNCH((k_pss_cross_rows<1>), gx, dim3(256), 0, s, c->d_x, nullptr, nullptr, d_small, N, M, d_xs, nullptr, S, s0, Sc,
-                            Sb, ld, bs, N + 1);
-            } else {
-                sep_blocks_b(s, c->d_x, d_ell, d_sig, d_small, sp, N, M, Sb, ld, bs, nullptr, Bc);
-                NMGP_LAUNCH((k_pss_cross_rows<0>), gx, dim3(256), 0, s, c->d_x, d_ell, d_sig, d_small, N, M, d_xs, d_star, S, s0, Sc, Sb,
-                            ld, bs, N + 1);
-            }
-            set_row(s, Sb, ld, N, yt, N, BM, bs, N);
-            nmgp_potrf(c, Sb, ld, N, 1 + Sc, 0, d_info, BM, bs, 1, 1);          // precise = 1, as chol_predict (nmgp_eig.hip) and why
-            ps_rows_reduce(s, Sb, ld, bs, N, N + 1, N, Sc, part, BM, dots, sqs, (long long)S, (long long)s0);
-        }
-        NMGP_LAUNCH(k_pss_combine, dim3(cdiv((long long)SMo, 256), Bc), dim3(256), 0, s, dots, sqs, d_small, d_star, S, M,
-                    stationary ? 1 : 0, kss_jitter ? 1 : 0, d_mean, d_var);
-        double* hm = mean + (size_t)h0 * SMo;
-        double* hv = var + (size_t)h0 * SMo;
-        HIP_TRY(c, hipMemcpyAsync(hm, d_mean, Bc * SMo * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(hv, d_var, Bc * SMo * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (star_out && !stationary)
-            HIP_TRY(c, hipMemcpyAsync(star_out + (size_t)h0 * S2, d_star, Bc * S2 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(hinfo.data(), d_info, (size_t)BM * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        NMGP_TRY(nmgp_take_launch_error(c));
-        // per-draw status as nmgp_predsample_svc reports it: a failing draw yields NaN rows, not a failed call
-        for (int b = 0; b < Bc; ++b) {
-            int st = 0;
-            for (int p = 0; p < M && st == 0; ++p) st = hinfo[(size_t)b * M + p];
-            if (st == 0)
-                for (size_t k = 0; k < SMo; ++k)
-                    if (!std::isfinite(hm[b * SMo + k]) || !std::isfinite(hv[b * SMo + k])) {
-                        st = NMGP_NUM_NAN;
-                        break;
-                    }
-            if (st != 0)
-                for (size_t k = 0; k < SMo; ++k) hm[b * SMo + k] = hv[b * SMo + k] = std::nan("");
-            if (status) status[h0 + b] = st;
-        }
     }
-    return 0;
-}
+    static int prep(const PsCall& k) {
+        nmgp_ctx* c = k.c;
+        const int N = k.N, M = k.M, sp = pss_small_per(M);
+        double* small = k.at(k.o_small);
+        HIP_TRY(c, hipMemcpyAsync(small, k.host.data(), (size_t)k.Bc * sp * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (stationary)
+            NMGP_LAUNCH(k_pss_rotate_y, dim3(cdiv(N, 256), k.Bc), dim3(256), 0, c->stream, c->d_Y, small, N, M, k.at(k.o_yt));
+        else
+            sep_prep_b(c->stream, k.pars, k.P, c->d_Y, small, sp, N, M, k.at(k.o_ell), k.at(k.o_sig), k.at(k.o_yt), k.Bc);
+        return 0;
+    }
+    static int star(const PsCall& k) {
+        pss_star(k.c->stream, k.W0, k.W1, k.cv0, k.cv1, k.pars, k.P, k.z, k.N, k.S, k.hyper[0], k.hyper[3], k.star, k.Bc);
+        return 0;
+    }
+    static int build_cov(const PsCall& k) {
+        nmgp_ctx* c = k.c;
+        if (stationary)
+            NMGP_LAUNCH(k_pss_sta_blocks, dim3(cdiv(k.N, 256), k.N, k.Bc), dim3(256), 0, c->stream, c->d_x, k.at(k.o_small), k.N, k.M,
+                        k.Sb, k.ld, k.bs);
+        else
+            sep_blocks_b(c->stream, c->d_x, k.at(k.o_ell), k.at(k.o_sig), k.at(k.o_small), pss_small_per(k.M), k.N, k.M, k.Sb, k.ld,
+                         k.bs, nullptr, k.Bc);
+        return 0;
+    }
+    static int cross_rows(const PsCall& k) {
+        nmgp_ctx* c = k.c;
+        const dim3 gx(k.N, cdiv(k.Sc, 256), k.Bc);
+        if (stationary)
+            NMGP_LAUNCH((k_pss_cross_rows<1>), gx, dim3(256), 0, c->stream, c->d_x, nullptr, nullptr, k.at(k.o_small), k.N, k.M, k.xs,
+                        nullptr, k.S, k.s0, k.Sc, k.Sb, k.ld, k.bs, k.N + 1);
+        else
+            NMGP_LAUNCH((k_pss_cross_rows<0>), gx, dim3(256), 0, c->stream, c->d_x, k.at(k.o_ell), k.at(k.o_sig), k.at(k.o_small), k.N,
+                        k.M, k.xs, k.star, k.S, k.s0, k.Sc, k.Sb, k.ld, k.bs, k.N + 1);
+        return 0;
+    }
+    static int finish(const PsCall& k) {                 // dots / sqs [B, M, S] -> mean / var [B, S, M]
+        NMGP_LAUNCH(k_pss_combine, dim3(cdiv((long long)k.S * k.M, 256), k.Bc), dim3(256), 0, k.c->stream, k.dots, k.sqs,
+                    k.at(k.o_small), k.star, k.S, k.M, stationary ? 1 : 0, k.flags ? 1 : 0, k.mean, k.var);
+        return 0;
+    }
+};
 
 }  // namespace
 
 extern "C" int nmgp_predsample_sep(nmgp_ctx* c, const double* pars, int H, const double hyper[9], const double* xs, int S,
                                    int kss_jitter, const double* z, const double* star_in, double* mean, double* var,
                                    double* star_out, int* status) {
-    if (!c) return NMGP_E_NULL;
-    return predsample_kron(c, false, pars, H, hyper, xs, S, kss_jitter, z, star_in, mean, var, star_out, status);
+    return ps_predict<PsKron<false>>(c, pars, H, hyper, xs, nullptr, S, kss_jitter, z, star_in, mean, var, star_out, status);
 }
 
 extern "C" int nmgp_predsample_sta(nmgp_ctx* c, const double* pars, int H, const double* xs, int S, double* mean, double* var,
                                    int* status) {
-    if (!c) return NMGP_E_NULL;
-    return predsample_kron(c, true, pars, H, nullptr, xs, S, 0, nullptr, nullptr, mean, var, nullptr, status);
+    return ps_predict<PsKron<true>>(c, pars, H, nullptr, xs, nullptr, S, 0, nullptr, nullptr, mean, var, nullptr, status);
 }
