@@ -2258,13 +2258,19 @@ __global__ __launch_bounds__(512, OCC) void k_panel_step(double* __restrict__ Ab
 // up to date with the NP blocks and with block k and factors it (potf2b_core_mfma); its X blocks reach the MFMA's other side
 // through LDS (Xs, aliasing the operands), and its diagonal block is loaded only when the first X block has gone there.
 // No workgroup waits for another: every operand is final since the previous launch.
+// Every launch runs at 4 waves/SIMD (two workgroups per CU) and STREAMS: the prologue issues every load it needs before it waits
+// for the first of them ((1) below), and while a workgroup's matrix pipes work on previous block p, the rows' X of block p + 1 is
+// already on its way into the registers block p has finished with ((2) below), so a workgroup no longer depends on its
+// co-resident one being out of phase.  Measured on one MI355X (one headline step, 128 chains, profiles/leafpipe_*): <1, true>
+// 2.76 -> 2.44 ms, <2, true> 3.93 -> 3.23 ms, <3, false> 4.32 -> 3.90 ms (at 6 waves/SIMD the rotation does not fit 80
+// registers: 80 spilled); k_panel_step<1, 4> is as it was.
 // Rows of L^-T (gradient evaluations, the A phase of the structured value path): rows t_fresh0 <= row < t_fresh1 (absolute) have
 // entered since the node began; nobody has written their block k, which starts from zero and is not loaded.  What the
 // catch-up reads of such rows left of their own block is either written by an earlier launch of the node or inside the seeded band
 // (k_xtri_seed: three blocks left of the row's own; <3, false> reaches exactly that far).
 // ---------------------------------------------------------------------------------------------
-template <int NP, bool FACT, int OCC>
-__global__ __launch_bounds__(512, OCC) void k_leaf_step(double* __restrict__ Ab, int lda, int ck, int m_act, long long bstride,
+template <int NP, bool FACT>
+__global__ __launch_bounds__(512, 4) void k_leaf_step(double* __restrict__ Ab, int lda, int ck, int m_act, long long bstride,
                                                        int* __restrict__ info, int istride, int T, int nbatch, int t_fresh0,
                                                        int t_fresh1) {
     constexpr int kOpsC = 2560;                                         // doubles; after opsT
@@ -2293,28 +2299,33 @@ __global__ __launch_bounds__(512, OCC) void k_leaf_step(double* __restrict__ Ab,
     auto colp = [&](int col) { return A + (size_t)col * lda; };
     double oc[8], ot[5];
     v4d Xp[4], Tk[4];
-    auto load_ops = [&](int p) {                                 // -L[block k, previous block p]
+    auto load_ops = [&](int p) {                                 // L[block k, previous block p] (store_ops negates)
         const int cb = ck - 64 * (NP - p);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) oc[j] = -(colp(cb + 4 * (wu + 8 * (j & 1))) + ck + 16 * (j >> 1))[vops];
+        for (int j = 0; j < 8; ++j) oc[j] = (colp(cb + 4 * (wu + 8 * (j & 1))) + ck + 16 * (j >> 1))[vops];
     };
     auto store_ops = [&]() {                                     // element j: q = j >> 1, sx = w + 8 (j & 1), lane
+        __builtin_amdgcn_sched_barrier(0);                       // (the negation, hoisted to the loads, would wait for them there)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) smem[kOpsC + (((j >> 1) * 4 + (j & 1) * 2 + (wu >> 2)) * 64 + lane) * 4 + (wu & 3)] = oc[j];
+        for (int j = 0; j < 8; ++j) smem[kOpsC + (((j >> 1) * 4 + (j & 1) * 2 + (wu >> 2)) * 64 + lane) * 4 + (wu & 3)] = -oc[j];
     };
-    auto load_x = [&](int p) {                                   // the rows' X in previous block p
-        const int cb = ck - 64 * (NP - p);
+    // the rows' 16-column group `g` of the 64-column block at column cb, as BUFFER loads (one descriptor per block, the column as
+    // scalar offset): a masked lane gives an offset beyond the descriptor's range, for which the hardware fetches nothing and
+    // returns zero, so the loads need no branch around them.  Only without one does hipcc count the loads in flight exactly
+    // (s_waitcnt vmcnt(N)): the two sides of a lane-masked branch merge to the smaller count, and the wait of an earlier load then
+    // drains the row loads as well.
+    auto row_block = [&](int cb) { return __builtin_amdgcn_make_buffer_rsrc(colp(cb), (short)0, 0x7fffffff, 0x00020000); };
+    auto load_group = [&](v4d& dst, __amdgpu_buffer_rsrc_t blk, int g, unsigned voff) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) Xp[q] = v4d{0.0, 0.0, 0.0, 0.0};
-        if (rv) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Xp[q][r] = colp(cb + 16 * q + 4 * r)[vrow];
-        }
+        for (int r = 0; r < 4; ++r)
+            dst[r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(blk, (int)voff, (16 * g + 4 * r) * lda * 8, 0));
     };
-    // (1) operands of the first catch-up and of the solve, through registers into LDS; the row loads are issued behind them (the
-    // operand registers are free again, see k_panel_step<2>)
+    const unsigned kMasked = 0x80000000u;                        // (in range: offset + 8 <= 0x7fffffff)
+    const unsigned vxoff = rv ? vrow * 8u : kMasked, vtoff = tload ? vrow * 8u : kMasked;
+    // (1) every load of the prologue is issued before the first of them is waited for: the operands of the first catch-up and of
+    // the solve (L2 hits) first, then the rows' own block and their X in the first previous block (HBM).  The operands' way to LDS
+    // waits for the operands only, and the rows travel across the barrier.  (Which entry of the diagonal block a lane fetches
+    // is a select on the address, and what it makes of it a select on the value: a branch per entry costs a drained queue each.)
     load_ops(0);
     {
         const double* L = A + (size_t)ck * lda + ck;              // diagonal block k (factor + inverted 16x16 blocks)
@@ -2323,44 +2334,49 @@ __global__ __launch_bounds__(512, OCC) void k_leaf_step(double* __restrict__ Ab,
             const int idx = tid + 512 * j;                        // 0 .. 2559
             const int blk = idx >> 8, kk = (idx >> 6) & 3, l = idx & 63;
             const int rr = l & 15, kc = 4 * kk + (l >> 4);
-            double v;
-            if (blk < 6) {
+            if (j < 3) {                                          // blk < 6
                 const int q = blk == 0 ? 1 : (blk < 3 ? 2 : 3);
                 const int pp = blk == 0 ? 0 : (blk < 3 ? blk - 1 : blk - 3);
-                v = -L[(size_t)(16 * pp + kc) * lda + 16 * q + rr];
+                ot[j] = L[(size_t)(16 * pp + kc) * lda + 16 * q + rr];
             } else {
                 const int q = blk - 6;                   // inv(L_qq)[rr][kc] (kc < rr) sits at row 16 q + kc, column 16 q + rr
-                if (kc < rr) v = L[(size_t)(16 * q + rr) * lda + 16 * q + kc];
-                else if (kc == rr) v = 1.0 / L[(size_t)(16 * q + rr) * lda + 16 * q + rr];
-                else v = 0.0;
+                ot[j] = L[(size_t)(16 * q + rr) * lda + 16 * q + (kc < rr ? kc : rr)];
             }
-            ot[j] = v;
         }
+    }
+    {
+        const __amdgpu_buffer_rsrc_t own = row_block(ck), x0 = row_block(ck - 64 * NP);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) load_group(Tk[q], own, q, vtoff);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) load_group(Xp[q], x0, q, vxoff);
     }
     store_ops();
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
         const int idx = tid + 512 * j;
         const int blk = idx >> 8, kk = (idx >> 6) & 3, l = idx & 63;
-        smem[(blk * 64 + l) * 4 + kk] = ot[j];
+        const int rr = l & 15, kc = 4 * kk + (l >> 4);
+        const double v = j < 3 ? -ot[j] : (kc < rr ? ot[j] : (kc == rr ? 1.0 / ot[j] : 0.0));
+        smem[(blk * 64 + l) * 4 + kk] = v;
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) Tk[q] = v4d{0.0, 0.0, 0.0, 0.0};
-    if (tload) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Tk[q][r] = colp(ck + 16 * q + 4 * r)[vrow];
-    }
-    load_x(0);
     __syncthreads();
     // (2) catch-up, previous block by previous block in ascending k:  T_q -= X[rows, p] L[block k, p]^T
-    // (the next block's loads are issued behind the barrier: hoisted above the MFMAs they would want a third row block)
+    // The X registers rotate by 16-column group.  After the 16 MFMAs of group sg of block p, Xp[sg] is dead, and the four loads
+    // of block p + 1's group sg go into those same registers right there: they travel under the remaining MFMAs of block p and
+    // across the barrier pair, and no third row block is ever live.  The operands of block p + 1 (L2 hits) are loaded AHEAD of
+    // the row loads (oc[] is free since store_ops), so that their way to LDS waits for nothing that comes from HBM.
+    // Workgroup 0's idle waves issue the (masked) loads too: a branch around them would make the counts inexact again.  hipcc
+    // waits vmcnt(23) .. (16) in front of the operands' LDS stores and vmcnt(15) .. in front of the next block's MFMAs; with
+    // lane-masked branches both were vmcnt(0) (measured: half the gain).
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-        if (!wg0 || isC) {
+        const bool more = p + 1 < NP;
+        if (more) load_ops(p + 1);
+        const __amdgpu_buffer_rsrc_t xnext = row_block(ck - 64 * (NP - p - 1));
 #pragma unroll
-            for (int sg = 0; sg < 4; ++sg)
+        for (int sg = 0; sg < 4; ++sg) {
+            if (!wg0 || isC) {
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -2368,18 +2384,12 @@ __global__ __launch_bounds__(512, OCC) void k_leaf_step(double* __restrict__ Ab,
                         const double a = reinterpret_cast<const double*>(&opsC[(q * 4 + sg) * 64 + lane])[kk];
                         Tk[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Xp[sg][kk], Tk[q], 0, 0, 0);
                     }
-        }
-        if (p + 1 < NP) {
-            __syncthreads();                                      // every wave is done with the operands of block p
-            load_ops(p + 1);
-            if constexpr (OCC > 4) {                              // 16 operand registers + two row blocks do not fit 80 VGPRs:
-                store_ops();                                      // the operands go to LDS before the row loads are issued
-                __builtin_amdgcn_sched_barrier(0);
-                load_x(p + 1);
-            } else {
-                load_x(p + 1);
-                store_ops();
             }
+            if (more) load_group(Xp[sg], xnext, sg, vxoff);
+        }
+        if (more) {
+            __syncthreads();                                      // every wave is done with the operands of block p
+            store_ops();
             __syncthreads();
         }
     }
@@ -2607,13 +2617,13 @@ struct Factorisation {
                             0, f0, xtri > 0 ? n + extra - 64 * NMGP_XTRI_SEED_BLOCKS : kNoTriRows,
                             stamps ? stamps + (size_t)(ck / 64) * 16 : nullptr);
             else if (k == 1)
-                NMGP_LAUNCH((k_leaf_step<1, true, 4>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, kNoTriRows,
+                NMGP_LAUNCH((k_leaf_step<1, true>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, kNoTriRows,
                             kNoTriRows);
             else if (k == 2)
-                NMGP_LAUNCH((k_leaf_step<2, true, 4>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, f0,
+                NMGP_LAUNCH((k_leaf_step<2, true>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, f0,
                             xtri > 0 ? f0 + 128 : kNoTriRows);
             else
-                NMGP_LAUNCH((k_leaf_step<3, false, 6>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, f0,
+                NMGP_LAUNCH((k_leaf_step<3, false>), grid, dim3(512), 0, s, A, lda, ck, m_act, bs, info, is, T, batch, f0,
                             xtri > 0 ? f0 + 192 : kNoTriRows);
         }
     }
