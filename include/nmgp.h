@@ -383,6 +383,22 @@ int nmgp_kron_inv_logdet(nmgp_ctx* ctx, double sigma2, const double* B, int M, c
  * through the factorisation as an extra row: out_z = L^-1 rhs.  algo: 1 = custom gfx950 factorisation, 0 = rocSOLVER. */
 int nmgp_cholesky(nmgp_ctx* ctx, const double* A, int n, const double* rhs, double* out_L, double* out_z,
                   int algo);
+/* Developer entry of the BATCHED custom factorisation, laid out as the batched objectives lay it out: `batch` symmetric
+ * [n,n] matrices A [batch,n,n] (only the triangle nmgp_cholesky reads -- the row-major upper one -- is uploaded), below each of
+ * them `extra` dense rows (rows: [batch,extra,n], NULL iff extra = 0) and, with want_xtri = 1, a zero pad row if n + extra is
+ * odd and the n seeded rows that turn into X = L^-T.  precise = 1: the accuracy-first diagonal blocks and solves.
+ *   out_L    [batch,n,n]      as nmgp_cholesky's (out_L^T is the lower factor); the other triangle is returned as zeros
+ *   out_rows [batch,extra,n]  the dense rows on exit, R L^-T (NULL iff extra = 0)
+ *   out_X    [batch,n,n]      want_xtri: out_X^T is X; only X's upper triangle is promised, what lies left of its diagonal is
+ *                             whatever the buffer held (NaN under NMGP_POISON=1) apart from the seeded band
+ *   out_inv  [batch,n,n]      want_inv = 1 | 2 (needs want_xtri, NMGP_E_STATE otherwise): -X X^T = -A^-1 as the gradient paths
+ *                             build it, out_inv^T's lower triangle (1) or both triangles (2)
+ *   status   [batch]          0, or k > 0: leading minor k of that matrix is not positive definite.  Such a matrix does not
+ *                             fail the call (return value 0); its outputs are unspecified, the other matrices' are not touched.
+ * No device buffer is cleared first: under NMGP_POISON=1 everything the production callers leave unwritten stays NaN. */
+int nmgp_cholesky_batch(nmgp_ctx* ctx, const double* A, int n, int batch, const double* rows, int extra, int want_xtri,
+                        int want_inv, int precise, double* out_L, double* out_rows, double* out_X, double* out_inv,
+                        int* status);
 
 /* ---- deterministic prediction (prediction.py:912-988, 337-408, 1566-1638) -------------------- */
 /* Nonseparable: predictive mean / variance of y at S new inputs xs given MAP parameters.

@@ -78,6 +78,7 @@ SIGNATURES = {
     "nmgp_mvn_logpdf_dense": (I, [V, P, P, P, I, P, I, D, P]),
     "nmgp_kron_inv_logdet": (I, [V, D, P, I, P, I, P, P]),
     "nmgp_cholesky": (I, [V, P, I, P, P, P, I]),
+    "nmgp_cholesky_batch": (I, [V, P, I, I, P, I, I, I, I, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predict_svc": (I, [V, P, P, P, I, P, P, P]),
     "nmgp_predict_sep": (I, [V, P, P, P, I, P, P]),
     "nmgp_predict_sta": (I, [V, P, P, I, P, P]),
@@ -602,6 +603,41 @@ class Context:
         self.check(self.lib.nmgp_cholesky(self.h, ptr(A), n, ptr(rhsa), ptr(out), ptr(z), int(algo)))
         L = np.tril(out.T)           # the library's column-major lower triangle == row-major upper
         return (L, z) if rhsa is not None else L
+
+    def cholesky_batch(self, A, rows=None, want_xtri=False, want_inv=0, precise=False):
+        """The batched custom factorisation on caller-supplied matrices, laid out and launched as the batched objectives do it.
+        A [B, n, n] symmetric (only the triangle ``cholesky`` reads is uploaded), rows [B, extra, n] dense rows carried below each
+        matrix.  Returns (L, R, X, Sinv, status) in the orientation of ``cholesky``: L [B, n, n] lower factors, R [B, extra, n] =
+        rows L^-T (None without rows), X [B, n, n] = L^-T with want_xtri (only its upper triangle is promised: left of the diagonal
+        it holds whatever the device buffer held), Sinv [B, n, n] = -X X^T with want_inv (1: lower triangle, the rest zero; 2: both
+        triangles), status [B] (0, or the first leading minor that is not positive definite: such a matrix does not raise)."""
+        A = as_f64(A)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise NmgpError("A must be [B, n, n]")
+        B, n = A.shape[0], A.shape[1]
+        ra = None if rows is None else as_f64(rows)
+        if ra is not None and (ra.ndim != 3 or ra.shape[0] != B or ra.shape[2] != n):
+            raise NmgpError("rows must be [B=%d, extra, n=%d]" % (B, n))
+        if ra is not None and ra.shape[1] == 0:
+            ra = None
+        extra = 0 if ra is None else ra.shape[1]
+        L = np.empty((B, n, n))
+        R = None if ra is None else np.empty((B, extra, n))
+        X = np.empty((B, n, n)) if want_xtri else None
+        Sinv = np.empty((B, n, n)) if want_inv else None
+        status = np.zeros(B, dtype=np.int32)
+        self.check(self.lib.nmgp_cholesky_batch(self.h, ptr(A), n, B, ptr(ra), extra, int(bool(want_xtri)), int(want_inv),
+                                                int(bool(precise)), ptr(L), ptr(R), ptr(X), ptr(Sinv),
+                                                status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        # the library's column-major matrices are the row-major transposes
+        L = np.ascontiguousarray(L.transpose(0, 2, 1))
+        if X is not None:
+            X = np.ascontiguousarray(X.transpose(0, 2, 1))
+        if Sinv is not None:
+            Sinv = np.ascontiguousarray(Sinv.transpose(0, 2, 1))
+            if int(want_inv) == 1:
+                Sinv = np.tril(Sinv)          # the other triangle is not written
+        return L, R, X, Sinv, status
 
     # -- prediction -----------------------------------------------------------------------------
     def predict_svc(self, pars, hyper, xs):

@@ -1771,6 +1771,74 @@ static int download(nmgp_ctx* c, double* h, const double* d, size_t nelem) {
     return nmgp_take_launch_error(c);
 }
 
+// Developer entry of the batched factorisation: the buffer layout and the launch sequence of nmgp_svc_batch_eval's dense path
+// (matrix + dense rows [+ pad + seeded rows of L^-T], potrf, inverse SYRK) on caller-supplied matrices, every output returned as a
+// matrix.  The scratch buffers are NOT cleared: what the production callers leave unwritten (the strict upper triangle, the rows of
+// L^-T left of the seeded band and right of the diagonal block) is unwritten here, NaN under NMGP_POISON=1.
+extern "C" int nmgp_cholesky_batch(nmgp_ctx* c, const double* A, int n, int batch, const double* rows, int extra, int want_xtri,
+                                   int want_inv, int precise, double* out_L, double* out_rows, double* out_X, double* out_inv,
+                                   int* status) {
+    if (!c) return NMGP_E_NULL;
+    if (!A || !out_L || !status) return nmgp_fail(c, NMGP_E_NULL, "A/out_L/status must not be NULL");
+    if (n <= 0 || n > 65535 || batch <= 0 || batch > 65535 || extra < 0 || extra > 65535)
+        return nmgp_fail(c, NMGP_E_SHAPE, "bad shape n=%d batch=%d extra=%d", n, batch, extra);
+    if ((extra > 0) != (rows != nullptr) || (extra > 0) != (out_rows != nullptr))
+        return nmgp_fail(c, NMGP_E_NULL, "rows/out_rows must be given exactly when extra > 0");
+    if ((want_xtri & ~1) || want_inv < 0 || want_inv > 2 || (precise & ~1))
+        return nmgp_fail(c, NMGP_E_SHAPE, "bad flags want_xtri=%d want_inv=%d precise=%d", want_xtri, want_inv, precise);
+    if (want_inv && !want_xtri) return nmgp_fail(c, NMGP_E_STATE, "want_inv needs the rows of L^-T (want_xtri)");
+    if ((want_xtri && !out_X) || (want_inv && !out_inv)) return nmgp_fail(c, NMGP_E_NULL, "out_X/out_inv must not be NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    // rows: n (matrix) + extra (dense); with the rows of L^-T: + pad, so that X starts on an even row, + n
+    const int xpad = want_xtri ? ((n + extra) & 1) : 0, xoff = n + extra + xpad;
+    const int ld = (int)nmgp_ld((size_t)xoff + (want_xtri ? n : 0));
+    const long long bs = (long long)ld * n;
+    const size_t nn = (size_t)n * n, rn = (size_t)extra * n;
+    double *S, *dA, *dr, *dinv = nullptr;
+    NMGP_TRY(nmgp_scratch_get(c, 2, (size_t)batch * bs, &S));
+    NMGP_TRY(nmgp_scratch_get(c, 3, (size_t)batch * rn + (size_t)batch / 2 + 1, &dr));
+    NMGP_TRY(upload(c, 4, A, (size_t)batch * nn, &dA));
+    if (want_inv) NMGP_TRY(nmgp_scratch_get(c, 5, (size_t)batch * nn, &dinv));
+    int* info = reinterpret_cast<int*>(dr + (size_t)batch * rn);
+    HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)batch * sizeof(int), s));
+    copy_lower(s, dA, n, S, ld, bs, batch);
+    if (extra > 0) HIP_TRY(c, hipMemcpyAsync(dr, rows, (size_t)batch * rn * sizeof(double), hipMemcpyHostToDevice, s));
+    {
+        StageScope sp(c, NMGP_STAGE_CHOL);
+        for (int e = 0; e < extra; ++e) set_row(s, S, ld, n + e, dr + (size_t)e * n, n, batch, bs, (long long)rn);
+        if (want_xtri) identity_rows(s, S, ld, n + extra, n, xpad, batch, bs);
+        nmgp_potrf(c, S, ld, n, extra + xpad, want_xtri ? n : 0, info, batch, bs, 1, precise);
+    }
+    if (want_inv) {
+        StageScope sp(c, NMGP_STAGE_INVERSE);
+        syrk_lower(s, S + xoff, ld, dinv, n, n, n, n, batch, bs, (long long)nn, want_inv);     // -X X^T
+    }
+    std::vector<double> hr((size_t)batch * rn);
+    for (int b = 0; b < batch; ++b) {
+        const double* Sb = S + (size_t)b * bs;
+        HIP_TRY(c, hipMemcpy2DAsync(out_L + b * nn, (size_t)n * sizeof(double), Sb, (size_t)ld * sizeof(double),
+                                    (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, s));
+        if (extra > 0)
+            HIP_TRY(c, hipMemcpy2DAsync(hr.data() + b * rn, (size_t)extra * sizeof(double), Sb + n, (size_t)ld * sizeof(double),
+                                        (size_t)extra * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, s));
+        if (want_xtri)
+            HIP_TRY(c, hipMemcpy2DAsync(out_X + b * nn, (size_t)n * sizeof(double), Sb + xoff, (size_t)ld * sizeof(double),
+                                        (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, s));
+    }
+    if (want_inv) HIP_TRY(c, hipMemcpyAsync(out_inv, dinv, (size_t)batch * nn * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(status, info, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    NMGP_TRY(nmgp_take_launch_error(c));
+    for (int b = 0; b < batch; ++b) {
+        // column j of the buffer is row j of out_L: what lies above the factor's diagonal (the inverted 16x16 blocks) is not L
+        for (int j = 1; j < n; ++j) std::memset(out_L + b * nn + (size_t)j * n, 0, (size_t)j * sizeof(double));
+        for (int j = 0; j < n; ++j)
+            for (int e = 0; e < extra; ++e) out_rows[b * rn + (size_t)e * n + j] = hr[b * rn + (size_t)j * extra + e];
+    }
+    return 0;
+}
+
 extern "C" int nmgp_pairwise_distances(nmgp_ctx* c, const double* x1, int n1, const double* x2, int n2, int d,
                                        double* out) {
     if (!c) return NMGP_E_NULL;

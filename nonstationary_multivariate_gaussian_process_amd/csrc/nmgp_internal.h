@@ -397,6 +397,8 @@ void prior_trsv(hipStream_t s, bool trans, const double* L0, int ld0, long long 
                 double* R, int N, int nrhs, int batch, int cps = 1);
 void diag_logsum2(hipStream_t s, const double* L, int ld, int n, double* out);
 void fill_lower_to_full(hipStream_t s, double* A, int ld, int n, int batch = 1);
+// dst's lower triangle = that of the dense column-major src [batch, n, n] (n, batch <= 65535: grid dimensions)
+void copy_lower(hipStream_t s, const double* src, int n, double* dst, int ld, long long dstride, int batch);
 void transpose_y(hipStream_t s, const double* Y, int N, int M, double* y);
 void svc_prior_rhs(hipStream_t s, const double* pars, int N, int T, double mu_l, double mu_L, double* R, int ld,
                    int batch = 1);

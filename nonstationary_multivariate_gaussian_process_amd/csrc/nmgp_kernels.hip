@@ -760,6 +760,17 @@ void fill_lower_to_full(hipStream_t s, double* A, int ld, int n, int batch) {
     NMGP_LAUNCH(k_sym_fill, dim3(cdiv(n, 64), cdiv(n, 64), batch), dim3(256), 0, s, A, ld, n);
 }
 
+// lower triangle (diagonal included) of the dense column-major matrices src [batch, n, n] into dst (leading dimension ld, matrix z
+// at dst + z * dstride); nothing else of dst is written
+__global__ void k_copy_lower(const double* __restrict__ src, int n, double* __restrict__ dst, int ld, long long dstride) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+    if (i < n && i >= j) dst[(size_t)blockIdx.z * dstride + (size_t)j * ld + i] = src[((size_t)blockIdx.z * n + j) * n + i];
+}
+
+void copy_lower(hipStream_t s, const double* src, int n, double* dst, int ld, long long dstride, int batch) {
+    NMGP_LAUNCH(k_copy_lower, dim3(cdiv(n, 256), n, batch), dim3(256), 0, s, src, n, dst, ld, dstride);
+}
+
 // y[m N + i] = Y[i, m]  (logpos.py:338)
 __global__ void k_transpose_y(const double* __restrict__ Y, int N, int M, double* __restrict__ y) {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
