@@ -212,6 +212,11 @@ def test_sep_against_oracle_ragged_sizes(ctx, N, M, seed):
     assert vec_relerr(grad, gref) < GRAD_TOL
     lik, glik = ctx.logpos_sep(pars, hv, prior=False, want_grad=True)
     assert lik[0] == -lik[1]
+    # the likelihood gradient on its own, block by block: under the priors (10-20x its norm here) it is a small part of `grad`
+    import objective_cases
+    _, glik_ref = O.nlogpos_obj(pars, d["Y"], d["x"], **sim.HYPER_SEP, verbose=True, Prior=False, grad=True)
+    worst, block = objective_cases.block_errors(glik, glik_ref, ("sep", N, M))
+    assert worst < objective_cases.GRAD_TIGHT, (block, worst)
 
 
 @pytest.mark.parametrize("name", golden_names("sta_"))
