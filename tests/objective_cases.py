@@ -120,8 +120,11 @@ def load_oracle(path):
 def blocks(model, N, M):
     """[(name, index)] of the gradient's blocks.  Nonseparable [tilde_l N | uL N x T location-major | sigma2]: tilde_l, each of the T
     slot columns g[N + t : N + N T : T] (named by the slot's row and column in L), the sigma2 entry.  Separable
-    [tilde_l N | tilde_sigma N | uL_vec T | sigma2]: the four of them."""
+    [tilde_l N | tilde_sigma N | uL_vec T | sigma2]: the four of them.  Stationary ("sta") [tilde_l | tilde_sigma | uL_vec T | sigma2]:
+    the same four, the two curves scalars (the eigen-formulation sweep, tests/eig_objective_cases.py)."""
     T = n_slots(M)
+    if model == "sta":
+        return [("tilde_l", slice(0, 1)), ("tilde_sigma", slice(1, 2)), ("uL_vec", slice(2, 2 + T)), ("sigma2", slice(2 + T, 3 + T))]
     if model == "svc":
         r, c = np.tril_indices(M)
         out = [("tilde_l", slice(0, N))]
@@ -149,12 +152,13 @@ def block_errors(g, gref, layout):
     return tab[name], name
 
 
-def blocks_over_bar(g, gref, layout, bar=GRAD_TIGHT):
-    """[(block, error, bar)] of the blocks that miss their bar: `bar`, or the block's entry in BLOCK_BARS."""
+def blocks_over_bar(g, gref, layout, bar=GRAD_TIGHT, bars=None):
+    """[(block, error, bar)] of the blocks that miss their bar: `bar`, or the block's entry in BLOCK_BARS (`bars`: the table of
+    another sweep)."""
     tab = block_table(g, gref, layout)
     bad = []
     for name, e in tab.items():
-        b = BLOCK_BARS.get(layout + (name,), bar)
+        b = (BLOCK_BARS if bars is None else bars).get(layout + (name,), bar)
         if not e < b:
             bad.append((name, e, b))
     return bad

@@ -41,9 +41,10 @@ def ctx():
 # ---------------------------------------------------------------------------------------------------
 # the measures (also run by the NMGP_POISON child, which imports this module)
 # ---------------------------------------------------------------------------------------------------
-def hold_to_oracle(case, entry, layout, got, refs, rows=None):
+def hold_to_oracle(case, entry, layout, got, refs, rows=None, sweep="objective_sweep", bars=None):
     """got[prior] = (out [B, 5 | 6], grad [B, P]) of one entry, priors off and on; refs[b][prior] = the oracle's (out, grad) of batch
-    row b; rows: the batch rows to compare (all).  Records the achieved errors and fails with every miss named."""
+    row b; rows: the batch rows to compare (all).  Records the achieved errors and fails with every miss named.  sweep, bars: the
+    record's prefix and the block-bar table of another sweep that reuses the measure (tests/test_gpu_eig_objective.py)."""
     model, N, M = layout
     (out0, g0), (out1, g1) = got[False], got[True]
     rows = range(len(refs)) if rows is None else rows
@@ -61,7 +62,7 @@ def hold_to_oracle(case, entry, layout, got, refs, rows=None):
         eb, name = C.block_errors(g0[b], gr0, layout)
         if not eb <= worst[0]:
             worst = (eb, name, b)
-        for name, err, bar in C.blocks_over_bar(g0[b], gr0, layout):
+        for name, err, bar in C.blocks_over_bar(g0[b], gr0, layout, bars=bars):
             bad.append("row %d: gradient block %s %.3g >= %.0e" % (b, name, err, bar))
         # priors on
         errs = dict(neglog=(relerr(out1[b][0], r1[0]), VAL_TOL), loglik1=(relerr(out1[b][1], r1[1]), LIK_TOL),
@@ -74,7 +75,7 @@ def hold_to_oracle(case, entry, layout, got, refs, rows=None):
         if out1[b][1] != out0[b][1]:
             bad.append("row %d: the likelihood changes with the prior flag: %r, %r" % (b, out1[b][1], out0[b][1]))
     e["block"] = worst[0]
-    tag = "objective_sweep/%s_%s/%s" % (model, case, entry)
+    tag = "%s/%s_%s/%s" % (sweep, model, case, entry)
     print("%s: loglik %.3g worst block %.3g (%s, row %d) | priors on: neglog %.3g loglik %.3g gp %.3g rest %.3g prior grad %.3g"
           % (tag, e["loglik"], worst[0], worst[1], worst[2], e["neglog"], e["loglik1"], e["gp"], e["rest"], e["prior_grad"]))
     record_parity(tag + "/prior0", loglik=(e["loglik"], C.LIK_TIGHT), worst_block=(e["block"], C.GRAD_TIGHT))

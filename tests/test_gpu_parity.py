@@ -696,6 +696,7 @@ def test_large_batches_at_full_size_match_the_golden_vector_and_single_evaluatio
 def test_separable_cholesky_and_eigen_formulations_agree():
     """The default separable/stationary path factors M blocks wB[p] K + sigma2 I with the batched Cholesky; the
     reference's eigen-trick formulation (distributions.py:26-52) stays selectable and must give the same numbers."""
+    # (the eigen formulation block by block, M = 1 .. 8 and every ragged tile: tests/test_gpu_eig_objective.py)
     import os
     from nonstationary_multivariate_gaussian_process_amd import _lib
     res = {}
