@@ -1041,12 +1041,46 @@ extern "C" int nmgp_sep_batch_eval(nmgp_ctx* c, const double* pars, int B, const
 // =================================================================================================
 // stationary objective
 // =================================================================================================
+// The default (Cholesky) formulation evaluates one chain as a batch of one (sta_batch_core, below): the substitution-based panels and
+// the one-pass adjoint k_sta_reduce_b, which never forms the N per-location entries whose sum cancels ~1e4-fold in d / d tilde_l.
+// What remains here, logpos_sta_retry, is the deterministic jitter retry (kron_likelihood_with_retry) of a chain whose blocks failed
+// numerically, the eigen formulation, and N beyond the block kernels' offsets; it never calls back into the batch.  The fall-through
+// is for a numerical failure (`bad`) alone, which is rare and pays the batch of one before attempt 0 repeats the factorisation; an
+// API or runtime error inside sta_batch_core (a slab that cannot be allocated, a launch error) is returned, not retried on the other
+// path.  The retry body still sums the N per-location entries: its tilde_l is good to ~1e-7 of the gradient only.
+namespace {
+
+int sta_batch_core(nmgp_ctx* c, const double* pars, int B, const double hyper[5], int prior, double* out5, double* grad, int* status,
+                   std::vector<char>& bad, const SepChunkSubjects& sub);
+
+// the block kernels address a block with 32-bit byte offsets, as the separable entry's: N <= 11,584
+bool sta_blocks_fit(int N) { return (long long)(2 * (long long)N + 18) * N * 8 < 0x7fffffffLL; }
+
+int logpos_sta_retry(nmgp_ctx* c, const double* pars, const double hyper[5], int prior, double out5[5], double* grad);
+
+}  // namespace
+
 extern "C" int nmgp_logpos_sta(nmgp_ctx* c, const double* pars, const double hyper[5], int prior, double out5[5],
                                double* grad) {
     if (!c) return NMGP_E_NULL;
     if (!pars || !hyper || !out5) return nmgp_fail(c, NMGP_E_NULL, "pars/hyper/out5 must not be NULL");
     NMGP_TRY(require_data(c));
     HIP_TRY(c, hipSetDevice(c->device));
+    if (c->sep_algo == 1 && sta_blocks_fit(c->N)) {
+        int status = 0;
+        std::vector<char> bad(1, 0);
+        NMGP_TRY(sta_batch_core(c, pars, 1, hyper, prior, out5, grad, &status, bad, SepChunkSubjects()));      // the resident subject
+        if (!bad[0]) {
+            c->last_sep_attempts = 0;
+            return 0;
+        }
+    }
+    return logpos_sta_retry(c, pars, hyper, prior, out5, grad);
+}
+
+namespace {
+
+int logpos_sta_retry(nmgp_ctx* c, const double* pars, const double hyper[5], int prior, double out5[5], double* grad) {
     const int N = c->N, M = c->M, T = c->T;
     const size_t P = (size_t)T + 3;
     const double mu_l = hyper[0], sd_l = hyper[1], a = hyper[2], b = hyper[3], cc = hyper[4];
@@ -1110,6 +1144,8 @@ extern "C" int nmgp_logpos_sta(nmgp_ctx* c, const double* pars, const double hyp
     return 0;
 }
 
+}  // namespace
+
 // =================================================================================================
 // stationary objective, B chains per launch sequence
 // =================================================================================================
@@ -1124,8 +1160,8 @@ extern "C" int nmgp_logpos_sta(nmgp_ctx* c, const double* pars, const double hyp
 //   d ll / dB, d ll / d sigma2 as in sep_batch_core
 // -- no N x N weighted sum, no per-location adjoint, no K_x read back.  The factorisation runs the substitution-based (`precise`)
 // panel kernels, whose bits do not depend on the schedule the batch size selects: a chain's result does not depend on its
-// neighbours, and B = 1 runs the same kernels.  A chain that fails numerically is re-evaluated through nmgp_logpos_sta (the
-// reference's jitter retries); NMGP_SEP=eig and N beyond the block kernel's offsets evaluate chain by chain.
+// neighbours, and B = 1 runs the same kernels (nmgp_logpos_sta is that batch of one).  A chain that fails numerically is re-evaluated
+// through logpos_sta_retry (the reference's jitter retries); NMGP_SEP=eig and N beyond the block kernel's offsets evaluate chain by chain.
 namespace {
 
 struct StaBatchLayout {
@@ -1344,7 +1380,7 @@ extern "C" int nmgp_sta_batch_eval(nmgp_ctx* c, const double* pars, int B, const
     SepResidentSwap swap(c);
     auto one_by_one = [&](int b) -> int {
         if (multi) NMGP_TRY(swap.to(b / cps));
-        int rc = nmgp_logpos_sta(c, pars + (size_t)b * P, hyper, prior, out5 + (size_t)b * 5, want_grad ? grad + (size_t)b * P : nullptr);
+        int rc = logpos_sta_retry(c, pars + (size_t)b * P, hyper, prior, out5 + (size_t)b * 5, want_grad ? grad + (size_t)b * P : nullptr);
         if (rc < 0) return rc;
         if (rc > 0) {
             for (int k = 0; k < 5; ++k) out5[(size_t)b * 5 + k] = std::nan("");
@@ -1355,10 +1391,8 @@ extern "C" int nmgp_sta_batch_eval(nmgp_ctx* c, const double* pars, int B, const
         }
         return 0;
     };
-    // (the block kernels address a block with 32-bit byte offsets, as the separable entry's: N <= 11,584 -- beyond that, and for the
-    // eigen formulation, the chains are evaluated one by one)
-    const bool blocks_fit = (long long)(2 * (long long)N + 18) * N * 8 < 0x7fffffffLL;
-    if (c->sep_algo != 1 || !blocks_fit) {
+    // (beyond the block kernels' offsets, and for the eigen formulation, the chains are evaluated one by one)
+    if (c->sep_algo != 1 || !sta_blocks_fit(N)) {
         for (int b = 0; b < B; ++b) NMGP_TRY(one_by_one(b));
         return 0;
     }

@@ -10,8 +10,9 @@ from conftest import STA_KEYS
 from nonstationary_multivariate_gaussian_process_amd import sim
 
 # (N, M): even and odd N (the two block-build kernels: 128 x 32 tiles with 16-byte stores / 64 x 64 tiles), the 64- and 128-wide tile
-# edges (63 / 64 / 65, 127 / 128 / 129), more than one tile per column group of the reduction and its stride-256 loop (257: 15 tiles),
-# every M instantiation 1 .. 8
+# edges (63 / 64 / 65, 127 / 128 / 129), more than one tile per workgroup column of the block build (per = ceil(ntl / 8)) and the
+# stride-256 loop of the reduction's |alpha|^2 (257: 15 tiles, two per build column; the reduction's 128 column groups still hold one
+# tile each up to N = 960 -- two tiles per group: tests/sta_objective_cases.py), every M instantiation 1 .. 8
 SHAPES = [(1, 1), (2, 2), (8, 8), (63, 2), (64, 3), (65, 3), (127, 5), (128, 4), (129, 8), (200, 6), (257, 7)]
 UNSORTED = (65, 3)                       # the shape of the subject with unsorted, unevenly spaced inputs
 FD_SHAPES = [(8, 8), (65, 3), (127, 5)]  # the oracle's gradient against central differences

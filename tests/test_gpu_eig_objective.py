@@ -60,8 +60,9 @@ def ctxs():
 # ---------------------------------------------------------------------------------------------------
 # the entries and the measures (also run by the NMGP_POISON child, which imports this module)
 # ---------------------------------------------------------------------------------------------------
-def hold_sta_to_oracle(case, entry, layout, got, refs, rows=None):
-    """hold_to_oracle for the stationary layout: four blocks, five components (none of them a GP prior)."""
+def hold_sta_to_oracle(case, entry, layout, got, refs, rows=None, tag=None, bars=None):
+    """hold_to_oracle for the stationary layout: four blocks, five components (none of them a GP prior).  tag, bars: the record's
+    name and the table of block bars of another sweep (tests/test_gpu_sta_objective.py)."""
     model, N, M = layout
     (out0, g0), (out1, g1) = got[False], got[True]
     rows = range(len(refs)) if rows is None else rows
@@ -78,7 +79,7 @@ def hold_sta_to_oracle(case, entry, layout, got, refs, rows=None):
         eb, name = OC.block_errors(g0[b], gr0, layout)
         if not eb <= worst[0]:
             worst = (eb, name, b)
-        for name, err, bar in E.blocks_over_bar(g0[b], gr0, layout):
+        for name, err, bar in OC.blocks_over_bar(g0[b], gr0, layout, E.GRAD_TIGHT, E.BLOCK_BARS if bars is None else bars):
             bad.append("row %d: gradient block %s %.3g >= %.0e" % (b, name, err, bar))
         errs = dict(neglog=(relerr(out1[b][0], r1[0]), VAL_TOL), loglik1=(relerr(out1[b][1], r1[1]), LIK_TOL),
                     rest=(relerr(out1[b][2:], r1[2:]), VAL_TOL), prior_grad=(vec_relerr(g1[b] - g0[b], gr1 - gr0), GRAD_TOL))
@@ -89,10 +90,11 @@ def hold_sta_to_oracle(case, entry, layout, got, refs, rows=None):
         if out1[b][1] != out0[b][1]:
             bad.append("row %d: the likelihood changes with the prior flag: %r, %r" % (b, out1[b][1], out0[b][1]))
     e["block"] = worst[0]
-    tag = "%s/%s_%s/%s" % (SWEEP, model, case, entry)
+    tag = "%s/%s_%s/%s" % (SWEEP, model, case, entry) if tag is None else tag
     print("%s: loglik %.3g worst block %.3g (%s, row %d) | priors on: neglog %.3g loglik %.3g rest %.3g prior grad %.3g"
           % (tag, e["loglik"], worst[0], worst[1], worst[2], e["neglog"], e["loglik1"], e["rest"], e["prior_grad"]))
-    record_parity(tag + "/prior0", loglik=(e["loglik"], E.LIK_TIGHT), worst_block=(e["block"], E.GRAD_TIGHT))
+    worst_bar = (E.BLOCK_BARS if bars is None else bars).get(tuple(layout) + (worst[1],), E.GRAD_TIGHT)       # the bar that block is held to
+    record_parity(tag + "/prior0", loglik=(e["loglik"], E.LIK_TIGHT), worst_block=(e["block"], worst_bar))
     record_parity(tag + "/prior1", neglog=(e["neglog"], VAL_TOL), loglik=(e["loglik1"], LIK_TOL), other_components=(e["rest"], VAL_TOL),
                   prior_grad=(e["prior_grad"], GRAD_TOL))
     assert not bad, "%s:\n  " % tag + "\n  ".join(bad)
