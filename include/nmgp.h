@@ -113,6 +113,27 @@ int nmgp_had_clear_subjects(nmgp_ctx* ctx);
  * NMGP_E_STATE without a set, NMGP_E_UNSUPPORTED under NMGP_CHOL=rocsolver. */
 int nmgp_had_subjects_eval(nmgp_ctx* ctx, const double* pars, int B, int chains_per_subject, const double hyper[8], int prior,
                            double* out5, double* grad, int* status);
+/* MAP and posterior-draw prediction for the set: B = S * draws_per_subject rows (row s * draws_per_subject + h is draw h of
+ * subject s; pars [B, Pmax] in the padded layout above) at each subject's OWN new inputs, nmgp_predsample_had's schedule with the
+ * subject as a table look-up and its conventions for z / star_in / star_out (slot 0 = tilde_l* before exp, slots 1 + t = the raw
+ * slots of L*, ONE conditional variance per prior; z == NULL: the conditional means; star_in skips the regression, z must then be
+ * NULL) and for the variance ((1 + 1e-6)(L* L*^T)_mm - |L^-1 k_f|^2 + exp(tilde_sigma2_err); a value <= 0 is replaced by 1e-6).
+ *   xs [S, Smax]: only the first nstar[s] entries of row s are read; nstar == NULL: all Smax; 0 <= nstar[s] <= Smax.
+ *   indx_star == NULL: all M outputs per input, mean / var [B, Smax, M]; indx_star [S, Smax]: output indx_star[s, j] only,
+ *   mean / var [B, Smax] (only the labels of real slots are read and range-checked).  z, star_in, star_out: [B, Smax, 1 + T].
+ * A padded new-input slot (j >= nstar[s]) gets +0.0 in mean, var and star_out, and nothing is read from xs, indx_star, z or
+ * star_in there: every mask comes from the nstar and nobs tables.  status [B]: 0, a leading minor inside the subject's nobs[s], or
+ * NMGP_NUM_NAN (the finiteness tests cover the row's real parameter slots and real outputs); a failing draw has NaN in every real
+ * output slot of its row, its neighbours keep their bits, the call returns 0.  Chunks of draws (NMGP_PREDSAMPLE_CHUNK,
+ * NMGP_PREDSAMPLE_SLAB_GB, read at every call) are whole subjects or parts of ONE subject's draws, one synchronisation each; a
+ * row's bits depend neither on the chunking, nor on draws_per_subject, nor on the other subjects of the set, nor on the slice of
+ * riding rows a new input falls into.  The set with its cached prior factors, the resident subject and a pending batched result
+ * stay as they were.  NMGP_E_STATE without a set or with z and star_in both given; NMGP_E_SHAPE for B != S * draws_per_subject,
+ * draws_per_subject < 1, Smax < 1, an nstar[s] outside [0, Smax] or a real label outside [0, M); NMGP_E_UNSUPPORTED under
+ * NMGP_CHOL=rocsolver. */
+int nmgp_predsample_had_subjects(nmgp_ctx* ctx, const double* pars, int B, int draws_per_subject, const double hyper[8],
+                                 const double* xs, const int* indx_star, const int* nstar, int Smax, const double* z,
+                                 const double* star_in, double* mean, double* var, double* star_out, int* status);
 
 /* ---- Hadamard form of the separable model: one cross-output matrix shared by all observations ----
  * logpos.nlogpos_obj_hadamard / logpos_hadamard (logpos.py:465-563), prediction.point_predmap_hadamard / pointwise_predmap_hadmard

@@ -89,6 +89,8 @@ SIGNATURES = {
     "nmgp_had_set_subjects": (I, [V, P, ctypes.POINTER(ctypes.c_int), P, ctypes.POINTER(ctypes.c_int), I, I, I]),
     "nmgp_had_clear_subjects": (I, [V]),
     "nmgp_had_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_predsample_had_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
+                                         ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_covariance": (I, [V, P, P]),
     "nmgp_predict_hads": (I, [V, P, P, P, I, P, P, P]),
@@ -883,6 +885,66 @@ class Context:
         self.check(self.lib.nmgp_had_subjects_eval(self.h, ptr(pars), B, int(chains_per_subject), ptr(hyper), int(bool(prior)),
                                                    ptr(out), ptr(grad), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out, grad, status
+
+    def predsample_had_subjects(self, pars, hyper, xs, indx_star=None, nstar=None, draws_per_subject=1, z=None, star=None):
+        """MAP and posterior-draw prediction for the cohort (``nmgp_predsample_had_subjects``), padded arrays as the C entry takes
+        them: pars [B = S * draws_per_subject, Pmax] (row s * draws_per_subject + h = draw h of subject s), xs [S, Smax] of which
+        the first nstar[s] entries of row s are read (nstar=None: all Smax), indx_star [S, Smax] or None (all M outputs per input),
+        z / star [B, Smax, 1+T] as ``predsample_had``.  Returns (mean, var [B, Smax(, M)], star [B, Smax, 1+T], status [B]); padded
+        new-input slots hold +0.0, a draw with non-zero status has NaN in its real slots.  ``hadamard.cohort_predict`` is the ragged
+        form."""
+        cohort = getattr(self, "_cohort", None)
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        hyper, xs = as_f64(hyper).reshape(-1), as_f64(xs)
+        if hyper.shape[0] != 8:
+            raise NmgpError("hyper must have 8 entries, got %d" % hyper.shape[0])
+        H = int(draws_per_subject)
+        if pars.ndim != 2 or xs.ndim != 2 or xs.shape[1] < 1 or H < 1:
+            raise NmgpError("pars must be [B, Pmax], xs [S, Smax >= 1] and draws_per_subject >= 1; got %s, %s, %d"
+                            % (pars.shape, xs.shape, H))
+        S, Smax = xs.shape
+        B = pars.shape[0]
+        if cohort is not None:
+            M = cohort[2]
+            T = M * (M + 1) // 2
+            P_ = cohort[1] * (1 + T) + 1
+            if S != cohort[0] or B != S * H or pars.shape[1] != P_:
+                raise NmgpError("pars must be [S * draws_per_subject = %d, Nmax(1+T)+1 = %d] and xs [S = %d, Smax]; got %s, %s"
+                                % (cohort[0] * H, P_, cohort[0], pars.shape, xs.shape))
+        else:                            # (no set: the entry refuses the call; the shapes only have to be self-consistent)
+            M, T = 1, None
+        ipt = ctypes.POINTER(ctypes.c_int)
+        ia = na = None
+        if indx_star is not None:
+            if hasattr(indx_star, "detach"):
+                indx_star = indx_star.detach().cpu().numpy()
+            ia = np.ascontiguousarray(np.asarray(indx_star), dtype=np.int32)
+            if ia.shape != (S, Smax):
+                raise NmgpError("indx_star must be [S=%d, Smax=%d], got %s" % (S, Smax, ia.shape))
+        if nstar is not None:
+            na = np.ascontiguousarray(np.asarray(nstar).reshape(-1), dtype=np.int32)
+            if na.shape[0] != S:
+                raise NmgpError("nstar must have one entry per subject (S=%d), got %d" % (S, na.shape[0]))
+        if z is not None and star is not None:
+            raise NmgpError("star= replaces the regression: z must be None")
+        za, sa = (None if a is None else as_f64(a) for a in (z, star))
+        W = None if T is None else 1 + T
+        for name, a in (("z", za), ("star", sa)):
+            if a is not None and (a.ndim != 3 or a.shape[:2] != (B, Smax) or (W is not None and a.shape[2] != W)):
+                raise NmgpError("%s must be [B=%d, Smax=%d, 1+T], got %s" % (name, B, Smax, a.shape))
+        if W is None:
+            W = next((a.shape[2] for a in (za, sa) if a is not None), 2)
+        shape = (B, Smax, M) if ia is None else (B, Smax)
+        mean, var = np.empty(shape), np.empty(shape)
+        star_out = np.empty((B, Smax, W))
+        status = np.zeros(B, dtype=np.int32)
+        self.check(self.lib.nmgp_predsample_had_subjects(
+            self.h, ptr(pars), B, H, ptr(hyper), ptr(xs), None if ia is None else ia.ctypes.data_as(ipt),
+            None if na is None else na.ctypes.data_as(ipt), Smax, ptr(za), ptr(sa), ptr(mean), ptr(var), ptr(star_out),
+            status.ctypes.data_as(ipt)))
+        return mean, var, star_out, status
 
     def predict_had(self, pars, hyper, xs):
         """(mean [S, M], var [S, M], star [S, 1+T]) of the resident Hadamard subject at the new inputs xs."""

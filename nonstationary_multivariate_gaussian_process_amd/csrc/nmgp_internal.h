@@ -176,8 +176,8 @@ struct nmgp_ctx {
     double* ss_Y = nullptr;     // [S, N, M] row-major (k_sep_prep_b rotates it per chain)
     std::vector<PriorFactor> ss_priors;  // L: [S] x (ld x N), logdet: [S]
     // Hadamard cohort (nmgp_had_set_subjects, nmgp_hadamard_cohort.hip): hc_S ragged subjects padded to hc_Nmax.  Independent of the
-    // resident subject (N / M / T above are not touched); only nmgp_had_subjects_eval looks at it; nmgp_had_subjects_free drops it
-    // with its prior factors
+    // resident subject (N / M / T above are not touched); only nmgp_had_subjects_eval and nmgp_predsample_had_subjects look at it;
+    // nmgp_had_subjects_free drops it with its prior factors
     int hc_S = 0, hc_Nmax = 0, hc_M = 0, hc_T = 0;
     double* hc_x = nullptr;     // [S, Nmax] (zeros in the padded slots)
     double* hc_y = nullptr;     // [S, Nmax] (zeros in the padded slots)

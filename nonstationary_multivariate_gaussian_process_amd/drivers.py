@@ -1181,6 +1181,23 @@ class HadamardCohortMAP:
                 pars[int(s)] = p
         return pars, hist, alive
 
+    def predict(self, pars, xs, indx_star=None):
+        """MAP prediction (one draw, no noise) for every subject at its own new inputs, on the contexts and sets this object holds:
+        ONE ``nmgp_predsample_had_subjects`` per bucket.  ``pars[s]`` ``[P_s]`` (or ``[k, P_s]`` as :meth:`run` returns them: row 0
+        is used), ``xs[s]`` ``[S_s]``, ``indx_star[s]`` ``[S_s]`` labels or None (all M outputs).  Returns a list, in the caller's
+        subject order, of ``(mean [S_s(, M)], var, star [S_s, 1+T], status)``."""
+        from . import hadamard
+        if not (len(pars) == len(xs) == len(self.nobs)) or (indx_star is not None and len(indx_star) != len(self.nobs)):
+            raise ValueError("pars, xs (and indx_star) must hold one entry per subject")
+        out = [None] * len(self.nobs)
+        for ctx, idx in zip(self.ctxs, self.buckets):
+            res = hadamard.cohort_predict(ctx, [np.atleast_2d(np.asarray(pars[s], dtype=np.float64))[:1] for s in idx],
+                                          [xs[s] for s in idx], self.hyper,
+                                          indx_star=None if indx_star is None else [indx_star[s] for s in idx])
+            for s, (mean, var, star, status) in zip(idx, res):
+                out[int(s)] = (mean[0], var[0], star[0], int(status[0]))
+        return out
+
 
 class BatchedHMCHadamard(_HadamardSubject, LockStepHMC):
     """B independent HMC chains of the Hadamard nonseparable model of one subject in lock-step: every leapfrog step evaluates
@@ -1664,6 +1681,70 @@ def posterior_predict_hadamard(x, indx, y, hyper_pars, samples, xs, indx_star=No
     out = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
     out["L_star"] = star[:, :, 1:][status == 0]
     out["corr_quantiles"] = correlation_quantiles(out["L_star"], M)
+    return out
+
+
+def posterior_predict_hadamard_cohort(subjects, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, max_flop_waste=0.5,
+                                      ctxs=None):
+    """:func:`posterior_predict_hadamard` for a cohort of subjects of RAGGED size: ``subjects`` a list of ``(x, indx, y)``,
+    ``samples[s]`` [iters, chains, P_s] or [H, P_s] (thinned evenly to ``draws``; the same number of draws for every subject),
+    ``xs[s]`` [S_s] the subject's own new inputs, ``indx_star[s]`` [S_s] labels or None.  One subject set per bucket of
+    ``hadamard.cohort_buckets(nobs, max_flop_waste)`` and ONE ``nmgp_predsample_had_subjects`` per bucket (``ctxs``: one context per
+    bucket, default new ones, closed on return).  The normals of subject s come from ``default_rng(seed + s)`` -- z first, then the
+    y* normals, as the single-subject driver draws them from ``default_rng(seed)`` -- so a subject's band does not depend on who
+    else is in the cohort.  Returns a list, in the caller's subject order, of that function's dicts (``L_star`` and
+    ``corr_quantiles`` included)."""
+    from . import _lib, hadamard
+    subjects = [(np.ascontiguousarray(x, dtype=np.float64).reshape(-1), np.asarray(indx).reshape(-1).astype(np.int32),
+                 np.ascontiguousarray(y, dtype=np.float64).reshape(-1)) for x, indx, y in subjects]
+    n = len(subjects)
+    if n < 1 or len(samples) != n or len(xs) != n or (indx_star is not None and len(indx_star) != n):
+        raise ValueError("subjects, samples, xs (and indx_star) must be lists of one positive length")
+    Ms = sorted({int(np.unique(s[1]).shape[0]) for s in subjects})
+    if len(Ms) != 1:
+        raise ValueError("the subjects have different numbers of distinct labels: %s" % Ms)
+    M = Ms[0]
+    T = M * (M + 1) // 2
+    hist = []
+    for S_ in samples:
+        S_ = np.asarray(S_, dtype=np.float64)
+        S_ = S_.reshape(-1, S_.shape[-1])
+        if draws is not None and int(draws) < S_.shape[0]:
+            S_ = S_[np.unique(np.round(np.linspace(0, S_.shape[0] - 1, int(draws))).astype(int))]
+        hist.append(S_)
+    H = hist[0].shape[0]
+    if any(h.shape[0] != H for h in hist):
+        raise ValueError("every subject must bring the same number of draws after thinning; got %s" % [h.shape[0] for h in hist])
+    hyper = np.array([float(hyper_pars[k]) for k in SVC_HYPER_KEYS])
+    xs = [np.asarray(v, dtype=np.float64).reshape(-1) for v in xs]
+    zs, zys = [], []
+    for s in range(n):
+        rng = np.random.default_rng(seed + s)
+        zs.append(rng.standard_normal((H, xs[s].shape[0], 1 + T)))
+        zys.append(rng.standard_normal((H, xs[s].shape[0]) + (() if indx_star is not None else (M,))))
+    nobs = [s[0].shape[0] for s in subjects]
+    buckets = hadamard.cohort_buckets(nobs, max_flop_waste)
+    if ctxs is not None and len(ctxs) != len(buckets):
+        raise ValueError("%d contexts for %d buckets" % (len(ctxs), len(buckets)))
+    out = [None] * n
+    for b, idx in enumerate(buckets):
+        ctx = ctxs[b] if ctxs is not None else _lib.Context()
+        try:
+            ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=M)
+            res = hadamard.cohort_predict(ctx, [hist[s] for s in idx], [xs[s] for s in idx], hyper,
+                                          indx_star=None if indx_star is None else [indx_star[s] for s in idx],
+                                          z=[zs[s] for s in idx])
+        finally:
+            if ctxs is None:
+                ctx.close()
+            elif ctx.h:
+                ctx.had_clear_subjects()
+        for s, (mean, var, star, status) in zip(idx, res):
+            s = int(s)
+            d = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zys[s], star[:, :, 0], status)
+            d["L_star"] = star[:, :, 1:][status == 0]
+            d["corr_quantiles"] = correlation_quantiles(d["L_star"], M)
+            out[s] = d
     return out
 
 

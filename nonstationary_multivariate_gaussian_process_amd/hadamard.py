@@ -24,7 +24,9 @@ Under this package's OWN names (the reference has none for them, so nothing is i
   form of the reference's ``test_predmap_SVC_hadamard``;
 * ``cohort_pack`` / ``cohort_unpack`` / ``cohort_buckets``: host helpers of the cohort entry (``Context.had_set_subjects`` /
   ``had_subjects_eval``: S subjects of ragged size, padded to one order, S x k chains per launch sequence) -- the padded parameter
-  layout and the grouping of subjects of similar size; ``drivers.HadamardCohortMAP`` is the MAP loop on top of them.
+  layout and the grouping of subjects of similar size; ``drivers.HadamardCohortMAP`` is the MAP loop on top of them;
+* ``cohort_predict`` (with ``cohort_pack_inputs`` / ``cohort_unpack_outputs``): MAP and posterior-draw prediction for the cohort at
+  each subject's own new inputs, all subjects and draws in one device call (``nmgp_predsample_had_subjects``).
 
 Not provided: ``indexedpoint_predmap_SVC_hadamard`` / ``test_predmap_SVC_hadamard`` themselves (their variance is output 0's for
 every label; INTEGRATION.md says why).  The separable Hadamard model (``nlogpos_obj_hadamard``, ``point_predmap_hadamard``, ...) is
@@ -362,3 +364,74 @@ def cohort_buckets(nobs, max_flop_waste=0.5):
     if cur:
         buckets.append(np.array(cur, dtype=np.int64))
     return buckets
+
+
+# ---- prediction for the cohort: the padded new-input arrays of nmgp_predsample_had_subjects ------------------------------------------
+def cohort_pack_inputs(arrays, nstar=None, Smax=None, fill=0.0, dtype=np.float64):
+    """Ragged per-subject new-input arrays -> one padded array.  ``arrays[s]`` is ``[S_s]`` (``xs``, ``indx_star``) -> ``[S, Smax]``;
+    or ``[k, S_s, W]`` (``z``, ``star``; the same k and W for every subject) -> ``[S k, Smax, W]``, row ``s k + j`` = draw j of
+    subject s.  ``Smax`` defaults to ``max(S_s)`` (at least 1: a cohort with nothing to predict still has one padded slot);
+    ``fill`` goes into every padded slot (the device never reads those).  Returns ``(padded, nstar)``, nstar an int32 ``[S]``."""
+    arrs = [_np(a) for a in arrays]
+    if nstar is None:
+        nstar = [a.shape[0] if a.ndim == 1 else a.shape[1] for a in arrs]
+    nstar = np.asarray([int(n) for n in nstar], dtype=np.int32)
+    Smax = max(1, int(nstar.max())) if Smax is None else int(Smax)
+    if len(arrs) != nstar.shape[0] or len(arrs) < 1 or nstar.max() > Smax or Smax < 1:
+        raise ValueError("%d arrays for %d subjects, or a subject with more new inputs than Smax = %d" % (len(arrs), nstar.shape[0], Smax))
+    if arrs[0].ndim == 1:
+        out = np.full((len(arrs), Smax), fill, dtype=dtype)
+        for s, (a, n) in enumerate(zip(arrs, nstar)):
+            if a.shape != (n,):
+                raise ValueError("subject %d: expected [%d], got %s" % (s, n, a.shape))
+            out[s, :n] = a
+        return out, nstar
+    k, W = arrs[0].shape[0], arrs[0].shape[2]
+    out = np.full((len(arrs) * k, Smax, W), fill, dtype=dtype)
+    for s, (a, n) in enumerate(zip(arrs, nstar)):
+        if a.shape != (k, n, W):
+            raise ValueError("subject %d: expected [%d, %d, %d], got %s" % (s, k, n, W, a.shape))
+        out[s * k:(s + 1) * k, :n] = a
+    return out, nstar
+
+
+def cohort_unpack_outputs(A, nstar, draws_per_subject=1):
+    """The inverse on the output side: ``[S k, Smax, ...]`` -> a list of S arrays ``[k, S_s, ...]`` (copies); a status vector
+    ``[S k]`` -> a list of ``[k]``."""
+    A, k = np.asarray(A), int(draws_per_subject)
+    nstar = [int(n) for n in nstar]
+    if A.shape[0] != len(nstar) * k or (A.ndim > 1 and max(nstar) > A.shape[1]):
+        raise ValueError("array %s does not fit %d subjects x %d draws of at most Smax new inputs" % (A.shape, len(nstar), k))
+    if A.ndim == 1:
+        return [A[s * k:(s + 1) * k].copy() for s in range(len(nstar))]
+    return [A[s * k:(s + 1) * k, :n].copy() for s, n in enumerate(nstar)]
+
+
+def cohort_predict(ctx, draws, xs, hyper, indx_star=None, z=None, star=None):
+    """MAP and posterior-draw prediction for the cohort ``ctx`` holds (``Context.had_set_subjects``) at each subject's OWN new
+    inputs, in ONE device call (``nmgp_predsample_had_subjects``).  Ragged lists in the set's subject order: ``draws[s]`` ``[H, P_s]``
+    (or ``[P_s]``: H = 1; the same H for every subject), ``xs[s]`` ``[S_s]`` (``S_s = 0`` allowed), ``indx_star[s]`` ``[S_s]`` labels
+    (None: all M outputs per input), ``z[s]`` / ``star[s]`` ``[H, S_s, 1+T]`` as ``Context.predsample_had`` takes them.  Returns a list
+    of per-subject ``(mean [H, S_s(, M)], var, star [H, S_s, 1+T], status [H])``; a draw with non-zero status has NaN moments."""
+    cohort = getattr(ctx, "_cohort", None)
+    if cohort is None:
+        raise _lib.NmgpError("cohort_predict: no cohort is set (Context.had_set_subjects)")
+    S, Nmax, M = cohort
+    if not (len(draws) == len(xs) == S) or any(a is not None and len(a) != S for a in (indx_star, z, star)):
+        raise _lib.NmgpError("cohort_predict: draws, xs (and indx_star, z, star) must be lists of one entry per subject (S = %d)" % S)
+    vs = [np.atleast_2d(_np(v)) for v in draws]
+    T, H = _cohort_T(M), vs[0].shape[0]
+    nobs = []
+    for s, v in enumerate(vs):
+        n, rem = divmod(v.shape[1] - 1, 1 + T)
+        if rem or v.shape[0] != H:
+            raise _lib.NmgpError("cohort_predict: draws[%d] %s is not [H = %d, N_s (1 + T) + 1]" % (s, v.shape, H))
+        nobs.append(n)
+    x2, nstar = cohort_pack_inputs([_np(v).reshape(-1) for v in xs])
+    Smax = x2.shape[1]
+    i2 = None if indx_star is None else cohort_pack_inputs([_np(v).reshape(-1) for v in indx_star], nstar, Smax, 0, np.int32)[0]
+    z2, s2 = (None if a is None else cohort_pack_inputs([_np(v).reshape(H, int(n), 1 + T) for v, n in zip(a, nstar)], nstar, Smax)[0]
+              for a in (z, star))
+    mean, var, st, status = ctx.predsample_had_subjects(cohort_pack(vs, nobs, M, Nmax=Nmax), hyper, x2, indx_star=i2, nstar=nstar,
+                                                        draws_per_subject=H, z=z2, star=s2)
+    return list(zip(*(cohort_unpack_outputs(a, nstar, H) for a in (mean, var, st, status))))
