@@ -178,6 +178,27 @@ int nmgp_hadst_covariance(nmgp_ctx* ctx, const double* pars, double* out /*[N,N]
 int nmgp_predict_hadst(nmgp_ctx* ctx, const double* pars /*[H,T+3]*/, int H, const double* xs /*[S]*/,
                        const int* indx_star /*[S] or NULL*/, int S, double* mean, double* var, int* status /*[H] or NULL*/);
 
+/* ---- the cohort of ragged Hadamard subjects under the separable and the stationary model ---------
+ * Both entries read the set of nmgp_had_set_subjects (S subjects padded to Nmax <= 3500; see there for the padding) and follow
+ * nmgp_had_subjects_eval: B = S * chains_per_subject rows, row s * chains_per_subject + k is chain k of subject s; NMGP_E_STATE
+ * without a set, NMGP_E_SHAPE for B != S * chains_per_subject or chains_per_subject < 1, NMGP_E_UNSUPPORTED under
+ * NMGP_CHOL=rocsolver; chunks under NMGP_HAD_BATCH_SLAB_GB are whole subjects or parts of one subject's chains, one synchronisation
+ * per chunk; a chain's bits depend neither on the chunking nor on the other subjects of the set, and a subject with
+ * nobs[s] == Nmax gets the bits of the resident entry's likelihood.  hyper, the tuple, `prior`, status and the failing-row semantics
+ * are nmgp_hads_batch_eval's / nmgp_hadst_batch_eval's; a status k > 0 is a leading minor inside the subject's own nobs[s].  The three
+ * cohort entries may be interleaved on one set; the separable one shares the set's cached per-subject GP-prior factors.
+ *
+ * Separable: pars, grad [B, Pmax], Pmax = 2 Nmax + T + 1, the PADDED layout [tilde_l (Nmax) | tilde_sigma (Nmax) | L_vec (T) |
+ * tilde_sigma2_err]: subject s fills the first nobs[s] slots of the two curve blocks, the T shared slots and the last slot.  Padded
+ * slots are never read (a NaN or 1e300 there changes no bit, and the NMGP_NUM_NAN test covers the real slots only); their gradient
+ * is +0.0. */
+int nmgp_hads_subjects_eval(nmgp_ctx* ctx, const double* pars /*[B,Pmax]*/, int B, int chains_per_subject, const double hyper[9],
+                            int prior, double* out6 /*[B,6]*/, double* grad /*[B,Pmax] or NULL*/, int* status /*[B]*/);
+/* Stationary: the parameter vector has no per-observation part, so pars and grad are plain [B, T + 3].  No GP prior: neither the
+ * set's prior factors nor the prior stream are touched. */
+int nmgp_hadst_subjects_eval(nmgp_ctx* ctx, const double* pars /*[B,T+3]*/, int B, int chains_per_subject, const double hyper[5],
+                             int prior, double* out5 /*[B,5]*/, double* grad /*[B,T+3] or NULL*/, int* status /*[B]*/);
+
 /* ---- nonseparable ("SVC") objective:  logpos.nlogpos_obj_SVC / logpos_SVC, logpos.py:299-380 -- */
 /* hyper[8] = {mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L, a, b}.
  * out5 = {NegLog, loglik, log_prior_tilde_l, log_prior_uL_vecs, log_prior_sigma2_err} (the verbose tuple).

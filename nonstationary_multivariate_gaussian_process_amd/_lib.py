@@ -89,6 +89,8 @@ SIGNATURES = {
     "nmgp_had_set_subjects": (I, [V, P, ctypes.POINTER(ctypes.c_int), P, ctypes.POINTER(ctypes.c_int), I, I, I]),
     "nmgp_had_clear_subjects": (I, [V]),
     "nmgp_had_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_hads_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_hadst_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_had_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
                                          ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
@@ -885,6 +887,36 @@ class Context:
         self.check(self.lib.nmgp_had_subjects_eval(self.h, ptr(pars), B, int(chains_per_subject), ptr(hyper), int(bool(prior)),
                                                    ptr(out), ptr(grad), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out, grad, status
+
+    def _model_subjects_eval(self, fn, pars, hyper, prior, want_grad, chains_per_subject, width, plen, what):
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        cohort = getattr(self, "_cohort", None)
+        if pars.ndim != 2 or (cohort is not None and pars.shape[1] != plen(cohort[1], cohort[2] * (cohort[2] + 1) // 2)):
+            raise NmgpError("parameters must be [B, %s%s], got %s"
+                            % (what, "" if cohort is None else " = %d" % plen(cohort[1], cohort[2] * (cohort[2] + 1) // 2), pars.shape))
+        hyper = as_f64(hyper)
+        B, P_ = pars.shape
+        out = np.empty((B, width))
+        grad = np.empty((B, P_)) if want_grad else None
+        status = np.zeros(B, dtype=np.int32)
+        self.check(fn(self.h, ptr(pars), B, int(chains_per_subject), ptr(hyper), int(bool(prior)), ptr(out), ptr(grad),
+                      status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out, grad, status
+
+    def hads_subjects_eval(self, pars, hyper, prior=True, want_grad=False, chains_per_subject=1):
+        """The cohort under the separable model: pars [B = S * chains_per_subject, Pmax = 2 Nmax + T + 1] in the padded layout
+        (``hadamard_sep.cohort_pack``), hyper [9] as ``hads_batch_eval`` -> (out [B, 6], grad [B, Pmax] or None with +0.0 in the
+        padded slots, status [B]).  Padded parameter slots are never read."""
+        return self._model_subjects_eval(self.lib.nmgp_hads_subjects_eval, pars, hyper, prior, want_grad, chains_per_subject, 6,
+                                         lambda N, T: 2 * N + T + 1, "2 Nmax + T + 1")
+
+    def hadst_subjects_eval(self, pars, hyper, prior=True, want_grad=False, chains_per_subject=1):
+        """The cohort under the stationary model: pars [B = S * chains_per_subject, T + 3] (no per-observation part, so no padded
+        layout), hyper [5] as ``hadst_batch_eval`` -> (out [B, 5], grad [B, T + 3] or None, status [B])."""
+        return self._model_subjects_eval(self.lib.nmgp_hadst_subjects_eval, pars, hyper, prior, want_grad, chains_per_subject, 5,
+                                         lambda N, T: T + 3, "T + 3")
 
     def predsample_had_subjects(self, pars, hyper, xs, indx_star=None, nstar=None, draws_per_subject=1, z=None, star=None):
         """MAP and posterior-draw prediction for the cohort (``nmgp_predsample_had_subjects``), padded arrays as the C entry takes

@@ -609,6 +609,18 @@ int hadc_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, con
 
 }  // namespace
 
+// what the other two models' cohort entries (nmgp_hadamard_cohort_models.hip) share with this file: the set's two per-subject prior
+// factors of hyper[1..2] and hyper[4..5], and the masked trace
+int nmgp_hadc_priors(nmgp_ctx* c, const double* hyper, PriorFactor** p0, PriorFactor** p1) {
+    NMGP_TRY(hadc_get_prior(c, hyper[1], hyper[2], p0));
+    NMGP_TRY(hadc_get_prior(c, hyper[4], hyper[5], p1));
+    return hadc_get_prior(c, hyper[1], hyper[2], p0);
+}
+void nmgp_hadc_trace(hipStream_t s, const double* alpha, const double* Sinv, int ld, int N, const int* nobs, int cps, double* out,
+                     double ssign, int batch) {
+    NMGP_LAUNCH(k_hadc_trace, dim3(batch), dim3(1024), 0, s, alpha, Sinv, ld, N, nobs, cps, out, ssign);
+}
+
 void nmgp_had_subjects_free(nmgp_ctx* c) {
     if (c->hc_x) hipFree(c->hc_x);
     if (c->hc_y) hipFree(c->hc_y);
@@ -699,29 +711,12 @@ extern "C" int nmgp_had_subjects_eval(nmgp_ctx* c, const double* pars, int B, in
     const bool want_grad = grad != nullptr;
     // one pair of factors per subject (the cache is a vector: the second look-up may move its elements, so the first is re-resolved)
     PriorFactor *p0 = nullptr, *p1 = nullptr;
-    NMGP_TRY(hadc_get_prior(c, hyper[1], hyper[2], &p0));
-    NMGP_TRY(hadc_get_prior(c, hyper[4], hyper[5], &p1));
-    NMGP_TRY(hadc_get_prior(c, hyper[1], hyper[2], &p0));
-    double cap_gb = 96.0;
-    if (const char* e = std::getenv("NMGP_HAD_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
+    NMGP_TRY(nmgp_hadc_priors(c, hyper, &p0, &p1));
     const size_t per_chain = had_layout<HadCohort>(1, N, M, T, want_grad).total * sizeof(double);
-    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
-    Bc = std::min(Bc, 65535);                      // the chain is a grid dimension
-    if (Bc < 1)
-        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the Hadamard cohort at Nmax = %d needs %.1f GB of device workspace, above the "
-                         "NMGP_HAD_BATCH_SLAB_GB cap of %.0f GB", N, per_chain / 1e9, cap_gb);
-    // a chunk is a whole number of subjects, or a part of ONE subject's chains (then every chain of the chunk is that subject's)
-    const bool split = cps > Bc;
-    if (!split) Bc = (Bc / cps) * cps;
-    for (int b0 = 0; b0 < B;) {
-        const int s0 = b0 / cps;
-        int nb = std::min(Bc, B - b0);
-        if (split) nb = std::min(nb, (s0 + 1) * cps - b0);
-        NMGP_TRY(hadc_eval_chunk(c, pars + (size_t)b0 * P, nb, s0, split ? nb : cps, hyper, prior, p0, p1, out5 + (size_t)b0 * 5,
-                                 want_grad ? grad + (size_t)b0 * P : nullptr, status + b0));
-        b0 += nb;
-    }
-    return 0;
+    return hadc_for_chunks(c, B, cps, per_chain, "Hadamard cohort", [&](int b0, int nb, int s0, int ccps) {
+        return hadc_eval_chunk(c, pars + (size_t)b0 * P, nb, s0, ccps, hyper, prior, p0, p1, out5 + (size_t)b0 * 5,
+                               want_grad ? grad + (size_t)b0 * P : nullptr, status + b0);
+    });
 }
 
 // ---- MAP and posterior-draw prediction for the set: nmgp_predsample_had_subjects -------------------------------------------------------

@@ -1,0 +1,828 @@
+// The cohort of ragged Hadamard subjects (nmgp_had_set_subjects, nmgp_hadamard_cohort.hip) under the other two models:
+// nmgp_hads_subjects_eval (separable) and nmgp_hadst_subjects_eval (stationary).
+//
+// The set, its padding argument and its chunking rule are nmgp_hadamard_cohort.hip's: every subject is padded to Nmax with decoupled
+// unit observations, the padded part of every factor is the identity, and log det, z, alpha, the Mahalanobis terms and the prior
+// log-determinants gain exact zeros.  What does NOT take care of itself, per model:
+//   separable    tr S^-1 (one per padded observation), the N log 2 pi of the TWO GP-prior terms, the two centred prior right-hand
+//                sides, and the label-segmented reduction of d / d L_vec: the set's labels are zero-padded, so an unmasked walk would
+//                add the padded rows to the slots of label 0 (their partial rows are written as zeros here as well)
+//   stationary   tr S^-1, and the adjoint sums: a padded i has G_ii = -1/2 (the -1 on the padded diagonal of -S^-1), which would reach
+//                a_s (d / d tilde_sigma) and, through the zero-padded labels, the label-0 slots of L; there is no prior stream
+// The rule of nmgp_hadamard_cohort.hip holds: k_gibbs_*<M, true>, k_hads_* and k_hadst_* are shared by entries whose bits are pinned,
+// so no mask is threaded through them.  The kernels below are siblings with the originals' 64 x 64 tile, lane mapping, LDS staging,
+// expression order and fixed summation order, blockIdx.z = chain, subject = chain / cps of the chunk; a subject with N_s = Nmax gets
+// the resident path's bits.  Every mask comes from the device table of the subjects' sizes (nobs), never from a padded slot.
+//
+// Separable padded layout: [tilde_l (Nmax) | tilde_sigma (Nmax) | L_vec (T) | tilde_sigma2_err], Pmax = 2 Nmax + T + 1; subject s fills
+// the first nobs[s] slots of the two curve blocks.  The stationary vector has no per-observation part: [B, T + 3] as it is.
+#include "nmgp_hadamard_common.h"
+
+#include <algorithm>
+
+using namespace nmgpk;
+
+namespace {
+
+inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
+
+// ---- separable ------------------------------------------------------------------------------------------------------------------------
+
+// Real i: ell = exp(tilde_l), sig = exp(tilde_sigma), Rv[i, 0..M) = row c_i of the chain's L, zero-padded (k_hads_prep).  Padded i:
+// ell = sig = 1, Rv = 0 -- written, so that no later kernel reads what nobody wrote, and without reading the padded parameter slots.
+__global__ void k_hadcs_prep(const double* __restrict__ pars, const int* __restrict__ indx, const int* __restrict__ nobs, int cps,
+                             int N, int M, int T, double* __restrict__ ell, double* __restrict__ sig, double* __restrict__ Rv) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int sub = blockIdx.y / cps;                             // blockIdx.y = chain
+    const int Ns = nobs[sub];
+    pars += (size_t)blockIdx.y * ((size_t)2 * N + T + 1);
+    indx += (size_t)sub * N;
+    ell += (size_t)blockIdx.y * N;
+    sig += (size_t)blockIdx.y * N;
+    Rv += (size_t)blockIdx.y * N * M;
+    if (i >= Ns) {
+        ell[i] = 1.0;
+        sig[i] = 1.0;
+        for (int m = 0; m < M; ++m) Rv[(size_t)i * M + m] = 0.0;
+        return;
+    }
+    ell[i] = exp(pars[i]);
+    sig[i] = exp(pars[N + i]);
+    const int c = indx[i];
+    const double* u = pars + (size_t)2 * N + c * (c + 1) / 2;
+    for (int m = 0; m < M; ++m) Rv[(size_t)i * M + m] = (m <= c) ? u[m] : 0.0;
+}
+
+// k_gibbs_cov<M, true> on the real observations, delta_ij on the padded ones (k_hadc_cov with the amplitude s_i s_j).  In the lower
+// triangle a real row has real columns only, so the mask is the row's.  A tile whose rows are all padded only stores.
+template <int M>
+__global__ __launch_bounds__(256) void k_hadcs_cov(const double* __restrict__ x, const double* __restrict__ ell,
+                                                    const double* __restrict__ sig, const double* __restrict__ Rv,
+                                                    const double* __restrict__ pars, long long P, const int* __restrict__ nobs, int cps,
+                                                    double* __restrict__ S, int ld, int N, long long sstride) {
+    constexpr int TJ = 64;
+    __shared__ double sx[TJ], sl[TJ], ss[TJ], sR[TJ * M];
+    const int I = blockIdx.x, J = blockIdx.y;
+    if (I < J) return;
+    const int sub = blockIdx.z / cps;
+    const int Ns = nobs[sub];
+    x += (size_t)sub * N;
+    ell += (size_t)blockIdx.z * N;
+    sig += (size_t)blockIdx.z * N;
+    Rv += (size_t)blockIdx.z * N * M;
+    pars += (size_t)blockIdx.z * P;
+    S += (size_t)blockIdx.z * sstride;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    const int i = I * 64 + lane;
+    if (I * 64 >= Ns) {                                      // every row of the tile is padded: store only
+        if (i >= N) return;
+        for (int jj = 0; jj < TJ / 4; ++jj) {
+            const int j = j0 + w * (TJ / 4) + jj;
+            if (j >= N) break;
+            if (i < j) continue;
+            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
+        }
+        return;
+    }
+    if (tid < TJ) {
+        const int j = j0 + tid;
+        sx[tid] = (j < Ns) ? x[j] : 0.0;
+        sl[tid] = (j < Ns) ? ell[j] : 1.0;
+        ss[tid] = (j < Ns) ? sig[j] : 1.0;
+    }
+    for (int k = tid; k < TJ * M; k += 256) {
+        const size_t g = (size_t)j0 * M + k;
+        sR[k] = (g < (size_t)Ns * M) ? Rv[g] : 0.0;
+    }
+    __syncthreads();
+    if (i >= N) return;
+    const bool real = i < Ns;
+    const int ic = real ? i : 0;
+    const double sigma2 = exp(pars[P - 1]);
+    const double xi = x[ic], li = ell[ic], si = sig[ic];
+    const double xi2 = xi * xi, li2 = li * li;
+    double ri[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
+#pragma unroll 2
+    for (int jj = 0; jj < TJ / 4; ++jj) {
+        const int k = w * (TJ / 4) + jj;
+        const int j = j0 + k;
+        if (j >= N) break;
+        if (i < j) continue;
+        if (!real) {
+            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
+            continue;
+        }
+        const double xj = sx[k], lj = sl[k];
+        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);                           // kernels.py:20
+        const double A = li2 + lj * lj;                                                  // kernels.py:69
+        double kv = (si * ss[k]) * sqrt(2.0 * (li * lj) / A) * exp(-dist / A);           // kernels.py:70-72
+        if (i == j) kv = NMGP_JITTER + kv;                                               // kernels.py:64
+        double b = 0.0;
+#pragma unroll
+        for (int m = 0; m < M; ++m) b += ri[m] * sR[k * M + m];
+        double v = kv * b;
+        if (i == j) v += sigma2;
+        S[(size_t)j * ld + i] = v;
+    }
+}
+
+// two-column prior right-hand side (k_two_col_rhs_b): tilde_l - mu_l and tilde_sigma - mu_s on the real slots, zeros on the padded
+// ones, whose parameter slots are not read
+__global__ void k_hadcs_prior_rhs(const double* __restrict__ pars, const int* __restrict__ nobs, int cps, int N, int T, double mu_l,
+                                  double mu_s, double* __restrict__ R) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= N) return;
+    const int Ns = nobs[b / cps];
+    pars += (size_t)b * ((size_t)2 * N + T + 1);
+    const bool real = i < Ns;
+    R[((size_t)2 * b) * N + i] = real ? pars[i] - mu_l : 0.0;
+    R[((size_t)2 * b + 1) * N + i] = real ? pars[N + i] - mu_s : 0.0;
+}
+
+// k_hads_finalize with the subject's own N_s in the N log 2 pi of both GP-prior terms and the per-subject half log-determinants
+// (Nmax is the stride of the padded parameter layout only)
+__global__ void k_hadcs_finalize(const double* __restrict__ scal, const double* __restrict__ q, const double* __restrict__ hl_l,
+                                 const double* __restrict__ hl_s, const double* __restrict__ pars, const int* __restrict__ nobs,
+                                 int cps, int Nmax, int T, double a, double b, double var, double log_sd, int prior,
+                                 double* __restrict__ out6) {
+    if (threadIdx.x != 0) return;
+    const size_t P = (size_t)2 * Nmax + T + 1;
+    const int sub = blockIdx.x / cps;
+    const int N = nobs[sub];
+    hl_l += sub;
+    hl_s += sub;
+    scal += (size_t)blockIdx.x * 16;             // blockIdx.x = chain: [0] log det, [1] quadratic form, [8..13] the verbose tuple
+    out6 += (size_t)blockIdx.x * 16;
+    q += (size_t)blockIdx.x * 2;
+    pars += (size_t)blockIdx.x * P;
+    const double LOG2PI = 1.8378770664093453;
+    const double tse = pars[P - 1];
+    const double sigma2 = exp(tse);
+    const double loglik = -0.5 * scal[0] - 0.5 * scal[1];
+    const double lp_l = -0.5 * (N * LOG2PI + q[0]) - hl_l[0];
+    const double lp_s = -0.5 * (N * LOG2PI + q[1]) - hl_s[0];
+    double lp_L = 0.0;
+    for (int t = 0; t < T; ++t) {
+        const double v = pars[(size_t)2 * Nmax + t];
+        lp_L += -(v * v) / (2.0 * var) - log_sd - log(sqrt(2.0 * M_PI));
+    }
+    const double lp_s2 = (-a - 1.0) * log(sigma2) - b / sigma2;
+    double res = 0.0;
+    res += loglik;
+    if (prior) {
+        res += lp_l;
+        res += lp_s;
+        res += lp_L;
+        res += lp_s2;
+        res += tse;
+    }
+    out6[0] = -res;
+    out6[1] = loglik;
+    out6[2] = lp_l;
+    out6[3] = lp_s;
+    out6[4] = lp_L;
+    out6[5] = lp_s2;
+}
+
+// k_gibbs_adjoint<M, true> with j < N_s and i < N_s masks (k_hadc_adjoint with M + 2 components: slot 0 = tilde_l, slot 1 =
+// tilde_sigma, then the M row components): part[J][i][0 .. M + 2) of the real i, ZERO partial rows of the padded i (every J) and of
+// tiles with nothing real, so that the per-observation sums need no mask of their own.
+template <int M>
+__global__ __launch_bounds__(256) void k_hadcs_adjoint(const double* __restrict__ x, const double* __restrict__ ell,
+                                                        const double* __restrict__ sig, const double* __restrict__ Rv,
+                                                        const double* __restrict__ alpha, const double* __restrict__ Sneg, int ld,
+                                                        int N, const int* __restrict__ nobs, int cps, double* __restrict__ part,
+                                                        long long pstride) {
+    constexpr int TJ = 64, R0 = 2, W = M + R0;
+    __shared__ double sx[TJ], sl[TJ], ss[TJ], sR[TJ * M], sa[TJ];
+    __shared__ double red[2][4][64];
+    const int I = blockIdx.x, J = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    const size_t Nl = (size_t)N;
+    const int sub = blockIdx.z / cps;
+    const int Ns = nobs[sub];
+    {   // blockIdx.z = chain
+        const size_t z = blockIdx.z;
+        x += (size_t)sub * Nl;
+        ell += z * Nl;
+        sig += z * Nl;
+        Rv += z * Nl * M;
+        alpha += z * Nl;
+        Sneg += z * (size_t)ld * Nl;
+        part += z * (size_t)pstride;
+    }
+    const int i = I * 64 + lane;
+    const bool inN = i < N;
+    if (I * 64 >= Ns || j0 >= Ns) {                          // nothing real in the tile: zero partial rows
+        if (w == 0 && inN) {
+            double* o = part + ((size_t)J * Nl + i) * W;
+#pragma unroll
+            for (int t = 0; t < W; ++t) o[t] = 0.0;
+        }
+        return;
+    }
+    if (tid < TJ) {
+        const int j = j0 + tid;
+        sx[tid] = (j < Ns) ? x[j] : 0.0;
+        sl[tid] = (j < Ns) ? ell[j] : 1.0;
+        ss[tid] = (j < Ns) ? sig[j] : 1.0;
+        sa[tid] = (j < Ns) ? alpha[j] : 0.0;
+    }
+    for (int k = tid; k < TJ * M; k += 256) {
+        const size_t g = (size_t)j0 * M + k;
+        sR[k] = (g < (size_t)Ns * M) ? Rv[g] : 0.0;
+    }
+    __syncthreads();
+    const bool iv = i < Ns;
+    const int ic = iv ? i : Ns - 1;
+    const double xi = x[ic], li = ell[ic], si = sig[ic];
+    const double ai = alpha[ic];
+    const double xi2 = xi * xi, li2 = li * li;
+    double ri[M], acc[W];
+#pragma unroll
+    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
+#pragma unroll
+    for (int t = 0; t < W; ++t) acc[t] = 0.0;
+    if (iv) {
+        for (int jj = 0; jj < TJ / 4; ++jj) {
+            const int k = w * (TJ / 4) + jj;
+            const int j = j0 + k;
+            if (j >= Ns) break;
+            const double xj = sx[k], lj = sl[k];
+            const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
+            const double A = li2 + lj * lj;
+            const double k0 = (si * ss[k]) * sqrt(2.0 * (li * lj) / A) * exp(-dist / A);
+            const double kx = (i == j) ? (NMGP_JITTER + k0) : k0;
+            const double G = 0.5 * (ai * sa[k] + Sneg[(size_t)j * ld + i]);
+            const double gk = 2.0 * kx * G;
+            double dot = 0.0;
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                const double rj = sR[k * M + m];
+                acc[R0 + m] = fma(gk, rj, acc[R0 + m]);
+                dot = fma(ri[m], rj, dot);
+            }
+            const double gd = 2.0 * (G * dot) * k0;
+            acc[1] += gd;
+            if (i != j) {
+                const double dlogk = 0.5 - li2 / A + 2.0 * li2 * dist / (A * A);
+                acc[0] = fma(gd, dlogk, acc[0]);
+            }
+        }
+    }
+    double* o = part + ((size_t)J * Nl + (inN ? i : 0)) * W;
+#pragma unroll
+    for (int t = 0; t < W; ++t) {
+        red[t & 1][w][lane] = acc[t];
+        __syncthreads();
+        // (a padded i < Nmax has four zero accumulators: its row is written as +0.0)
+        if (w == 0 && inN) o[t] = (red[t & 1][0][lane] + red[t & 1][1][lane]) + (red[t & 1][2][lane] + red[t & 1][3][lane]);
+    }
+}
+
+// k_hads_grad_obs on the padded layout: per REAL observation the J partials summed in order, d NegLog / d tilde_l and / d tilde_sigma
+// with the prior gradients (R2: [Nmax, 2] column-major per chain), the summed row components into rsum for the label reduction; +0.0
+// in the padded curve slots (R2 is not applied there) and zero rsum rows; the sigma2 slot from the trace over the real observations.
+__global__ __launch_bounds__(256) void k_hadcs_grad_obs(const double* __restrict__ part, long long pstride, int NJ, int N, int M,
+                                                         int T, const int* __restrict__ nobs, int cps, const double* __restrict__ R2,
+                                                         const double* __restrict__ pars, const double* __restrict__ tr, double a,
+                                                         double b, int prior, double* __restrict__ rsum, double* __restrict__ grad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t P = (size_t)2 * N + T + 1;
+    const int Ns = nobs[blockIdx.y / cps];
+    {   // blockIdx.y = chain
+        const size_t z = blockIdx.y;
+        part += z * (size_t)pstride;
+        R2 += z * (size_t)2 * N;
+        pars += z * P;
+        tr += z * 2;
+        rsum += z * (size_t)N * M;
+        grad += z * P;
+    }
+    if (i == 0) {
+        const double sigma2 = exp(pars[P - 1]);
+        double g = sigma2 * (0.5 * (tr[0] - tr[1]));
+        if (prior) g += (-a - 1.0) + b / sigma2 + 1.0;
+        grad[P - 1] = -g;
+    }
+    if (i >= N) return;
+    if (i >= Ns) {
+        grad[i] = 0.0;
+        grad[(size_t)N + i] = 0.0;
+        for (int m = 0; m < M; ++m) rsum[(size_t)i * M + m] = 0.0;
+        return;
+    }
+    for (int t = 0; t < M + 2; ++t) {
+        double sacc = 0.0;
+        for (int J = 0; J < NJ; ++J) sacc += part[((size_t)J * N + i) * (M + 2) + t];
+        if (t < 2) {
+            if (prior) sacc -= R2[(size_t)t * N + i];
+            grad[(size_t)t * N + i] = -sacc;
+        } else {
+            rsum[(size_t)i * M + (t - 2)] = sacc;
+        }
+    }
+}
+
+// k_hads_grad_lvec over i < N_s only: the set's labels are zero-padded, so an unmasked walk would add the padded rows to label 0
+__global__ __launch_bounds__(256) void k_hadcs_grad_lvec(const double* __restrict__ rsum, const int* __restrict__ indx,
+                                                          const int* __restrict__ nobs, int cps, int N, int M, int T,
+                                                          const double* __restrict__ pars, double var, int prior,
+                                                          double* __restrict__ grad) {
+    __shared__ double sh[256];
+    const int t = blockIdx.x;
+    const size_t P = (size_t)2 * N + T + 1;
+    const int sub = blockIdx.y / cps;
+    const int Ns = nobs[sub];
+    indx += (size_t)sub * N;
+    rsum += (size_t)blockIdx.y * N * M;
+    pars += (size_t)blockIdx.y * P;
+    grad += (size_t)blockIdx.y * P;
+    int c = 0;
+    while ((c + 1) * (c + 2) / 2 <= t) ++c;
+    const int m = t - c * (c + 1) / 2;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < Ns; i += 256)
+        if (indx[i] == c) acc += rsum[(size_t)i * M + m];
+    acc = block_sum_256(acc, sh);
+    if (threadIdx.x == 0) {
+        if (prior) acc -= pars[(size_t)2 * N + t] / var;
+        grad[(size_t)2 * N + t] = -acc;
+    }
+}
+
+// ---- stationary -----------------------------------------------------------------------------------------------------------------------
+
+// B_f[a, b] = <row a of L, row b of L> of the packed lower triangle Lvec (hadst_bf of nmgp_hadamard_sta.hip)
+template <int M>
+__device__ inline double hadcst_bf(const double* __restrict__ Lvec, int a, int b) {
+    const int lo = a < b ? a : b;
+    double acc = 0.0;
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+        if (m <= lo) acc += Lvec[a * (a + 1) / 2 + m] * Lvec[b * (b + 1) / 2 + m];
+    return acc;
+}
+
+// hadst_stage of nmgp_hadamard_sta.hip with the subject's N_s as the bound of the j side: sp = {l, s2, sigma2_err}, sB = B_f [M, M],
+// su = x_j / l and sc = c_j of the real j (0 beyond).  The caller synchronises.
+template <int M>
+__device__ inline void hadcst_stage(const double* __restrict__ pars, long long P, const double* __restrict__ x,
+                                    const int* __restrict__ indx, int Ns, int j0, double* sp, double* sB, double* su, int* sc) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const int j = j0 + tid;
+        const double l = exp(pars[0]);
+        su[tid] = (j < Ns) ? x[j] / l : 0.0;
+        sc[tid] = (j < Ns) ? indx[j] : 0;
+        if (tid == 0) {
+            const double sg = exp(pars[1]);
+            sp[0] = l;
+            sp[1] = sg * sg;
+            sp[2] = exp(pars[P - 1]);
+        }
+    } else if (tid - 64 < M * M) {
+        const int k = tid - 64;
+        sB[k] = hadcst_bf<M>(pars + 2, k / M, k % M);
+    }
+}
+
+// k_hadst_cov on the real observations, delta_ij on the padded ones; a tile whose rows are all padded only stores
+template <int M>
+__global__ __launch_bounds__(256) void k_hadcst_cov(const double* __restrict__ x, const int* __restrict__ indx,
+                                                     const double* __restrict__ pars, long long P, const int* __restrict__ nobs,
+                                                     int cps, double* __restrict__ S, int ld, int N, long long sstride) {
+    constexpr int TJ = 64;
+    __shared__ double su[TJ], sB[M * M], sp[3];
+    __shared__ int sc[TJ];
+    const int I = blockIdx.x, J = blockIdx.y;
+    if (I < J) return;
+    const int sub = blockIdx.z / cps;
+    const int Ns = nobs[sub];
+    x += (size_t)sub * N;
+    indx += (size_t)sub * N;
+    pars += (size_t)blockIdx.z * P;
+    S += (size_t)blockIdx.z * sstride;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    const int i = I * 64 + lane;
+    if (I * 64 >= Ns) {                                      // every row of the tile is padded: store only
+        if (i >= N) return;
+        for (int jj = 0; jj < TJ / 4; ++jj) {
+            const int j = j0 + w * (TJ / 4) + jj;
+            if (j >= N) break;
+            if (i < j) continue;
+            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
+        }
+        return;
+    }
+    hadcst_stage<M>(pars, P, x, indx, Ns, j0, sp, sB, su, sc);
+    __syncthreads();
+    if (i >= N) return;
+    const bool real = i < Ns;
+    const int ic = real ? i : 0;
+    const double s2 = sp[1], s2e = sp[2];
+    const double ui = x[ic] / sp[0];
+    const double ui2 = ui * ui;
+    const double* bi = sB + indx[ic] * M;
+#pragma unroll 2
+    for (int jj = 0; jj < TJ / 4; ++jj) {
+        const int k = w * (TJ / 4) + jj;
+        const int j = j0 + k;
+        if (j >= N) break;
+        if (i < j) continue;
+        if (!real) {
+            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
+            continue;
+        }
+        const double uj = su[k];
+        const double dist = (ui2 + uj * uj) - 2.0 * (ui * uj);          // kernels.py:20
+        double kv = exp(-0.5 * dist) * s2;                              // kernels.py:42
+        if (i == j) kv = NMGP_JITTER + kv;                              // kernels.py:35
+        double v = kv * bi[sc[k]];
+        if (i == j) v += s2e;
+        S[(size_t)j * ld + i] = v;
+    }
+}
+
+// k_hadst_adjoint with i, j < N_s: part[t][J][i] (component-major) of the real i, ZERO for the padded i (every J) and for tiles with
+// nothing real, so that k_hadcst_grad_final reads nothing that nobody wrote.  A padded i has G_ii = -1/2; it reaches no sum.
+template <int M>
+__global__ __launch_bounds__(256) void k_hadcst_adjoint(const double* __restrict__ x, const int* __restrict__ indx,
+                                                         const double* __restrict__ pars, long long P,
+                                                         const double* __restrict__ alpha, const double* __restrict__ Sneg, int ld,
+                                                         int N, const int* __restrict__ nobs, int cps, double* __restrict__ part,
+                                                         long long pstride) {
+    constexpr int TJ = 64;
+    __shared__ double su[TJ], sB[M * M], sp[3], sR[TJ * M], sa[TJ];
+    __shared__ int sc[TJ];
+    __shared__ double red[2][4][64];
+    const int I = blockIdx.x, J = blockIdx.y, NJ = gridDim.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    const size_t Nl = (size_t)N;
+    const int sub = blockIdx.z / cps;
+    const int Ns = nobs[sub];
+    {   // blockIdx.z = chain
+        const size_t z = blockIdx.z;
+        x += (size_t)sub * Nl;
+        indx += (size_t)sub * Nl;
+        pars += z * (size_t)P;
+        alpha += z * Nl;
+        Sneg += z * (size_t)ld * Nl;
+        part += z * (size_t)pstride;
+    }
+    const int i = I * 64 + lane;
+    const bool inN = i < N;
+    if (I * 64 >= Ns || j0 >= Ns) {                          // nothing real in the tile: zeros
+        if (w == 0 && inN) {
+#pragma unroll
+            for (int t = 0; t < M + 2; ++t) part[((size_t)t * NJ + J) * Nl + i] = 0.0;
+        }
+        return;
+    }
+    hadcst_stage<M>(pars, P, x, indx, Ns, j0, sp, sB, su, sc);
+    if (tid < TJ) sa[tid] = (j0 + tid < Ns) ? alpha[j0 + tid] : 0.0;
+    for (int k = tid; k < TJ * M; k += 256) {           // r_j = row c_j of L, zero-padded to M
+        const int j = j0 + k / M, m = k % M;
+        const int cj = (j < Ns) ? indx[j] : 0;
+        sR[k] = (j < Ns && m <= cj) ? pars[2 + cj * (cj + 1) / 2 + m] : 0.0;
+    }
+    __syncthreads();
+    const bool iv = i < Ns;
+    const int ic = iv ? i : Ns - 1;
+    const double s2 = sp[1], ai = alpha[ic];
+    const double ui = x[ic] / sp[0];
+    const double ui2 = ui * ui;
+    const double* bi = sB + indx[ic] * M;
+    double acc[M + 2];
+#pragma unroll
+    for (int t = 0; t < M + 2; ++t) acc[t] = 0.0;
+    if (iv) {
+        for (int jj = 0; jj < TJ / 4; ++jj) {
+            const int k = w * (TJ / 4) + jj;
+            const int j = j0 + k;
+            if (j >= Ns) break;
+            const double uj = su[k];
+            const double dist = (ui2 + uj * uj) - 2.0 * (ui * uj);
+            const double e = exp(-0.5 * dist) * s2;
+            const double G = 0.5 * (ai * sa[k] + Sneg[(size_t)j * ld + i]);
+            const double ge = G * e;
+            const double gk = (i == j) ? G * (NMGP_JITTER + e) : ge;
+            const double gb = ge * bi[sc[k]];
+            acc[0] = fma(gb, dist, acc[0]);
+            acc[1] += gb;
+#pragma unroll
+            for (int m = 0; m < M; ++m) acc[2 + m] = fma(gk, sR[k * M + m], acc[2 + m]);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < M + 2; ++t) {
+        red[t & 1][w][lane] = acc[t];
+        __syncthreads();
+        // (a padded i < Nmax has four zero accumulators: +0.0)
+        if (w == 0 && inN)
+            part[((size_t)t * NJ + J) * Nl + i] =
+                (red[t & 1][0][lane] + red[t & 1][1][lane]) + (red[t & 1][2][lane] + red[t & 1][3][lane]);
+    }
+}
+
+// k_hadst_grad_final walking i < N_s only, with the subject's labels
+__global__ __launch_bounds__(256) void k_hadcst_grad_final(const double* __restrict__ part, long long pstride, int NJ, int N, int M,
+                                                            int T, const int* __restrict__ indx, const int* __restrict__ nobs, int cps,
+                                                            const double* __restrict__ pars, const double* __restrict__ tr, double mu_l,
+                                                            double var_l, double var_c, double a, double b, int prior,
+                                                            double* __restrict__ grad) {
+    __shared__ double sh[256];
+    const int t = blockIdx.x, P = T + 3;
+    const int sub = blockIdx.y / cps;
+    const int Ns = nobs[sub];
+    indx += (size_t)sub * N;
+    part += (size_t)blockIdx.y * (size_t)pstride;
+    pars += (size_t)blockIdx.y * P;
+    tr += (size_t)blockIdx.y * 2;
+    grad += (size_t)blockIdx.y * P;
+    if (t == P - 1) {                      // (uniform over the workgroup)
+        if (threadIdx.x == 0) {
+            const double sigma2 = exp(pars[P - 1]);
+            double g = sigma2 * (0.5 * (tr[0] - tr[1]));
+            if (prior) g += (-a - 1.0) + b / sigma2 + 1.0;
+            grad[P - 1] = -g;
+        }
+        return;
+    }
+    int comp = t, c = -1;                  // component of the partial rows; label of an L slot
+    if (t >= 2) {
+        const int tl = t - 2;
+        c = 0;
+        while ((c + 1) * (c + 2) / 2 <= tl) ++c;
+        comp = 2 + (tl - c * (c + 1) / 2);
+    }
+    const double* pc = part + (size_t)comp * NJ * N;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < Ns; i += 256) {
+        if (c >= 0 && indx[i] != c) continue;
+        double sacc = 0.0;
+        for (int J = 0; J < NJ; ++J) sacc += pc[(size_t)J * N + i];
+        acc += sacc;
+    }
+    acc = block_sum_256(acc, sh);
+    if (threadIdx.x == 0) {
+        double g = (t == 0) ? acc : 2.0 * acc;
+        if (prior && t == 0) g -= (pars[0] - mu_l) / var_l;
+        if (prior && t >= 2) g -= pars[t] / var_c;
+        grad[t] = -g;
+    }
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------------
+
+// what a model hook sees of a cohort chunk: the chunk's slice of the set's tables (chain z belongs to subject z / cps of the slice)
+struct CohChunk {
+    nmgp_ctx* c;
+    const HadLayout& L;
+    double* slab;
+    int B, s0, cps, N, M, T;
+    const double *x, *hyper;
+    const int *indx, *nobs;
+    int prior;
+    bool want_grad;
+    PriorFactor *p0, *p1;
+    double* at(size_t o) const { return slab + o; }
+};
+
+// The two models as the cohort schedule sees them (the Model of nmgp_hadamard_common.h with the subject as a table look-up); P,
+// part_width and extras are the resident models', at N = Nmax.
+struct CohSep {
+    static constexpr int WIDTH = 6;
+    static constexpr bool GP_PRIORS = true;
+    static constexpr const char* NOUN = "separable Hadamard cohort";
+    static size_t P(int N, int T) { return (size_t)2 * N + T + 1; }
+    static size_t part_width(int M) { return M + 2; }
+    template <class Take>
+    static void extras(HadLayout& L, Take take, size_t Bs, size_t N, int M, int, bool want_grad) {
+        L.o_ell = take(Bs * N); L.o_sig = take(Bs * N); L.o_Rv = take(Bs * N * M); L.o_R = take(Bs * N * 2); L.o_q = take(Bs * 2);
+        if (want_grad) { L.o_R2 = take(Bs * N * 2); L.o_rsum = take(Bs * N * M); }
+    }
+    // the real slots of a padded vector: the finiteness test covers these only
+    static bool finite_in(const double* p, size_t N, size_t Ns, int T) {
+        for (size_t t = 0; t < Ns; ++t)
+            if (!std::isfinite(p[t]) || !std::isfinite(p[N + t])) return false;
+        for (size_t t = 2 * N; t < 2 * N + T + 1; ++t)
+            if (!std::isfinite(p[t])) return false;
+        return true;
+    }
+    static int build_cov(const CohChunk& k) {
+        hipStream_t s = k.c->stream;
+        const int N = k.N, M = k.M, B = k.B;
+        double *dP = k.at(k.L.o_P), *ell = k.at(k.L.o_ell), *sig = k.at(k.L.o_sig), *Rv = k.at(k.L.o_Rv);
+        NMGP_LAUNCH(k_hadcs_prep, dim3(cdiv(N, 256), B), dim3(256), 0, s, dP, k.indx, k.nobs, k.cps, N, M, k.T, ell, sig, Rv);
+        const dim3 grid(cdiv(N, 64), cdiv(N, 64), B);
+        NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadcs_cov<MM>), grid, dim3(256), 0, s, k.x, ell, sig, Rv, dP, (long long)P(N, k.T), k.nobs,
+                                        k.cps, k.at(k.L.o_S), k.L.ld, N, k.L.bs));
+        return 0;
+    }
+    // hadc_eval_chunk's prior half with two columns per chain, then the finaliser
+    static int value_epilogue(const CohChunk& k, PriorStreamScope& ps) {
+        nmgp_ctx* c = k.c;
+        const int N = k.N, T = k.T, B = k.B, s0 = k.s0, cps = k.cps;
+        const NormalF32 nc(0.0, k.hyper[8]);
+        double *dP = k.at(k.L.o_P), *scal = k.at(k.L.o_scal), *R = k.at(k.L.o_R);
+        const long long f0 = (long long)k.p0->ld * N, f1 = (long long)k.p1->ld * N;
+        const double *L0 = k.p0->L + (size_t)s0 * f0, *L1 = k.p1->L + (size_t)s0 * f1;
+        {
+            NmgpStage sp(c, NMGP_STAGE_PRIOR, ps.sp, 0.0, 0.0);
+            NMGP_LAUNCH(k_hadcs_prior_rhs, dim3(cdiv(N, 256), B), dim3(256), 0, ps.sp, dP, k.nobs, cps, N, T, k.hyper[0], k.hyper[3], R);
+            prior_trsv(ps.sp, false, L0, k.p0->ld, f0, L1, k.p1->ld, f1, R, N, 2, B, cps);
+            col_sumsq(ps.sp, R, N, N, B * 2, k.at(k.L.o_q));
+            if (k.want_grad && k.prior) {
+                double* R2 = k.at(k.L.o_R2);
+                HIP_TRY(c, hipMemcpyAsync(R2, R, (size_t)B * N * 2 * sizeof(double), hipMemcpyDeviceToDevice, ps.sp));
+                prior_trsv(ps.sp, true, L0, k.p0->ld, f0, L1, k.p1->ld, f1, R2, N, 2, B, cps);
+            }
+        }
+        ps.done();
+        ps.join();
+        NmgpStage sp(c, NMGP_STAGE_REDUCE);
+        NMGP_LAUNCH(k_hadcs_finalize, dim3(B), dim3(64), 0, c->stream, scal, k.at(k.L.o_q), k.p0->logdet + s0, k.p1->logdet + s0, dP, k.nobs,
+                    cps, N, T, k.hyper[6], k.hyper[7], nc.var, nc.log_sd, k.prior, scal + 8);
+        return 0;
+    }
+    static int adjoint_grad(const CohChunk& k) {
+        hipStream_t s = k.c->stream;
+        const int N = k.N, M = k.M, T = k.T, B = k.B, NJ = (N + 63) / 64;
+        const long long pstride = (long long)k.L.part_per;
+        const NormalF32 nc(0.0, k.hyper[8]);
+        double *dP = k.at(k.L.o_P), *part = k.at(k.L.o_part), *rsum = k.at(k.L.o_rsum), *dg = k.at(k.L.o_grad);
+        const dim3 grid(cdiv(N, 64), cdiv(N, 64), B);
+        NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadcs_adjoint<MM>), grid, dim3(256), 0, s, k.x, k.at(k.L.o_ell), k.at(k.L.o_sig), k.at(k.L.o_Rv),
+                                        k.at(k.L.o_alpha), k.at(k.L.o_Sneg), N, N, k.nobs, k.cps, part, pstride));
+        NMGP_LAUNCH(k_hadcs_grad_obs, dim3(cdiv(N, 256), B), dim3(256), 0, s, part, pstride, NJ, N, M, T, k.nobs, k.cps, k.at(k.L.o_R2), dP,
+                    k.at(k.L.o_tr), k.hyper[6], k.hyper[7], k.prior, rsum, dg);
+        NMGP_LAUNCH(k_hadcs_grad_lvec, dim3(T, B), dim3(256), 0, s, rsum, k.indx, k.nobs, k.cps, N, M, T, dP, nc.var, k.prior, dg);
+        return 0;
+    }
+};
+
+struct CohSta {
+    static constexpr int WIDTH = 5;
+    static constexpr bool GP_PRIORS = false;
+    static constexpr const char* NOUN = "stationary Hadamard cohort";
+    static size_t P(int, int T) { return (size_t)T + 3; }
+    static size_t part_width(int M) { return M + 2; }
+    template <class Take>
+    static void extras(HadLayout&, Take, size_t, size_t, int, int, bool) {}
+    static bool finite_in(const double* p, size_t, size_t, int T) {
+        for (int t = 0; t < T + 3; ++t)
+            if (!std::isfinite(p[t])) return false;
+        return true;
+    }
+    static int build_cov(const CohChunk& k) {
+        const int N = k.N;
+        const dim3 grid(cdiv(N, 64), cdiv(N, 64), k.B);
+        NMGP_HADS_SWITCH(k.M, NMGP_LAUNCH((k_hadcst_cov<MM>), grid, dim3(256), 0, k.c->stream, k.x, k.indx, k.at(k.L.o_P),
+                                          (long long)P(N, k.T), k.nobs, k.cps, k.at(k.L.o_S), k.L.ld, N, k.L.bs));
+        return 0;
+    }
+    static int value_epilogue(const CohChunk& k) {           // no term of the tuple depends on N: the resident finaliser as it is
+        nmgp_hadst_finalize(k.c->stream, k.at(k.L.o_scal), k.at(k.L.o_P), k.T, k.hyper, k.prior, k.B);
+        return 0;
+    }
+    static int adjoint_grad(const CohChunk& k) {
+        hipStream_t s = k.c->stream;
+        const int N = k.N, M = k.M, T = k.T;
+        const long long P_ = (long long)P(N, T), pstride = (long long)k.L.part_per;
+        const NormalF32 nl(k.hyper[0], k.hyper[1]), nc(0.0, k.hyper[4]);
+        double *dP = k.at(k.L.o_P), *part = k.at(k.L.o_part);
+        const dim3 grid(cdiv(N, 64), cdiv(N, 64), k.B);
+        NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadcst_adjoint<MM>), grid, dim3(256), 0, s, k.x, k.indx, dP, P_, k.at(k.L.o_alpha),
+                                        k.at(k.L.o_Sneg), N, N, k.nobs, k.cps, part, pstride));
+        NMGP_LAUNCH(k_hadcst_grad_final, dim3((unsigned)P_, k.B), dim3(256), 0, s, part, pstride, (N + 63) / 64, N, M, T, k.indx, k.nobs,
+                    k.cps, dP, k.at(k.L.o_tr), nl.mean, nl.var, nc.var, k.hyper[2], k.hyper[3], k.prior, k.at(k.L.o_grad));
+        return 0;
+    }
+};
+
+// chains [0, B) of `pars` (already offset by the caller): chain z belongs to subject s0 + z / cps.  hadc_eval_chunk's sequence at
+// n = Nmax with the model's hooks: value and gradient halves enqueued back to back, ONE synchronisation.
+template <class Model>
+int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, const double* hyper, int prior, PriorFactor* p0,
+                    PriorFactor* p1, double* out, double* grad, int* status) {
+    constexpr int W = Model::WIDTH;
+    const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T;
+    const size_t P = Model::P(N, T);
+    const bool want_grad = grad != nullptr;
+    hipStream_t s = c->stream;
+    const HadLayout L = had_layout<Model>(B, N, M, T, want_grad);
+    double* slab;
+    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
+    double *dP = slab + L.o_P, *z = slab + L.o_z, *scal = slab + L.o_scal, *S = slab + L.o_S;
+    int* info = reinterpret_cast<int*>(slab + L.o_info);
+    const int ld = L.ld;
+    const long long bs = L.bs;
+    // the tables of the chunk's first subject
+    const double* y = c->hc_y + (size_t)s0 * N;
+    const int* nobs = c->hc_nobs + s0;
+    const CohChunk k{c, L, slab, B, s0, cps, N, M, T, c->hc_x + (size_t)s0 * N, hyper, c->hc_indx + (size_t)s0 * N, nobs, prior,
+                     want_grad, p0, p1};
+    HIP_TRY(c, hipMemcpyAsync(dP, pars, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)B * sizeof(int), s));
+    std::optional<PriorStreamScope> ps;          // fork now, enqueue the prior solves after the factorisation's launches
+    if constexpr (Model::GP_PRIORS) ps.emplace(c);
+    {
+        NmgpStage sp(c, NMGP_STAGE_COV);
+        int r = Model::build_cov(k);
+        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+    }
+    {
+        NmgpStage sp(c, NMGP_STAGE_CHOL);
+        set_row(s, S, ld, N, y, N, B, bs, N, cps);                        // y (zero-padded at set time) rides along as row Nmax
+        if (want_grad) identity_rows(s, S, ld, N + 1, N, L.xpad, B, bs);
+        nmgp_potrf(c, S, ld, N, want_grad ? 1 + L.xpad : 1, want_grad ? N : 0, info, B, bs, 1);
+        get_row(s, S, ld, N, z, N, B, bs, N);                             // z = L^-1 y
+    }
+    {
+        NmgpStage sp(c, NMGP_STAGE_REDUCE);
+        chol_logdet_quad(s, S, ld, N, z, scal, scal + 1, B, bs, 16);
+        if constexpr (!Model::GP_PRIORS) NMGP_TRY(Model::value_epilogue(k));     // the finaliser alone: in this stage
+    }
+    if constexpr (Model::GP_PRIORS) NMGP_TRY(Model::value_epilogue(k, *ps));     // prior stream, join, finaliser
+    std::vector<double> hs((size_t)B * 16);
+    std::vector<int> hi(B);
+    HIP_TRY(c, hipMemcpyAsync(hs.data(), scal, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(hi.data(), info, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (want_grad) {
+        double *alpha = slab + L.o_alpha, *Sneg = slab + L.o_Sneg, *part = slab + L.o_part;
+        {
+            NmgpStage sp(c, NMGP_STAGE_SOLVE);
+            tri_gemv_upper(s, S + L.xoff, ld, N, z, alpha, part, B, bs, (long long)L.part_per);    // alpha = L^-T z = X z
+        }
+        {
+            NmgpStage sp(c, NMGP_STAGE_INVERSE);
+            syrk_lower(s, S + L.xoff, ld, Sneg, N, N, N, N, B, bs, (long long)N * N, 2);          // -S^-1 = -X X^T, both triangles
+        }
+        {
+            NmgpStage sp(c, NMGP_STAGE_ADJOINT);
+            nmgp_hadc_trace(s, alpha, Sneg, N, N, nobs, cps, slab + L.o_tr, -1.0, B);             // over the real observations
+            int r = Model::adjoint_grad(k);
+            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
+        }
+        HIP_TRY(c, hipMemcpyAsync(grad, slab + L.o_grad, (size_t)B * P * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));          // the one synchronisation of the chunk
+    NMGP_TRY(nmgp_take_launch_error(c));
+    for (int z_ = 0; z_ < B; ++z_) {
+        int st = hi[z_];
+        double* o = out + (size_t)z_ * W;
+        for (int t = 0; t < W; ++t) o[t] = hs[(size_t)z_ * 16 + 8 + t];
+        const bool finite_in = Model::finite_in(pars + (size_t)z_ * P, (size_t)N, (size_t)c->hc_nobs_h[s0 + z_ / cps], T);
+        if (!finite_in || (st == 0 && (!std::isfinite(o[0]) || !std::isfinite(o[1])))) st = NMGP_NUM_NAN;
+        if (st != 0) {
+            for (int t = 0; t < W; ++t) o[t] = std::nan("");
+            if (want_grad) std::fill(grad + (size_t)z_ * P, grad + (size_t)(z_ + 1) * P, 0.0);
+        }
+        status[z_] = st;
+    }
+    return 0;
+}
+
+template <class Model>
+int cohm_subjects_eval(nmgp_ctx* c, const double* pars, int B, int cps, const double* hyper, int prior, double* out, double* grad,
+                       int* status) {
+    if (!c) return NMGP_E_NULL;
+    if (!pars || !hyper || !out || !status)
+        return nmgp_fail(c, NMGP_E_NULL, "pars/hyper/out%d/status must not be NULL", Model::WIDTH);
+    if (c->hc_S <= 0) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_subjects must be called first");
+    if (c->chol_algo != 1)
+        return nmgp_fail(c, NMGP_E_UNSUPPORTED, "the Hadamard entries run on the custom factorisation only (riding rows)");
+    if (cps < 1 || (long long)B != (long long)c->hc_S * cps)
+        return nmgp_fail(c, NMGP_E_SHAPE, "B = %d must be %d subjects x chains_per_subject = %d", B, c->hc_S, cps);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T;
+    const size_t P = Model::P(N, T);
+    const bool want_grad = grad != nullptr;
+    PriorFactor *p0 = nullptr, *p1 = nullptr;
+    if constexpr (Model::GP_PRIORS) NMGP_TRY(nmgp_hadc_priors(c, hyper, &p0, &p1));
+    const size_t per_chain = had_layout<Model>(1, N, M, T, want_grad).total * sizeof(double);
+    return hadc_for_chunks(c, B, cps, per_chain, Model::NOUN, [&](int b0, int nb, int s0, int ccps) {
+        return cohm_eval_chunk<Model>(c, pars + (size_t)b0 * P, nb, s0, ccps, hyper, prior, p0, p1, out + (size_t)b0 * Model::WIDTH,
+                                      want_grad ? grad + (size_t)b0 * P : nullptr, status + b0);
+    });
+}
+
+}  // namespace
+
+extern "C" int nmgp_hads_subjects_eval(nmgp_ctx* c, const double* pars, int B, int chains_per_subject, const double hyper[9], int prior,
+                                       double* out6, double* grad, int* status) {
+    return cohm_subjects_eval<CohSep>(c, pars, B, chains_per_subject, hyper, prior, out6, grad, status);
+}
+
+extern "C" int nmgp_hadst_subjects_eval(nmgp_ctx* c, const double* pars, int B, int chains_per_subject, const double hyper[5], int prior,
+                                        double* out5, double* grad, int* status) {
+    return cohm_subjects_eval<CohSta>(c, pars, B, chains_per_subject, hyper, prior, out5, grad, status);
+}

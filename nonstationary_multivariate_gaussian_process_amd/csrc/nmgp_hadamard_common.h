@@ -197,6 +197,17 @@ int gibbs_adjoint(hipStream_t s, const double* x, const double* ell, const doubl
     return 0;
 }
 
+// Normal(mean, sd) with Python-number arguments: torch rounds both to float32, squares and takes the logarithm there
+struct NormalF32 {
+    double mean, var, log_sd;
+    NormalF32(double m, double sd) {
+        const float m32 = (float)m, s32 = (float)sd;
+        mean = (double)m32;
+        var = (double)(s32 * s32);
+        log_sd = (double)std::log(s32);
+    }
+};
+
 // ---- the host skeleton ---------------------------------------------------------------------------------------------------------
 
 // device workspace of a chunk of B chains, in doubles (every piece at an even offset)
@@ -411,4 +422,29 @@ int had_covariance(nmgp_ctx* c, const double* pars, double* out) {
                                 (size_t)N, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return nmgp_take_launch_error(c);
+}
+
+// The chunk loop of the three cohort entries (nmgp_hadamard_cohort.hip, nmgp_hadamard_cohort_models.hip): B = S * cps chains in chunks
+// below NMGP_HAD_BATCH_SLAB_GB (default 96, at least 1) for `per_chain` bytes of workspace per chain.  A chunk is a whole number of
+// subjects, or a part of ONE subject's chains (then every chain of the chunk is that subject's), so that no kernel takes a chain
+// offset.  eval(b0, nb, s0, cps of the chunk) evaluates chains [b0, b0 + nb), the first of which belongs to subject s0.
+template <class Eval>
+int hadc_for_chunks(nmgp_ctx* c, int B, int cps, size_t per_chain, const char* noun, Eval eval) {
+    double cap_gb = 96.0;
+    if (const char* e = std::getenv("NMGP_HAD_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
+    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
+    Bc = std::min(Bc, 65535);                      // the chain is a grid dimension
+    if (Bc < 1)
+        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the %s at Nmax = %d needs %.1f GB of device workspace, above the "
+                         "NMGP_HAD_BATCH_SLAB_GB cap of %.0f GB", noun, c->hc_Nmax, per_chain / 1e9, cap_gb);
+    const bool split = cps > Bc;
+    if (!split) Bc = (Bc / cps) * cps;
+    for (int b0 = 0; b0 < B;) {
+        const int s0 = b0 / cps;
+        int nb = std::min(Bc, B - b0);
+        if (split) nb = std::min(nb, (s0 + 1) * cps - b0);
+        NMGP_TRY(eval(b0, nb, s0, split ? nb : cps));
+        b0 += nb;
+    }
+    return 0;
 }

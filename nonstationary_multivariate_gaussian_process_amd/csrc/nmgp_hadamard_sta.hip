@@ -321,17 +321,6 @@ int hadst_adjoint(hipStream_t s, const double* x, const int* indx, const double*
     return 0;
 }
 
-// Normal(mean, sd) with Python-number arguments: torch rounds both to float32, squares and takes the logarithm there
-struct NormalF32 {
-    double mean, var, log_sd;
-    NormalF32(double m, double sd) {
-        const float m32 = (float)m, s32 = (float)sd;
-        mean = (double)m32;
-        var = (double)(s32 * s32);
-        log_sd = (double)std::log(s32);
-    }
-};
-
 // hooks of the stationary model into the shared schedule (nmgp_hadamard_common.h); hyper = {mu_tilde_l, sigma_tilde_l, a, b, c}
 struct HadSta {
     static constexpr int WIDTH = 5;
@@ -348,10 +337,7 @@ struct HadSta {
     }
     static int value_epilogue(const HadChunk& k) {
         nmgp_ctx* c = k.c;
-        const NormalF32 nl(k.hyper[0], k.hyper[1]), nc(0.0, k.hyper[4]);
-        double* scal = k.at(k.L.o_scal);
-        NMGP_LAUNCH(k_hadst_finalize, dim3(k.B), dim3(64), 0, c->stream, scal, k.at(k.L.o_P), c->T, nl.mean, nl.var, nl.log_sd, nc.var,
-                    nc.log_sd, k.hyper[2], k.hyper[3], k.prior, scal + 8);
+        nmgp_hadst_finalize(c->stream, k.at(k.L.o_scal), k.at(k.L.o_P), c->T, k.hyper, k.prior, k.B);
         return 0;
     }
     static int adjoint_grad(const HadChunk& k) {
@@ -393,6 +379,14 @@ struct PsHadSt : PsHadamard {
 };
 
 }  // namespace
+
+// the scalar epilogue of `batch` chains (scal: 16 doubles per chain, the tuple into scal[8 ..]); no term depends on N, so the cohort
+// entry (nmgp_hadamard_cohort_models.hip) shares it
+void nmgp_hadst_finalize(hipStream_t s, double* scal, const double* pars, int T, const double* hyper, int prior, int batch) {
+    const NormalF32 nl(hyper[0], hyper[1]), nc(0.0, hyper[4]);
+    NMGP_LAUNCH(k_hadst_finalize, dim3(batch), dim3(64), 0, s, scal, pars, T, nl.mean, nl.var, nl.log_sd, nc.var, nc.log_sd, hyper[2],
+                hyper[3], prior, scal + 8);
+}
 
 // B chains of the resident Hadamard subject under the stationary model: pars [B, T + 3] -> out5 [B, 5] (the verbose tuples), grad
 // [B, T + 3] = d NegLog / d pars or NULL, status [B]; see had_batch_eval.  hyper = {mu_tilde_l, sigma_tilde_l, a, b, c}.

@@ -176,8 +176,9 @@ struct nmgp_ctx {
     double* ss_Y = nullptr;     // [S, N, M] row-major (k_sep_prep_b rotates it per chain)
     std::vector<PriorFactor> ss_priors;  // L: [S] x (ld x N), logdet: [S]
     // Hadamard cohort (nmgp_had_set_subjects, nmgp_hadamard_cohort.hip): hc_S ragged subjects padded to hc_Nmax.  Independent of the
-    // resident subject (N / M / T above are not touched); only nmgp_had_subjects_eval and nmgp_predsample_had_subjects look at it;
-    // nmgp_had_subjects_free drops it with its prior factors
+    // resident subject (N / M / T above are not touched); only the cohort entries look at it (nmgp_had_subjects_eval,
+    // nmgp_hads_subjects_eval, nmgp_hadst_subjects_eval, nmgp_predsample_had_subjects); nmgp_had_subjects_free drops it with its
+    // prior factors
     int hc_S = 0, hc_Nmax = 0, hc_M = 0, hc_T = 0;
     double* hc_x = nullptr;     // [S, Nmax] (zeros in the padded slots)
     double* hc_y = nullptr;     // [S, Nmax] (zeros in the padded slots)
@@ -332,6 +333,14 @@ void had_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, 
 void nmgp_hads_prep(hipStream_t s, const double* pars, const int* indx, int N, int M, double* ell, double* sig, double* Rv, int batch);
 int nmgp_hads_cov_build(hipStream_t s, const double* x, const double* ell, const double* sig, const double* Rv, const double* pars,
                         long long P, double* S, int ld, int N, int M, int batch, long long sstride);
+// stationary Hadamard model (nmgp_hadamard_sta.hip): the scalar epilogue of `batch` chains, scal[0 .. 1] -> the tuple in scal[8 ..]
+void nmgp_hadst_finalize(hipStream_t s, double* scal, const double* pars, int T, const double* hyper, int prior, int batch);
+// Hadamard cohort (nmgp_hadamard_cohort.hip), shared by the three models' entries: the set's per-subject factors of hyper[1..2] and
+// hyper[4..5] (the first re-resolved after the second look-up, which may grow the cache), and out[2 z] = sum_{r < N_s} alpha_r^2,
+// out[2 z + 1] = ssign sum_{r < N_s} Sinv[r, r] of chain z, N_s = nobs[z / cps]
+int nmgp_hadc_priors(nmgp_ctx* c, const double* hyper, PriorFactor** p0, PriorFactor** p1);
+void nmgp_hadc_trace(hipStream_t s, const double* alpha, const double* Sinv, int ld, int N, const int* nobs, int cps, double* out,
+                     double ssign, int batch);
 // kernels templated over the number of outputs M <= 8
 #define NMGP_HADS_SWITCH(M, CALL)               \
     switch (M) {                                \

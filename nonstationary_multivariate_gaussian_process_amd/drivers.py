@@ -1114,13 +1114,24 @@ class HadamardMAP(_HadamardSubject, LockStepMAP):
         return self._eval(P)
 
 
-class HadamardCohortMAP:
-    """The MAP loop of :class:`HadamardMAP` for a cohort of subjects of RAGGED size: ``subjects`` is a list of ``(x, indx, y)``,
-    ``init_pars`` a list of ``[k, P_s]`` (k = ``chains_per_subject`` restarts of subject s, ``P_s = N_s (1 + T) + 1``).  The subjects
-    are split into buckets of similar size (``hadamard.cohort_buckets(nobs, max_flop_waste)``); every bucket is one subject set
-    (``nmgp_had_set_subjects``, padded to the bucket's largest subject) on a ``Context`` of its own, held for the whole run, and
-    every Adam iteration makes ONE ``nmgp_had_subjects_eval`` per bucket, followed by :class:`LockStepMAP`'s update on the padded
-    rows -- padded slots have zero gradient and therefore never move.  ``ctxs``: one context per bucket (default: new ones)."""
+class _HadamardCohortLoop:
+    """The cohort MAP loop shared by the three Hadamard models: buckets of similar size (``hadamard.cohort_buckets``), one subject set
+    (``nmgp_had_set_subjects``) per bucket on a ``Context`` of its own, held for the whole run, ONE ``*_subjects_eval`` per bucket and
+    Adam iteration, :class:`LockStepMAP`'s update on the rows of the entry's layout.  A model names its hyper-parameter keys, its
+    ``Context`` entry and how per-subject vectors are packed into / unpacked from that layout."""
+
+    HYPER_KEYS = SVC_HYPER_KEYS
+    EVAL = "had_subjects_eval"
+
+    @staticmethod
+    def _pack(vectors, nobs, M):
+        from . import hadamard
+        return hadamard.cohort_pack(vectors, nobs, M)
+
+    @staticmethod
+    def _unpack(P, nobs, M, k):
+        from . import hadamard
+        return hadamard.cohort_unpack(P, nobs, M, k)
 
     def __init__(self, subjects, hyper_pars, init_pars, lr=2e-1, chains_per_subject=1, max_flop_waste=0.5, ctxs=None):
         from . import _lib, hadamard
@@ -1134,7 +1145,7 @@ class HadamardCohortMAP:
         if len(Ms) != 1:
             raise ValueError("the subjects have different numbers of distinct labels: %s" % Ms)
         self.M, self.k = Ms[0], k
-        self.hyper = np.array([float(hyper_pars[key]) for key in SVC_HYPER_KEYS])
+        self.hyper = np.array([float(hyper_pars[key]) for key in self.HYPER_KEYS])
         self.buckets = hadamard.cohort_buckets(self.nobs, max_flop_waste)
         if ctxs is not None and len(ctxs) != len(self.buckets):
             raise ValueError("%d contexts for %d buckets" % (len(ctxs), len(self.buckets)))
@@ -1143,10 +1154,10 @@ class HadamardCohortMAP:
         self.maps = []
         for ctx, idx in zip(self.ctxs, self.buckets):
             ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=self.M)
-            m = LockStepMAP(hadamard.cohort_pack([init_pars[s] for s in idx], [self.nobs[s] for s in idx], self.M), lr=lr)
+            m = LockStepMAP(self._pack([init_pars[s] for s in idx], [self.nobs[s] for s in idx], self.M), lr=lr)
             if m.P.shape[0] != len(idx) * k:
                 raise ValueError("init_pars must hold chains_per_subject = %d vectors per subject" % k)
-            m.value_and_grad = (lambda P, ctx=ctx: ctx.had_subjects_eval(P, self.hyper, True, True, k))
+            m.value_and_grad = (lambda P, ctx=ctx: getattr(ctx, self.EVAL)(P, self.hyper, True, True, k))
             self.maps.append(m)
 
     def close(self):
@@ -1165,7 +1176,6 @@ class HadamardCohortMAP:
     def run(self, N_opt, callback=None):
         """Returns (list of per-subject pars [k, P_s], target_value_hist [N_opt, S k] = -NegLog per iteration, alive [S k]), rows and
         columns in the caller's subject order."""
-        from . import hadamard
         B = len(self.nobs) * self.k
         hist = np.zeros((N_opt, B))
         for i in range(N_opt):
@@ -1177,9 +1187,18 @@ class HadamardCohortMAP:
         pars, alive = [None] * len(self.nobs), np.zeros(B, dtype=bool)
         for m, idx in zip(self.maps, self.buckets):
             alive[self._rows(idx)] = m.alive
-            for s, p in zip(idx, hadamard.cohort_unpack(m.P, [self.nobs[s] for s in idx], self.M, self.k)):
+            for s, p in zip(idx, self._unpack(m.P, [self.nobs[s] for s in idx], self.M, self.k)):
                 pars[int(s)] = p
         return pars, hist, alive
+
+
+class HadamardCohortMAP(_HadamardCohortLoop):
+    """The MAP loop of :class:`HadamardMAP` for a cohort of subjects of RAGGED size: ``subjects`` is a list of ``(x, indx, y)``,
+    ``init_pars`` a list of ``[k, P_s]`` (k = ``chains_per_subject`` restarts of subject s, ``P_s = N_s (1 + T) + 1``).  The subjects
+    are split into buckets of similar size (``hadamard.cohort_buckets(nobs, max_flop_waste)``); every bucket is one subject set
+    (``nmgp_had_set_subjects``, padded to the bucket's largest subject) on a ``Context`` of its own, held for the whole run, and
+    every Adam iteration makes ONE ``nmgp_had_subjects_eval`` per bucket, followed by :class:`LockStepMAP`'s update on the padded
+    rows -- padded slots have zero gradient and therefore never move.  ``ctxs``: one context per bucket (default: new ones)."""
 
     def predict(self, pars, xs, indx_star=None):
         """MAP prediction (one draw, no noise) for every subject at its own new inputs, on the contexts and sets this object holds:
@@ -1245,6 +1264,26 @@ class HadamardSepMAP(_HadamardSepSubject, LockStepMAP):
         return self._eval(P)
 
 
+class HadamardSepCohortMAP(_HadamardCohortLoop):
+    """:class:`HadamardCohortMAP`'s loop under the separable model, against :class:`HadamardSepMAP` subject by subject:
+    ``init_pars[s]`` ``[k, 2 N_s + T + 1]``, the hyper-parameter keys of the per-subject driver, ONE ``nmgp_hads_subjects_eval`` per
+    bucket and Adam iteration on the padded layout of ``hadamard_sep.cohort_pack`` (padded slots have zero gradient and never move).
+    No prediction for the cohort under this model yet."""
+
+    HYPER_KEYS = SEP_HYPER_KEYS
+    EVAL = "hads_subjects_eval"
+
+    @staticmethod
+    def _pack(vectors, nobs, M):
+        from . import hadamard_sep
+        return hadamard_sep.cohort_pack(vectors, nobs, M)
+
+    @staticmethod
+    def _unpack(P, nobs, M, k):
+        from . import hadamard_sep
+        return hadamard_sep.cohort_unpack(P, nobs, M, k)
+
+
 class BatchedHMCHadamardSep(_HadamardSepSubject, LockStepHMC):
     """B independent HMC chains of the separable Hadamard model of one subject in lock-step: every leapfrog step evaluates
     ``logpos.nlogpos_obj_hadamard`` and its gradient for all chains with one ``nmgp_hads_batch_eval``.  The leapfrog update runs on
@@ -1285,6 +1324,24 @@ class HadamardStaMAP(_HadamardStaSubject, LockStepMAP):
 
     def value_and_grad(self, P):
         return self._eval(P)
+
+
+class HadamardStaCohortMAP(_HadamardCohortLoop):
+    """:class:`HadamardCohortMAP`'s loop under the stationary model, against :class:`HadamardStaMAP` subject by subject:
+    ``init_pars[s]`` ``[k, T + 3]`` (the vector has no per-observation part, so rows are stacked as they are), the hyper-parameter keys
+    and the update of the per-subject driver (every entry moves, ``tilde_sigma`` included, as there), ONE
+    ``nmgp_hadst_subjects_eval`` per bucket and Adam iteration.  No prediction for the cohort under this model yet."""
+
+    HYPER_KEYS = STA_HYPER_KEYS
+    EVAL = "hadst_subjects_eval"
+
+    @staticmethod
+    def _pack(vectors, nobs, M):
+        return np.concatenate([np.atleast_2d(np.asarray(v, dtype=np.float64)) for v in vectors], axis=0)
+
+    @staticmethod
+    def _unpack(P, nobs, M, k):
+        return [np.array(P[s * k:(s + 1) * k]) for s in range(len(nobs))]
 
 
 class BatchedHMCHadamardSta(_HadamardStaSubject, LockStepHMC):

@@ -110,3 +110,44 @@ def pointwise_predmap_hadmard(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, 
 
 
 pointwise_predmap_hadamard = pointwise_predmap_hadmard
+
+
+# ---- a cohort of ragged subjects: the padded parameter layout of nmgp_hads_subjects_eval ------------------------------------------------
+def cohort_pack(vectors, nobs, M, Nmax=None, fill=0.0):
+    """Reference-layout vectors of S ragged subjects -> the padded layout of ``Context.hads_subjects_eval``; the contract of
+    ``hadamard.cohort_pack``.  ``vectors[s]`` is ``[k, P_s]`` (or ``[P_s]``: k = 1), ``P_s = 2 nobs[s] + T + 1``, the same k for every
+    subject; the result is ``[S k, Pmax = 2 Nmax + T + 1]`` with row ``s k + j`` = vector j of subject s: its ``tilde_l`` in the first
+    ``nobs[s]`` slots of the first block, its ``tilde_sigma`` in the first ``nobs[s]`` slots of the second, ``L_vec`` and
+    ``tilde_sigma2_err`` in the last ``T + 1`` slots, ``fill`` in every padded slot (the device never reads those).  Parameters and
+    gradients alike."""
+    nobs = [int(n) for n in nobs]
+    T = int(M) * (int(M) + 1) // 2
+    Nmax = max(nobs) if Nmax is None else int(Nmax)
+    if len(vectors) != len(nobs) or max(nobs) > Nmax:
+        raise ValueError("%d vectors for %d subjects, or a subject larger than Nmax = %d" % (len(vectors), len(nobs), Nmax))
+    vs = [np.atleast_2d(_np(v)) for v in vectors]
+    k = vs[0].shape[0]
+    out = np.full((len(nobs) * k, 2 * Nmax + T + 1), float(fill))
+    for s, (v, n) in enumerate(zip(vs, nobs)):
+        if v.shape != (k, 2 * n + T + 1):
+            raise ValueError("subject %d: expected [%d, 2 nobs + T + 1 = %d], got %s" % (s, k, 2 * n + T + 1, v.shape))
+        rows = out[s * k:(s + 1) * k]
+        rows[:, :n] = v[:, :n]
+        rows[:, Nmax:Nmax + n] = v[:, n:2 * n]
+        rows[:, 2 * Nmax:] = v[:, 2 * n:]
+    return out
+
+
+def cohort_unpack(P, nobs, M, chains_per_subject=1):
+    """The inverse of :func:`cohort_pack`: ``[S k, Pmax]`` -> a list of S arrays ``[k, P_s]`` (copies)."""
+    P = np.atleast_2d(_np(P))
+    nobs = [int(n) for n in nobs]
+    T, k = int(M) * (int(M) + 1) // 2, int(chains_per_subject)
+    Nmax, rem = divmod(P.shape[1] - T - 1, 2)
+    if rem or Nmax < 0 or P.shape[0] != len(nobs) * k or max(nobs) > Nmax:
+        raise ValueError("P %s does not fit %d subjects x %d chains of at most 2 Nmax + T + 1 slots, T = %d" % (P.shape, len(nobs), k, T))
+    out = []
+    for s, n in enumerate(nobs):
+        rows = P[s * k:(s + 1) * k]
+        out.append(np.concatenate([rows[:, :n], rows[:, Nmax:Nmax + n], rows[:, 2 * Nmax:]], axis=1))
+    return out
