@@ -1,5 +1,7 @@
-// A cohort of Hadamard subjects of RAGGED size per launch sequence (nonseparable model): nmgp_had_set_subjects,
-// nmgp_had_clear_subjects, nmgp_had_subjects_eval, and the set's predictor nmgp_predsample_had_subjects (second half of the file).
+// A cohort of Hadamard subjects of RAGGED size per launch sequence: the set (nmgp_had_set_subjects, nmgp_had_clear_subjects), its
+// per-subject GP-prior factors, the masked trace, the nonseparable model's own small kernels, and the set's predictor
+// nmgp_predsample_had_subjects (second half of the file).  The three evaluation entries, their model hooks and their one chunk
+// skeleton are in nmgp_hadamard_cohort_models.hip.
 //
 // The blocked Cholesky batch wants one matrix order, so every subject of a set is padded to the set's Nmax with decoupled unit
 // observations: for a padded i >= N_s, S[i, i] = 1, S[i, j] = S[j, i] = 0, y[i] = 0, and the same in both GP-prior covariances
@@ -10,15 +12,14 @@
 // of the 1 + T prior terms (N_s, not Nmax), and the centred prior right-hand sides (zero in the padded slots).
 //
 // Everything between the covariance build and the adjoint is the library's own with n = Nmax (set_row, identity_rows, nmgp_potrf with
-// precise panels, get_row, chol_logdet_quad, tri_gemv_upper, syrk_lower, col_sumsq, prior_trsv with per-subject factor strides).  The
-// kernels below are this entry's own: k_gibbs_cov / k_gibbs_adjoint (nmgp_hadamard_common.h) are shared by three models whose bits and
-// register budgets are pinned, so no mask is threaded through them; k_hadc_cov / k_hadc_adjoint keep their tile shape, lane mapping,
-// LDS staging and expression order, so that a subject with N_s = Nmax gets the resident path's bits.  Every mask comes from the
-// device table of the subjects' sizes (nobs), never from the contents of a padded slot.
+// precise panels, get_row, chol_logdet_quad, tri_gemv_upper, syrk_lower, col_sumsq, prior_trsv with per-subject factor strides).
+// k_gibbs_cov / k_gibbs_adjoint (nmgp_hadamard_common.h) are shared by three models whose bits and register budgets are pinned, so no
+// mask is threaded through them; the masked pair k_hadc_cov<M, AMP> / k_hadc_adjoint<M, AMP> stands below them in that header.  Every
+// mask comes from the device table of the subjects' sizes (nobs), never from the contents of a padded slot.
 //
-// Chunks of chains under NMGP_HAD_BATCH_SLAB_GB are aligned to subjects: a chunk is (first subject, chains per subject) or a part of
-// ONE subject's chains, so that no kernel takes a chain offset -- the chain z of a chunk belongs to subject z / cps of the chunk's
-// slice of the tables.
+// Chunks of chains under NMGP_HAD_BATCH_SLAB_GB (had_for_chunks) are aligned to subjects: a chunk is (first subject, chains per
+// subject) or a part of ONE subject's chains, so that no kernel takes a chain offset -- the chain z of a chunk belongs to subject
+// z / cps of the chunk's slice of the tables.
 #include "nmgp_hadamard_common.h"
 #include "nmgp_predsample_common.h"
 
@@ -70,81 +71,6 @@ __global__ void k_hadc_prep(const double* __restrict__ pars, const int* __restri
     const int c = indx[i];
     const double* u = pars + N + (size_t)i * T + c * (c + 1) / 2;
     for (int m = 0; m < M; ++m) Rv[(size_t)i * M + m] = (m <= c) ? u[m] : 0.0;
-}
-
-// The whole Nmax x Nmax lower triangle of every chain's S: k_gibbs_cov<M, false> on the real observations (same tile, lanes, LDS
-// staging and expression order), delta_ij on the padded ones.  In the lower triangle i >= j, so a real row has real columns only and
-// the mask is the row's.  A tile whose rows are all padded stores and does nothing else.
-template <int M>
-__global__ __launch_bounds__(256) void k_hadc_cov(const double* __restrict__ x, const double* __restrict__ ell,
-                                                   const double* __restrict__ Rv, const double* __restrict__ pars, long long P,
-                                                   const int* __restrict__ nobs, int cps, double* __restrict__ S, int ld, int N,
-                                                   long long sstride) {
-    constexpr int TJ = 64;
-    __shared__ double sx[TJ], sl[TJ], sR[TJ * M];
-    const int I = blockIdx.x, J = blockIdx.y;
-    if (I < J) return;
-    const int sub = blockIdx.z / cps;
-    const int Ns = nobs[sub];
-    x += (size_t)sub * N;
-    ell += (size_t)blockIdx.z * N;
-    Rv += (size_t)blockIdx.z * N * M;
-    pars += (size_t)blockIdx.z * P;
-    S += (size_t)blockIdx.z * sstride;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j0 = J * TJ;
-    const int i = I * 64 + lane;
-    if (I * 64 >= Ns) {                                      // every row of the tile is padded: store only
-        if (i >= N) return;
-        for (int jj = 0; jj < TJ / 4; ++jj) {
-            const int j = j0 + w * (TJ / 4) + jj;
-            if (j >= N) break;
-            if (i < j) continue;
-            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
-        }
-        return;
-    }
-    if (tid < TJ) {
-        const int j = j0 + tid;
-        sx[tid] = (j < Ns) ? x[j] : 0.0;
-        sl[tid] = (j < Ns) ? ell[j] : 1.0;
-    }
-    for (int k = tid; k < TJ * M; k += 256) {
-        const size_t g = (size_t)j0 * M + k;
-        sR[k] = (g < (size_t)Ns * M) ? Rv[g] : 0.0;
-    }
-    __syncthreads();
-    if (i >= N) return;
-    const bool real = i < Ns;
-    const int ic = real ? i : 0;
-    const double sigma2 = exp(pars[P - 1]);
-    const double xi = x[ic], li = ell[ic];
-    const double xi2 = xi * xi, li2 = li * li;
-    double ri[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
-#pragma unroll 2
-    for (int jj = 0; jj < TJ / 4; ++jj) {
-        const int k = w * (TJ / 4) + jj;
-        const int j = j0 + k;
-        if (j >= N) break;
-        if (i < j) continue;
-        if (!real) {
-            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
-            continue;
-        }
-        const double xj = sx[k], lj = sl[k];
-        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);   // kernels.py:20
-        const double A = li2 + lj * lj;                          // kernels.py:69
-        double kv = sqrt(2.0 * (li * lj) / A) * exp(-dist / A);  // kernels.py:70-72
-        if (i == j) kv = NMGP_JITTER + kv;                       // kernels.py:64
-        double b = 0.0;
-#pragma unroll
-        for (int m = 0; m < M; ++m) b += ri[m] * sR[k * M + m];
-        double v = kv * b;
-        if (i == j) v += sigma2;
-        S[(size_t)j * ld + i] = v;
-    }
 }
 
 // The masked GP-prior covariance of every subject: RBF(x; alpha, beta) + jitter I on the real observations (the expressions of
@@ -268,98 +194,6 @@ __global__ __launch_bounds__(1024) void k_hadc_trace(const double* __restrict__ 
     }
 }
 
-// k_gibbs_adjoint<M, false> with j < N_s and i < N_s masks (same layout and expression order): part[J][i][0 .. M + 1) of the real i,
-// ZERO partial rows of the padded i (every J), so that the final sum needs no mask of its own.
-template <int M>
-__global__ __launch_bounds__(256) void k_hadc_adjoint(const double* __restrict__ x, const double* __restrict__ ell,
-                                                       const double* __restrict__ Rv, const double* __restrict__ alpha,
-                                                       const double* __restrict__ Sneg, int ld, int N, const int* __restrict__ nobs,
-                                                       int cps, double* __restrict__ part, long long pstride) {
-    constexpr int TJ = 64, W = M + 1;
-    __shared__ double sx[TJ], sl[TJ], sR[TJ * M], sa[TJ];
-    __shared__ double red[2][4][64];
-    const int I = blockIdx.x, J = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j0 = J * TJ;
-    const size_t Nl = (size_t)N;
-    const int sub = blockIdx.z / cps;
-    const int Ns = nobs[sub];
-    {   // blockIdx.z = chain
-        const size_t z = blockIdx.z;
-        x += (size_t)sub * Nl;
-        ell += z * Nl;
-        Rv += z * Nl * M;
-        alpha += z * Nl;
-        Sneg += z * (size_t)ld * Nl;
-        part += z * (size_t)pstride;
-    }
-    const int i = I * 64 + lane;
-    const bool inN = i < N;
-    if (I * 64 >= Ns || j0 >= Ns) {                          // nothing real in the tile: zero partial rows
-        if (w == 0 && inN) {
-            double* o = part + ((size_t)J * Nl + i) * W;
-#pragma unroll
-            for (int t = 0; t < W; ++t) o[t] = 0.0;
-        }
-        return;
-    }
-    if (tid < TJ) {
-        const int j = j0 + tid;
-        sx[tid] = (j < Ns) ? x[j] : 0.0;
-        sl[tid] = (j < Ns) ? ell[j] : 1.0;
-        sa[tid] = (j < Ns) ? alpha[j] : 0.0;
-    }
-    for (int k = tid; k < TJ * M; k += 256) {
-        const size_t g = (size_t)j0 * M + k;
-        sR[k] = (g < (size_t)Ns * M) ? Rv[g] : 0.0;
-    }
-    __syncthreads();
-    const bool iv = i < Ns;
-    const int ic = iv ? i : Ns - 1;
-    const double xi = x[ic], li = ell[ic];
-    const double ai = alpha[ic];
-    const double xi2 = xi * xi, li2 = li * li;
-    double ri[M], acc[W];
-#pragma unroll
-    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
-#pragma unroll
-    for (int t = 0; t < W; ++t) acc[t] = 0.0;
-    if (iv) {
-        for (int jj = 0; jj < TJ / 4; ++jj) {
-            const int k = w * (TJ / 4) + jj;
-            const int j = j0 + k;
-            if (j >= Ns) break;
-            const double xj = sx[k], lj = sl[k];
-            const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
-            const double A = li2 + lj * lj;
-            const double k0 = sqrt(2.0 * (li * lj) / A) * exp(-dist / A);
-            const double kx = (i == j) ? (NMGP_JITTER + k0) : k0;
-            const double G = 0.5 * (ai * sa[k] + Sneg[(size_t)j * ld + i]);
-            const double gk = 2.0 * kx * G;
-            double dot = 0.0;
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                const double rj = sR[k * M + m];
-                acc[1 + m] = fma(gk, rj, acc[1 + m]);
-                dot = fma(ri[m], rj, dot);
-            }
-            const double gd = 2.0 * (G * dot) * k0;
-            if (i != j) {
-                const double dlogk = 0.5 - li2 / A + 2.0 * li2 * dist / (A * A);
-                acc[0] = fma(gd, dlogk, acc[0]);
-            }
-        }
-    }
-    double* o = part + ((size_t)J * Nl + (inN ? i : 0)) * W;
-#pragma unroll
-    for (int t = 0; t < W; ++t) {
-        red[t & 1][w][lane] = acc[t];
-        __syncthreads();
-        // (a padded i < Nmax has four zero accumulators: its row is written as +0.0)
-        if (w == 0 && inN) o[t] = (red[t & 1][0][lane] + red[t & 1][1][lane]) + (red[t & 1][2][lane] + red[t & 1][3][lane]);
-    }
-}
-
 // k_had_grad_final on the padded layout: the J partials summed in order, the c_i + 1 components of d / d r_i scattered into row c_i's
 // slots, the prior gradients of all T columns, for the real i; +0.0 in every padded slot; the sigma2 slot from the trace over the real
 // observations (tr, k_hadc_trace).
@@ -413,31 +247,6 @@ __global__ __launch_bounds__(256) void k_hadc_grad_final(const double* __restric
         grad[N + (size_t)i * T + t] = g;
     }
 }
-
-int hadc_cov_build(hipStream_t s, const double* x, const double* ell, const double* Rv, const double* pars, long long P,
-                   const int* nobs, int cps, double* S, int ld, int N, int M, int batch, long long sstride) {
-    const dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);
-    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadc_cov<MM>), grid, dim3(256), 0, s, x, ell, Rv, pars, P, nobs, cps, S, ld, N, sstride));
-    return 0;
-}
-
-int hadc_adjoint(hipStream_t s, const double* x, const double* ell, const double* Rv, const double* alpha, const double* Sneg, int ld,
-                 int N, int M, const int* nobs, int cps, double* part, long long pstride, int batch) {
-    const dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);
-    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadc_adjoint<MM>), grid, dim3(256), 0, s, x, ell, Rv, alpha, Sneg, ld, N, nobs, cps, part, pstride));
-    return 0;
-}
-
-// the workspace of a chunk is the resident entry's (had_layout), at N = Nmax
-struct HadCohort {
-    static size_t P(int N, int T) { return (size_t)N * (1 + T) + 1; }
-    static size_t part_width(int M) { return M + 1; }
-    template <class Take>
-    static void extras(HadLayout& L, Take take, size_t Bs, size_t N, int M, int T, bool want_grad) {
-        L.o_ell = take(Bs * N); L.o_Rv = take(Bs * N * M); L.o_R = take(Bs * N * (1 + T)); L.o_q = take(Bs * (1 + T));
-        if (want_grad) L.o_R2 = take(Bs * N * (1 + T));
-    }
-};
 
 void free_factors(std::vector<PriorFactor>& v) {
     for (auto& pf : v) {
@@ -498,119 +307,29 @@ int hadc_get_prior(nmgp_ctx* c, double alpha, double beta, PriorFactor** out) {
     return 0;
 }
 
-// chains [0, B) of `pars` (already offset by the caller): chain z belongs to subject s0 + z / cps.  had_eval_chunk's sequence at
-// n = Nmax: value and gradient halves enqueued back to back, ONE synchronisation.
-int hadc_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, const double* hyper, int prior, PriorFactor* p0,
-                    PriorFactor* p1, double* out, double* grad, int* status) {
-    const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T;
-    const size_t P = HadCohort::P(N, T);
-    const bool want_grad = grad != nullptr;
-    hipStream_t s = c->stream;
-    const HadLayout L = had_layout<HadCohort>(B, N, M, T, want_grad);
-    double* slab;
-    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
-    double *dP = slab + L.o_P, *z = slab + L.o_z, *scal = slab + L.o_scal, *S = slab + L.o_S;
-    double *ell = slab + L.o_ell, *Rv = slab + L.o_Rv;
-    int* info = reinterpret_cast<int*>(slab + L.o_info);
-    const int ld = L.ld;
-    const long long bs = L.bs;
-    // the tables of the chunk's first subject
-    const double* x = c->hc_x + (size_t)s0 * N;
-    const double* y = c->hc_y + (size_t)s0 * N;
-    const int* indx = c->hc_indx + (size_t)s0 * N;
-    const int* nobs = c->hc_nobs + s0;
-    const double mu_l = hyper[0], mu_L = hyper[3], a = hyper[6], b = hyper[7];
-    HIP_TRY(c, hipMemcpyAsync(dP, pars, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)B * sizeof(int), s));
-    PriorStreamScope ps(c);          // fork now, enqueue the prior solves after the factorisation's launches
-    {
-        NmgpStage sp(c, NMGP_STAGE_COV);
-        NMGP_LAUNCH(k_hadc_prep, dim3(cdiv(N, 256), B), dim3(256), 0, s, dP, indx, nobs, cps, N, M, T, ell, Rv);
-        int r = hadc_cov_build(s, x, ell, Rv, dP, (long long)P, nobs, cps, S, ld, N, M, B, bs);
-        if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-    }
-    {
-        NmgpStage sp(c, NMGP_STAGE_CHOL);
-        set_row(s, S, ld, N, y, N, B, bs, N, cps);                        // y (zero-padded at set time) rides along as row Nmax
-        if (want_grad) identity_rows(s, S, ld, N + 1, N, L.xpad, B, bs);
-        nmgp_potrf(c, S, ld, N, want_grad ? 1 + L.xpad : 1, want_grad ? N : 0, info, B, bs, 1);
-        get_row(s, S, ld, N, z, N, B, bs, N);                             // z = L^-1 y
-    }
-    {
-        NmgpStage sp(c, NMGP_STAGE_REDUCE);
-        chol_logdet_quad(s, S, ld, N, z, scal, scal + 1, B, bs, 16);
-    }
-    {   // the GP-prior half on the forked prior stream (had_gp_prior_terms), against the factors of subject s0 + z / cps
-        double* R = slab + L.o_R;
-        const long long f0 = (long long)p0->ld * N, f1 = (long long)p1->ld * N;
-        const double *L0 = p0->L + (size_t)s0 * f0, *L1 = p1->L + (size_t)s0 * f1;
-        {
-            NmgpStage sp(c, NMGP_STAGE_PRIOR, ps.sp, 0.0, 0.0);
-            NMGP_LAUNCH(k_hadc_prior_rhs, dim3(cdiv(N, 256), B), dim3(256), 0, ps.sp, dP, nobs, cps, N, T, mu_l, mu_L, R, N);
-            prior_trsv(ps.sp, false, L0, p0->ld, f0, L1, p1->ld, f1, R, N, 1 + T, B, cps);
-            col_sumsq(ps.sp, R, N, N, B * (1 + T), slab + L.o_q);
-            if (want_grad && prior) {
-                double* R2 = slab + L.o_R2;
-                HIP_TRY(c, hipMemcpyAsync(R2, R, (size_t)B * N * (1 + T) * sizeof(double), hipMemcpyDeviceToDevice, ps.sp));
-                prior_trsv(ps.sp, true, L0, p0->ld, f0, L1, p1->ld, f1, R2, N, 1 + T, B, cps);
-            }
-        }
-        ps.done();
-        ps.join();
-        NmgpStage sp(c, NMGP_STAGE_REDUCE);
-        NMGP_LAUNCH(k_hadc_finalize, dim3(B), dim3(64), 0, s, scal, scal + 1, slab + L.o_q, p0->logdet + s0, p1->logdet + s0, dP,
-                    (long long)P, nobs, cps, T, a, b, 0.0, prior, scal + 8, 16);
-    }
-    std::vector<double> hs((size_t)B * 16);
-    std::vector<int> hi(B);
-    HIP_TRY(c, hipMemcpyAsync(hs.data(), scal, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(hi.data(), info, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (want_grad) {
-        double *alpha = slab + L.o_alpha, *Sneg = slab + L.o_Sneg, *part = slab + L.o_part;
-        {
-            NmgpStage sp(c, NMGP_STAGE_SOLVE);
-            tri_gemv_upper(s, S + L.xoff, ld, N, z, alpha, part, B, bs, (long long)L.part_per);    // alpha = L^-T z = X z
-        }
-        {
-            NmgpStage sp(c, NMGP_STAGE_INVERSE);
-            syrk_lower(s, S + L.xoff, ld, Sneg, N, N, N, N, B, bs, (long long)N * N, 2);          // -S^-1 = -X X^T, both triangles
-        }
-        {
-            NmgpStage sp(c, NMGP_STAGE_ADJOINT);
-            NMGP_LAUNCH(k_hadc_trace, dim3(B), dim3(1024), 0, s, alpha, Sneg, N, N, nobs, cps, slab + L.o_tr, -1.0);
-            int r = hadc_adjoint(s, x, ell, Rv, alpha, Sneg, N, N, M, nobs, cps, part, (long long)L.part_per, B);
-            if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
-            NMGP_LAUNCH(k_hadc_grad_final, dim3(cdiv(N, 256), B), dim3(256), 0, s, part, (long long)L.part_per, (N + 63) / 64, N, M, T,
-                        indx, nobs, cps, slab + L.o_R2, N, dP, slab + L.o_tr, a, b, prior, slab + L.o_grad);
-        }
-        HIP_TRY(c, hipMemcpyAsync(grad, slab + L.o_grad, (size_t)B * P * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(c, hipStreamSynchronize(s));          // the one synchronisation of the chunk
-    NMGP_TRY(nmgp_take_launch_error(c));
-    for (int z_ = 0; z_ < B; ++z_) {
-        int st = hi[z_];
-        double* o = out + (size_t)z_ * 5;
-        for (int t = 0; t < 5; ++t) o[t] = hs[(size_t)z_ * 16 + 8 + t];
-        // the finiteness test covers the chain's REAL slots only
-        const size_t Ns = (size_t)c->hc_nobs_h[s0 + z_ / cps];
-        const double* p = pars + (size_t)z_ * P;
-        bool finite_in = std::isfinite(p[P - 1]);
-        for (size_t t = 0; t < Ns && finite_in; ++t) finite_in = std::isfinite(p[t]);
-        for (size_t t = 0; t < Ns * T && finite_in; ++t) finite_in = std::isfinite(p[(size_t)N + t]);
-        if (!finite_in || (st == 0 && (!std::isfinite(o[0]) || !std::isfinite(o[1])))) st = NMGP_NUM_NAN;
-        if (st != 0) {
-            for (int t = 0; t < 5; ++t) o[t] = std::nan("");
-            if (want_grad) std::fill(grad + (size_t)z_ * P, grad + (size_t)(z_ + 1) * P, 0.0);
-        }
-        status[z_] = st;
-    }
-    return 0;
-}
-
 }  // namespace
 
-// what the other two models' cohort entries (nmgp_hadamard_cohort_models.hip) share with this file: the set's two per-subject prior
-// factors of hyper[1..2] and hyper[4..5], and the masked trace
+// what the evaluation entries (nmgp_hadamard_cohort_models.hip) take from this file: the set's two per-subject prior factors of
+// hyper[1..2] and hyper[4..5], the masked trace, and the launches of the nonseparable model's own kernels (CohNon's hooks)
+void nmgp_hadc_prep(hipStream_t s, const double* pars, const int* indx, const int* nobs, int cps, int N, int M, int T, double* ell,
+                    double* Rv, int batch) {
+    NMGP_LAUNCH(k_hadc_prep, dim3(cdiv(N, 256), batch), dim3(256), 0, s, pars, indx, nobs, cps, N, M, T, ell, Rv);
+}
+void nmgp_hadc_prior_rhs(hipStream_t s, const double* pars, const int* nobs, int cps, int N, int T, double mu_l, double mu_L, double* R,
+                         int ld, int batch) {
+    NMGP_LAUNCH(k_hadc_prior_rhs, dim3(cdiv(N, 256), batch), dim3(256), 0, s, pars, nobs, cps, N, T, mu_l, mu_L, R, ld);
+}
+void nmgp_hadc_finalize(hipStream_t s, double* scal, const double* q, const double* hl_l, const double* hl_L, const double* pars,
+                        long long P, const int* nobs, int cps, int T, double a, double b, int prior, int batch) {
+    NMGP_LAUNCH(k_hadc_finalize, dim3(batch), dim3(64), 0, s, scal, scal + 1, q, hl_l, hl_L, pars, P, nobs, cps, T, a, b, 0.0, prior,
+                scal + 8, 16);
+}
+void nmgp_hadc_grad_final(hipStream_t s, const double* part, long long pstride, int N, int M, int T, const int* indx, const int* nobs,
+                          int cps, const double* R2, const double* pars, const double* tr, double a, double b, int prior, double* grad,
+                          int batch) {
+    NMGP_LAUNCH(k_hadc_grad_final, dim3(cdiv(N, 256), batch), dim3(256), 0, s, part, pstride, (N + 63) / 64, N, M, T, indx, nobs, cps, R2,
+                N, pars, tr, a, b, prior, grad);
+}
 int nmgp_hadc_priors(nmgp_ctx* c, const double* hyper, PriorFactor** p0, PriorFactor** p1) {
     NMGP_TRY(hadc_get_prior(c, hyper[1], hyper[2], p0));
     NMGP_TRY(hadc_get_prior(c, hyper[4], hyper[5], p1));
@@ -693,30 +412,6 @@ extern "C" int nmgp_had_clear_subjects(nmgp_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     nmgp_had_subjects_free(c);
     return 0;
-}
-
-extern "C" int nmgp_had_subjects_eval(nmgp_ctx* c, const double* pars, int B, int chains_per_subject, const double hyper[8], int prior,
-                                      double* out5, double* grad, int* status) {
-    if (!c) return NMGP_E_NULL;
-    if (!pars || !hyper || !out5 || !status) return nmgp_fail(c, NMGP_E_NULL, "pars/hyper/out5/status must not be NULL");
-    if (c->hc_S <= 0) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_subjects must be called first");
-    if (c->chol_algo != 1)
-        return nmgp_fail(c, NMGP_E_UNSUPPORTED, "the Hadamard entries run on the custom factorisation only (riding rows)");
-    const int cps = chains_per_subject;
-    if (cps < 1 || (long long)B != (long long)c->hc_S * cps)
-        return nmgp_fail(c, NMGP_E_SHAPE, "B = %d must be %d subjects x chains_per_subject = %d", B, c->hc_S, cps);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T;
-    const size_t P = HadCohort::P(N, T);
-    const bool want_grad = grad != nullptr;
-    // one pair of factors per subject (the cache is a vector: the second look-up may move its elements, so the first is re-resolved)
-    PriorFactor *p0 = nullptr, *p1 = nullptr;
-    NMGP_TRY(nmgp_hadc_priors(c, hyper, &p0, &p1));
-    const size_t per_chain = had_layout<HadCohort>(1, N, M, T, want_grad).total * sizeof(double);
-    return hadc_for_chunks(c, B, cps, per_chain, "Hadamard cohort", [&](int b0, int nb, int s0, int ccps) {
-        return hadc_eval_chunk(c, pars + (size_t)b0 * P, nb, s0, ccps, hyper, prior, p0, p1, out5 + (size_t)b0 * 5,
-                               want_grad ? grad + (size_t)b0 * P : nullptr, status + b0);
-    });
 }
 
 // ---- MAP and posterior-draw prediction for the set: nmgp_predsample_had_subjects -------------------------------------------------------
@@ -933,7 +628,7 @@ extern "C" int nmgp_predsample_had_subjects(nmgp_ctx* c, const double* pars, int
     }
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const size_t P = HadCohort::P(N, T);
+    const size_t P = (size_t)N * (1 + T) + 1;
     const int per = PsHadamard::rows(M, indexed);
     // riding rows per factorisation: the resident entry's rule at Nmax
     const int smax = PsHadamard::smax(N, M, indexed);
@@ -1025,7 +720,7 @@ extern "C" int nmgp_predsample_had_subjects(nmgp_ctx* c, const double* pars, int
             const int Sc = std::min(smax, Smax - j0), E = Sc * per;
             {
                 NmgpStage sp(c, NMGP_STAGE_COV);
-                int r = hadc_cov_build(st, x, ell, Rv, dP, (long long)P, nobs, cps, Sb, ld, N, M, nb, bs);
+                int r = hadc_cov_build<false>(st, x, ell, nullptr, Rv, dP, (long long)P, nobs, cps, Sb, ld, N, M, nb, bs);
                 if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
                 set_row(st, Sb, ld, N, y, N, nb, bs, N, cps);               // the subject's y (zero-padded at set time) rides as row Nmax
                 const dim3 grid(N, cdiv(E, 256), nb);

@@ -1,16 +1,23 @@
-// The cohort of ragged Hadamard subjects (nmgp_had_set_subjects, nmgp_hadamard_cohort.hip) under the other two models:
-// nmgp_hads_subjects_eval (separable) and nmgp_hadst_subjects_eval (stationary).
+// The cohort of ragged Hadamard subjects (nmgp_had_set_subjects, nmgp_hadamard_cohort.hip) under the three models: the entries
+// nmgp_had_subjects_eval (nonseparable), nmgp_hads_subjects_eval (separable) and nmgp_hadst_subjects_eval (stationary), ONE argument
+// check and chunk loop (cohm_subjects_eval<Model>, had_for_chunks), ONE launch sequence of a chunk (cohm_eval_chunk<Model>) and one
+// struct of hooks per model (CohNon, CohSep, CohSta), as the resident entries have in nmgp_hadamard_common.h.  The two skeletons stay
+// two functions: they differ in where N comes from, the stride of the riding y row, the trace, the finiteness range and the lifetime
+// of the prior factors.
 //
-// The set, its padding argument and its chunking rule are nmgp_hadamard_cohort.hip's: every subject is padded to Nmax with decoupled
-// unit observations, the padded part of every factor is the identity, and log det, z, alpha, the Mahalanobis terms and the prior
-// log-determinants gain exact zeros.  What does NOT take care of itself, per model:
+// The set and its padding argument are nmgp_hadamard_cohort.hip's: every subject is padded to Nmax with decoupled unit observations,
+// the padded part of every factor is the identity, and log det, z, alpha, the Mahalanobis terms and the prior log-determinants gain
+// exact zeros.  What does NOT take care of itself, per model:
+//   nonseparable tr S^-1 (one per padded observation), the N log 2 pi of the 1 + T GP-prior terms and their centred right-hand sides
+//                (k_hadc_* of nmgp_hadamard_cohort.hip, which the predictor there shares)
 //   separable    tr S^-1 (one per padded observation), the N log 2 pi of the TWO GP-prior terms, the two centred prior right-hand
 //                sides, and the label-segmented reduction of d / d L_vec: the set's labels are zero-padded, so an unmasked walk would
 //                add the padded rows to the slots of label 0 (their partial rows are written as zeros here as well)
 //   stationary   tr S^-1, and the adjoint sums: a padded i has G_ii = -1/2 (the -1 on the padded diagonal of -S^-1), which would reach
 //                a_s (d / d tilde_sigma) and, through the zero-padded labels, the label-0 slots of L; there is no prior stream
-// The rule of nmgp_hadamard_cohort.hip holds: k_gibbs_*<M, true>, k_hads_* and k_hadst_* are shared by entries whose bits are pinned,
-// so no mask is threaded through them.  The kernels below are siblings with the originals' 64 x 64 tile, lane mapping, LDS staging,
+// k_gibbs_*, k_hads_* and k_hadst_* are shared by entries whose bits are pinned, so no mask is threaded through them.  The masked
+// Gibbs pair of the first two models is k_hadc_cov<M, AMP> / k_hadc_adjoint<M, AMP> (nmgp_hadamard_common.h); the kernels below are
+// the separable and stationary models' own, siblings with the originals' 64 x 64 tile, lane mapping, LDS staging (hadst_stage),
 // expression order and fixed summation order, blockIdx.z = chain, subject = chain / cps of the chunk; a subject with N_s = Nmax gets
 // the resident path's bits.  Every mask comes from the device table of the subjects' sizes (nobs), never from a padded slot.
 //
@@ -52,82 +59,6 @@ __global__ void k_hadcs_prep(const double* __restrict__ pars, const int* __restr
     const int c = indx[i];
     const double* u = pars + (size_t)2 * N + c * (c + 1) / 2;
     for (int m = 0; m < M; ++m) Rv[(size_t)i * M + m] = (m <= c) ? u[m] : 0.0;
-}
-
-// k_gibbs_cov<M, true> on the real observations, delta_ij on the padded ones (k_hadc_cov with the amplitude s_i s_j).  In the lower
-// triangle a real row has real columns only, so the mask is the row's.  A tile whose rows are all padded only stores.
-template <int M>
-__global__ __launch_bounds__(256) void k_hadcs_cov(const double* __restrict__ x, const double* __restrict__ ell,
-                                                    const double* __restrict__ sig, const double* __restrict__ Rv,
-                                                    const double* __restrict__ pars, long long P, const int* __restrict__ nobs, int cps,
-                                                    double* __restrict__ S, int ld, int N, long long sstride) {
-    constexpr int TJ = 64;
-    __shared__ double sx[TJ], sl[TJ], ss[TJ], sR[TJ * M];
-    const int I = blockIdx.x, J = blockIdx.y;
-    if (I < J) return;
-    const int sub = blockIdx.z / cps;
-    const int Ns = nobs[sub];
-    x += (size_t)sub * N;
-    ell += (size_t)blockIdx.z * N;
-    sig += (size_t)blockIdx.z * N;
-    Rv += (size_t)blockIdx.z * N * M;
-    pars += (size_t)blockIdx.z * P;
-    S += (size_t)blockIdx.z * sstride;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j0 = J * TJ;
-    const int i = I * 64 + lane;
-    if (I * 64 >= Ns) {                                      // every row of the tile is padded: store only
-        if (i >= N) return;
-        for (int jj = 0; jj < TJ / 4; ++jj) {
-            const int j = j0 + w * (TJ / 4) + jj;
-            if (j >= N) break;
-            if (i < j) continue;
-            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
-        }
-        return;
-    }
-    if (tid < TJ) {
-        const int j = j0 + tid;
-        sx[tid] = (j < Ns) ? x[j] : 0.0;
-        sl[tid] = (j < Ns) ? ell[j] : 1.0;
-        ss[tid] = (j < Ns) ? sig[j] : 1.0;
-    }
-    for (int k = tid; k < TJ * M; k += 256) {
-        const size_t g = (size_t)j0 * M + k;
-        sR[k] = (g < (size_t)Ns * M) ? Rv[g] : 0.0;
-    }
-    __syncthreads();
-    if (i >= N) return;
-    const bool real = i < Ns;
-    const int ic = real ? i : 0;
-    const double sigma2 = exp(pars[P - 1]);
-    const double xi = x[ic], li = ell[ic], si = sig[ic];
-    const double xi2 = xi * xi, li2 = li * li;
-    double ri[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
-#pragma unroll 2
-    for (int jj = 0; jj < TJ / 4; ++jj) {
-        const int k = w * (TJ / 4) + jj;
-        const int j = j0 + k;
-        if (j >= N) break;
-        if (i < j) continue;
-        if (!real) {
-            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
-            continue;
-        }
-        const double xj = sx[k], lj = sl[k];
-        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);                           // kernels.py:20
-        const double A = li2 + lj * lj;                                                  // kernels.py:69
-        double kv = (si * ss[k]) * sqrt(2.0 * (li * lj) / A) * exp(-dist / A);           // kernels.py:70-72
-        if (i == j) kv = NMGP_JITTER + kv;                                               // kernels.py:64
-        double b = 0.0;
-#pragma unroll
-        for (int m = 0; m < M; ++m) b += ri[m] * sR[k * M + m];
-        double v = kv * b;
-        if (i == j) v += sigma2;
-        S[(size_t)j * ld + i] = v;
-    }
 }
 
 // two-column prior right-hand side (k_two_col_rhs_b): tilde_l - mu_l and tilde_sigma - mu_s on the real slots, zeros on the padded
@@ -186,103 +117,6 @@ __global__ void k_hadcs_finalize(const double* __restrict__ scal, const double* 
     out6[3] = lp_s;
     out6[4] = lp_L;
     out6[5] = lp_s2;
-}
-
-// k_gibbs_adjoint<M, true> with j < N_s and i < N_s masks (k_hadc_adjoint with M + 2 components: slot 0 = tilde_l, slot 1 =
-// tilde_sigma, then the M row components): part[J][i][0 .. M + 2) of the real i, ZERO partial rows of the padded i (every J) and of
-// tiles with nothing real, so that the per-observation sums need no mask of their own.
-template <int M>
-__global__ __launch_bounds__(256) void k_hadcs_adjoint(const double* __restrict__ x, const double* __restrict__ ell,
-                                                        const double* __restrict__ sig, const double* __restrict__ Rv,
-                                                        const double* __restrict__ alpha, const double* __restrict__ Sneg, int ld,
-                                                        int N, const int* __restrict__ nobs, int cps, double* __restrict__ part,
-                                                        long long pstride) {
-    constexpr int TJ = 64, R0 = 2, W = M + R0;
-    __shared__ double sx[TJ], sl[TJ], ss[TJ], sR[TJ * M], sa[TJ];
-    __shared__ double red[2][4][64];
-    const int I = blockIdx.x, J = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j0 = J * TJ;
-    const size_t Nl = (size_t)N;
-    const int sub = blockIdx.z / cps;
-    const int Ns = nobs[sub];
-    {   // blockIdx.z = chain
-        const size_t z = blockIdx.z;
-        x += (size_t)sub * Nl;
-        ell += z * Nl;
-        sig += z * Nl;
-        Rv += z * Nl * M;
-        alpha += z * Nl;
-        Sneg += z * (size_t)ld * Nl;
-        part += z * (size_t)pstride;
-    }
-    const int i = I * 64 + lane;
-    const bool inN = i < N;
-    if (I * 64 >= Ns || j0 >= Ns) {                          // nothing real in the tile: zero partial rows
-        if (w == 0 && inN) {
-            double* o = part + ((size_t)J * Nl + i) * W;
-#pragma unroll
-            for (int t = 0; t < W; ++t) o[t] = 0.0;
-        }
-        return;
-    }
-    if (tid < TJ) {
-        const int j = j0 + tid;
-        sx[tid] = (j < Ns) ? x[j] : 0.0;
-        sl[tid] = (j < Ns) ? ell[j] : 1.0;
-        ss[tid] = (j < Ns) ? sig[j] : 1.0;
-        sa[tid] = (j < Ns) ? alpha[j] : 0.0;
-    }
-    for (int k = tid; k < TJ * M; k += 256) {
-        const size_t g = (size_t)j0 * M + k;
-        sR[k] = (g < (size_t)Ns * M) ? Rv[g] : 0.0;
-    }
-    __syncthreads();
-    const bool iv = i < Ns;
-    const int ic = iv ? i : Ns - 1;
-    const double xi = x[ic], li = ell[ic], si = sig[ic];
-    const double ai = alpha[ic];
-    const double xi2 = xi * xi, li2 = li * li;
-    double ri[M], acc[W];
-#pragma unroll
-    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
-#pragma unroll
-    for (int t = 0; t < W; ++t) acc[t] = 0.0;
-    if (iv) {
-        for (int jj = 0; jj < TJ / 4; ++jj) {
-            const int k = w * (TJ / 4) + jj;
-            const int j = j0 + k;
-            if (j >= Ns) break;
-            const double xj = sx[k], lj = sl[k];
-            const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
-            const double A = li2 + lj * lj;
-            const double k0 = (si * ss[k]) * sqrt(2.0 * (li * lj) / A) * exp(-dist / A);
-            const double kx = (i == j) ? (NMGP_JITTER + k0) : k0;
-            const double G = 0.5 * (ai * sa[k] + Sneg[(size_t)j * ld + i]);
-            const double gk = 2.0 * kx * G;
-            double dot = 0.0;
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                const double rj = sR[k * M + m];
-                acc[R0 + m] = fma(gk, rj, acc[R0 + m]);
-                dot = fma(ri[m], rj, dot);
-            }
-            const double gd = 2.0 * (G * dot) * k0;
-            acc[1] += gd;
-            if (i != j) {
-                const double dlogk = 0.5 - li2 / A + 2.0 * li2 * dist / (A * A);
-                acc[0] = fma(gd, dlogk, acc[0]);
-            }
-        }
-    }
-    double* o = part + ((size_t)J * Nl + (inN ? i : 0)) * W;
-#pragma unroll
-    for (int t = 0; t < W; ++t) {
-        red[t & 1][w][lane] = acc[t];
-        __syncthreads();
-        // (a padded i < Nmax has four zero accumulators: its row is written as +0.0)
-        if (w == 0 && inN) o[t] = (red[t & 1][0][lane] + red[t & 1][1][lane]) + (red[t & 1][2][lane] + red[t & 1][3][lane]);
-    }
 }
 
 // k_hads_grad_obs on the padded layout: per REAL observation the J partials summed in order, d NegLog / d tilde_l and / d tilde_sigma
@@ -358,40 +192,6 @@ __global__ __launch_bounds__(256) void k_hadcs_grad_lvec(const double* __restric
 
 // ---- stationary -----------------------------------------------------------------------------------------------------------------------
 
-// B_f[a, b] = <row a of L, row b of L> of the packed lower triangle Lvec (hadst_bf of nmgp_hadamard_sta.hip)
-template <int M>
-__device__ inline double hadcst_bf(const double* __restrict__ Lvec, int a, int b) {
-    const int lo = a < b ? a : b;
-    double acc = 0.0;
-#pragma unroll
-    for (int m = 0; m < M; ++m)
-        if (m <= lo) acc += Lvec[a * (a + 1) / 2 + m] * Lvec[b * (b + 1) / 2 + m];
-    return acc;
-}
-
-// hadst_stage of nmgp_hadamard_sta.hip with the subject's N_s as the bound of the j side: sp = {l, s2, sigma2_err}, sB = B_f [M, M],
-// su = x_j / l and sc = c_j of the real j (0 beyond).  The caller synchronises.
-template <int M>
-__device__ inline void hadcst_stage(const double* __restrict__ pars, long long P, const double* __restrict__ x,
-                                    const int* __restrict__ indx, int Ns, int j0, double* sp, double* sB, double* su, int* sc) {
-    const int tid = threadIdx.x;
-    if (tid < 64) {
-        const int j = j0 + tid;
-        const double l = exp(pars[0]);
-        su[tid] = (j < Ns) ? x[j] / l : 0.0;
-        sc[tid] = (j < Ns) ? indx[j] : 0;
-        if (tid == 0) {
-            const double sg = exp(pars[1]);
-            sp[0] = l;
-            sp[1] = sg * sg;
-            sp[2] = exp(pars[P - 1]);
-        }
-    } else if (tid - 64 < M * M) {
-        const int k = tid - 64;
-        sB[k] = hadcst_bf<M>(pars + 2, k / M, k % M);
-    }
-}
-
 // k_hadst_cov on the real observations, delta_ij on the padded ones; a tile whose rows are all padded only stores
 template <int M>
 __global__ __launch_bounds__(256) void k_hadcst_cov(const double* __restrict__ x, const int* __restrict__ indx,
@@ -421,7 +221,7 @@ __global__ __launch_bounds__(256) void k_hadcst_cov(const double* __restrict__ x
         }
         return;
     }
-    hadcst_stage<M>(pars, P, x, indx, Ns, j0, sp, sB, su, sc);
+    hadst_stage<M>(pars, P, x, indx, Ns, j0, sp, sB, su, sc);
     __syncthreads();
     if (i >= N) return;
     const bool real = i < Ns;
@@ -486,7 +286,7 @@ __global__ __launch_bounds__(256) void k_hadcst_adjoint(const double* __restrict
         }
         return;
     }
-    hadcst_stage<M>(pars, P, x, indx, Ns, j0, sp, sB, su, sc);
+    hadst_stage<M>(pars, P, x, indx, Ns, j0, sp, sB, su, sc);
     if (tid < TJ) sa[tid] = (j0 + tid < Ns) ? alpha[j0 + tid] : 0.0;
     for (int k = tid; k < TJ * M; k += 256) {           // r_j = row c_j of L, zero-padded to M
         const int j = j0 + k / M, m = k % M;
@@ -592,12 +392,90 @@ struct CohChunk {
     const int *indx, *nobs;
     int prior;
     bool want_grad;
-    PriorFactor *p0, *p1;
+    PriorFactor *p0, *p1;      // GP_PRIORS: the set's per-subject factors of hyper[1..2] and hyper[4..5]
+    PriorStreamScope* ps;      // GP_PRIORS: the forked prior stream
     double* at(size_t o) const { return slab + o; }
 };
 
-// The two models as the cohort schedule sees them (the Model of nmgp_hadamard_common.h with the subject as a table look-up); P,
-// part_width and extras are the resident models', at N = Nmax.
+// The GP-prior half of a cohort value epilogue (had_gp_prior_terms against the factors of subject s0 + z / cps): rhs(stream, R) fills
+// R with the nc centred prior columns of every chain, zeros on the padded observations; then L X = R -> q = column sums of squares ->
+// with gradients and priors R2 = Sigma_prior^-1 (v - mu).  Ends with the join, so the finaliser may follow.
+template <class Rhs>
+int hadc_gp_prior_terms(const CohChunk& k, int nc, Rhs rhs) {
+    nmgp_ctx* c = k.c;
+    PriorStreamScope& ps = *k.ps;
+    const int N = k.N, B = k.B;
+    double* R = k.at(k.L.o_R);
+    const long long f0 = (long long)k.p0->ld * N, f1 = (long long)k.p1->ld * N;
+    const double *L0 = k.p0->L + (size_t)k.s0 * f0, *L1 = k.p1->L + (size_t)k.s0 * f1;
+    {
+        NmgpStage sp(c, NMGP_STAGE_PRIOR, ps.sp, 0.0, 0.0);
+        rhs(ps.sp, R);
+        prior_trsv(ps.sp, false, L0, k.p0->ld, f0, L1, k.p1->ld, f1, R, N, nc, B, k.cps);
+        col_sumsq(ps.sp, R, N, N, B * nc, k.at(k.L.o_q));
+        if (k.want_grad && k.prior) {
+            double* R2 = k.at(k.L.o_R2);
+            HIP_TRY(c, hipMemcpyAsync(R2, R, (size_t)B * N * nc * sizeof(double), hipMemcpyDeviceToDevice, ps.sp));
+            prior_trsv(ps.sp, true, L0, k.p0->ld, f0, L1, k.p1->ld, f1, R2, N, nc, B, k.cps);
+        }
+    }
+    ps.done();
+    ps.join();
+    return 0;
+}
+
+// The three models as the cohort schedule sees them (the Model of nmgp_hadamard_common.h with the subject as a table look-up, and
+// finite_in(p, Nmax, N_s, T): whether the REAL slots of a padded vector are finite); P, part_width and extras are the resident
+// models', at N = Nmax.
+struct CohNon {
+    static constexpr int WIDTH = 5;
+    static constexpr bool GP_PRIORS = true;
+    static constexpr const char* NOUN = "Hadamard cohort";
+    static size_t P(int N, int T) { return (size_t)N * (1 + T) + 1; }
+    static size_t part_width(int M) { return M + 1; }
+    template <class Take>
+    static void extras(HadLayout& L, Take take, size_t Bs, size_t N, int M, int T, bool want_grad) {
+        L.o_ell = take(Bs * N); L.o_Rv = take(Bs * N * M); L.o_R = take(Bs * N * (1 + T)); L.o_q = take(Bs * (1 + T));
+        if (want_grad) L.o_R2 = take(Bs * N * (1 + T));
+    }
+    static bool finite_in(const double* p, size_t N, size_t Ns, int T) {
+        if (!std::isfinite(p[N * (1 + T)])) return false;
+        for (size_t t = 0; t < Ns; ++t)
+            if (!std::isfinite(p[t])) return false;
+        for (size_t t = 0; t < Ns * T; ++t)
+            if (!std::isfinite(p[N + t])) return false;
+        return true;
+    }
+    static int build_cov(const CohChunk& k) {
+        hipStream_t s = k.c->stream;
+        double *dP = k.at(k.L.o_P), *ell = k.at(k.L.o_ell), *Rv = k.at(k.L.o_Rv);
+        nmgp_hadc_prep(s, dP, k.indx, k.nobs, k.cps, k.N, k.M, k.T, ell, Rv, k.B);
+        return hadc_cov_build<false>(s, k.x, ell, nullptr, Rv, dP, (long long)P(k.N, k.T), k.nobs, k.cps, k.at(k.L.o_S), k.L.ld, k.N, k.M,
+                                     k.B, k.L.bs);
+    }
+    static int value_epilogue(const CohChunk& k) {
+        const int N = k.N, T = k.T, B = k.B;
+        double *dP = k.at(k.L.o_P), *scal = k.at(k.L.o_scal);
+        NMGP_TRY(hadc_gp_prior_terms(k, 1 + T, [&](hipStream_t sp, double* R) {
+            nmgp_hadc_prior_rhs(sp, dP, k.nobs, k.cps, N, T, k.hyper[0], k.hyper[3], R, N, B);
+        }));
+        NmgpStage sp(k.c, NMGP_STAGE_REDUCE);
+        nmgp_hadc_finalize(k.c->stream, scal, k.at(k.L.o_q), k.p0->logdet + k.s0, k.p1->logdet + k.s0, dP, (long long)P(N, T), k.nobs, k.cps,
+                           T, k.hyper[6], k.hyper[7], k.prior, B);
+        return 0;
+    }
+    static int adjoint_grad(const CohChunk& k) {
+        hipStream_t s = k.c->stream;
+        const long long pstride = (long long)k.L.part_per;
+        double* part = k.at(k.L.o_part);
+        NMGP_TRY(hadc_adjoint<false>(s, k.x, k.at(k.L.o_ell), nullptr, k.at(k.L.o_Rv), k.at(k.L.o_alpha), k.at(k.L.o_Sneg), k.N, k.N, k.M,
+                                     k.nobs, k.cps, part, pstride, k.B));
+        nmgp_hadc_grad_final(s, part, pstride, k.N, k.M, k.T, k.indx, k.nobs, k.cps, k.at(k.L.o_R2), k.at(k.L.o_P), k.at(k.L.o_tr),
+                             k.hyper[6], k.hyper[7], k.prior, k.at(k.L.o_grad), k.B);
+        return 0;
+    }
+};
+
 struct CohSep {
     static constexpr int WIDTH = 6;
     static constexpr bool GP_PRIORS = true;
@@ -609,7 +487,6 @@ struct CohSep {
         L.o_ell = take(Bs * N); L.o_sig = take(Bs * N); L.o_Rv = take(Bs * N * M); L.o_R = take(Bs * N * 2); L.o_q = take(Bs * 2);
         if (want_grad) { L.o_R2 = take(Bs * N * 2); L.o_rsum = take(Bs * N * M); }
     }
-    // the real slots of a padded vector: the finiteness test covers these only
     static bool finite_in(const double* p, size_t N, size_t Ns, int T) {
         for (size_t t = 0; t < Ns; ++t)
             if (!std::isfinite(p[t]) || !std::isfinite(p[N + t])) return false;
@@ -622,35 +499,18 @@ struct CohSep {
         const int N = k.N, M = k.M, B = k.B;
         double *dP = k.at(k.L.o_P), *ell = k.at(k.L.o_ell), *sig = k.at(k.L.o_sig), *Rv = k.at(k.L.o_Rv);
         NMGP_LAUNCH(k_hadcs_prep, dim3(cdiv(N, 256), B), dim3(256), 0, s, dP, k.indx, k.nobs, k.cps, N, M, k.T, ell, sig, Rv);
-        const dim3 grid(cdiv(N, 64), cdiv(N, 64), B);
-        NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadcs_cov<MM>), grid, dim3(256), 0, s, k.x, ell, sig, Rv, dP, (long long)P(N, k.T), k.nobs,
-                                        k.cps, k.at(k.L.o_S), k.L.ld, N, k.L.bs));
-        return 0;
+        return hadc_cov_build<true>(s, k.x, ell, sig, Rv, dP, (long long)P(N, k.T), k.nobs, k.cps, k.at(k.L.o_S), k.L.ld, N, M, B, k.L.bs);
     }
-    // hadc_eval_chunk's prior half with two columns per chain, then the finaliser
-    static int value_epilogue(const CohChunk& k, PriorStreamScope& ps) {
-        nmgp_ctx* c = k.c;
-        const int N = k.N, T = k.T, B = k.B, s0 = k.s0, cps = k.cps;
+    static int value_epilogue(const CohChunk& k) {
+        const int N = k.N, T = k.T, B = k.B;
         const NormalF32 nc(0.0, k.hyper[8]);
-        double *dP = k.at(k.L.o_P), *scal = k.at(k.L.o_scal), *R = k.at(k.L.o_R);
-        const long long f0 = (long long)k.p0->ld * N, f1 = (long long)k.p1->ld * N;
-        const double *L0 = k.p0->L + (size_t)s0 * f0, *L1 = k.p1->L + (size_t)s0 * f1;
-        {
-            NmgpStage sp(c, NMGP_STAGE_PRIOR, ps.sp, 0.0, 0.0);
-            NMGP_LAUNCH(k_hadcs_prior_rhs, dim3(cdiv(N, 256), B), dim3(256), 0, ps.sp, dP, k.nobs, cps, N, T, k.hyper[0], k.hyper[3], R);
-            prior_trsv(ps.sp, false, L0, k.p0->ld, f0, L1, k.p1->ld, f1, R, N, 2, B, cps);
-            col_sumsq(ps.sp, R, N, N, B * 2, k.at(k.L.o_q));
-            if (k.want_grad && k.prior) {
-                double* R2 = k.at(k.L.o_R2);
-                HIP_TRY(c, hipMemcpyAsync(R2, R, (size_t)B * N * 2 * sizeof(double), hipMemcpyDeviceToDevice, ps.sp));
-                prior_trsv(ps.sp, true, L0, k.p0->ld, f0, L1, k.p1->ld, f1, R2, N, 2, B, cps);
-            }
-        }
-        ps.done();
-        ps.join();
-        NmgpStage sp(c, NMGP_STAGE_REDUCE);
-        NMGP_LAUNCH(k_hadcs_finalize, dim3(B), dim3(64), 0, c->stream, scal, k.at(k.L.o_q), k.p0->logdet + s0, k.p1->logdet + s0, dP, k.nobs,
-                    cps, N, T, k.hyper[6], k.hyper[7], nc.var, nc.log_sd, k.prior, scal + 8);
+        double *dP = k.at(k.L.o_P), *scal = k.at(k.L.o_scal);
+        NMGP_TRY(hadc_gp_prior_terms(k, 2, [&](hipStream_t sp, double* R) {
+            NMGP_LAUNCH(k_hadcs_prior_rhs, dim3(cdiv(N, 256), B), dim3(256), 0, sp, dP, k.nobs, k.cps, N, T, k.hyper[0], k.hyper[3], R);
+        }));
+        NmgpStage sp(k.c, NMGP_STAGE_REDUCE);
+        NMGP_LAUNCH(k_hadcs_finalize, dim3(B), dim3(64), 0, k.c->stream, scal, k.at(k.L.o_q), k.p0->logdet + k.s0, k.p1->logdet + k.s0, dP,
+                    k.nobs, k.cps, N, T, k.hyper[6], k.hyper[7], nc.var, nc.log_sd, k.prior, scal + 8);
         return 0;
     }
     static int adjoint_grad(const CohChunk& k) {
@@ -659,9 +519,8 @@ struct CohSep {
         const long long pstride = (long long)k.L.part_per;
         const NormalF32 nc(0.0, k.hyper[8]);
         double *dP = k.at(k.L.o_P), *part = k.at(k.L.o_part), *rsum = k.at(k.L.o_rsum), *dg = k.at(k.L.o_grad);
-        const dim3 grid(cdiv(N, 64), cdiv(N, 64), B);
-        NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadcs_adjoint<MM>), grid, dim3(256), 0, s, k.x, k.at(k.L.o_ell), k.at(k.L.o_sig), k.at(k.L.o_Rv),
-                                        k.at(k.L.o_alpha), k.at(k.L.o_Sneg), N, N, k.nobs, k.cps, part, pstride));
+        NMGP_TRY(hadc_adjoint<true>(s, k.x, k.at(k.L.o_ell), k.at(k.L.o_sig), k.at(k.L.o_Rv), k.at(k.L.o_alpha), k.at(k.L.o_Sneg), N, N, M,
+                                    k.nobs, k.cps, part, pstride, B));
         NMGP_LAUNCH(k_hadcs_grad_obs, dim3(cdiv(N, 256), B), dim3(256), 0, s, part, pstride, NJ, N, M, T, k.nobs, k.cps, k.at(k.L.o_R2), dP,
                     k.at(k.L.o_tr), k.hyper[6], k.hyper[7], k.prior, rsum, dg);
         NMGP_LAUNCH(k_hadcs_grad_lvec, dim3(T, B), dim3(256), 0, s, rsum, k.indx, k.nobs, k.cps, N, M, T, dP, nc.var, k.prior, dg);
@@ -708,7 +567,7 @@ struct CohSta {
     }
 };
 
-// chains [0, B) of `pars` (already offset by the caller): chain z belongs to subject s0 + z / cps.  hadc_eval_chunk's sequence at
+// chains [0, B) of `pars` (already offset by the caller): chain z belongs to subject s0 + z / cps.  had_eval_chunk's sequence at
 // n = Nmax with the model's hooks: value and gradient halves enqueued back to back, ONE synchronisation.
 template <class Model>
 int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, const double* hyper, int prior, PriorFactor* p0,
@@ -728,12 +587,12 @@ int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, con
     // the tables of the chunk's first subject
     const double* y = c->hc_y + (size_t)s0 * N;
     const int* nobs = c->hc_nobs + s0;
-    const CohChunk k{c, L, slab, B, s0, cps, N, M, T, c->hc_x + (size_t)s0 * N, hyper, c->hc_indx + (size_t)s0 * N, nobs, prior,
-                     want_grad, p0, p1};
     HIP_TRY(c, hipMemcpyAsync(dP, pars, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)B * sizeof(int), s));
     std::optional<PriorStreamScope> ps;          // fork now, enqueue the prior solves after the factorisation's launches
     if constexpr (Model::GP_PRIORS) ps.emplace(c);
+    const CohChunk k{c, L, slab, B, s0, cps, N, M, T, c->hc_x + (size_t)s0 * N, hyper, c->hc_indx + (size_t)s0 * N, nobs, prior,
+                     want_grad, p0, p1, ps ? &*ps : nullptr};
     {
         NmgpStage sp(c, NMGP_STAGE_COV);
         int r = Model::build_cov(k);
@@ -751,7 +610,7 @@ int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, con
         chol_logdet_quad(s, S, ld, N, z, scal, scal + 1, B, bs, 16);
         if constexpr (!Model::GP_PRIORS) NMGP_TRY(Model::value_epilogue(k));     // the finaliser alone: in this stage
     }
-    if constexpr (Model::GP_PRIORS) NMGP_TRY(Model::value_epilogue(k, *ps));     // prior stream, join, finaliser
+    if constexpr (Model::GP_PRIORS) NMGP_TRY(Model::value_epilogue(k));          // prior stream, join, finaliser (a stage of its own)
     std::vector<double> hs((size_t)B * 16);
     std::vector<int> hi(B);
     HIP_TRY(c, hipMemcpyAsync(hs.data(), scal, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -806,16 +665,22 @@ int cohm_subjects_eval(nmgp_ctx* c, const double* pars, int B, int cps, const do
     const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T;
     const size_t P = Model::P(N, T);
     const bool want_grad = grad != nullptr;
+    // one pair of factors per subject (the cache is a vector: the second look-up may move its elements, so the first is re-resolved)
     PriorFactor *p0 = nullptr, *p1 = nullptr;
     if constexpr (Model::GP_PRIORS) NMGP_TRY(nmgp_hadc_priors(c, hyper, &p0, &p1));
     const size_t per_chain = had_layout<Model>(1, N, M, T, want_grad).total * sizeof(double);
-    return hadc_for_chunks(c, B, cps, per_chain, Model::NOUN, [&](int b0, int nb, int s0, int ccps) {
+    return had_for_chunks(c, B, cps, per_chain, Model::NOUN, "at Nmax", N, [&](int b0, int nb, int s0, int ccps) {
         return cohm_eval_chunk<Model>(c, pars + (size_t)b0 * P, nb, s0, ccps, hyper, prior, p0, p1, out + (size_t)b0 * Model::WIDTH,
                                       want_grad ? grad + (size_t)b0 * P : nullptr, status + b0);
     });
 }
 
 }  // namespace
+
+extern "C" int nmgp_had_subjects_eval(nmgp_ctx* c, const double* pars, int B, int chains_per_subject, const double hyper[8], int prior,
+                                      double* out5, double* grad, int* status) {
+    return cohm_subjects_eval<CohNon>(c, pars, B, chains_per_subject, hyper, prior, out5, grad, status);
+}
 
 extern "C" int nmgp_hads_subjects_eval(nmgp_ctx* c, const double* pars, int B, int chains_per_subject, const double hyper[9], int prior,
                                        double* out6, double* grad, int* status) {

@@ -18,7 +18,9 @@
 // Kernels: k_gibbs_cov<M, AMP> / k_gibbs_adjoint<M, AMP> with their launchers; AMP = false is the nonseparable model (unit
 // amplitude), AMP = true the separable one (K_x carries s_i s_j).  A 64 x 64 tile of observations per 256-thread workgroup, lanes
 // along i (a wave stores / loads 512 contiguous bytes of one column), the j side staged in LDS, blockIdx.z = chain; fixed summation
-// order and no atomics, so B chains in one launch give the bits of B launches.
+// order and no atomics, so B chains in one launch give the bits of B launches.  Below them: the masked pair of the cohort of ragged
+// subjects, k_hadc_cov<M, AMP> / k_hadc_adjoint<M, AMP> (the same kernels with the subject's size from a device table; its host
+// skeleton is in nmgp_hadamard_cohort_models.hip), and hadst_bf / hadst_stage, the staging of the stationary model's kernels.
 #pragma once
 
 #include "nmgp_internal.h"
@@ -197,6 +199,246 @@ int gibbs_adjoint(hipStream_t s, const double* x, const double* ell, const doubl
     return 0;
 }
 
+// ---- the masked Gibbs kernels of the cohort (ragged subjects padded to Nmax, nmgp_hadamard_cohort.hip) ---------------------------
+// The resident pair above is shared by entries whose bits and register budgets are pinned, so no mask is threaded through it; this
+// pair keeps its tile shape, lane mapping, LDS staging, expression order and its handling of AMP, so that a subject with N_s = Nmax
+// gets the resident path's bits.  blockIdx.z = chain, subject = chain / cps of the chunk, N_s = nobs[subject]: every mask comes from
+// the device table of the subjects' sizes, never from the contents of a padded slot.
+
+// k_gibbs_cov on the real observations, delta_ij on the padded ones: the whole Nmax x Nmax lower triangle.  There i >= j, so a real
+// row has real columns only and the mask is the row's.  A tile whose rows are all padded stores and does nothing else.
+template <int M, bool AMP>
+__global__ __launch_bounds__(256) void k_hadc_cov(const double* __restrict__ x, const double* __restrict__ ell,
+                                                   const double* __restrict__ sig, const double* __restrict__ Rv,
+                                                   const double* __restrict__ pars, long long P, const int* __restrict__ nobs, int cps,
+                                                   double* __restrict__ S, int ld, int N, long long sstride) {
+    constexpr int TJ = 64;
+    __shared__ double sx[TJ], sl[TJ], ss[AMP ? TJ : 1], sR[TJ * M];
+    const int I = blockIdx.x, J = blockIdx.y;
+    if (I < J) return;
+    const int sub = blockIdx.z / cps;
+    const int Ns = nobs[sub];
+    x += (size_t)sub * N;
+    ell += (size_t)blockIdx.z * N;
+    if constexpr (AMP) sig += (size_t)blockIdx.z * N;
+    Rv += (size_t)blockIdx.z * N * M;
+    pars += (size_t)blockIdx.z * P;
+    S += (size_t)blockIdx.z * sstride;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    const int i = I * 64 + lane;
+    if (I * 64 >= Ns) {                                      // every row of the tile is padded: store only
+        if (i >= N) return;
+        for (int jj = 0; jj < TJ / 4; ++jj) {
+            const int j = j0 + w * (TJ / 4) + jj;
+            if (j >= N) break;
+            if (i < j) continue;
+            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
+        }
+        return;
+    }
+    if (tid < TJ) {
+        const int j = j0 + tid;
+        sx[tid] = (j < Ns) ? x[j] : 0.0;
+        sl[tid] = (j < Ns) ? ell[j] : 1.0;
+        if constexpr (AMP) ss[tid] = (j < Ns) ? sig[j] : 1.0;
+    }
+    for (int k = tid; k < TJ * M; k += 256) {
+        const size_t g = (size_t)j0 * M + k;
+        sR[k] = (g < (size_t)Ns * M) ? Rv[g] : 0.0;
+    }
+    __syncthreads();
+    if (i >= N) return;
+    const bool real = i < Ns;
+    const int ic = real ? i : 0;
+    const double sigma2 = exp(pars[P - 1]);
+    const double xi = x[ic], li = ell[ic];
+    [[maybe_unused]] double si = 0.0;
+    if constexpr (AMP) si = sig[ic];
+    const double xi2 = xi * xi, li2 = li * li;
+    double ri[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
+#pragma unroll 2
+    for (int jj = 0; jj < TJ / 4; ++jj) {
+        const int k = w * (TJ / 4) + jj;
+        const int j = j0 + k;
+        if (j >= N) break;
+        if (i < j) continue;
+        if (!real) {
+            S[(size_t)j * ld + i] = (i == j) ? 1.0 : 0.0;
+            continue;
+        }
+        const double xj = sx[k], lj = sl[k];
+        const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);   // kernels.py:20
+        const double A = li2 + lj * lj;                          // kernels.py:69
+        double kv;                                               // kernels.py:70-72
+        if constexpr (AMP) kv = (si * ss[k]) * sqrt(2.0 * (li * lj) / A) * exp(-dist / A);
+        else kv = sqrt(2.0 * (li * lj) / A) * exp(-dist / A);
+        if (i == j) kv = NMGP_JITTER + kv;                       // kernels.py:64
+        double b = 0.0;
+#pragma unroll
+        for (int m = 0; m < M; ++m) b += ri[m] * sR[k * M + m];
+        double v = kv * b;
+        if (i == j) v += sigma2;
+        S[(size_t)j * ld + i] = v;
+    }
+}
+
+// k_gibbs_adjoint with j < N_s and i < N_s masks: part[J][i][0 .. W) of the real i, ZERO partial rows of the padded i (every J) and
+// of tiles with nothing real, so that the sums over J and over the observations need no mask of their own.
+template <int M, bool AMP>
+__global__ __launch_bounds__(256) void k_hadc_adjoint(const double* __restrict__ x, const double* __restrict__ ell,
+                                                       const double* __restrict__ sig, const double* __restrict__ Rv,
+                                                       const double* __restrict__ alpha, const double* __restrict__ Sneg, int ld,
+                                                       int N, const int* __restrict__ nobs, int cps, double* __restrict__ part,
+                                                       long long pstride) {
+    constexpr int TJ = 64, R0 = AMP ? 2 : 1, W = M + R0;
+    __shared__ double sx[TJ], sl[TJ], ss[AMP ? TJ : 1], sR[TJ * M], sa[TJ];
+    __shared__ double red[2][4][64];
+    const int I = blockIdx.x, J = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j0 = J * TJ;
+    const size_t Nl = (size_t)N;
+    const int sub = blockIdx.z / cps;
+    const int Ns = nobs[sub];
+    {   // blockIdx.z = chain
+        const size_t z = blockIdx.z;
+        x += (size_t)sub * Nl;
+        ell += z * Nl;
+        if constexpr (AMP) sig += z * Nl;
+        Rv += z * Nl * M;
+        alpha += z * Nl;
+        Sneg += z * (size_t)ld * Nl;
+        part += z * (size_t)pstride;
+    }
+    const int i = I * 64 + lane;
+    const bool inN = i < N;
+    if (I * 64 >= Ns || j0 >= Ns) {                          // nothing real in the tile: zero partial rows
+        if (w == 0 && inN) {
+            double* o = part + ((size_t)J * Nl + i) * W;
+#pragma unroll
+            for (int t = 0; t < W; ++t) o[t] = 0.0;
+        }
+        return;
+    }
+    if (tid < TJ) {
+        const int j = j0 + tid;
+        sx[tid] = (j < Ns) ? x[j] : 0.0;
+        sl[tid] = (j < Ns) ? ell[j] : 1.0;
+        if constexpr (AMP) ss[tid] = (j < Ns) ? sig[j] : 1.0;
+        sa[tid] = (j < Ns) ? alpha[j] : 0.0;
+    }
+    for (int k = tid; k < TJ * M; k += 256) {
+        const size_t g = (size_t)j0 * M + k;
+        sR[k] = (g < (size_t)Ns * M) ? Rv[g] : 0.0;
+    }
+    __syncthreads();
+    const bool iv = i < Ns;
+    const int ic = iv ? i : Ns - 1;
+    const double xi = x[ic], li = ell[ic];
+    [[maybe_unused]] double si = 0.0;
+    if constexpr (AMP) si = sig[ic];
+    const double ai = alpha[ic];
+    const double xi2 = xi * xi, li2 = li * li;
+    double ri[M], acc[W];
+#pragma unroll
+    for (int m = 0; m < M; ++m) ri[m] = Rv[(size_t)ic * M + m];
+#pragma unroll
+    for (int t = 0; t < W; ++t) acc[t] = 0.0;
+    if (iv) {
+        for (int jj = 0; jj < TJ / 4; ++jj) {
+            const int k = w * (TJ / 4) + jj;
+            const int j = j0 + k;
+            if (j >= Ns) break;
+            const double xj = sx[k], lj = sl[k];
+            const double dist = (xi2 + xj * xj) - 2.0 * (xi * xj);
+            const double A = li2 + lj * lj;
+            double k0;
+            if constexpr (AMP) k0 = (si * ss[k]) * sqrt(2.0 * (li * lj) / A) * exp(-dist / A);
+            else k0 = sqrt(2.0 * (li * lj) / A) * exp(-dist / A);
+            const double kx = (i == j) ? (NMGP_JITTER + k0) : k0;
+            const double G = 0.5 * (ai * sa[k] + Sneg[(size_t)j * ld + i]);
+            const double gk = 2.0 * kx * G;
+            double dot = 0.0;
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                const double rj = sR[k * M + m];
+                acc[R0 + m] = fma(gk, rj, acc[R0 + m]);
+                dot = fma(ri[m], rj, dot);
+            }
+            const double gd = 2.0 * (G * dot) * k0;
+            if constexpr (AMP) acc[1] += gd;
+            if (i != j) {
+                const double dlogk = 0.5 - li2 / A + 2.0 * li2 * dist / (A * A);
+                acc[0] = fma(gd, dlogk, acc[0]);
+            }
+        }
+    }
+    double* o = part + ((size_t)J * Nl + (inN ? i : 0)) * W;
+#pragma unroll
+    for (int t = 0; t < W; ++t) {
+        red[t & 1][w][lane] = acc[t];
+        __syncthreads();
+        // (a padded i < Nmax has four zero accumulators: its row is written as +0.0)
+        if (w == 0 && inN) o[t] = (red[t & 1][0][lane] + red[t & 1][1][lane]) + (red[t & 1][2][lane] + red[t & 1][3][lane]);
+    }
+}
+
+// launchers of the masked pair (x: the chunk's first subject's row of the [S, Nmax] table; `sig` as above)
+template <bool AMP>
+int hadc_cov_build(hipStream_t s, const double* x, const double* ell, const double* sig, const double* Rv, const double* pars,
+                   long long P, const int* nobs, int cps, double* S, int ld, int N, int M, int batch, long long sstride) {
+    const dim3 grid((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64), batch);
+    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadc_cov<MM, AMP>), grid, dim3(256), 0, s, x, ell, sig, Rv, pars, P, nobs, cps, S, ld, N, sstride));
+    return 0;
+}
+
+template <bool AMP>
+int hadc_adjoint(hipStream_t s, const double* x, const double* ell, const double* sig, const double* Rv, const double* alpha,
+                 const double* Sneg, int ld, int N, int M, const int* nobs, int cps, double* part, long long pstride, int batch) {
+    const dim3 grid((unsigned)((N + 63) / 64), (unsigned)((N + 63) / 64), batch);
+    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadc_adjoint<MM, AMP>), grid, dim3(256), 0, s, x, ell, sig, Rv, alpha, Sneg, ld, N, nobs, cps, part,
+                                    pstride));
+    return 0;
+}
+
+// ---- device helpers of the stationary model's kernels (k_hadst_* of nmgp_hadamard_sta.hip, k_hadcst_* of the cohort) -----------------
+
+// B_f[a, b] = <row a of L, row b of L> of the packed lower triangle Lvec
+template <int M>
+__device__ inline double hadst_bf(const double* __restrict__ Lvec, int a, int b) {
+    const int lo = a < b ? a : b;
+    double acc = 0.0;
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+        if (m <= lo) acc += Lvec[a * (a + 1) / 2 + m] * Lvec[b * (b + 1) / 2 + m];
+    return acc;
+}
+
+// The chain's scalars, once per workgroup: sp = {l, s2, sigma2_err}, sB = B_f [M, M]; and the j side of the tile: su = x_j / l and
+// sc = c_j for j < nreal (the resident kernels pass N, the cohort's the subject's N_s), 0 beyond.  The caller synchronises.
+template <int M>
+__device__ inline void hadst_stage(const double* __restrict__ pars, long long P, const double* __restrict__ x,
+                                   const int* __restrict__ indx, int nreal, int j0, double* sp, double* sB, double* su, int* sc) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const int j = j0 + tid;
+        const double l = exp(pars[0]);
+        su[tid] = (j < nreal) ? x[j] / l : 0.0;
+        sc[tid] = (j < nreal) ? indx[j] : 0;
+        if (tid == 0) {
+            const double sg = exp(pars[1]);
+            sp[0] = l;
+            sp[1] = sg * sg;
+            sp[2] = exp(pars[P - 1]);
+        }
+    } else if (tid - 64 < M * M) {
+        const int k = tid - 64;
+        sB[k] = hadst_bf<M>(pars + 2, k / M, k % M);
+    }
+}
+
 // Normal(mean, sd) with Python-number arguments: torch rounds both to float32, squares and takes the logarithm there
 struct NormalF32 {
     double mean, var, log_sd;
@@ -366,6 +608,32 @@ int had_eval_chunk(nmgp_ctx* c, const double* pars, int B, const double* hyper, 
     return 0;
 }
 
+// The chunk loop of the resident and the cohort entries: B = S * cps chains in chunks below NMGP_HAD_BATCH_SLAB_GB (default 96, at
+// least 1) for `per_chain` bytes of workspace per chain.  A chunk is a whole number of subjects, or a part of ONE subject's chains
+// (then every chain of the chunk is that subject's), so that no kernel takes a chain offset; the resident entries are one subject of
+// B chains.  eval(b0, nb, s0, cps of the chunk) evaluates chains [b0, b0 + nb), the first of which belongs to subject s0.  `noun`,
+// `at` and `n` name the model and its order in the refusal.
+template <class Eval>
+int had_for_chunks(nmgp_ctx* c, int B, int cps, size_t per_chain, const char* noun, const char* at, int n, Eval eval) {
+    double cap_gb = 96.0;
+    if (const char* e = std::getenv("NMGP_HAD_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
+    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
+    Bc = std::min(Bc, 65535);                      // the chain is a grid dimension
+    if (Bc < 1)
+        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the %s %s = %d needs %.1f GB of device workspace, above the "
+                         "NMGP_HAD_BATCH_SLAB_GB cap of %.0f GB", noun, at, n, per_chain / 1e9, cap_gb);
+    const bool split = cps > Bc;
+    if (!split) Bc = (Bc / cps) * cps;
+    for (int b0 = 0; b0 < B;) {
+        const int s0 = b0 / cps;
+        int nb = std::min(Bc, B - b0);
+        if (split) nb = std::min(nb, (s0 + 1) * cps - b0);
+        NMGP_TRY(eval(b0, nb, s0, split ? nb : cps));
+        b0 += nb;
+    }
+    return 0;
+}
+
 // B chains of the resident Hadamard subject: pars [B, P] -> out [B, WIDTH] (the verbose tuples), grad [B, P] = d NegLog / d pars or
 // NULL, status [B] (0, a leading-minor index, NMGP_NUM_NAN; a failing chain has a NaN row, a zero gradient row, and does not fail
 // the call).  The workspace is the entry's own, evaluated in chunks of chains below NMGP_HAD_BATCH_SLAB_GB (default 96, at least 1).
@@ -380,19 +648,12 @@ int had_batch_eval(nmgp_ctx* c, const double* pars, int B, const double* hyper, 
     const int N = c->N, M = c->M, T = c->T;
     const size_t P = Model::P(N, T);
     const bool want_grad = grad != nullptr;
-    double cap_gb = 96.0;
-    if (const char* e = std::getenv("NMGP_HAD_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
     const size_t per_chain = had_layout<Model>(1, N, M, T, want_grad).total * sizeof(double);
-    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
-    Bc = std::min(Bc, 65535);                      // the chain is a grid dimension
-    if (Bc < 1)
-        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the %s model at N = %d needs %.1f GB of device workspace, above the "
-                         "NMGP_HAD_BATCH_SLAB_GB cap of %.0f GB", Model::NOUN, N, per_chain / 1e9, cap_gb);
-    for (int b0 = 0; b0 < B; b0 += Bc) {
-        const int nb = std::min(Bc, B - b0);
-        NMGP_TRY(had_eval_chunk<Model>(c, pars + (size_t)b0 * P, nb, hyper, prior, out + (size_t)b0 * Model::WIDTH,
-                                       want_grad ? grad + (size_t)b0 * P : nullptr, status + b0));
-    }
+    // one "subject" of B chains: one chunk when B fits under the cap, chunks of the cap's chains otherwise
+    NMGP_TRY(had_for_chunks(c, B, B, per_chain, Model::NOUN, "model at N", N, [&](int b0, int nb, int, int) {
+        return had_eval_chunk<Model>(c, pars + (size_t)b0 * P, nb, hyper, prior, out + (size_t)b0 * Model::WIDTH,
+                                     want_grad ? grad + (size_t)b0 * P : nullptr, status + b0);
+    }));
     c->last_kind = 0;
     return 0;
 }
@@ -424,27 +685,3 @@ int had_covariance(nmgp_ctx* c, const double* pars, double* out) {
     return nmgp_take_launch_error(c);
 }
 
-// The chunk loop of the three cohort entries (nmgp_hadamard_cohort.hip, nmgp_hadamard_cohort_models.hip): B = S * cps chains in chunks
-// below NMGP_HAD_BATCH_SLAB_GB (default 96, at least 1) for `per_chain` bytes of workspace per chain.  A chunk is a whole number of
-// subjects, or a part of ONE subject's chains (then every chain of the chunk is that subject's), so that no kernel takes a chain
-// offset.  eval(b0, nb, s0, cps of the chunk) evaluates chains [b0, b0 + nb), the first of which belongs to subject s0.
-template <class Eval>
-int hadc_for_chunks(nmgp_ctx* c, int B, int cps, size_t per_chain, const char* noun, Eval eval) {
-    double cap_gb = 96.0;
-    if (const char* e = std::getenv("NMGP_HAD_BATCH_SLAB_GB")) cap_gb = std::max(1.0, std::atof(e));
-    int Bc = (int)std::min<double>((double)B, std::floor(cap_gb * 1e9 / (double)per_chain));
-    Bc = std::min(Bc, 65535);                      // the chain is a grid dimension
-    if (Bc < 1)
-        return nmgp_fail(c, NMGP_E_SHAPE, "one chain of the %s at Nmax = %d needs %.1f GB of device workspace, above the "
-                         "NMGP_HAD_BATCH_SLAB_GB cap of %.0f GB", noun, c->hc_Nmax, per_chain / 1e9, cap_gb);
-    const bool split = cps > Bc;
-    if (!split) Bc = (Bc / cps) * cps;
-    for (int b0 = 0; b0 < B;) {
-        const int s0 = b0 / cps;
-        int nb = std::min(Bc, B - b0);
-        if (split) nb = std::min(nb, (s0 + 1) * cps - b0);
-        NMGP_TRY(eval(b0, nb, s0, split ? nb : cps));
-        b0 += nb;
-    }
-    return 0;
-}

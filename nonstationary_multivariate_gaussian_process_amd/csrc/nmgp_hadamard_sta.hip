@@ -25,39 +25,8 @@ namespace {
 
 inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
-// B_f[a, b] = <row a of L, row b of L> of the packed lower triangle Lvec
-template <int M>
-__device__ inline double hadst_bf(const double* __restrict__ Lvec, int a, int b) {
-    const int lo = a < b ? a : b;
-    double acc = 0.0;
-#pragma unroll
-    for (int m = 0; m < M; ++m)
-        if (m <= lo) acc += Lvec[a * (a + 1) / 2 + m] * Lvec[b * (b + 1) / 2 + m];
-    return acc;
-}
-
-// The chain's scalars, once per workgroup: sp = {l, s2, sigma2_err}, sB = B_f [M, M]; and the j side of the tile: su = x_j / l, sc = c_j.
-// The caller synchronises.
-template <int M>
-__device__ inline void hadst_stage(const double* __restrict__ pars, long long P, const double* __restrict__ x,
-                                   const int* __restrict__ indx, int N, int j0, double* sp, double* sB, double* su, int* sc) {
-    const int tid = threadIdx.x;
-    if (tid < 64) {
-        const int j = j0 + tid;
-        const double l = exp(pars[0]);
-        su[tid] = (j < N) ? x[j] / l : 0.0;
-        sc[tid] = (j < N) ? indx[j] : 0;
-        if (tid == 0) {
-            const double sg = exp(pars[1]);
-            sp[0] = l;
-            sp[1] = sg * sg;
-            sp[2] = exp(pars[P - 1]);
-        }
-    } else if (tid - 64 < M * M) {
-        const int k = tid - 64;
-        sB[k] = hadst_bf<M>(pars + 2, k / M, k % M);
-    }
-}
+// (hadst_bf<M> and hadst_stage<M>, the chain's scalars and the j side of a tile, are in nmgp_hadamard_common.h: the cohort's
+// kernels stage the same way)
 
 // S[i, j] = B_f[c_i, c_j] (s2 exp(-d_ij / 2) + jitter d_ij) + sigma2_err d_ij, lower triangle, column-major with leading dimension ld
 template <int M>

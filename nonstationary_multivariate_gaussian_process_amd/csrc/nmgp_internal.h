@@ -341,6 +341,18 @@ void nmgp_hadst_finalize(hipStream_t s, double* scal, const double* pars, int T,
 int nmgp_hadc_priors(nmgp_ctx* c, const double* hyper, PriorFactor** p0, PriorFactor** p1);
 void nmgp_hadc_trace(hipStream_t s, const double* alpha, const double* Sinv, int ld, int N, const int* nobs, int cps, double* out,
                      double ssign, int batch);
+// ... and the nonseparable model's own kernels on the padded layout [batch, Nmax (1 + T) + 1], chain z of subject z / cps: ell and Rv
+// (1 / 0 on padded observations), the 1 + T centred prior columns R (zeros on padded observations), scal[0 .. 1] -> the tuple in
+// scal[8 ..] with N_s log 2 pi, and the final gradient from the adjoint partial rows (+0.0 in padded slots)
+void nmgp_hadc_prep(hipStream_t s, const double* pars, const int* indx, const int* nobs, int cps, int N, int M, int T, double* ell,
+                    double* Rv, int batch);
+void nmgp_hadc_prior_rhs(hipStream_t s, const double* pars, const int* nobs, int cps, int N, int T, double mu_l, double mu_L, double* R,
+                         int ld, int batch);
+void nmgp_hadc_finalize(hipStream_t s, double* scal, const double* q, const double* hl_l, const double* hl_L, const double* pars,
+                        long long P, const int* nobs, int cps, int T, double a, double b, int prior, int batch);
+void nmgp_hadc_grad_final(hipStream_t s, const double* part, long long pstride, int N, int M, int T, const int* indx, const int* nobs,
+                          int cps, const double* R2, const double* pars, const double* tr, double a, double b, int prior, double* grad,
+                          int batch);
 // kernels templated over the number of outputs M <= 8
 #define NMGP_HADS_SWITCH(M, CALL)               \
     switch (M) {                                \

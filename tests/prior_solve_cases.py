@@ -435,7 +435,7 @@ INVENTORY = {
     "had_prior_solve/trsv": "had_prior_solve, N <= 3500: k_prior_trsv",
     "had_prior_solve/trsm_same": "had_prior_solve beyond N = 3500 or under rocblas, pl == pL: one dtrsm over B (1 + T) columns",
     "had_prior_solve/trsm_pair": "the same, pl != pL: two strided-batched dtrsm with R + N and stride (1 + T) N",
-    "cohort/trsv": "hadc_eval_chunk: k_prior_trsv with per-subject factor offsets",
+    "cohort/trsv": "hadc_gp_prior_terms: k_prior_trsv with per-subject factor offsets",
     "cohort/trsv_chunked": "the same in chunks that start at a later subject: factors and log-determinants offset by s0 > 0",
     "gp_project/trsv": "gp_project (nmgp_predict_svc / _sep): k_prior_trsv, forward and transposed",
     "gp_project/trsm": "gp_project under rocblas: the dtrsm pair",
@@ -506,8 +506,8 @@ def branch_of(table, tag, context, variant, entry):
 
 def cohort_chunks(nsub, cps, Nmax, M, cap_gb, want_grad=True):
     """[(first subject, chains)] of the chunks nmgp_had_subjects_eval makes of nsub x cps chains under an NMGP_HAD_BATCH_SLAB_GB of
-    cap_gb (floored at 1): had_layout<HadCohort> of one chain, every piece rounded up to an even count of doubles, then the chunk rule
-    of csrc/nmgp_hadamard_cohort.hip."""
+    cap_gb (floored at 1): had_layout<CohNon> of one chain, every piece rounded up to an even count of doubles, then the chunk rule
+    (had_for_chunks, csrc/nmgp_hadamard_common.h)."""
     T, N = n_slots(M), Nmax
     P = N * (1 + T) + 1
     ld = ((2 * N + 2 if want_grad else N + 1) + 15) // 16 * 16
