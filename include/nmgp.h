@@ -198,6 +198,32 @@ int nmgp_hads_subjects_eval(nmgp_ctx* ctx, const double* pars /*[B,Pmax]*/, int 
  * set's prior factors nor the prior stream are touched. */
 int nmgp_hadst_subjects_eval(nmgp_ctx* ctx, const double* pars /*[B,T+3]*/, int B, int chains_per_subject, const double hyper[5],
                              int prior, double* out5 /*[B,5]*/, double* grad /*[B,T+3] or NULL*/, int* status /*[B]*/);
+/* MAP and posterior-draw prediction for the set under the two models.  Both entries follow nmgp_predsample_had_subjects in every
+ * convention not named here: B = S * draws_per_subject rows, row s * draws_per_subject + h is draw h of subject s; xs [S, Smax] with
+ * the table nstar (NULL: all Smax; 0 <= nstar[s] <= Smax); indx_star == NULL: mean / var [B, Smax, M], indx_star [S, Smax]: mean / var
+ * [B, Smax]; a padded new input gets +0.0 in mean, var and star_out, and nothing is read from a padded slot of pars, xs, indx_star, z
+ * or star_in, nor from the padded part of the set's x / indx / y: every mask comes from the nobs and nstar tables; status [B] (the
+ * finiteness tests cover the row's real parameter slots and real outputs), a failing draw has NaN in its real output slots and leaves
+ * its neighbours' bits alone; chunks under NMGP_PREDSAMPLE_CHUNK / NMGP_PREDSAMPLE_SLAB_GB (read at every call) are whole subjects
+ * or parts of ONE subject's draws, one synchronisation each; a row's bits depend neither on the chunking, nor on
+ * draws_per_subject, nor on the other subjects of the set, nor on the slice a new input falls into; a subject with nobs[s] == Nmax and
+ * nstar[s] == Smax gets the bits of the resident entry under the same starred values; the same error codes for the same mistakes,
+ * NMGP_E_UNSUPPORTED under NMGP_CHOL=rocsolver; the set, its prior factors, the resident subject and a pending batched result stay
+ * as they were.
+ *
+ * Separable: pars [B, 2 Nmax + T + 1] in the padded layout of nmgp_hads_subjects_eval (real slots: [0, N_s), [Nmax, Nmax + N_s), the
+ * T + 1 shared ones); z / star_in / star_out [B, Smax, 2] (tilde_l*, tilde_sigma* before exp) under nmgp_predsample_hads's rules
+ * (z == NULL: the conditional means; star_in skips the regression and z must then be NULL: NMGP_E_STATE; a conditional variance < 0
+ * is replaced by 1e-6).  var = B_f[m, m] (sigma*^2 + 1e-6) - |L^-1 k_f|^2 + sigma2_err, a value <= 0 replaced by 1e-6.  The priors
+ * hyper[1..2] and hyper[4..5] are looked up in the set's cache, shared with the nonseparable entries and nmgp_hads_subjects_eval. */
+int nmgp_predsample_hads_subjects(nmgp_ctx* ctx, const double* pars /*[B,2Nmax+T+1]*/, int B, int draws_per_subject,
+                                  const double hyper[9], const double* xs, const int* indx_star, const int* nstar, int Smax,
+                                  const double* z, const double* star_in, double* mean, double* var, double* star_out, int* status);
+/* Stationary: pars [B, T + 3], every slot real; no latent curve, no hyper, no z, no starred values.  draws_per_subject = 1 is the MAP
+ * predictor, > 1 the posterior-draw predictor, as nmgp_predict_hadst is.  var = B_f[m, m] (s^2 + 1e-6) - |L^-1 k_f|^2 + sigma2_err
+ * with the same replacement.  Neither the set's prior factors nor the prior stream are touched. */
+int nmgp_predict_hadst_subjects(nmgp_ctx* ctx, const double* pars /*[B,T+3]*/, int B, int draws_per_subject, const double* xs,
+                                const int* indx_star, const int* nstar, int Smax, double* mean, double* var, int* status);
 
 /* ---- nonseparable ("SVC") objective:  logpos.nlogpos_obj_SVC / logpos_SVC, logpos.py:299-380 -- */
 /* hyper[8] = {mu_tilde_l, alpha_tilde_l, beta_tilde_l, mu_L, alpha_L, beta_L, a, b}.

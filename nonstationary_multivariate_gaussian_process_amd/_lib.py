@@ -93,6 +93,10 @@ SIGNATURES = {
     "nmgp_hadst_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_had_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
                                          ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_predsample_hads_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
+                                          ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_predict_hadst_subjects": (I, [V, P, I, I, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P,
+                                        ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_batch_eval": (I, [V, P, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_covariance": (I, [V, P, P]),
     "nmgp_predict_hads": (I, [V, P, P, P, I, P, P, P]),
@@ -918,20 +922,29 @@ class Context:
         return self._model_subjects_eval(self.lib.nmgp_hadst_subjects_eval, pars, hyper, prior, want_grad, chains_per_subject, 5,
                                          lambda N, T: T + 3, "T + 3")
 
-    def predsample_had_subjects(self, pars, hyper, xs, indx_star=None, nstar=None, draws_per_subject=1, z=None, star=None):
-        """MAP and posterior-draw prediction for the cohort (``nmgp_predsample_had_subjects``), padded arrays as the C entry takes
-        them: pars [B = S * draws_per_subject, Pmax] (row s * draws_per_subject + h = draw h of subject s), xs [S, Smax] of which
-        the first nstar[s] entries of row s are read (nstar=None: all Smax), indx_star [S, Smax] or None (all M outputs per input),
-        z / star [B, Smax, 1+T] as ``predsample_had``.  Returns (mean, var [B, Smax(, M)], star [B, Smax, 1+T], status [B]); padded
-        new-input slots hold +0.0, a draw with non-zero status has NaN in its real slots.  ``hadamard.cohort_predict`` is the ragged
-        form."""
+    # the three cohort predictors as the binding sees them: C entry, entries of hyper (0: the entry takes no hyper, z or star and
+    # returns no starred values), length of a parameter row and its name, starred values per draw and input and their name
+    _COHORT_PREDICTORS = {
+        "had": dict(entry="nmgp_predsample_had_subjects", nhyper=8, plen=lambda N, T: N * (1 + T) + 1, what="Nmax(1+T)+1",
+                    width=lambda T: 1 + T, wname="1+T"),
+        "sep": dict(entry="nmgp_predsample_hads_subjects", nhyper=9, plen=lambda N, T: 2 * N + T + 1, what="2 Nmax + T + 1",
+                    width=lambda T: 2, wname="2"),
+        "sta": dict(entry="nmgp_predict_hadst_subjects", nhyper=0, plen=lambda N, T: T + 3, what="T + 3", width=None, wname=None),
+    }
+
+    def _predict_subjects(self, model, pars, xs, hyper=None, indx_star=None, nstar=None, draws_per_subject=1, z=None, star=None):
+        """The three cohort predictors' binding: shape checks against the set's (S, Nmax, M), the padded output arrays, the call."""
+        d = self._COHORT_PREDICTORS[model]
+        fn = getattr(self.lib, d["entry"])
         cohort = getattr(self, "_cohort", None)
         pars = as_f64(pars)
         if pars.ndim == 1:
             pars = pars[None]
-        hyper, xs = as_f64(hyper).reshape(-1), as_f64(xs)
-        if hyper.shape[0] != 8:
-            raise NmgpError("hyper must have 8 entries, got %d" % hyper.shape[0])
+        xs = as_f64(xs)
+        if d["nhyper"]:
+            hyper = as_f64(hyper).reshape(-1)
+            if hyper.shape[0] != d["nhyper"]:
+                raise NmgpError("hyper must have %d entries, got %d" % (d["nhyper"], hyper.shape[0]))
         H = int(draws_per_subject)
         if pars.ndim != 2 or xs.ndim != 2 or xs.shape[1] < 1 or H < 1:
             raise NmgpError("pars must be [B, Pmax], xs [S, Smax >= 1] and draws_per_subject >= 1; got %s, %s, %d"
@@ -941,10 +954,10 @@ class Context:
         if cohort is not None:
             M = cohort[2]
             T = M * (M + 1) // 2
-            P_ = cohort[1] * (1 + T) + 1
+            P_ = d["plen"](cohort[1], T)
             if S != cohort[0] or B != S * H or pars.shape[1] != P_:
-                raise NmgpError("pars must be [S * draws_per_subject = %d, Nmax(1+T)+1 = %d] and xs [S = %d, Smax]; got %s, %s"
-                                % (cohort[0] * H, P_, cohort[0], pars.shape, xs.shape))
+                raise NmgpError("pars must be [S * draws_per_subject = %d, %s = %d] and xs [S = %d, Smax]; got %s, %s"
+                                % (cohort[0] * H, d["what"], P_, cohort[0], pars.shape, xs.shape))
         else:                            # (no set: the entry refuses the call; the shapes only have to be self-consistent)
             M, T = 1, None
         ipt = ctypes.POINTER(ctypes.c_int)
@@ -959,24 +972,51 @@ class Context:
             na = np.ascontiguousarray(np.asarray(nstar).reshape(-1), dtype=np.int32)
             if na.shape[0] != S:
                 raise NmgpError("nstar must have one entry per subject (S=%d), got %d" % (S, na.shape[0]))
+        shape = (B, Smax, M) if ia is None else (B, Smax)
+        mean, var = np.empty(shape), np.empty(shape)
+        status = np.zeros(B, dtype=np.int32)
+        ii, ni = (None if a is None else a.ctypes.data_as(ipt) for a in (ia, na))
+        if not d["nhyper"]:
+            self.check(fn(self.h, ptr(pars), B, H, ptr(xs), ii, ni, Smax, ptr(mean), ptr(var), status.ctypes.data_as(ipt)))
+            return mean, var, status
         if z is not None and star is not None:
             raise NmgpError("star= replaces the regression: z must be None")
         za, sa = (None if a is None else as_f64(a) for a in (z, star))
-        W = None if T is None else 1 + T
+        W = None if T is None else d["width"](T)
         for name, a in (("z", za), ("star", sa)):
             if a is not None and (a.ndim != 3 or a.shape[:2] != (B, Smax) or (W is not None and a.shape[2] != W)):
-                raise NmgpError("%s must be [B=%d, Smax=%d, 1+T], got %s" % (name, B, Smax, a.shape))
+                raise NmgpError("%s must be [B=%d, Smax=%d, %s], got %s" % (name, B, Smax, d["wname"], a.shape))
         if W is None:
             W = next((a.shape[2] for a in (za, sa) if a is not None), 2)
-        shape = (B, Smax, M) if ia is None else (B, Smax)
-        mean, var = np.empty(shape), np.empty(shape)
         star_out = np.empty((B, Smax, W))
-        status = np.zeros(B, dtype=np.int32)
-        self.check(self.lib.nmgp_predsample_had_subjects(
-            self.h, ptr(pars), B, H, ptr(hyper), ptr(xs), None if ia is None else ia.ctypes.data_as(ipt),
-            None if na is None else na.ctypes.data_as(ipt), Smax, ptr(za), ptr(sa), ptr(mean), ptr(var), ptr(star_out),
-            status.ctypes.data_as(ipt)))
+        self.check(fn(self.h, ptr(pars), B, H, ptr(hyper), ptr(xs), ii, ni, Smax, ptr(za), ptr(sa), ptr(mean), ptr(var), ptr(star_out),
+                      status.ctypes.data_as(ipt)))
         return mean, var, star_out, status
+
+    def predsample_had_subjects(self, pars, hyper, xs, indx_star=None, nstar=None, draws_per_subject=1, z=None, star=None):
+        """MAP and posterior-draw prediction for the cohort (``nmgp_predsample_had_subjects``), padded arrays as the C entry takes
+        them: pars [B = S * draws_per_subject, Pmax] (row s * draws_per_subject + h = draw h of subject s), xs [S, Smax] of which
+        the first nstar[s] entries of row s are read (nstar=None: all Smax), indx_star [S, Smax] or None (all M outputs per input),
+        z / star [B, Smax, 1+T] as ``predsample_had``.  Returns (mean, var [B, Smax(, M)], star [B, Smax, 1+T], status [B]); padded
+        new-input slots hold +0.0, a draw with non-zero status has NaN in its real slots.  ``hadamard.cohort_predict`` is the ragged
+        form."""
+        return self._predict_subjects("had", pars, xs, hyper=hyper, indx_star=indx_star, nstar=nstar,
+                                      draws_per_subject=draws_per_subject, z=z, star=star)
+
+    def predsample_hads_subjects(self, pars, hyper, xs, indx_star=None, nstar=None, draws_per_subject=1, z=None, star=None):
+        """The cohort predictor under the separable model (``nmgp_predsample_hads_subjects``): pars [B, 2 Nmax + T + 1] in the padded
+        layout of ``hads_subjects_eval`` (``hadamard_sep.cohort_pack``), hyper [9], z / star [B, Smax, 2] (tilde_l*, tilde_sigma*
+        before exp) as ``predsample_hads``; everything else as ``predsample_had_subjects``.  Returns (mean, var [B, Smax(, M)],
+        star [B, Smax, 2], status [B]).  ``hadamard_sep.cohort_predict`` is the ragged form."""
+        return self._predict_subjects("sep", pars, xs, hyper=hyper, indx_star=indx_star, nstar=nstar,
+                                      draws_per_subject=draws_per_subject, z=z, star=star)
+
+    def predict_hadst_subjects(self, pars, xs, indx_star=None, nstar=None, draws_per_subject=1):
+        """The cohort predictor under the stationary model (``nmgp_predict_hadst_subjects``): pars [B, T + 3] (draws_per_subject = 1:
+        the MAP predictor; more: posterior draws), no hyper, z or starred values; xs, indx_star, nstar as
+        ``predsample_had_subjects``.  Returns (mean, var [B, Smax(, M)], status [B]).  ``hadamard_sta.cohort_predict`` is the ragged
+        form."""
+        return self._predict_subjects("sta", pars, xs, indx_star=indx_star, nstar=nstar, draws_per_subject=draws_per_subject)
 
     def predict_had(self, pars, hyper, xs):
         """(mean [S, M], var [S, M], star [S, 1+T]) of the resident Hadamard subject at the new inputs xs."""

@@ -23,7 +23,7 @@ LIB = os.path.join(PKG, "libnmgp_hip.so")
 SOURCES = ["nmgp_kernels.hip", "nmgp_kernels_eig.hip", "nmgp_kernels_sep.hip", "nmgp_kernels_sta.hip", "nmgp_chol.hip", "nmgp_metric.hip", "nmgp_api.hip", "nmgp_eig.hip",
            "nmgp_predsample.hip", "nmgp_predsample_sep.hip", "nmgp_hadamard.hip", "nmgp_hadamard_sep.hip",
            "nmgp_predsample_hadamard.hip", "nmgp_hadamard_sta.hip", "nmgp_predsample_had.hip", "nmgp_hadamard_cohort.hip",
-           "nmgp_hadamard_cohort_models.hip"]
+           "nmgp_hadamard_cohort_models.hip", "nmgp_predsample_had_cohort.hip"]
 ID_SOURCE = "nmgp_build_id.hip"        # compiled last, with -DNMGP_BUILD_ID="<tree id>"
 HEADERS = [os.path.join(INCLUDE, "nmgp.h"), os.path.join(CSRC, "nmgp_internal.h"), os.path.join(CSRC, "nmgp_hadamard_common.h"),
            os.path.join(CSRC, "nmgp_predsample_common.h")]

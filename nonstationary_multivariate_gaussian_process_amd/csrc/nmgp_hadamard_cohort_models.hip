@@ -438,14 +438,7 @@ struct CohNon {
         L.o_ell = take(Bs * N); L.o_Rv = take(Bs * N * M); L.o_R = take(Bs * N * (1 + T)); L.o_q = take(Bs * (1 + T));
         if (want_grad) L.o_R2 = take(Bs * N * (1 + T));
     }
-    static bool finite_in(const double* p, size_t N, size_t Ns, int T) {
-        if (!std::isfinite(p[N * (1 + T)])) return false;
-        for (size_t t = 0; t < Ns; ++t)
-            if (!std::isfinite(p[t])) return false;
-        for (size_t t = 0; t < Ns * T; ++t)
-            if (!std::isfinite(p[N + t])) return false;
-        return true;
-    }
+    static bool finite_in(const double* p, size_t N, size_t Ns, int T) { return hadc_finite_non(p, N, Ns, T); }
     static int build_cov(const CohChunk& k) {
         hipStream_t s = k.c->stream;
         double *dP = k.at(k.L.o_P), *ell = k.at(k.L.o_ell), *Rv = k.at(k.L.o_Rv);
@@ -487,18 +480,12 @@ struct CohSep {
         L.o_ell = take(Bs * N); L.o_sig = take(Bs * N); L.o_Rv = take(Bs * N * M); L.o_R = take(Bs * N * 2); L.o_q = take(Bs * 2);
         if (want_grad) { L.o_R2 = take(Bs * N * 2); L.o_rsum = take(Bs * N * M); }
     }
-    static bool finite_in(const double* p, size_t N, size_t Ns, int T) {
-        for (size_t t = 0; t < Ns; ++t)
-            if (!std::isfinite(p[t]) || !std::isfinite(p[N + t])) return false;
-        for (size_t t = 2 * N; t < 2 * N + T + 1; ++t)
-            if (!std::isfinite(p[t])) return false;
-        return true;
-    }
+    static bool finite_in(const double* p, size_t N, size_t Ns, int T) { return hadc_finite_sep(p, N, Ns, T); }
     static int build_cov(const CohChunk& k) {
         hipStream_t s = k.c->stream;
         const int N = k.N, M = k.M, B = k.B;
         double *dP = k.at(k.L.o_P), *ell = k.at(k.L.o_ell), *sig = k.at(k.L.o_sig), *Rv = k.at(k.L.o_Rv);
-        NMGP_LAUNCH(k_hadcs_prep, dim3(cdiv(N, 256), B), dim3(256), 0, s, dP, k.indx, k.nobs, k.cps, N, M, k.T, ell, sig, Rv);
+        nmgp_hadcs_prep(s, dP, k.indx, k.nobs, k.cps, N, M, k.T, ell, sig, Rv, B);
         return hadc_cov_build<true>(s, k.x, ell, sig, Rv, dP, (long long)P(N, k.T), k.nobs, k.cps, k.at(k.L.o_S), k.L.ld, N, M, B, k.L.bs);
     }
     static int value_epilogue(const CohChunk& k) {
@@ -536,17 +523,10 @@ struct CohSta {
     static size_t part_width(int M) { return M + 2; }
     template <class Take>
     static void extras(HadLayout&, Take, size_t, size_t, int, int, bool) {}
-    static bool finite_in(const double* p, size_t, size_t, int T) {
-        for (int t = 0; t < T + 3; ++t)
-            if (!std::isfinite(p[t])) return false;
-        return true;
-    }
+    static bool finite_in(const double* p, size_t N, size_t Ns, int T) { return hadc_finite_sta(p, N, Ns, T); }
     static int build_cov(const CohChunk& k) {
-        const int N = k.N;
-        const dim3 grid(cdiv(N, 64), cdiv(N, 64), k.B);
-        NMGP_HADS_SWITCH(k.M, NMGP_LAUNCH((k_hadcst_cov<MM>), grid, dim3(256), 0, k.c->stream, k.x, k.indx, k.at(k.L.o_P),
-                                          (long long)P(N, k.T), k.nobs, k.cps, k.at(k.L.o_S), k.L.ld, N, k.L.bs));
-        return 0;
+        return nmgp_hadcst_cov_build(k.c->stream, k.x, k.indx, k.at(k.L.o_P), (long long)P(k.N, k.T), k.nobs, k.cps, k.at(k.L.o_S), k.L.ld,
+                                     k.N, k.M, k.B, k.L.bs);
     }
     static int value_epilogue(const CohChunk& k) {           // no term of the tuple depends on N: the resident finaliser as it is
         nmgp_hadst_finalize(k.c->stream, k.at(k.L.o_scal), k.at(k.L.o_P), k.T, k.hyper, k.prior, k.B);
@@ -676,6 +656,19 @@ int cohm_subjects_eval(nmgp_ctx* c, const double* pars, int B, int cps, const do
 }
 
 }  // namespace
+
+// what the prediction entries (nmgp_predsample_had_cohort.hip) share with the evaluations: the separable model's masked unpacking and
+// the stationary model's masked covariance
+void nmgp_hadcs_prep(hipStream_t s, const double* pars, const int* indx, const int* nobs, int cps, int N, int M, int T, double* ell,
+                     double* sig, double* Rv, int batch) {
+    NMGP_LAUNCH(k_hadcs_prep, dim3(cdiv(N, 256), batch), dim3(256), 0, s, pars, indx, nobs, cps, N, M, T, ell, sig, Rv);
+}
+int nmgp_hadcst_cov_build(hipStream_t s, const double* x, const int* indx, const double* pars, long long P, const int* nobs, int cps,
+                          double* S, int ld, int N, int M, int batch, long long sstride) {
+    const dim3 grid(cdiv(N, 64), cdiv(N, 64), batch);
+    NMGP_HADS_SWITCH(M, NMGP_LAUNCH((k_hadcst_cov<MM>), grid, dim3(256), 0, s, x, indx, pars, P, nobs, cps, S, ld, N, sstride));
+    return 0;
+}
 
 extern "C" int nmgp_had_subjects_eval(nmgp_ctx* c, const double* pars, int B, int chains_per_subject, const double hyper[8], int prior,
                                       double* out5, double* grad, int* status) {

@@ -403,6 +403,29 @@ int hadc_adjoint(hipStream_t s, const double* x, const double* ell, const double
     return 0;
 }
 
+// Whether the REAL slots of a cohort parameter vector are finite (N = the set's Nmax, Ns = the subject's size): the range of the
+// NMGP_NUM_NAN test of the cohort's evaluation and prediction entries, per model.
+inline bool hadc_finite_non(const double* p, size_t N, size_t Ns, int T) {       // [tilde_l (N) | L_vecs (N T) | tilde_sigma2_err]
+    if (!std::isfinite(p[N * (1 + T)])) return false;
+    for (size_t t = 0; t < Ns; ++t)
+        if (!std::isfinite(p[t])) return false;
+    for (size_t t = 0; t < Ns * T; ++t)
+        if (!std::isfinite(p[N + t])) return false;
+    return true;
+}
+inline bool hadc_finite_sep(const double* p, size_t N, size_t Ns, int T) {       // [tilde_l (N) | tilde_sigma (N) | L_vec (T) | s2e]
+    for (size_t t = 0; t < Ns; ++t)
+        if (!std::isfinite(p[t]) || !std::isfinite(p[N + t])) return false;
+    for (size_t t = 2 * N; t < 2 * N + T + 1; ++t)
+        if (!std::isfinite(p[t])) return false;
+    return true;
+}
+inline bool hadc_finite_sta(const double* p, size_t, size_t, int T) {            // all T + 3 slots: no per-observation part
+    for (int t = 0; t < T + 3; ++t)
+        if (!std::isfinite(p[t])) return false;
+    return true;
+}
+
 // ---- device helpers of the stationary model's kernels (k_hadst_* of nmgp_hadamard_sta.hip, k_hadcst_* of the cohort) -----------------
 
 // B_f[a, b] = <row a of L, row b of L> of the packed lower triangle Lvec

@@ -353,6 +353,13 @@ void nmgp_hadc_finalize(hipStream_t s, double* scal, const double* q, const doub
 void nmgp_hadc_grad_final(hipStream_t s, const double* part, long long pstride, int N, int M, int T, const int* indx, const int* nobs,
                           int cps, const double* R2, const double* pars, const double* tr, double a, double b, int prior, double* grad,
                           int batch);
+// ... and of nmgp_hadamard_cohort_models.hip, shared with the prediction entries (nmgp_predsample_had_cohort.hip): the separable
+// model's unpacking on the padded layout [batch, 2 Nmax + T + 1] (ell = sig = 1, Rv = 0 on padded observations) and the stationary
+// model's masked covariance (delta_ij on the padded observations); x, indx, nobs: the chunk's first subject's rows of the set's tables
+void nmgp_hadcs_prep(hipStream_t s, const double* pars, const int* indx, const int* nobs, int cps, int N, int M, int T, double* ell,
+                     double* sig, double* Rv, int batch);
+int nmgp_hadcst_cov_build(hipStream_t s, const double* x, const int* indx, const double* pars, long long P, const int* nobs, int cps,
+                          double* S, int ld, int N, int M, int batch, long long sstride);
 // kernels templated over the number of outputs M <= 8
 #define NMGP_HADS_SWITCH(M, CALL)               \
     switch (M) {                                \

@@ -1118,7 +1118,7 @@ class _HadamardCohortLoop:
     """The cohort MAP loop shared by the three Hadamard models: buckets of similar size (``hadamard.cohort_buckets``), one subject set
     (``nmgp_had_set_subjects``) per bucket on a ``Context`` of its own, held for the whole run, ONE ``*_subjects_eval`` per bucket and
     Adam iteration, :class:`LockStepMAP`'s update on the rows of the entry's layout.  A model names its hyper-parameter keys, its
-    ``Context`` entry and how per-subject vectors are packed into / unpacked from that layout."""
+    ``Context`` entry, how per-subject vectors are packed into / unpacked from that layout, and its cohort predictor."""
 
     HYPER_KEYS = SVC_HYPER_KEYS
     EVAL = "had_subjects_eval"
@@ -1132,6 +1132,11 @@ class _HadamardCohortLoop:
     def _unpack(P, nobs, M, k):
         from . import hadamard
         return hadamard.cohort_unpack(P, nobs, M, k)
+
+    @staticmethod
+    def _predict(ctx, hyper, draws, xs, indx_star):
+        from . import hadamard
+        return hadamard.cohort_predict(ctx, draws, xs, hyper, indx_star=indx_star)
 
     def __init__(self, subjects, hyper_pars, init_pars, lr=2e-1, chains_per_subject=1, max_flop_waste=0.5, ctxs=None):
         from . import _lib, hadamard
@@ -1169,6 +1174,22 @@ class _HadamardCohortLoop:
                 ctx.had_clear_subjects()
         self.ctxs = []
 
+    def predict(self, pars, xs, indx_star=None):
+        """MAP prediction (one draw, no noise) for every subject at its own new inputs, on the contexts and sets this object holds:
+        ONE cohort prediction call of the model (``nmgp_predsample_had_subjects`` / ``nmgp_predsample_hads_subjects`` /
+        ``nmgp_predict_hadst_subjects``) per bucket.  ``pars[s]`` ``[P_s]`` (or ``[k, P_s]`` as :meth:`run` returns them: row 0 is
+        used), ``xs[s]`` ``[S_s]``, ``indx_star[s]`` ``[S_s]`` labels or None (all M outputs).  Returns a list, in the caller's subject
+        order, of ``(mean [S_s(, M)], var, star [S_s, width], status)``; the stationary model has no ``star``."""
+        if not (len(pars) == len(xs) == len(self.nobs)) or (indx_star is not None and len(indx_star) != len(self.nobs)):
+            raise ValueError("pars, xs (and indx_star) must hold one entry per subject")
+        out = [None] * len(self.nobs)
+        for ctx, idx in zip(self.ctxs, self.buckets):
+            res = self._predict(ctx, self.hyper, [np.atleast_2d(np.asarray(pars[s], dtype=np.float64))[:1] for s in idx],
+                                [xs[s] for s in idx], None if indx_star is None else [indx_star[s] for s in idx])
+            for s, r in zip(idx, res):
+                out[int(s)] = tuple(a[0] for a in r[:-1]) + (int(r[-1][0]),)
+        return out
+
     def _rows(self, idx):
         """columns of the caller's [.., S k] order that a bucket's rows fill"""
         return (np.asarray(idx)[:, None] * self.k + np.arange(self.k)[None, :]).reshape(-1)
@@ -1199,23 +1220,6 @@ class HadamardCohortMAP(_HadamardCohortLoop):
     (``nmgp_had_set_subjects``, padded to the bucket's largest subject) on a ``Context`` of its own, held for the whole run, and
     every Adam iteration makes ONE ``nmgp_had_subjects_eval`` per bucket, followed by :class:`LockStepMAP`'s update on the padded
     rows -- padded slots have zero gradient and therefore never move.  ``ctxs``: one context per bucket (default: new ones)."""
-
-    def predict(self, pars, xs, indx_star=None):
-        """MAP prediction (one draw, no noise) for every subject at its own new inputs, on the contexts and sets this object holds:
-        ONE ``nmgp_predsample_had_subjects`` per bucket.  ``pars[s]`` ``[P_s]`` (or ``[k, P_s]`` as :meth:`run` returns them: row 0
-        is used), ``xs[s]`` ``[S_s]``, ``indx_star[s]`` ``[S_s]`` labels or None (all M outputs).  Returns a list, in the caller's
-        subject order, of ``(mean [S_s(, M)], var, star [S_s, 1+T], status)``."""
-        from . import hadamard
-        if not (len(pars) == len(xs) == len(self.nobs)) or (indx_star is not None and len(indx_star) != len(self.nobs)):
-            raise ValueError("pars, xs (and indx_star) must hold one entry per subject")
-        out = [None] * len(self.nobs)
-        for ctx, idx in zip(self.ctxs, self.buckets):
-            res = hadamard.cohort_predict(ctx, [np.atleast_2d(np.asarray(pars[s], dtype=np.float64))[:1] for s in idx],
-                                          [xs[s] for s in idx], self.hyper,
-                                          indx_star=None if indx_star is None else [indx_star[s] for s in idx])
-            for s, (mean, var, star, status) in zip(idx, res):
-                out[int(s)] = (mean[0], var[0], star[0], int(status[0]))
-        return out
 
 
 class BatchedHMCHadamard(_HadamardSubject, LockStepHMC):
@@ -1268,7 +1272,7 @@ class HadamardSepCohortMAP(_HadamardCohortLoop):
     """:class:`HadamardCohortMAP`'s loop under the separable model, against :class:`HadamardSepMAP` subject by subject:
     ``init_pars[s]`` ``[k, 2 N_s + T + 1]``, the hyper-parameter keys of the per-subject driver, ONE ``nmgp_hads_subjects_eval`` per
     bucket and Adam iteration on the padded layout of ``hadamard_sep.cohort_pack`` (padded slots have zero gradient and never move).
-    No prediction for the cohort under this model yet."""
+    :meth:`predict` is ``hadamard_sep.cohort_predict`` per bucket."""
 
     HYPER_KEYS = SEP_HYPER_KEYS
     EVAL = "hads_subjects_eval"
@@ -1282,6 +1286,11 @@ class HadamardSepCohortMAP(_HadamardCohortLoop):
     def _unpack(P, nobs, M, k):
         from . import hadamard_sep
         return hadamard_sep.cohort_unpack(P, nobs, M, k)
+
+    @staticmethod
+    def _predict(ctx, hyper, draws, xs, indx_star):
+        from . import hadamard_sep
+        return hadamard_sep.cohort_predict(ctx, draws, xs, hyper, indx_star=indx_star)
 
 
 class BatchedHMCHadamardSep(_HadamardSepSubject, LockStepHMC):
@@ -1330,7 +1339,8 @@ class HadamardStaCohortMAP(_HadamardCohortLoop):
     """:class:`HadamardCohortMAP`'s loop under the stationary model, against :class:`HadamardStaMAP` subject by subject:
     ``init_pars[s]`` ``[k, T + 3]`` (the vector has no per-observation part, so rows are stacked as they are), the hyper-parameter keys
     and the update of the per-subject driver (every entry moves, ``tilde_sigma`` included, as there), ONE
-    ``nmgp_hadst_subjects_eval`` per bucket and Adam iteration.  No prediction for the cohort under this model yet."""
+    ``nmgp_hadst_subjects_eval`` per bucket and Adam iteration.  :meth:`predict` is ``hadamard_sta.cohort_predict`` per bucket (no
+    starred values: ``(mean, var, status)`` per subject)."""
 
     HYPER_KEYS = STA_HYPER_KEYS
     EVAL = "hadst_subjects_eval"
@@ -1342,6 +1352,11 @@ class HadamardStaCohortMAP(_HadamardCohortLoop):
     @staticmethod
     def _unpack(P, nobs, M, k):
         return [np.array(P[s * k:(s + 1) * k]) for s in range(len(nobs))]
+
+    @staticmethod
+    def _predict(ctx, hyper, draws, xs, indx_star):
+        from . import hadamard_sta
+        return hadamard_sta.cohort_predict(ctx, draws, xs, indx_star=indx_star)
 
 
 class BatchedHMCHadamardSta(_HadamardStaSubject, LockStepHMC):
@@ -1741,16 +1756,12 @@ def posterior_predict_hadamard(x, indx, y, hyper_pars, samples, xs, indx_star=No
     return out
 
 
-def posterior_predict_hadamard_cohort(subjects, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, max_flop_waste=0.5,
-                                      ctxs=None):
-    """:func:`posterior_predict_hadamard` for a cohort of subjects of RAGGED size: ``subjects`` a list of ``(x, indx, y)``,
-    ``samples[s]`` [iters, chains, P_s] or [H, P_s] (thinned evenly to ``draws``; the same number of draws for every subject),
-    ``xs[s]`` [S_s] the subject's own new inputs, ``indx_star[s]`` [S_s] labels or None.  One subject set per bucket of
-    ``hadamard.cohort_buckets(nobs, max_flop_waste)`` and ONE ``nmgp_predsample_had_subjects`` per bucket (``ctxs``: one context per
-    bucket, default new ones, closed on return).  The normals of subject s come from ``default_rng(seed + s)`` -- z first, then the
-    y* normals, as the single-subject driver draws them from ``default_rng(seed)`` -- so a subject's band does not depend on who
-    else is in the cohort.  Returns a list, in the caller's subject order, of that function's dicts (``L_star`` and
-    ``corr_quantiles`` included)."""
+def _posterior_predict_cohort(subjects, samples, xs, indx_star, draws, seed, max_flop_waste, ctxs, width, predict, summarize):
+    """What the three cohort posterior predictors share: the subjects as arrays, every history thinned to one number of draws, the
+    normals of subject s from ``default_rng(seed + s)`` in the single-subject driver's order (``width(T)`` starred-value normals
+    per draw and input first -- none for width 0 --, then the y* normals), the buckets of ``hadamard.cohort_buckets``, one subject set
+    and ONE ``predict(ctx, draws, xs, indx_star, z)`` per bucket on ``ctxs`` (default: new contexts, closed on return), and
+    ``summarize(M, result, zy, draws)`` per subject, returned in the caller's subject order."""
     from . import _lib, hadamard
     subjects = [(np.ascontiguousarray(x, dtype=np.float64).reshape(-1), np.asarray(indx).reshape(-1).astype(np.int32),
                  np.ascontiguousarray(y, dtype=np.float64).reshape(-1)) for x, indx, y in subjects]
@@ -1761,7 +1772,7 @@ def posterior_predict_hadamard_cohort(subjects, hyper_pars, samples, xs, indx_st
     if len(Ms) != 1:
         raise ValueError("the subjects have different numbers of distinct labels: %s" % Ms)
     M = Ms[0]
-    T = M * (M + 1) // 2
+    W = width(M * (M + 1) // 2)
     hist = []
     for S_ in samples:
         S_ = np.asarray(S_, dtype=np.float64)
@@ -1772,12 +1783,11 @@ def posterior_predict_hadamard_cohort(subjects, hyper_pars, samples, xs, indx_st
     H = hist[0].shape[0]
     if any(h.shape[0] != H for h in hist):
         raise ValueError("every subject must bring the same number of draws after thinning; got %s" % [h.shape[0] for h in hist])
-    hyper = np.array([float(hyper_pars[k]) for k in SVC_HYPER_KEYS])
     xs = [np.asarray(v, dtype=np.float64).reshape(-1) for v in xs]
     zs, zys = [], []
     for s in range(n):
         rng = np.random.default_rng(seed + s)
-        zs.append(rng.standard_normal((H, xs[s].shape[0], 1 + T)))
+        zs.append(rng.standard_normal((H, xs[s].shape[0], W)) if W else None)
         zys.append(rng.standard_normal((H, xs[s].shape[0]) + (() if indx_star is not None else (M,))))
     nobs = [s[0].shape[0] for s in subjects]
     buckets = hadamard.cohort_buckets(nobs, max_flop_waste)
@@ -1788,21 +1798,77 @@ def posterior_predict_hadamard_cohort(subjects, hyper_pars, samples, xs, indx_st
         ctx = ctxs[b] if ctxs is not None else _lib.Context()
         try:
             ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=M)
-            res = hadamard.cohort_predict(ctx, [hist[s] for s in idx], [xs[s] for s in idx], hyper,
-                                          indx_star=None if indx_star is None else [indx_star[s] for s in idx],
-                                          z=[zs[s] for s in idx])
+            res = predict(ctx, [hist[s] for s in idx], [xs[s] for s in idx],
+                          None if indx_star is None else [indx_star[s] for s in idx], [zs[s] for s in idx] if W else None)
         finally:
             if ctxs is None:
                 ctx.close()
             elif ctx.h:
                 ctx.had_clear_subjects()
-        for s, (mean, var, star, status) in zip(idx, res):
-            s = int(s)
-            d = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zys[s], star[:, :, 0], status)
-            d["L_star"] = star[:, :, 1:][status == 0]
-            d["corr_quantiles"] = correlation_quantiles(d["L_star"], M)
-            out[s] = d
+        for s, r in zip(idx, res):
+            out[int(s)] = summarize(M, r, zys[int(s)], hist[int(s)])
     return out
+
+
+def posterior_predict_hadamard_cohort(subjects, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, max_flop_waste=0.5,
+                                      ctxs=None):
+    """:func:`posterior_predict_hadamard` for a cohort of subjects of RAGGED size: ``subjects`` a list of ``(x, indx, y)``,
+    ``samples[s]`` [iters, chains, P_s] or [H, P_s] (thinned evenly to ``draws``; the same number of draws for every subject),
+    ``xs[s]`` [S_s] the subject's own new inputs, ``indx_star[s]`` [S_s] labels or None.  One subject set per bucket of
+    ``hadamard.cohort_buckets(nobs, max_flop_waste)`` and ONE ``nmgp_predsample_had_subjects`` per bucket (``ctxs``: one context per
+    bucket, default new ones, closed on return).  The normals of subject s come from ``default_rng(seed + s)`` -- z first, then the
+    y* normals, as the single-subject driver draws them from ``default_rng(seed)`` -- so a subject's band does not depend on who
+    else is in the cohort.  Returns a list, in the caller's subject order, of that function's dicts (``L_star`` and
+    ``corr_quantiles`` included)."""
+    from . import hadamard
+    hyper = np.array([float(hyper_pars[k]) for k in SVC_HYPER_KEYS])
+
+    def summarize(M, r, zy, _):
+        mean, var, star, status = r
+        d = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
+        d["L_star"] = star[:, :, 1:][status == 0]
+        d["corr_quantiles"] = correlation_quantiles(d["L_star"], M)
+        return d
+
+    return _posterior_predict_cohort(subjects, samples, xs, indx_star, draws, seed, max_flop_waste, ctxs, lambda T: 1 + T,
+                                     lambda ctx, h, x_, ix, z: hadamard.cohort_predict(ctx, h, x_, hyper, indx_star=ix, z=z), summarize)
+
+
+def posterior_predict_hadamard_sep_cohort(subjects, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, max_flop_waste=0.5,
+                                          ctxs=None):
+    """:func:`posterior_predict_hadamard_sep` for a cohort of subjects of RAGGED size, with the arguments, buckets, thinning and
+    per-subject generators ``default_rng(seed + s)`` of :func:`posterior_predict_hadamard_cohort`: ``samples[s]``
+    [iters, chains, 2 N_s + T + 1] or [H, 2 N_s + T + 1], ONE ``nmgp_predsample_hads_subjects`` per bucket.  Returns a list, in the
+    caller's subject order, of that function's dicts (``tilde_sigma_star`` included)."""
+    from . import hadamard_sep
+    hyper = np.array([float(hyper_pars[k]) for k in SEP_HYPER_KEYS])
+
+    def summarize(M, r, zy, _):
+        mean, var, star, status = r
+        d = summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, star[:, :, 0], status)
+        d["tilde_sigma_star"] = star[:, :, 1][status == 0]
+        return d
+
+    return _posterior_predict_cohort(subjects, samples, xs, indx_star, draws, seed, max_flop_waste, ctxs, lambda T: 2,
+                                     lambda ctx, h, x_, ix, z: hadamard_sep.cohort_predict(ctx, h, x_, hyper, indx_star=ix, z=z),
+                                     summarize)
+
+
+def posterior_predict_hadamard_sta_cohort(subjects, hyper_pars, samples, xs, indx_star=None, draws=None, seed=0, max_flop_waste=0.5,
+                                          ctxs=None):
+    """:func:`posterior_predict_hadamard_sta` for a cohort of subjects of RAGGED size, with the arguments, buckets, thinning and
+    per-subject generators ``default_rng(seed + s)`` of :func:`posterior_predict_hadamard_cohort`: ``samples[s]`` [iters, chains, T + 3]
+    or [H, T + 3], ONE ``nmgp_predict_hadst_subjects`` per bucket; only y* is sampled, and ``hyper_pars`` is accepted for symmetry and
+    not used.  Returns a list, in the caller's subject order, of that function's dicts."""
+    from . import hadamard_sta
+
+    def summarize(M, r, zy, h):
+        mean, var, status = r
+        tl = np.repeat(h[:, :1], mean.shape[1], axis=1)
+        return summarize_posterior_predictive(mean, var, mean + np.sqrt(var) * zy, tl, status)
+
+    return _posterior_predict_cohort(subjects, samples, xs, indx_star, draws, seed, max_flop_waste, ctxs, lambda T: 0,
+                                     lambda ctx, h, x_, ix, z: hadamard_sta.cohort_predict(ctx, h, x_, indx_star=ix), summarize)
 
 
 def correlation_quantiles(L_star, M, quantiles=(2.5, 50.0, 97.5)):

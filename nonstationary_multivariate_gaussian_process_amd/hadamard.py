@@ -407,31 +407,42 @@ def cohort_unpack_outputs(A, nstar, draws_per_subject=1):
     return [A[s * k:(s + 1) * k, :n].copy() for s, n in enumerate(nstar)]
 
 
+def _cohort_predict(ctx, who, call, draws, xs, indx_star, z, star, rows_of, width):
+    """The ragged-to-padded half the three models' ``cohort_predict`` share.  ``rows_of(vs, H, Nmax, M, T)`` checks the per-subject
+    draws ``vs[s] [H, P_s]`` (the same H for every subject) and returns the entry's parameter rows; ``width(T)`` is the number of starred values per draw and input
+    (0: the model has none); ``call(pars, x2, i2, nstar, H, z2, s2)`` is the device call on the padded arrays."""
+    cohort = getattr(ctx, "_cohort", None)
+    if cohort is None:
+        raise _lib.NmgpError("%s: no cohort is set (Context.had_set_subjects)" % who)
+    S, Nmax, M = cohort
+    if not (len(draws) == len(xs) == S) or any(a is not None and len(a) != S for a in (indx_star, z, star)):
+        raise _lib.NmgpError("%s: draws, xs (and indx_star, z, star) must be lists of one entry per subject (S = %d)" % (who, S))
+    vs = [np.atleast_2d(_np(v)) for v in draws]
+    T, H = _cohort_T(M), vs[0].shape[0]
+    pars = rows_of(vs, H, Nmax, M, T)
+    x2, nstar = cohort_pack_inputs([_np(v).reshape(-1) for v in xs])
+    Smax, W = x2.shape[1], width(T)
+    i2 = None if indx_star is None else cohort_pack_inputs([_np(v).reshape(-1) for v in indx_star], nstar, Smax, 0, np.int32)[0]
+    z2, s2 = (None if a is None else cohort_pack_inputs([_np(v).reshape(H, int(n), W) for v, n in zip(a, nstar)], nstar, Smax)[0]
+              for a in (z, star))
+    return list(zip(*(cohort_unpack_outputs(a, nstar, H) for a in call(pars, x2, i2, nstar, H, z2, s2))))
+
+
 def cohort_predict(ctx, draws, xs, hyper, indx_star=None, z=None, star=None):
     """MAP and posterior-draw prediction for the cohort ``ctx`` holds (``Context.had_set_subjects``) at each subject's OWN new
     inputs, in ONE device call (``nmgp_predsample_had_subjects``).  Ragged lists in the set's subject order: ``draws[s]`` ``[H, P_s]``
     (or ``[P_s]``: H = 1; the same H for every subject), ``xs[s]`` ``[S_s]`` (``S_s = 0`` allowed), ``indx_star[s]`` ``[S_s]`` labels
     (None: all M outputs per input), ``z[s]`` / ``star[s]`` ``[H, S_s, 1+T]`` as ``Context.predsample_had`` takes them.  Returns a list
     of per-subject ``(mean [H, S_s(, M)], var, star [H, S_s, 1+T], status [H])``; a draw with non-zero status has NaN moments."""
-    cohort = getattr(ctx, "_cohort", None)
-    if cohort is None:
-        raise _lib.NmgpError("cohort_predict: no cohort is set (Context.had_set_subjects)")
-    S, Nmax, M = cohort
-    if not (len(draws) == len(xs) == S) or any(a is not None and len(a) != S for a in (indx_star, z, star)):
-        raise _lib.NmgpError("cohort_predict: draws, xs (and indx_star, z, star) must be lists of one entry per subject (S = %d)" % S)
-    vs = [np.atleast_2d(_np(v)) for v in draws]
-    T, H = _cohort_T(M), vs[0].shape[0]
-    nobs = []
-    for s, v in enumerate(vs):
-        n, rem = divmod(v.shape[1] - 1, 1 + T)
-        if rem or v.shape[0] != H:
-            raise _lib.NmgpError("cohort_predict: draws[%d] %s is not [H = %d, N_s (1 + T) + 1]" % (s, v.shape, H))
-        nobs.append(n)
-    x2, nstar = cohort_pack_inputs([_np(v).reshape(-1) for v in xs])
-    Smax = x2.shape[1]
-    i2 = None if indx_star is None else cohort_pack_inputs([_np(v).reshape(-1) for v in indx_star], nstar, Smax, 0, np.int32)[0]
-    z2, s2 = (None if a is None else cohort_pack_inputs([_np(v).reshape(H, int(n), 1 + T) for v, n in zip(a, nstar)], nstar, Smax)[0]
-              for a in (z, star))
-    mean, var, st, status = ctx.predsample_had_subjects(cohort_pack(vs, nobs, M, Nmax=Nmax), hyper, x2, indx_star=i2, nstar=nstar,
-                                                        draws_per_subject=H, z=z2, star=s2)
-    return list(zip(*(cohort_unpack_outputs(a, nstar, H) for a in (mean, var, st, status))))
+    def rows_of(vs, H, Nmax, M, T):
+        nobs = []
+        for s, v in enumerate(vs):
+            n, rem = divmod(v.shape[1] - 1, 1 + T)
+            if rem or v.shape[0] != H:
+                raise _lib.NmgpError("cohort_predict: draws[%d] %s is not [H = %d, N_s (1 + T) + 1]" % (s, v.shape, H))
+            nobs.append(n)
+        return cohort_pack(vs, nobs, M, Nmax=Nmax)
+
+    return _cohort_predict(ctx, "cohort_predict", lambda pars, x2, i2, nstar, H, z2, s2: ctx.predsample_had_subjects(
+        pars, hyper, x2, indx_star=i2, nstar=nstar, draws_per_subject=H, z=z2, star=s2), draws, xs, indx_star, z, star, rows_of,
+        lambda T: 1 + T)

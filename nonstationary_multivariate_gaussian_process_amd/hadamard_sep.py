@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .hadamard import _as_tensor, _bands, _f, _labels, _np, _objective
+from .hadamard import _as_tensor, _bands, _cohort_predict, _f, _labels, _np, _objective
 
 LOGPOS_NAMES = ("nlogpos_obj_hadamard", "logpos_hadamard")
 PREDICTION_NAMES = ("point_predmap_hadamard", "pointwise_predmap_hadmard", "pointwise_predmap_hadamard")
@@ -151,3 +151,22 @@ def cohort_unpack(P, nobs, M, chains_per_subject=1):
         rows = P[s * k:(s + 1) * k]
         out.append(np.concatenate([rows[:, :n], rows[:, Nmax:Nmax + n], rows[:, 2 * Nmax:]], axis=1))
     return out
+
+
+def cohort_predict(ctx, draws, xs, hyper, indx_star=None, z=None, star=None):
+    """MAP and posterior-draw prediction under the separable model for the cohort ``ctx`` holds (``Context.had_set_subjects``), in ONE
+    device call (``nmgp_predsample_hads_subjects``); the contract of ``hadamard.cohort_predict`` with ``draws[s]``
+    ``[H, 2 N_s + T + 1]``, ``hyper [9]`` and ``z[s]`` / ``star[s]`` ``[H, S_s, 2]`` (tilde_l*, tilde_sigma* before exp) as
+    ``Context.predsample_hads`` takes them.  Returns per-subject ``(mean [H, S_s(, M)], var, star [H, S_s, 2], status [H])``."""
+    def rows_of(vs, H, Nmax, M, T):
+        nobs = []
+        for s, v in enumerate(vs):
+            n, rem = divmod(v.shape[1] - T - 1, 2)
+            if rem or n < 1 or v.shape[0] != H:
+                raise _lib.NmgpError("hadamard_sep.cohort_predict: draws[%d] %s is not [H = %d, 2 N_s + T + 1]" % (s, v.shape, H))
+            nobs.append(n)
+        return cohort_pack(vs, nobs, M, Nmax=Nmax)
+
+    return _cohort_predict(ctx, "hadamard_sep.cohort_predict", lambda pars, x2, i2, nstar, H, z2, s2: ctx.predsample_hads_subjects(
+        pars, hyper, x2, indx_star=i2, nstar=nstar, draws_per_subject=H, z=z2, star=s2), draws, xs, indx_star, z, star, rows_of,
+        lambda T: 2)

@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .hadamard import _as_tensor, _bands, _f, _labels, _np, _objective
+from .hadamard import _as_tensor, _bands, _cohort_predict, _f, _labels, _np, _objective
 
 LOGPOS_NAMES = ("nlogpos_obj_hadamard_S", "logpos_hadamard_S")
 PREDICTION_NAMES = ("point_predmap_S_hadamard", "pointwise_predmap_S_hadamard")
@@ -115,3 +115,18 @@ def indexed_predict(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, x
     mean, var = _moments(tilde_l, tilde_sigma, L_vec, tilde_sigma2_err, x, indx, y, x_test, indx_test)
     return (torch.from_numpy(np.ascontiguousarray(mean)).type(torch.DoubleTensor),
             torch.from_numpy(np.sqrt(var)).type(torch.DoubleTensor))
+
+
+def cohort_predict(ctx, draws, xs, indx_star=None):
+    """Prediction under the stationary model for the cohort ``ctx`` holds (``Context.had_set_subjects``), in ONE device call
+    (``nmgp_predict_hadst_subjects``): ``draws[s]`` ``[H, T + 3]`` (or ``[T + 3]``: the MAP predictor; the same H for every subject),
+    ``xs[s]`` ``[S_s]``, ``indx_star[s]`` ``[S_s]`` labels or None (all M outputs per input).  The model has no latent curve: no
+    hyper, no normals, no starred values.  Returns per-subject ``(mean [H, S_s(, M)], var, status [H])``."""
+    def rows_of(vs, H, Nmax, M, T):
+        for s, v in enumerate(vs):
+            if v.shape != (H, T + 3):
+                raise _lib.NmgpError("hadamard_sta.cohort_predict: draws[%d] %s is not [H = %d, T + 3 = %d]" % (s, v.shape, H, T + 3))
+        return np.concatenate(vs, axis=0)
+
+    return _cohort_predict(ctx, "hadamard_sta.cohort_predict", lambda pars, x2, i2, nstar, H, z2, s2: ctx.predict_hadst_subjects(
+        pars, x2, indx_star=i2, nstar=nstar, draws_per_subject=H), draws, xs, indx_star, None, None, rows_of, lambda T: 0)
