@@ -198,6 +198,40 @@ int nmgp_hads_subjects_eval(nmgp_ctx* ctx, const double* pars /*[B,Pmax]*/, int 
  * set's prior factors nor the prior stream are touched. */
 int nmgp_hadst_subjects_eval(nmgp_ctx* ctx, const double* pars /*[B,T+3]*/, int B, int chains_per_subject, const double hyper[5],
                              int prior, double* out5 /*[B,5]*/, double* grad /*[B,T+3] or NULL*/, int* status /*[B]*/);
+/* ---- device-resident HMC trajectories of the cohort (drivers.HadamardCohortHMC / SepCohortHMC / StaCohortHMC) ----
+ * ONE family for the three models on the set of nmgp_had_set_subjects: model = NMGP_HAD_MODEL_NONSEP (hyper[8]), _SEP (hyper[9]) or
+ * _STA (hyper[5]); rows as in the *_subjects_eval entries (B = S * chains_per_subject, row s * chains_per_subject + k is chain k of
+ * subject s), Pmax the model's padded width (T + 3 for the stationary model, where every slot is real).
+ *   begin    uploads the start positions and evaluates value + gradient there: out [B, W] and status [B] are the model's
+ *            *_subjects_eval's, bit for bit, failing rows included.  Positions, gradients and a per-chain `bad` flag stay on the
+ *            device; model, hyper, prior and chains_per_subject are fixed until end.  A second begin replaces the first.
+ *   set_mass kind 0: identity (the default after begin); kind 1: minv [B, Pmax] = diag(M^-1) per chain row in the padded layout, of
+ *            which only the real slots are read; NMGP_E_SHAPE unless they are finite and > 0 (the mass then stays what it was).
+ *   traj     nsteps leapfrog steps with step size eps[s] for every chain of subject s, momenta p0 [B, Pmax], one value + gradient
+ *            evaluation per step (the chunks of the evaluation entries under NMGP_HAD_BATCH_SLAB_GB) and ONE synchronisation at the
+ *            end.  Returns the end point q1, p1 (or NULL), the kinetic energy there kin1 [B] = 1/2 sum over the real slots of
+ *            p1 minv p1 (or NULL), U1 [B] = NegLog (+inf where failed) and failed [B] = 1 if the potential was undefined at any point
+ *            (a chain that is bad at the start counts).  The device then holds the END state.
+ *   commit   accept [B]: 0 puts a chain's position, gradient and flag back to what they were before the trajectory.
+ *   end      frees the state (also done by nmgp_had_set_subjects, nmgp_had_clear_subjects and the context).
+ * Padded slots of pars, p0 and minv are never read (NaN there changes no bit); padded slots of q1 come back as uploaded, those of p1
+ * are +0.0.  A chain's bits depend neither on the chunking nor on the other subjects nor on Nmax.  The state is in allocations of its
+ * own: every other entry of the context may be called between begin and traj.  NMGP_E_STATE without a set or without begin (a
+ * replaced or cleared set included); NMGP_E_SHAPE for a bad model, B != S * chains_per_subject, chains_per_subject < 1, nsteps < 1 or
+ * an eps[s] that is not finite and positive; NMGP_E_UNSUPPORTED under NMGP_CHOL=rocsolver.  An API-level failure inside traj puts the
+ * start state back and demands a new begin. */
+#define NMGP_HAD_MODEL_NONSEP 0
+#define NMGP_HAD_MODEL_SEP    1
+#define NMGP_HAD_MODEL_STA    2
+int nmgp_had_subjects_traj_begin(nmgp_ctx* ctx, int model, const double* pars /*[B,Pmax]*/, int B, int chains_per_subject,
+                                 const double* hyper, int prior, double* out /*[B,W]*/, int* status /*[B]*/);
+int nmgp_had_subjects_traj_set_mass(nmgp_ctx* ctx, int kind, const double* minv /*[B,Pmax] or NULL*/);
+int nmgp_had_subjects_traj(nmgp_ctx* ctx, const double* eps /*[S]*/, int nsteps, const double* p0 /*[B,Pmax]*/,
+                           double* q1 /*[B,Pmax]*/, double* p1 /*[B,Pmax] or NULL*/, double* kin1 /*[B] or NULL*/,
+                           double* U1 /*[B]*/, int* failed /*[B]*/);
+int nmgp_had_subjects_traj_commit(nmgp_ctx* ctx, const int* accept /*[B]*/);
+int nmgp_had_subjects_traj_end(nmgp_ctx* ctx);
+
 /* MAP and posterior-draw prediction for the set under the two models.  Both entries follow nmgp_predsample_had_subjects in every
  * convention not named here: B = S * draws_per_subject rows, row s * draws_per_subject + h is draw h of subject s; xs [S, Smax] with
  * the table nstar (NULL: all Smax; 0 <= nstar[s] <= Smax); indx_star == NULL: mean / var [B, Smax, M], indx_star [S, Smax]: mean / var

@@ -91,6 +91,11 @@ SIGNATURES = {
     "nmgp_had_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hads_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_hadst_subjects_eval": (I, [V, P, I, I, P, I, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_had_subjects_traj_begin": (I, [V, I, P, I, I, P, I, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_had_subjects_traj_set_mass": (I, [V, I, P]),
+    "nmgp_had_subjects_traj": (I, [V, P, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_had_subjects_traj_commit": (I, [V, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_had_subjects_traj_end": (I, [V]),
     "nmgp_predsample_had_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
                                          ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_hads_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
@@ -864,10 +869,12 @@ class Context:
         self.check(self.lib.nmgp_had_set_subjects(self.h, ptr(x), indx.ctypes.data_as(ip), ptr(y), nobs.ctypes.data_as(ip),
                                                   x.shape[0], x.shape[1], int(M)))
         self._cohort = (x.shape[0], x.shape[1], int(M))
+        self._cohort_traj = None          # (a new set ends a begun trajectory)
 
     def had_clear_subjects(self):
         self.check(self.lib.nmgp_had_clear_subjects(self.h))
         self._cohort = None
+        self._cohort_traj = None
 
     def had_subjects_eval(self, pars, hyper, prior=True, want_grad=False, chains_per_subject=1):
         """B = S * chains_per_subject chains of the cohort in one launch sequence: pars [B, Pmax = Nmax(1+T)+1] in the padded layout
@@ -921,6 +928,84 @@ class Context:
         layout), hyper [5] as ``hadst_batch_eval`` -> (out [B, 5], grad [B, T + 3] or None, status [B])."""
         return self._model_subjects_eval(self.lib.nmgp_hadst_subjects_eval, pars, hyper, prior, want_grad, chains_per_subject, 5,
                                          lambda N, T: T + 3, "T + 3")
+
+    # -- device-resident HMC trajectories of the cohort (one family for the three models) -----------
+    # model name -> (NMGP_HAD_MODEL_*, entries of hyper, width of the tuple, length of a padded row and its name)
+    _COHORT_TRAJ_MODELS = {
+        "non": (0, 8, 5, lambda N, T: N * (1 + T) + 1, "Nmax(1+T)+1"),
+        "sep": (1, 9, 6, lambda N, T: 2 * N + T + 1, "2 Nmax + T + 1"),
+        "sta": (2, 5, 5, lambda N, T: T + 3, "T + 3"),
+    }
+
+    def _traj_rows(self, a, what):
+        """[B, Pmax] of the begun trajectory; without one the C entry refuses the call (NMGP_E_STATE) before it reads anything"""
+        a = as_f64(a)
+        shape = getattr(self, "_cohort_traj", None)
+        if a.ndim != 2 or (shape is not None and a.shape != shape):
+            raise NmgpError("%s must be [B, Pmax]%s, got %s" % (what, "" if shape is None else " = [%d, %d]" % shape, a.shape))
+        return a
+
+    def had_subjects_traj_begin(self, model, pars, hyper, prior=True, chains_per_subject=1):
+        """Starts the device-resident trajectories of the cohort at ``pars`` [B = S * chains_per_subject, Pmax] (the padded layout of
+        the model's ``*_subjects_eval``; ``model`` is "non", "sep" or "sta") -> (out [B, W], status [B]) of that entry, bit for bit.
+        Positions and gradients then stay on the device until ``had_subjects_traj_end``."""
+        if model not in self._COHORT_TRAJ_MODELS:
+            raise NmgpError("model must be one of 'non', 'sep', 'sta'; got %r" % (model,))
+        code, nhyper, width, plen, what = self._COHORT_TRAJ_MODELS[model]
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        cohort = getattr(self, "_cohort", None)
+        if pars.ndim != 2 or (cohort is not None and pars.shape[1] != plen(cohort[1], cohort[2] * (cohort[2] + 1) // 2)):
+            raise NmgpError("parameters must be [B, %s%s], got %s"
+                            % (what, "" if cohort is None else " = %d" % plen(cohort[1], cohort[2] * (cohort[2] + 1) // 2), pars.shape))
+        hyper = as_f64(hyper).reshape(-1)
+        if hyper.shape[0] != nhyper:
+            raise NmgpError("hyper must hold %d entries for model %r, got %d" % (nhyper, model, hyper.shape[0]))
+        B = pars.shape[0]
+        out = np.empty((B, width))
+        status = np.zeros(B, dtype=np.int32)
+        self._cohort_traj = None
+        self.check(self.lib.nmgp_had_subjects_traj_begin(self.h, code, ptr(pars), B, int(chains_per_subject), ptr(hyper),
+                                                         int(bool(prior)), ptr(out), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        self._cohort_traj = pars.shape
+        return out, status
+
+    def had_subjects_traj_set_mass(self, minv=None):
+        """None: identity; else diag(M^-1) per chain row [B, Pmax] in the padded layout (only the real slots are read; > 0 there)."""
+        if minv is None:
+            self.check(self.lib.nmgp_had_subjects_traj_set_mass(self.h, 0, None))
+            return
+        minv = self._traj_rows(minv, "minv")
+        self.check(self.lib.nmgp_had_subjects_traj_set_mass(self.h, 1, ptr(minv)))
+
+    def had_subjects_traj(self, eps, nsteps, p0, want_p1=True, want_kin=False):
+        """One leapfrog trajectory per chain from the resident state: step size ``eps[s]`` for the chains of subject s, momenta
+        ``p0`` [B, Pmax] -> (q1 [B, Pmax], p1 [B, Pmax] or None, kin1 [B] or None, U1 [B] (inf for failed chains), failed [B] bool)."""
+        p0 = self._traj_rows(p0, "momenta")
+        B, P_ = p0.shape
+        cohort = getattr(self, "_cohort", None)
+        eps = as_f64(eps).reshape(-1)
+        if cohort is not None and eps.shape[0] != cohort[0]:
+            raise NmgpError("eps must hold one step size per subject (%d), got %d" % (cohort[0], eps.shape[0]))
+        q1, U1 = np.empty((B, P_)), np.empty(B)
+        p1 = np.empty((B, P_)) if want_p1 else None
+        kin1 = np.empty(B) if want_kin else None
+        failed = np.zeros(B, dtype=np.int32)
+        self.check(self.lib.nmgp_had_subjects_traj(self.h, ptr(eps), int(nsteps), ptr(p0), ptr(q1), ptr(p1), ptr(kin1), ptr(U1),
+                                                   failed.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return q1, p1, kin1, U1, failed.astype(bool)
+
+    def had_subjects_traj_commit(self, accept):
+        acc = np.ascontiguousarray(np.asarray(accept).astype(np.int32))
+        shape = getattr(self, "_cohort_traj", None)
+        if acc.ndim != 1 or (shape is not None and acc.shape[0] != shape[0]):
+            raise NmgpError("accept must be [B]%s, got %s" % ("" if shape is None else " = [%d]" % shape[0], acc.shape))
+        self.check(self.lib.nmgp_had_subjects_traj_commit(self.h, acc.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+
+    def had_subjects_traj_end(self):
+        self.check(self.lib.nmgp_had_subjects_traj_end(self.h))
+        self._cohort_traj = None
 
     # the three cohort predictors as the binding sees them: C entry, entries of hyper (0: the entry takes no hyper, z or star and
     # returns no starred values), length of a parameter row and its name, starred values per draw and input and their name

@@ -439,6 +439,15 @@ struct CohNon {
         if (want_grad) L.o_R2 = take(Bs * N * (1 + T));
     }
     static bool finite_in(const double* p, size_t N, size_t Ns, int T) { return hadc_finite_non(p, N, Ns, T); }
+    // the padded layout [tilde_l (N) | L_vecs (N T) | tilde_sigma2_err] as the device sees it (hadc_finite_non walks the same slots):
+    // whether slot i is real, the number of real slots, and the slot of the j-th real one
+    __host__ __device__ static bool real_slot(long long i, int N, int Ns, int T) {
+        return i < N ? i < Ns : (i < (long long)N * (1 + T) ? i - N < (long long)Ns * T : true);
+    }
+    __host__ __device__ static long long n_real(int Ns, int T) { return (long long)Ns * (1 + T) + 1; }
+    __host__ __device__ static long long slot_of(long long j, int N, int Ns, int T) {
+        return j < Ns ? j : (j < (long long)Ns * (1 + T) ? N + (j - Ns) : (long long)N * (1 + T));
+    }
     static int build_cov(const CohChunk& k) {
         hipStream_t s = k.c->stream;
         double *dP = k.at(k.L.o_P), *ell = k.at(k.L.o_ell), *Rv = k.at(k.L.o_Rv);
@@ -481,6 +490,12 @@ struct CohSep {
         if (want_grad) { L.o_R2 = take(Bs * N * 2); L.o_rsum = take(Bs * N * M); }
     }
     static bool finite_in(const double* p, size_t N, size_t Ns, int T) { return hadc_finite_sep(p, N, Ns, T); }
+    // [tilde_l (N) | tilde_sigma (N) | L_vec (T) | tilde_sigma2_err] (hadc_finite_sep walks the same slots)
+    __host__ __device__ static bool real_slot(long long i, int N, int Ns, int) { return i < N ? i < Ns : (i < 2LL * N ? i - N < Ns : true); }
+    __host__ __device__ static long long n_real(int Ns, int T) { return 2LL * Ns + T + 1; }
+    __host__ __device__ static long long slot_of(long long j, int N, int Ns, int) {
+        return j < Ns ? j : (j < 2LL * Ns ? N + (j - Ns) : 2LL * N + (j - 2LL * Ns));
+    }
     static int build_cov(const CohChunk& k) {
         hipStream_t s = k.c->stream;
         const int N = k.N, M = k.M, B = k.B;
@@ -524,6 +539,10 @@ struct CohSta {
     template <class Take>
     static void extras(HadLayout&, Take, size_t, size_t, int, int, bool) {}
     static bool finite_in(const double* p, size_t N, size_t Ns, int T) { return hadc_finite_sta(p, N, Ns, T); }
+    // all T + 3 slots are real (hadc_finite_sta)
+    __host__ __device__ static bool real_slot(long long, int, int, int) { return true; }
+    __host__ __device__ static long long n_real(int, int T) { return (long long)T + 3; }
+    __host__ __device__ static long long slot_of(long long j, int, int, int) { return j; }
     static int build_cov(const CohChunk& k) {
         return nmgp_hadcst_cov_build(k.c->stream, k.x, k.indx, k.at(k.L.o_P), (long long)P(k.N, k.T), k.nobs, k.cps, k.at(k.L.o_S), k.L.ld,
                                      k.N, k.M, k.B, k.L.bs);
@@ -547,27 +566,22 @@ struct CohSta {
     }
 };
 
-// chains [0, B) of `pars` (already offset by the caller): chain z belongs to subject s0 + z / cps.  had_eval_chunk's sequence at
-// n = Nmax with the model's hooks: value and gradient halves enqueued back to back, ONE synchronisation.
+// The ENQUEUE half of a chunk's evaluation: chains [0, B), chain z belonging to subject s0 + z / cps, positions already on the device
+// at slab + L.o_P; had_eval_chunk's sequence at n = Nmax with the model's hooks, value and gradient halves back to back.  Leaves
+// info / scal (and with want_grad the gradient rows at slab + L.o_grad) in the slab.  Nothing here touches the host or synchronises:
+// the evaluation entries follow it with cohm_chunk_epilogue, the trajectories with device copies.
 template <class Model>
-int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, const double* hyper, int prior, PriorFactor* p0,
-                    PriorFactor* p1, double* out, double* grad, int* status) {
-    constexpr int W = Model::WIDTH;
+int cohm_enqueue_chunk(nmgp_ctx* c, const HadLayout& L, double* slab, int B, int s0, int cps, const double* hyper, int prior,
+                       PriorFactor* p0, PriorFactor* p1, bool want_grad) {
     const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T;
-    const size_t P = Model::P(N, T);
-    const bool want_grad = grad != nullptr;
     hipStream_t s = c->stream;
-    const HadLayout L = had_layout<Model>(B, N, M, T, want_grad);
-    double* slab;
-    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
-    double *dP = slab + L.o_P, *z = slab + L.o_z, *scal = slab + L.o_scal, *S = slab + L.o_S;
+    double *z = slab + L.o_z, *scal = slab + L.o_scal, *S = slab + L.o_S;
     int* info = reinterpret_cast<int*>(slab + L.o_info);
     const int ld = L.ld;
     const long long bs = L.bs;
     // the tables of the chunk's first subject
     const double* y = c->hc_y + (size_t)s0 * N;
     const int* nobs = c->hc_nobs + s0;
-    HIP_TRY(c, hipMemcpyAsync(dP, pars, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemsetAsync(info, 0, (size_t)B * sizeof(int), s));
     std::optional<PriorStreamScope> ps;          // fork now, enqueue the prior solves after the factorisation's launches
     if constexpr (Model::GP_PRIORS) ps.emplace(c);
@@ -591,10 +605,6 @@ int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, con
         if constexpr (!Model::GP_PRIORS) NMGP_TRY(Model::value_epilogue(k));     // the finaliser alone: in this stage
     }
     if constexpr (Model::GP_PRIORS) NMGP_TRY(Model::value_epilogue(k));          // prior stream, join, finaliser (a stage of its own)
-    std::vector<double> hs((size_t)B * 16);
-    std::vector<int> hi(B);
-    HIP_TRY(c, hipMemcpyAsync(hs.data(), scal, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(hi.data(), info, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
     if (want_grad) {
         double *alpha = slab + L.o_alpha, *Sneg = slab + L.o_Sneg, *part = slab + L.o_part;
         {
@@ -611,8 +621,25 @@ int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, con
             int r = Model::adjoint_grad(k);
             if (r) return nmgp_fail(c, r, "unsupported number of outputs M=%d", M);
         }
-        HIP_TRY(c, hipMemcpyAsync(grad, slab + L.o_grad, (size_t)B * P * sizeof(double), hipMemcpyDeviceToHost, s));
     }
+    return 0;
+}
+
+// The HOST epilogue of a chunk's evaluation: the copies out of the slab, the ONE synchronisation of the chunk, and the status loop
+// (`pars` are the caller's rows: the NMGP_NUM_NAN test reads their real slots).
+template <class Model>
+int cohm_chunk_epilogue(nmgp_ctx* c, const HadLayout& L, double* slab, const double* pars, int B, int s0, int cps, double* out,
+                        double* grad, int* status) {
+    constexpr int W = Model::WIDTH;
+    const int N = c->hc_Nmax, T = c->hc_T;
+    const size_t P = Model::P(N, T);
+    const bool want_grad = grad != nullptr;
+    hipStream_t s = c->stream;
+    std::vector<double> hs((size_t)B * 16);
+    std::vector<int> hi(B);
+    HIP_TRY(c, hipMemcpyAsync(hs.data(), slab + L.o_scal, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(hi.data(), slab + L.o_info, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (want_grad) HIP_TRY(c, hipMemcpyAsync(grad, slab + L.o_grad, (size_t)B * P * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));          // the one synchronisation of the chunk
     NMGP_TRY(nmgp_take_launch_error(c));
     for (int z_ = 0; z_ < B; ++z_) {
@@ -628,6 +655,21 @@ int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, con
         status[z_] = st;
     }
     return 0;
+}
+
+// chains [0, B) of `pars` (already offset by the caller): the upload, the two halves back to back, ONE synchronisation.
+template <class Model>
+int cohm_eval_chunk(nmgp_ctx* c, const double* pars, int B, int s0, int cps, const double* hyper, int prior, PriorFactor* p0,
+                    PriorFactor* p1, double* out, double* grad, int* status) {
+    const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T;
+    const size_t P = Model::P(N, T);
+    const bool want_grad = grad != nullptr;
+    const HadLayout L = had_layout<Model>(B, N, M, T, want_grad);
+    double* slab;
+    NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
+    HIP_TRY(c, hipMemcpyAsync(slab + L.o_P, pars, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    NMGP_TRY(cohm_enqueue_chunk<Model>(c, L, slab, B, s0, cps, hyper, prior, p0, p1, want_grad));
+    return cohm_chunk_epilogue<Model>(c, L, slab, pars, B, s0, cps, out, grad, status);
 }
 
 template <class Model>
@@ -654,6 +696,298 @@ int cohm_subjects_eval(nmgp_ctx* c, const double* pars, int B, int cps, const do
                                       want_grad ? grad + (size_t)b0 * P : nullptr, status + b0);
     });
 }
+
+
+// ---- device-resident leapfrog trajectories of the cohort (drivers._HadamardCohortHMC) ------------------------------------------------
+// nmgp_svc_batch_traj's loop on the padded rows of a subject set: q, p, g stay in HBM between the chunked evaluations of a
+// trajectory.  Every mask comes from the nobs table and the model's layout (Model::real_slot), never from a slot's contents; the step
+// size is the subject's.  The arithmetic is the host loop's of drivers._HadamardCohortHMC, operation for operation, so both give the
+// same bits.
+
+// after a chunk's evaluation: bad[z] = the potential is undefined for chain z (factorisation status, a non-finite value, or a real
+// slot of the position that went non-finite: the three tests of cohm_chunk_epilogue); failed |= bad; U[z] = NegLog (the slab is the
+// next chunk's)
+__global__ void k_hadc_hmc_status(const int* __restrict__ info, const double* __restrict__ scal, const int* __restrict__ qbad,
+                                  int* __restrict__ bad, int* __restrict__ failed, double* __restrict__ U, int B) {
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z >= B) return;
+    const double v0 = scal[(size_t)z * 16 + 8], v1 = scal[(size_t)z * 16 + 9];
+    const int b = (qbad[z] != 0 || info[z] != 0 || !isfinite(v0) || !isfinite(v1)) ? 1 : 0;
+    bad[z] = b;
+    if (b) failed[z] = 1;
+    U[z] = v0;
+}
+
+// Rows z0 + blockIdx.y of the set, subject z / cps.  Real slots: p -= (kick eps[s]) g for the chains whose gradient is defined, then
+// -- if drift -- q += eps[s] (minv p).  Padded slots are neither read nor written, except that the FIRST kick of a trajectory
+// writes +0.0 to the padded slots of p.  Statement by statement as k_hmc_kick_drift (the build has no contraction).
+template <class Model>
+__global__ __launch_bounds__(256) void k_hadc_hmc_kick_drift(double* __restrict__ p, const double* __restrict__ g, double* __restrict__ q,
+                                                              const double* __restrict__ minv, const int* __restrict__ bad,
+                                                              int* __restrict__ qbad, const int* __restrict__ nobs,
+                                                              const double* __restrict__ eps, int cps, int z0, double kick, int drift,
+                                                              int first, int N, int T, long long P) {
+    const int z = z0 + blockIdx.y;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    const int s = z / cps;
+    const size_t o = (size_t)z * P + i;
+    if (!Model::real_slot(i, N, nobs[s], T)) {
+        if (first) p[o] = 0.0;
+        return;
+    }
+    const double e = eps[s];
+    const double c = kick * e;
+    double pv = p[o];
+    if (!bad[z]) {
+        const double t = c * g[o];
+        pv = pv - t;
+        p[o] = pv;
+    }
+    if (drift) {
+        const double v = minv ? minv[o] * pv : pv;
+        const double t2 = e * v;
+        const double qn = q[o] + t2;
+        q[o] = qn;
+        if (!isfinite(qn)) qbad[z] = 1;          // (every writer stores the same word)
+    }
+}
+
+// kin[z] = 1/2 sum over the REAL slots of p v, v = minv p or p.  One workgroup per chain, k_hmc_kinetic's order on the chain's real
+// slots counted without the padding (slot_of): a strided fma partial per thread, then the shared-memory tree -- so the bits depend
+// on the chain alone, not on Nmax, B, the chunking or the other subjects.
+template <class Model>
+__global__ __launch_bounds__(256) void k_hadc_hmc_kinetic(const double* __restrict__ p, const double* __restrict__ minv,
+                                                           const int* __restrict__ nobs, int cps, int N, int T, long long P,
+                                                           double* __restrict__ kin) {
+    __shared__ double red[256];
+    const int z = blockIdx.x, t = threadIdx.x;
+    const int Ns = nobs[z / cps];
+    const long long nr = Model::n_real(Ns, T);
+    const double* pz = p + (size_t)z * P;
+    const double* mz = minv ? minv + (size_t)z * P : nullptr;
+    double acc = 0.0;
+    for (long long j = t; j < nr; j += 256) {
+        const long long i = Model::slot_of(j, N, Ns, T);
+        const double pv = pz[i];
+        const double v = mz ? mz[i] * pv : pv;
+        acc = fma(pv, v, acc);
+    }
+    red[t] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) red[t] += red[t + h];
+        __syncthreads();
+    }
+    if (t == 0) kin[z] = 0.5 * red[0];
+}
+
+// rejected chains (accept[z] == 0) get the real slots of their position and gradient, and their validity flag, back (k_hmc_restore;
+// padded slots of q never change)
+template <class Model>
+__global__ __launch_bounds__(256) void k_hadc_hmc_restore(double* __restrict__ q, double* __restrict__ g, const double* __restrict__ q0,
+                                                           const double* __restrict__ g0, int* __restrict__ bad,
+                                                           const int* __restrict__ bad0, const int* __restrict__ accept,
+                                                           const int* __restrict__ nobs, int cps, int z0, int N, int T, long long P) {
+    const int z = z0 + blockIdx.y;
+    if (accept[z]) return;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) bad[z] = bad0[z];
+    if (i >= P || !Model::real_slot(i, N, nobs[z / cps], T)) return;
+    const size_t o = (size_t)z * P + i;
+    q[o] = q0[o];
+    g[o] = g0[o];
+}
+
+// flag rows of ht_flags
+inline int* ht_bad(nmgp_ctx* c) { return c->ht_flags; }
+inline int* ht_bad0(nmgp_ctx* c) { return c->ht_flags + c->ht_B; }
+inline int* ht_failed(nmgp_ctx* c) { return c->ht_flags + 2 * (size_t)c->ht_B; }
+inline int* ht_accept(nmgp_ctx* c) { return c->ht_flags + 3 * (size_t)c->ht_B; }
+inline int* ht_qbad(nmgp_ctx* c) { return c->ht_flags + 4 * (size_t)c->ht_B; }
+
+// the elementwise launches over all B rows: the row is a grid dimension, so more than 65535 rows take several launches
+template <class Model>
+void cohm_kick_drift(nmgp_ctx* c, double kick, int drift, int first) {
+    const long long P = (long long)c->ht_P;
+    for (int z0 = 0; z0 < c->ht_B; z0 += 65535) {
+        const int nz = std::min(65535, c->ht_B - z0);
+        NMGP_LAUNCH((k_hadc_hmc_kick_drift<Model>), dim3((unsigned)((P + 255) / 256), nz), dim3(256), 0, c->stream, c->ht_p, c->ht_g,
+                    c->ht_q, c->ht_mass == 1 ? c->ht_minv : nullptr, ht_bad(c), ht_qbad(c), c->hc_nobs, c->ht_eps, c->ht_cps, z0, kick,
+                    drift, first, c->hc_Nmax, c->hc_T, P);
+    }
+}
+
+// One value+gradient evaluation of the resident positions, chunk by chunk (the chunks of cohm_subjects_eval): positions into the slab,
+// the enqueue half, gradient rows out, status and potential out.  No host synchronisation: the slab's reuse by the next chunk is
+// ordered by the stream.
+template <class Model>
+int cohm_traj_eval(nmgp_ctx* c) {
+    const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T, B = c->ht_B;
+    const size_t P = c->ht_P;
+    hipStream_t s = c->stream;
+    PriorFactor *p0 = nullptr, *p1 = nullptr;
+    if constexpr (Model::GP_PRIORS) NMGP_TRY(nmgp_hadc_priors(c, c->ht_hyper, &p0, &p1));
+    const size_t per_chain = had_layout<Model>(1, N, M, T, true).total * sizeof(double);
+    return had_for_chunks(c, B, c->ht_cps, per_chain, Model::NOUN, "at Nmax", N, [&](int b0, int nb, int s0, int ccps) {
+        const HadLayout L = had_layout<Model>(nb, N, M, T, true);
+        double* slab;
+        NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
+        const size_t bytes = (size_t)nb * P * sizeof(double);
+        HIP_TRY(c, hipMemcpyAsync(slab + L.o_P, c->ht_q + (size_t)b0 * P, bytes, hipMemcpyDeviceToDevice, s));
+        NMGP_TRY(cohm_enqueue_chunk<Model>(c, L, slab, nb, s0, ccps, c->ht_hyper, c->ht_prior, p0, p1, true));
+        HIP_TRY(c, hipMemcpyAsync(c->ht_g + (size_t)b0 * P, slab + L.o_grad, bytes, hipMemcpyDeviceToDevice, s));
+        NMGP_LAUNCH(k_hadc_hmc_status, dim3(cdiv(nb, 64)), dim3(64), 0, s, reinterpret_cast<const int*>(slab + L.o_info),
+                    slab + L.o_scal, ht_qbad(c) + b0, ht_bad(c) + b0, ht_failed(c) + b0, c->ht_U + b0, nb);
+        return 0;
+    });
+}
+
+// An API-level failure inside a trajectory call puts the start state back and demands a fresh begin (traj_abort of the complete-data
+// family); the first failure's message is kept.
+int cohm_traj_abort(nmgp_ctx* c, int rc) {
+    const size_t bytes = (size_t)c->ht_B * c->ht_P * sizeof(double);
+    const std::string msg = c->err;
+    hipMemcpyAsync(c->ht_q, c->ht_q0, bytes, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(c->ht_g, c->ht_g0, bytes, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(ht_bad(c), ht_bad0(c), (size_t)c->ht_B * sizeof(int), hipMemcpyDeviceToDevice, c->stream);
+    hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    c->ht_model = -1;          // (the buffers go with the next begin, end or set)
+    c->err = msg;
+    return rc;
+}
+
+template <class Model>
+int cohm_subjects_traj_begin(nmgp_ctx* c, int model, const double* pars, int B, int cps, const double* hyper, int prior, double* out,
+                             int* status) {
+    const size_t P = Model::P(c->hc_Nmax, c->hc_T), n = (size_t)B * P;
+    // the start point is the evaluation entry's, bits and failing rows included; its gradient rows go back up next to the positions
+    std::vector<double> grad(n);
+    NMGP_TRY(cohm_subjects_eval<Model>(c, pars, B, cps, hyper, prior, out, grad.data(), status));
+    nmgp_had_traj_free(c);
+    auto fail = [c](int r) {
+        const std::string msg = c->err;
+        nmgp_had_traj_free(c);
+        c->err = msg;
+        return r;
+    };
+    double** bufs[] = {&c->ht_q, &c->ht_p, &c->ht_g, &c->ht_q0, &c->ht_g0};
+    for (double** b : bufs)
+        if (int r = nmgp_dev_alloc(c, b, n)) return fail(r);
+    if (nmgp_dev_alloc(c, &c->ht_U, (size_t)B) != 0 || nmgp_dev_alloc(c, &c->ht_kin, (size_t)B) != 0 ||
+        nmgp_dev_alloc(c, &c->ht_eps, (size_t)c->hc_S) != 0)
+        return fail(NMGP_E_NOMEM);
+    if (hipMalloc((void**)&c->ht_flags, 5 * (size_t)B * sizeof(int)) != hipSuccess)
+        return fail(nmgp_fail(c, NMGP_E_NOMEM, "hipMalloc of the trajectory flags failed"));
+    std::vector<int> bad(B);
+    for (int z = 0; z < B; ++z) bad[z] = status[z] != 0;
+    hipStream_t s = c->stream;
+    bool ok = hipMemcpyAsync(c->ht_q, pars, n * sizeof(double), hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(c->ht_g, grad.data(), n * sizeof(double), hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemsetAsync(c->ht_flags, 0, 5 * (size_t)B * sizeof(int), s) == hipSuccess &&
+              hipMemcpyAsync(c->ht_flags, bad.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipStreamSynchronize(s) == hipSuccess;          // the sources are the caller's and this frame's
+    if (!ok) return fail(nmgp_fail(c, NMGP_E_HIP, "upload of the trajectory's start state failed (%s)", hipGetErrorString(hipGetLastError())));
+    c->ht_model = model;
+    c->ht_B = B;
+    c->ht_cps = cps;
+    c->ht_prior = prior;
+    c->ht_P = P;
+    c->ht_mass = 0;
+    std::copy(hyper, hyper + (model == 0 ? 8 : model == 1 ? 9 : 5), c->ht_hyper);
+    return 0;
+}
+
+template <class Model>
+int cohm_subjects_traj_set_mass(nmgp_ctx* c, int kind, const double* minv) {
+    const int N = c->hc_Nmax, T = c->hc_T, B = c->ht_B;
+    const size_t P = c->ht_P;
+    if (kind == 1)
+        for (int z = 0; z < B; ++z) {
+            const int Ns = c->hc_nobs_h[z / c->ht_cps];
+            for (size_t i = 0; i < P; ++i) {
+                const double m = minv[(size_t)z * P + i];
+                if (Model::real_slot((long long)i, N, Ns, T) && !(m > 0.0 && std::isfinite(m)))
+                    return nmgp_fail(c, NMGP_E_SHAPE, "minv[%d, %zu] = %g: diag(M^-1) must be finite and > 0 in every real slot", z, i, m);
+            }
+        }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (kind == 1) {
+        if (!c->ht_minv) NMGP_TRY(nmgp_dev_alloc(c, &c->ht_minv, (size_t)B * P));
+        HIP_TRY(c, hipMemcpyAsync(c->ht_minv, minv, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    c->ht_mass = kind;
+    return 0;
+}
+
+// nsteps leapfrog steps from the resident state with momenta p0: one chunked evaluation per step, the elementwise kernels over all B
+// rows between them, ONE synchronisation at the end however many chunks the set needs.
+template <class Model>
+int cohm_subjects_traj(nmgp_ctx* c, const double* eps, int nsteps, const double* p0, double* q1, double* p1, double* kin1, double* U1,
+                       int* failed) {
+    const int B = c->ht_B;
+    const size_t P = c->ht_P, bytes = (size_t)B * P * sizeof(double);
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(c->ht_eps, eps, (size_t)c->hc_S * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->ht_p, p0, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->ht_q0, c->ht_q, bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->ht_g0, c->ht_g, bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(ht_bad0(c), ht_bad(c), (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(ht_failed(c), ht_bad(c), (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));   // bad at the start: failed
+    HIP_TRY(c, hipMemsetAsync(ht_qbad(c), 0, (size_t)B * sizeof(int), s));
+    cohm_kick_drift<Model>(c, 0.5, 1, 1);
+    for (int step = 0; step < nsteps; ++step) {
+        if (int rc = cohm_traj_eval<Model>(c)) return cohm_traj_abort(c, rc);
+        const bool last = step == nsteps - 1;
+        cohm_kick_drift<Model>(c, last ? 0.5 : 1.0, last ? 0 : 1, 0);
+    }
+    if (kin1)
+        NMGP_LAUNCH((k_hadc_hmc_kinetic<Model>), dim3(B), dim3(256), 0, s, c->ht_p, c->ht_mass == 1 ? c->ht_minv : nullptr, c->hc_nobs,
+                    c->ht_cps, c->hc_Nmax, c->hc_T, (long long)P, c->ht_kin);
+    hipError_t e = hipMemcpyAsync(q1, c->ht_q, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && p1) e = hipMemcpyAsync(p1, c->ht_p, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && kin1) e = hipMemcpyAsync(kin1, c->ht_kin, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(U1, c->ht_U, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(failed, ht_failed(c), (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);          // the one synchronisation of the trajectory
+    if (e != hipSuccess)
+        return cohm_traj_abort(c, nmgp_fail(c, NMGP_E_HIP, "the end of the trajectory failed: %s", hipGetErrorString(e)));
+    if (int rc = nmgp_take_launch_error(c)) return cohm_traj_abort(c, rc);
+    for (int z = 0; z < B; ++z)
+        if (failed[z]) U1[z] = INFINITY;
+    return 0;
+}
+
+template <class Model>
+int cohm_subjects_traj_commit(nmgp_ctx* c, const int* accept) {
+    const long long P = (long long)c->ht_P;
+    HIP_TRY(c, hipMemcpyAsync(ht_accept(c), accept, (size_t)c->ht_B * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    for (int z0 = 0; z0 < c->ht_B; z0 += 65535) {
+        const int nz = std::min(65535, c->ht_B - z0);
+        NMGP_LAUNCH((k_hadc_hmc_restore<Model>), dim3((unsigned)((P + 255) / 256), nz), dim3(256), 0, c->stream, c->ht_q, c->ht_g, c->ht_q0,
+                    c->ht_g0, ht_bad(c), ht_bad0(c), ht_accept(c), c->hc_nobs, c->ht_cps, z0, c->hc_Nmax, c->hc_T, P);
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // `accept` is the caller's buffer
+    return nmgp_take_launch_error(c);
+}
+
+// the begun trajectory, or the refusal
+int cohm_traj_require(nmgp_ctx* c) {
+    if (c->hc_S <= 0) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_subjects must be called first");
+    if (c->ht_model < 0) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_subjects_traj_begin must be called first (on the current set)");
+    return 0;
+}
+
+#define COHM_MODEL_SWITCH(model, CALL)                \
+    do {                                              \
+        switch (model) {                              \
+            case 0: { using MODEL = CohNon; return CALL; } \
+            case 1: { using MODEL = CohSep; return CALL; } \
+            default: { using MODEL = CohSta; return CALL; } \
+        }                                             \
+    } while (0)
 
 }  // namespace
 
@@ -683,4 +1017,65 @@ extern "C" int nmgp_hads_subjects_eval(nmgp_ctx* c, const double* pars, int B, i
 extern "C" int nmgp_hadst_subjects_eval(nmgp_ctx* c, const double* pars, int B, int chains_per_subject, const double hyper[5], int prior,
                                         double* out5, double* grad, int* status) {
     return cohm_subjects_eval<CohSta>(c, pars, B, chains_per_subject, hyper, prior, out5, grad, status);
+}
+
+// ---- the trajectory family (see include/nmgp.h) ---------------------------------------------------------------------------------------
+void nmgp_had_traj_free(nmgp_ctx* c) {
+    double** bufs[] = {&c->ht_q, &c->ht_p, &c->ht_g, &c->ht_q0, &c->ht_g0, &c->ht_minv, &c->ht_U, &c->ht_kin, &c->ht_eps};
+    for (double** b : bufs) {
+        if (*b) hipFree(*b);
+        *b = nullptr;
+    }
+    if (c->ht_flags) hipFree(c->ht_flags);
+    c->ht_flags = nullptr;
+    c->ht_model = -1;
+    c->ht_B = c->ht_cps = c->ht_prior = c->ht_mass = 0;
+    c->ht_P = 0;
+}
+
+extern "C" int nmgp_had_subjects_traj_begin(nmgp_ctx* c, int model, const double* pars, int B, int chains_per_subject,
+                                            const double* hyper, int prior, double* out, int* status) {
+    if (!c) return NMGP_E_NULL;
+    if (model < 0 || model > 2) return nmgp_fail(c, NMGP_E_SHAPE, "model = %d must be 0 (nonseparable), 1 (separable) or 2 (stationary)", model);
+    // (NULL arguments, the set, the factorisation and B = S * chains_per_subject: the evaluation entry's own refusals)
+    COHM_MODEL_SWITCH(model, cohm_subjects_traj_begin<MODEL>(c, model, pars, B, chains_per_subject, hyper, prior, out, status));
+}
+
+extern "C" int nmgp_had_subjects_traj_set_mass(nmgp_ctx* c, int kind, const double* minv) {
+    if (!c) return NMGP_E_NULL;
+    NMGP_TRY(cohm_traj_require(c));
+    if (kind < 0 || kind > 1) return nmgp_fail(c, NMGP_E_SHAPE, "mass matrix kind must be 0 (identity) or 1 (diagonal per chain row)");
+    if (kind == 1 && !minv) return nmgp_fail(c, NMGP_E_NULL, "minv must not be NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    COHM_MODEL_SWITCH(c->ht_model, cohm_subjects_traj_set_mass<MODEL>(c, kind, minv));
+}
+
+extern "C" int nmgp_had_subjects_traj(nmgp_ctx* c, const double* eps, int nsteps, const double* p0, double* q1, double* p1,
+                                      double* kin1, double* U1, int* failed) {
+    if (!c) return NMGP_E_NULL;
+    if (!eps || !p0 || !q1 || !U1 || !failed) return nmgp_fail(c, NMGP_E_NULL, "eps/p0/q1/U1/failed must not be NULL");
+    NMGP_TRY(cohm_traj_require(c));
+    if (nsteps < 1) return nmgp_fail(c, NMGP_E_SHAPE, "nsteps = %d must be positive", nsteps);
+    for (int s = 0; s < c->hc_S; ++s)
+        if (!(eps[s] > 0.0) || !std::isfinite(eps[s]))
+            return nmgp_fail(c, NMGP_E_SHAPE, "eps[%d] = %g: every subject's step size must be finite and positive", s, eps[s]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    COHM_MODEL_SWITCH(c->ht_model, cohm_subjects_traj<MODEL>(c, eps, nsteps, p0, q1, p1, kin1, U1, failed));
+}
+
+extern "C" int nmgp_had_subjects_traj_commit(nmgp_ctx* c, const int* accept) {
+    if (!c) return NMGP_E_NULL;
+    if (!accept) return nmgp_fail(c, NMGP_E_NULL, "accept must not be NULL");
+    NMGP_TRY(cohm_traj_require(c));
+    HIP_TRY(c, hipSetDevice(c->device));
+    COHM_MODEL_SWITCH(c->ht_model, cohm_subjects_traj_commit<MODEL>(c, accept));
+}
+
+extern "C" int nmgp_had_subjects_traj_end(nmgp_ctx* c) {
+    if (!c) return NMGP_E_NULL;
+    if (c->ht_model < 0) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    nmgp_had_traj_free(c);
+    return 0;
 }

@@ -186,6 +186,22 @@ struct nmgp_ctx {
     int* hc_nobs = nullptr;     // [S] device table of the subjects' sizes: every mask comes from it
     std::vector<int> hc_nobs_h; // the same on the host
     std::vector<PriorFactor> hc_priors;  // L: [S] x (ld x Nmax) masked RBF + jitter, logdet: [S]
+    // device-resident HMC trajectories of the cohort (nmgp_had_subjects_traj_*, nmgp_hadamard_cohort_models.hip): allocations of their
+    // own, so that every other entry of the context may run between two calls.  ht_model < 0: no trajectory begun.
+    int ht_model = -1, ht_B = 0, ht_cps = 0, ht_prior = 0, ht_mass = 0;
+    size_t ht_P = 0;            // the model's padded width
+    double ht_hyper[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double* ht_q = nullptr;     // [B, Pmax] positions (padded slots as uploaded)
+    double* ht_p = nullptr;     // [B, Pmax] momenta
+    double* ht_g = nullptr;     // [B, Pmax] d NegLog / d q at ht_q
+    double* ht_q0 = nullptr;    // [B, Pmax] / ht_g0: the state before the trajectory
+    double* ht_g0 = nullptr;
+    double* ht_minv = nullptr;  // [B, Pmax] diag(M^-1) per chain row (ht_mass == 1)
+    double* ht_U = nullptr;     // [B] potential of the last evaluation
+    double* ht_kin = nullptr;   // [B]
+    double* ht_eps = nullptr;   // [S]
+    int* ht_flags = nullptr;    // [5, B]: bad (current position), bad0 (before the trajectory), failed, accept, qbad (a real slot of
+                                // the position went non-finite in a drift: the NMGP_NUM_NAN test of the evaluation entries)
     int last_sep_attempts = 0;  // jitter retries the last separable / stationary evaluation needed (0 = the exact covariance)
     bool last_want_grad = false;
     int last_kind = 0;          // 1 svc
@@ -216,6 +232,7 @@ int nmgp_get_batch_prior(nmgp_ctx* c, const double* xs, int S, std::vector<Prior
                          PriorFactor** out);
 void nmgp_sep_subjects_free(nmgp_ctx* c);      // drops the separable subject set (no-op without one)
 void nmgp_had_subjects_free(nmgp_ctx* c);      // drops the Hadamard cohort (no-op without one; nmgp_hadamard_cohort.hip)
+void nmgp_had_traj_free(nmgp_ctx* c);          // ends a begun cohort trajectory (no-op without one; nmgp_hadamard_cohort_models.hip)
 int nmgp_ensure_S(nmgp_ctx* c);
 size_t nmgp_ld(size_t rows);      // leading dimension of a factorisation buffer with `rows` rows
 // Cholesky of the n x n lower triangle (custom gfx950 factorisation or rocSOLVER, per ctx->chol_algo); `extra` rows

@@ -1388,6 +1388,212 @@ class BatchedHMCHadamardSta(_HadamardStaSubject, LockStepHMC):
         return np.stack([self.Minv @ row for row in p])
 
 
+# ---- HMC for a cohort of ragged Hadamard subjects: the sampler between the cohort's MAP and its predictive bands ---------------------
+class _HadamardCohortHMC(_HadamardCohortLoop):
+    """Lock-step HMC for a cohort of ragged Hadamard subjects, shared by the three models: the buckets, sets, contexts and pack /
+    unpack hooks of :class:`_HadamardCohortLoop`, :class:`LockStepHMC`'s arithmetic on the rows of the entry's padded layout with a
+    step size per subject.  ``init_positions[s]`` ``[k, P_s]`` (the same k for every subject); ``step_size`` a scalar or ``[S]``;
+    ``mass`` None or a list of ``diag(M)`` ``[P_s]`` per subject; ``step_jitter`` as :class:`BatchedHMC` (one factor per iteration
+    for all subjects, from a generator of its own).  Chain k of subject s draws from ``default_rng(seed + s k_total + k)`` in
+    :class:`HMCSampler`'s order -- ``P_s`` standard normals of the REAL length, then the uniform of the accept test -- so a subject's
+    draws do not depend on who else is in the cohort and equal those of the per-subject sampler with ``seed + s k_total``.
+
+    ``device_resident=True``: positions, momenta and gradients stay in HBM for a whole trajectory (``nmgp_had_subjects_traj``: one
+    chunked evaluation per leapfrog step, masked elementwise kernels between them, one synchronisation per trajectory and bucket).
+    ``device_resident=False``: the host loop over ``*_subjects_eval`` that DEFINES the arithmetic -- padded momentum is 0, the
+    kinetic energy is ``0.5 * (p * v).sum()`` over the real slots of a row; the resident loop with ``device_kinetic=False``
+    reproduces it bit for bit.  ``device_kinetic=True`` takes the end point's kinetic energy from the device and 1/2 |z|^2 for the
+    start.  ``evaluators``: one callable per bucket, padded rows -> ``(out, grad, status)``, instead of contexts (host loop only)."""
+
+    MODEL = "non"
+
+    def __init__(self, subjects, hyper_pars, init_positions, step_size=1e-4, num_steps_in_leap=20, seed=None, mass=None,
+                 step_jitter=0.0, device_resident=True, device_kinetic=False, max_flop_waste=0.5, ctxs=None, evaluators=None):
+        from . import hadamard
+        subjects = [(np.ascontiguousarray(x, dtype=np.float64).reshape(-1), np.asarray(indx).reshape(-1).astype(np.int32),
+                     np.ascontiguousarray(y, dtype=np.float64).reshape(-1)) for x, indx, y in subjects]
+        S = len(subjects)
+        if S < 1 or len(init_positions) != S:
+            raise ValueError("subjects and init_positions must be lists of one positive length")
+        starts = [np.atleast_2d(np.array(v, dtype=np.float64)) for v in init_positions]
+        k = starts[0].shape[0]
+        if any(v.shape[0] != k for v in starts):
+            raise ValueError("every subject must have the same number of chains")
+        self.nobs = [s[0].shape[0] for s in subjects]
+        Ms = sorted({int(np.unique(s[1]).shape[0]) for s in subjects})
+        if len(Ms) != 1:
+            raise ValueError("the subjects have different numbers of distinct labels: %s" % Ms)
+        self.M, self.k = Ms[0], k
+        self.hyper = np.array([float(hyper_pars[key]) for key in self.HYPER_KEYS])
+        self.L = int(num_steps_in_leap)
+        eps = np.asarray(step_size, dtype=np.float64)
+        self.eps = np.full(S, float(eps)) if eps.ndim == 0 else eps.reshape(-1).copy()
+        if self.eps.shape[0] != S or not np.all(np.isfinite(self.eps) & (self.eps > 0)):
+            raise ValueError("step_size must be a positive scalar or one positive value per subject")
+        if mass is not None and (len(mass) != S or any(np.shape(m) != (v.shape[1],) or np.any(np.asarray(m) <= 0) for m, v in zip(mass, starts))):
+            raise ValueError("mass must hold one positive diag(M) [P_s] per subject")
+        self.step_jitter = float(step_jitter)
+        self.jitter_rng = np.random.default_rng(None if seed is None else 7919 * (seed + 1))
+        self.rngs = [np.random.default_rng(None if seed is None else seed + b) for b in range(S * k)]
+        self.device_resident = bool(device_resident) and evaluators is None
+        self.device_kinetic = bool(device_kinetic) and self.device_resident
+        self.buckets = hadamard.cohort_buckets(self.nobs, max_flop_waste)
+        for name, given in (("contexts", ctxs), ("evaluators", evaluators)):
+            if given is not None and len(given) != len(self.buckets):
+                raise ValueError("%d %s for %d buckets" % (len(given), name, len(self.buckets)))
+        self._own_ctxs = ctxs is None and evaluators is None
+        if evaluators is not None:
+            self.ctxs = []
+        else:
+            from . import _lib
+            self.ctxs = list(ctxs) if ctxs is not None else [_lib.Context() for _ in self.buckets]
+        # per bucket: the padded rows q, the mask of their real slots, and (with a mass) sqrt(diag M) and diag(M^-1) in that layout
+        self.state = []
+        for b, idx in enumerate(self.buckets):
+            nb = [self.nobs[s] for s in idx]
+            st = {"idx": [int(s) for s in idx], "nobs": nb, "q": self._pack([starts[s] for s in idx], nb, self.M)}
+            st["mask"] = self._pack([np.ones_like(starts[s]) for s in idx], nb, self.M) == 1.0
+            st["mchol"] = st["minv"] = None
+            if mass is not None:
+                rows = lambda f: self._pack([np.tile(f(np.asarray(mass[s], dtype=np.float64)), (k, 1)) for s in idx], nb, self.M)
+                st["mchol"] = rows(np.sqrt)
+                st["minv"] = np.where(st["mask"], rows(lambda m: 1.0 / m), 1.0)
+            if evaluators is not None:
+                st["eval"] = evaluators[b]
+            else:
+                ctx = self.ctxs[b]
+                ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=self.M)
+                st["ctx"] = ctx
+                st["eval"] = (lambda P, ctx=ctx: getattr(ctx, self.EVAL)(P, self.hyper, True, True, k))
+            self.state.append(st)
+
+    def close(self):
+        """Ends the trajectories and drops the sets; closes the contexts this object created itself."""
+        for ctx in self.ctxs:
+            if ctx.h:
+                ctx.had_subjects_traj_end()
+        _HadamardCohortLoop.close(self)
+
+    @staticmethod
+    def _potential(res):
+        """U [B] and dU/dq [B, Pmax] of an evaluation; a chain whose potential is undefined gets U = inf and a zero gradient"""
+        out, g, status = res
+        U = np.array(out[:, 0])
+        bad = (np.asarray(status) != 0) | ~np.isfinite(U)
+        U[bad] = np.inf
+        if g is not None:
+            g[bad] = 0.0
+        return U, g
+
+    def _kinetic(self, st, p):
+        """0.5 * (p * v).sum() over the real slots of each row, v = diag(M^-1) p"""
+        v = p if st["minv"] is None else p * st["minv"]
+        return np.array([0.5 * (p[z][m] * v[z][m]).sum() for z, m in enumerate(st["mask"])])
+
+    def _host_traj(self, st, eps, p0):
+        """:meth:`LockStepHMC.run`'s trajectory on the bucket's padded rows with a step size per row; padded slots stay as they are"""
+        mask, q1, g, U1 = st["mask"], st["q"].copy(), st["g"], st["U"]
+        e = eps[:, None]
+        with np.errstate(invalid="ignore", over="ignore"):      # (padded slots may hold anything; np.where drops what they give)
+            p1 = np.where(mask, p0 - (0.5 * e) * g, 0.0)
+            failed = ~np.isfinite(U1)
+            g1 = g
+            for step in range(self.L):
+                v = p1 if st["minv"] is None else st["minv"] * p1
+                q1 = np.where(mask, q1 + e * v, q1)
+                U1, g1 = self._potential(st["eval"](q1))
+                failed |= ~np.isfinite(U1)
+                p1 = np.where(mask, p1 - (e if step < self.L - 1 else 0.5 * e) * g1, p1)
+        return q1, p1, np.where(failed, np.inf, U1), g1, failed
+
+    def run(self, sample_size):
+        """Returns ``(samples, info)``: ``samples[s]`` ``[n, k, P_s]`` in the caller's subject order (what the three
+        ``posterior_predict_hadamard*_cohort`` functions take), ``info`` with ``accept_rate`` ``[S k]``, ``energy_error`` ``[n, S k]``
+        and ``timing`` as :class:`BatchedHMC`."""
+        import time
+        n, k, S = int(sample_size), self.k, len(self.nobs)
+        samples = [None] * S
+        accepted, energy_err = np.zeros(S * k), np.zeros((n, S * k))
+        t_start = time.perf_counter()
+        for st in self.state:
+            if self.device_resident:
+                out, status = st["ctx"].had_subjects_traj_begin(self.MODEL, st["q"], self.hyper, True, k)
+                st["U"], _ = self._potential((out, None, status))
+                st["ctx"].had_subjects_traj_set_mass(st["minv"])
+            else:
+                st["U"], st["g"] = self._potential(st["eval"](st["q"]))
+            st["rows"] = self._rows(st["idx"])
+            st["real"] = [int(m.sum()) for m in st["mask"]]
+            st["samples"] = [np.zeros((n, k, st["real"][j * k])) for j in range(len(st["idx"]))]
+        t_loop = time.perf_counter()
+        t_traj = 0.0
+        for it in range(n):
+            jit = 1.0 if self.step_jitter <= 0 else 1.0 + self.step_jitter * self.jitter_rng.uniform(-1.0, 1.0)
+            for st in self.state:
+                rows, mask = st["rows"], st["mask"]
+                eps = np.repeat(self.eps[st["idx"]] * jit, k)            # per row
+                # the chains' own streams: P_s standard normals of the real length, then (below) the accept uniform
+                z = np.zeros(mask.shape)
+                for r, (b, m) in enumerate(zip(rows, mask)):
+                    z[r, m] = self.rngs[b].standard_normal(st["real"][r])
+                p0 = z if st["mchol"] is None else np.where(mask, z * st["mchol"], 0.0)
+                K0 = np.array([0.5 * (z[r][m] * z[r][m]).sum() for r, m in enumerate(mask)]) if self.device_kinetic else self._kinetic(st, p0)
+                H0 = st["U"] + K0
+                t0 = time.perf_counter()
+                if self.device_resident:
+                    q1, p1, K1, U1, failed = st["ctx"].had_subjects_traj(eps[::k], self.L, p0, want_p1=not self.device_kinetic,
+                                                                        want_kin=self.device_kinetic)
+                    U1 = np.where(failed, np.inf, U1)
+                else:
+                    q1, p1, U1, g1, failed = self._host_traj(st, eps, p0)
+                t_traj += time.perf_counter() - t0
+                if not self.device_kinetic:
+                    K1 = self._kinetic(st, p1)
+                H1 = U1 + K1
+                with np.errstate(invalid="ignore"):       # inf - inf: start and end potential both undefined
+                    dH = H1 - H0
+                u = np.array([np.log(self.rngs[b].random()) for b in rows])
+                acc = np.isfinite(dH) & (u < -dH)
+                if self.device_resident:
+                    st["ctx"].had_subjects_traj_commit(acc)
+                else:
+                    st["g"] = np.where(acc[:, None], g1, st["g"])
+                st["q"][acc] = q1[acc]
+                st["U"] = np.where(acc, U1, st["U"])
+                accepted[rows] += acc
+                energy_err[it, rows] = np.where(np.isfinite(dH), dH, np.nan)
+                for j, v in enumerate(self._unpack(st["q"], st["nobs"], self.M, k)):
+                    st["samples"][j][it] = v
+        t_end = time.perf_counter()
+        for st in self.state:
+            for j, s in enumerate(st["idx"]):
+                samples[s] = st["samples"][j]
+        timing = {"setup_seconds": t_loop - t_start, "loop_seconds": t_end - t_loop, "trajectory_call_seconds": t_traj,
+                  "device_share": t_traj / max(t_end - t_loop, 1e-12)}
+        return samples, {"accept_rate": accepted / max(n, 1), "energy_error": energy_err, "timing": timing}
+
+
+class HadamardCohortHMC(_HadamardCohortHMC):
+    """:class:`_HadamardCohortHMC` under the nonseparable model: ``init_positions[s]`` ``[k, N_s (1 + T) + 1]``, against
+    :class:`BatchedHMCHadamard` subject by subject; ``samples`` go to :func:`posterior_predict_hadamard_cohort`."""
+
+
+class HadamardSepCohortHMC(_HadamardCohortHMC, HadamardSepCohortMAP):
+    """:class:`_HadamardCohortHMC` under the separable model (keys, entry and layout of :class:`HadamardSepCohortMAP`):
+    ``init_positions[s]`` ``[k, 2 N_s + T + 1]``, against :class:`BatchedHMCHadamardSep`; ``samples`` go to
+    :func:`posterior_predict_hadamard_sep_cohort`."""
+
+    MODEL = "sep"
+
+
+class HadamardStaCohortHMC(_HadamardCohortHMC, HadamardStaCohortMAP):
+    """:class:`_HadamardCohortHMC` under the stationary model (keys, entry and layout of :class:`HadamardStaCohortMAP`; every slot of
+    the ``T + 3`` vector is real): against :class:`BatchedHMCHadamardSta`; ``samples`` go to
+    :func:`posterior_predict_hadamard_sta_cohort`."""
+
+    MODEL = "sta"
+
+
 # ---- stationary (LMC) model, complete data: the baseline ----------------------------------------------------------------------------
 class BatchedMAPStationary(LockStepMAP):
     """The MAP loop of ``Stationary_model_mpiKAISER.py`` (:func:`map_stationary` per subject) for ALL subjects of a rank, or B restarts
