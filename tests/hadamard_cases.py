@@ -1,6 +1,8 @@
 """Synthetic subjects for the Hadamard sweep (tests/test_hadamard_sweep_cpu.py, tests/test_gpu_hadamard_sweep.py): every M from 1 to 8,
 the edges of the 64 x 64 tiles, four label layouts next to the fixtures' interleaved one, and one slice wider than 256 riding rows.
-A plain module, not a conftest: both halves import it, so the CPU half checks the very subjects the GPU half runs."""
+A plain module, not a conftest: both halves import it, so the CPU half checks the very subjects the GPU half runs.  The cohort sets of
+tests/hadamard_cohort_cases.py are built from the same subjects; the measure the gradients are held to block by block, for the
+resident entries and the cohort alike, is at the end of this file (block_bar)."""
 import functools
 
 import numpy as np
@@ -192,3 +194,107 @@ def minor_chains(model):
     else:
         bad[N + 2 * T + 3:N + 2 * T + 6] = 0.0
     return np.stack([P[0], bad, P[1]])
+
+
+# ---- the gradients block by block ------------------------------------------------------------------------------------------------------
+# One whole-vector norm hides a block: at (129, 4, unsorted) the smallest slot column of the nonseparable likelihood gradient is 0.027
+# of ||g|| and the last observation's tilde_l entry 0.003 of it, so a slot column wrong by 1e-7 relative moves ||dg|| / ||g|| by
+# 2.7e-9, below the whole-vector 1e-8.  The gradients are therefore also taken block by block with the measure of
+# tests/objective_cases.py (block_table: ||d_b|| / max(||g_b||, 1e-3 ||g||)); "had" has the nonseparable complete-data layout ("svc":
+# tilde_l, every slot column of uL, sigma2), "sep" the separable one, "sta" the four scalars' one.
+#
+# Without the priors, and for "sta" with them too, every block of a subject is held to
+#     block_bar = min(GRAD_TIGHT, max(100 d_cpu, N_s cond(S) eps))
+# d_cpu: the worst block, over the subject's two chains, between two CPU references -- the per-subject restatement (ref_logpos) and the
+# padded formulation of the CPU halves (tests/test_hadamard_cohort_cpu.py, tests/test_hadamard_cohort_models_cpu.py) at the set's Nmax
+# (the resident sweep: Nmax = N_s); the factor 100 is the rule of prediction_cases.tight().  N_s cond(S) eps (eps = 2^-52, the larger
+# cond of the two chains) is what a backward-stable solve may lose at that conditioning.  No device figure enters a bar.  Measured on
+# the CPU (tests/test_hadamard_cohort_cpu.py::test_block_bars_rest_on_two_cpu_references prints both terms per subject):
+# d_cpu <= 2.7e-14 per block on sets F - H and <= 8.8e-14 on set I, over the three models; the bar comes to about 4e-11 at (257, 7) and
+# 8.6e-10 at (1030, 2), and at the smallest subjects to the 100 d_cpu term or to N_s eps itself (2.2e-16 at N_s = M = 1).  Achieved on
+# the MI355X (profiles/parity_hadamard_cohort_sweep.json): every block at or below 0.16 of its bar, 7 % at sets F - H (1.3e-13 against
+# 1.9e-12 at (6, 6)), about 2e-13 against 7.6e-10 on set I; the prior part at most 1.3e-8 against 1e-5.
+#
+# With the GP priors ("had", "sep": factors of condition number up to 1e11) the prior part g(prior) - g(no prior) is compared block by
+# block with the same difference of the restatement at the standing 1e-5; the CPU halves hold the two LAPACK blockings of that
+# reference (the subject alone, and padded to Nmax) to PRIOR_PART_REFERENCE = 1e-7 per block (measured: <= 7.9e-10 on sets A - H, <= 3.5e-9 on set I).
+GRAD_TIGHT = 1e-8
+MACHINE_EPS = 2.0 ** -52
+PRIOR_PART_REFERENCE = 1e-7
+LAYOUT = {"had": "svc", "sep": "sep", "sta": "sta"}
+# (layout name, N, M, block name) -> bar of a likelihood-gradient block that needs one of its own: ten times a discrepancy measured
+# between two CPU references, with the figure beside it (the rule of tests/objective_cases.py).  The subject (1, 1): one observation of
+# one output.  The two references of d_cpu run the same scalar operations there (d_cpu = 0 for "had" and "sep"), so the rule gives
+# N_s cond(S) eps = 1 eps = 2.2e-16, while the restatement itself is further than that from a closed form in np.longdouble
+# (tests/test_hadamard_cohort_cpu.py::test_the_single_observation_subject_has_bars_from_a_longdouble_reference; worst of the two chains):
+BLOCK_BARS = {
+    ("sep", 1, 1, "tilde_sigma"): 3.5e-15,       # measured 3.43e-16
+    ("sep", 1, 1, "uL_vec"): 2.9e-15,            # measured 2.85e-16
+    ("sep", 1, 1, "sigma2"): 3.4e-15,            # measured 3.37e-16
+    ("svc", 1, 1, "uL[0,0]"): 1.9e-15,           # measured 1.87e-16 ("had")
+    ("svc", 1, 1, "sigma2"): 5.9e-16,            # measured 5.80e-17 ("had")
+}
+
+
+def layout(model, N, M):
+    """the block layout of objective_cases.blocks for a model's gradient"""
+    return (LAYOUT[model], N, M)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(model, case, chain, prior):
+    """(verbose tuple, d NegLog / d pars) of the restatement on the subject alone; computed once, shared, left unchanged"""
+    c = build(case)
+    return ref_logpos(model, c["pars"][model][chain], c, prior, grad=True)
+
+
+@functools.lru_cache(maxsize=None)
+def padded_reference(model, case, chain, prior, Nmax):
+    """the same of the padded formulation the device runs, restated in the CPU halves, under LAPACK at order Nmax"""
+    from test_hadamard_cohort_cpu import padded_logpos
+    from test_hadamard_cohort_models_cpu import PADDED
+    c = build(case)
+    fn = padded_logpos if model == "had" else PADDED[model]
+    return fn(c["pars"][model][chain], c, Nmax, prior)
+
+
+@functools.lru_cache(maxsize=None)
+def cond_S(model, case, chain):
+    c = build(case)
+    return float(np.linalg.cond(ref_covariance(model, c["pars"][model][chain], c)))
+
+
+def block_table(g, gref, model, N, M):
+    from objective_cases import block_table as table
+    return table(g, gref, layout(model, N, M))
+
+
+@functools.lru_cache(maxsize=None)
+def block_bar_terms(model, case, Nmax=None):
+    """(d_cpu, N_s cond(S) eps) of a subject in a set padded to Nmax (None: the subject alone)"""
+    N, M = case[0], case[1]
+    Nmax = N if Nmax is None else Nmax
+    d = 0.0
+    for k in (0, 1):
+        for prior in ((False, True) if model == "sta" else (False,)):
+            tab = block_table(padded_reference(model, case, k, prior, Nmax)[1], reference(model, case, k, prior)[1], model, N, M)
+            d = max(d, max(tab.values()))
+    return d, N * max(cond_S(model, case, k) for k in (0, 1)) * MACHINE_EPS
+
+
+def block_bar(model, case, Nmax=None):
+    d, stable = block_bar_terms(model, case, Nmax)
+    return min(GRAD_TIGHT, max(100.0 * d, stable))
+
+
+def prior_part(model, case, chain, Nmax=None):
+    """g(prior) - g(no prior) of the restatement (Nmax: of the padded formulation at that order)"""
+    if Nmax is None:
+        return reference(model, case, chain, True)[1] - reference(model, case, chain, False)[1]
+    return padded_reference(model, case, chain, True, Nmax)[1] - padded_reference(model, case, chain, False, Nmax)[1]
+
+
+def block_entries(prefix, g, gref, model, N, M, bar, bars=None):
+    """{"prefix[block]": (achieved, bar)} for check(); `bars`: a table like BLOCK_BARS with the blocks that have a bar of their own"""
+    lay = layout(model, N, M)
+    return {"%s[%s]" % (prefix, name): (e, (bars or {}).get(lay + (name,), bar)) for name, e in block_table(g, gref, model, N, M).items()}

@@ -1,8 +1,6 @@
 """Helpers of the cohort tests of the separable ("sep") and stationary ("sta") Hadamard models (tests/test_hadamard_cohort_models_cpu.py,
 tests/test_gpu_hadamard_cohort_models.py) on the subject sets of tests/hadamard_cohort_cases.py: the two models' layouts, chains and
 references.  A plain module, not a conftest.  The arrays are shared: do not write into them."""
-import functools
-
 import numpy as np
 
 import hadamard_cases as hc
@@ -54,11 +52,9 @@ def hyper_of(model, cases):
     return hc.build(cases[0])["hyper"][model]
 
 
-@functools.lru_cache(maxsize=None)
 def reference(model, case, chain, prior):
     """(verbose tuple, d NegLog / d pars) of the restatement on the subject alone; computed once, shared, left unchanged"""
-    c = hc.build(case)
-    return hc.ref_logpos(model, c["pars"][model][chain], c, prior, grad=True)
+    return hc.reference(model, case, chain, prior)
 
 
 def workspace_per_chain(model, Nmax, M, want_grad=True):

@@ -3,7 +3,10 @@ unit observations) against the NumPy restatement hadamard_cases.ref_logpos("had"
 tests/hadamard_cohort_cases.py; tests/test_hadamard_cohort_cpu.py checks the new subjects' preconditions and the padded formulation.
 
 Bars: those of tests/test_gpu_hadamard_sweep.py for the model "had" (its eval_errors): without priors likelihood 1e-10 and gradient
-1e-8; with priors 1e-6 / 1e-9 / 1e-5; prior components 1e-6 on the log-det scale; the inverse-gamma entry 1e-12.  Padding inert, a
+1e-8; with priors 1e-6 / 1e-9 / 1e-5; prior components 1e-6 on the log-det scale; the inverse-gamma entry 1e-12; the gradient block by
+block too, without the priors at hadamard_cases.block_bar of the subject in its set (min(1e-8, max(100 d_cpu, N_s cond(S) eps)), both
+terms from the CPU half), the prior part g(prior) - g(no prior) at 1e-5.  Sets F - H (M = 4, 6, 7) run everything sets A - E run; set
+I (Nmax = 1030) with one chain per subject against the restatement and in "padding is inert".  Padding inert, a
 subject alone against its rows of the set, value-only against value + gradient, chunked against unchunked, and a subject without
 padding against the resident path's likelihood: bit for bit.  Driver: 1e-6 relative on the log-posterior history, the standing bar
 between two evaluation paths."""
@@ -48,29 +51,30 @@ def unpack(P, cases, k):
     return hadamard.cohort_unpack(P, cc.nobs(cases), cases[0][1], chains_per_subject=k)
 
 
-def meets_the_restatement(out, grad, status, cases, k, prior, tag):
-    """every chain's tuple and the real slots of its gradient against the restatement on the subject alone; padded slots +0.0"""
-    S = len(cases)
+def meets_the_restatement(out, grad, status, cases, k, prior, tag, plain):
+    """every chain's tuple and the real slots of its gradient against the restatement on the subject alone, the gradient block by
+    block too (`plain`: the entry's gradient without the priors, which the prior part is taken against); padded slots +0.0"""
+    S, M = len(cases), cases[0][1]
     Nmax = (grad.shape[1] - 1) // (1 + hc.build(cases[0])["T"])
     assert status.tolist() == [0] * (S * k) and out.shape == (S * k, 5)
-    pads = cc.padded_slots(cc.nobs(cases), cases[0][1], Nmax, k)
+    pads = cc.padded_slots(cc.nobs(cases), M, Nmax, k)
     assert np.all(grad[pads] == 0.0) and not np.any(np.signbit(grad[pads]))
-    real = unpack(grad, cases, k)
+    real, real_plain = unpack(grad, cases, k), unpack(plain, cases, k)
     for s, case in enumerate(cases):
         for j in range(k):
             ref_out, ref_grad = cc.reference(case, j, prior)
             check("hcohort/%s/k%d/prior%d/%s/chain%d" % (tag, k, prior, hc.case_id(case), j),
-                  **eval_errors("had", out[s * k + j], real[s][j], ref_out, ref_grad, prior, case[0]))
+                  **eval_errors("had", out[s * k + j], real[s][j], ref_out, ref_grad, prior, case[0], M, hc.block_bar("had", case, Nmax),
+                                without=(real_plain[s][j], cc.reference(case, j, False)[1])))
 
 
 def evaluate_set(ctx, cases, k, tag, Nmax=None):
     set_subjects(ctx, cases, Nmax)
     P = packed(cases, k, Nmax)
+    res = {prior: ctx.had_subjects_eval(P, hyper_of(cases), prior=prior, want_grad=True, chains_per_subject=k) for prior in (True, False)}
+    assert np.array_equal(res[False][0][:, 0], -res[False][0][:, 1])
     for prior in (True, False):
-        out, grad, status = ctx.had_subjects_eval(P, hyper_of(cases), prior=prior, want_grad=True, chains_per_subject=k)
-        if not prior:
-            assert np.array_equal(out[:, 0], -out[:, 1])
-        meets_the_restatement(out, grad, status, cases, k, prior, tag)
+        meets_the_restatement(*res[prior], cases, k, prior, tag, res[False][1])
 
 
 # ---- 1. against the restatement -----------------------------------------------------------------------------------------------------------
@@ -80,10 +84,24 @@ def test_every_chain_of_the_set_meets_the_restatement_on_its_subject_alone(ctx, 
     evaluate_set(ctx, cc.SETS[name], k, name)
 
 
+def test_set_I_meets_the_restatement_beyond_one_panel_and_one_trace_pass(ctx):
+    """Nmax = 1030, one chain per subject: N_s = 1030 and 1025 take k_hadc_trace's second pass and 513 and 640 do not, the factorisation
+    runs two 512-column panels (the identity-padded tail of the short subjects in the second), 2 Nmax + 2 = 2062 riding rows."""
+    evaluate_set(ctx, cc.SET_I, 1, "I")
+
+
 # ---- 2. padding is inert ----------------------------------------------------------------------------------------------------------------
 def test_padding_is_inert(ctx):
-    cases, k, M = cc.SET_A, 2, 2
-    sizes, Nmax = cc.nobs(cases), 128
+    padding_is_inert(ctx, cc.SET_A, 2)
+
+
+def test_padding_is_inert_in_set_I(ctx):
+    padding_is_inert(ctx, cc.SET_I, 1)
+
+
+def padding_is_inert(ctx, cases, k):
+    M, B = cases[0][1], len(cases) * k
+    sizes, Nmax = cc.nobs(cases), max(cc.nobs(cases))
     subs = cc.subjects(cases)
     x, y, indx = np.zeros((len(cases), Nmax)), np.zeros((len(cases), Nmax)), np.zeros((len(cases), Nmax), dtype=np.int32)
     for s, c in enumerate(subs):
@@ -102,17 +120,19 @@ def test_padding_is_inert(ctx):
         assert np.all(P[pads] == fill) if np.isfinite(fill) else np.all(np.isnan(P[pads]))
         for prior in (True, False):
             got = ctx.had_subjects_eval(P, hyper, prior=prior, want_grad=True, chains_per_subject=k)
-            assert got[2].tolist() == [0] * (len(cases) * k) and same_bits(got, clean[prior]), (fill, prior)
+            assert got[2].tolist() == [0] * B and same_bits(got, clean[prior]), (fill, prior)
             assert np.all(got[1][pads] == 0.0) and not np.any(np.signbit(got[1][pads]))
             val = ctx.had_subjects_eval(P, hyper, prior=prior, want_grad=False, chains_per_subject=k)
             assert val[1] is None and np.array_equal(val[0], clean[prior][0]) and val[2].tolist() == got[2].tolist()
     # a NaN in a REAL slot is reported for that chain alone
     P = packed(cases, k, fill=np.nan)
-    P[3, 1] = np.nan                                    # chain 1 of subject 1 (63 observations): tilde_l[1]
+    bad = 2 * k - 1                                     # the last chain of subject 1 (set A: 63 observations): tilde_l[1]
+    assert sizes[1] < Nmax and (k, bad) in ((2, 3), (1, 1))
+    P[bad, 1] = np.nan
     out, grad, status = ctx.had_subjects_eval(P, hyper, prior=True, want_grad=True, chains_per_subject=k)
     from nonstationary_multivariate_gaussian_process_amd import _lib
-    assert status.tolist() == [0, 0, 0, _lib.NUM_NAN] + [0] * 8 and np.all(np.isnan(out[3])) and not np.any(grad[3])
-    keep = np.arange(12) != 3
+    assert status.tolist() == [_lib.NUM_NAN if b == bad else 0 for b in range(B)] and np.all(np.isnan(out[bad])) and not np.any(grad[bad])
+    keep = np.arange(B) != bad
     assert same_bits([out[keep], grad[keep]], [clean[True][0][keep], clean[True][1][keep]])
 
 
@@ -301,7 +321,7 @@ import hadamard_cohort_cases as cc
 import test_gpu_hadamard_cohort as t
 from nonstationary_multivariate_gaussian_process_amd import _lib
 ctx = _lib.Context(0)
-for name in ("A", "D"):
+for name in ("A", "D", "F", "G", "H"):
     t.evaluate_set(ctx, cc.SETS[name], 2, "poison_" + name)      # a fresh (or grown) workspace: poisoned
     t.evaluate_set(ctx, cc.SETS[name], 2, "poison_" + name)      # the kept workspace: poisoned again
 ctx.close()

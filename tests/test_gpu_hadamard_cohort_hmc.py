@@ -1,5 +1,5 @@
 """Device-resident HMC trajectories of the Hadamard cohort (nmgp_had_subjects_traj_*) and the cohort HMC drivers: the three models on
-the subject sets A-E of tests/hadamard_cohort_cases.py.  Everything is compared bit for bit with the host loop's arithmetic over the
+the subject sets A-H of tests/hadamard_cohort_cases.py (set I, Nmax = 1030: one two-step trajectory per model).  Everything is compared bit for bit with the host loop's arithmetic over the
 models' *_subjects_eval entries (hh.host_trajectory), except the device's kinetic energy (a summation bound) and the comparison with
 the per-subject samplers on the resident entries (VAL_TOL, the standing bar between two evaluation paths)."""
 import math
@@ -19,7 +19,7 @@ from test_gpu_hadamard_sweep import VAL_TOL
 pytestmark = pytest.mark.gpu
 
 MODELS = hh.MODELS
-NAMES = ("A", "B", "C", "D", "E")
+NAMES = ("A", "B", "C", "D", "E", "F", "G", "H")
 P_SEED = 9100                       # momenta of the ABI-level tests
 DRIVER_SEED = 5200                  # test 10: every accept test of the reference runs is further than 1e-6 from its threshold
 
@@ -129,6 +129,20 @@ def test_resident_loop_is_the_host_loop(ctx, model, name):
     cases = cc.SETS[name]
     set_subjects(ctx, cases)
     assert len(list(abi_cases(ctx, model, cases))) == 8
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_resident_loop_is_the_host_loop_in_set_I(ctx, model):
+    """Nmax = 1030 (tests/hadamard_cohort_cases.py), one chain per subject: one trajectory of two steps with a diagonal mass."""
+    cases, k, nsteps = cc.SET_I, 1, 2
+    set_subjects(ctx, cases)
+    hyper, eps = hh.hyper_of(model, cases), hh.eps_of(len(cases))
+    P, mask, p0, minv = packed(model, cases, k), real_mask(model, cases, k), hh.momenta(model, cases, k, P_SEED), packed_minv(model, cases, k)
+    _, dev = device_traj(ctx, model, P, hyper, k, eps, nsteps, p0, minv)
+    ref = host_reference(ctx, model, P, hyper, k, mask, eps, nsteps, p0, minv)
+    ctx.had_subjects_traj_end()
+    assert not dev[4].any() and np.all(np.isfinite(dev[3]))
+    agree(dev, ref, mask)
 
 
 # ---- 3 ----------------------------------------------------------------------------------------------------------------------------------
@@ -543,6 +557,9 @@ ctx = _lib.Context(0)
 for model in t.MODELS:
     t.set_subjects(ctx, cc.SET_B)
     assert len(list(t.abi_cases(ctx, model, cc.SET_B))) == 8
+    for cases in (cc.SET_F, cc.SET_G, cc.SET_H):                 # M = 4, 6, 7: two chains, three steps, both masses
+        t.set_subjects(ctx, cases)
+        assert len(list(t.abi_cases(ctx, model, cases, ks=(2,), steps=(3,)))) == 2
 ctx.close()
 print("POISON_OK")
 """
@@ -550,7 +567,8 @@ print("POISON_OK")
 
 def test_poisoned_workspace():
     """NMGP_POISON=1 (read once per process: a fresh child, nothing preloaded) fills fresh buffers and the kept workspace with NaN
-    before every call: a resident buffer or a slab piece that nobody wrote would show up in test 2's comparison on set B."""
+    before every call: a resident buffer or a slab piece that nobody wrote would show up in test 2's comparison on set B and, with
+    two chains and three steps, on sets F, G and H."""
     env = dict(os.environ)
     env["NMGP_POISON"] = "1"
     env.pop("NMGP_HAD_BATCH_SLAB_GB", None)

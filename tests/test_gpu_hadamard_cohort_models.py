@@ -3,7 +3,9 @@ nmgp_hadst_subjects_eval on the set of nmgp_had_set_subjects against the NumPy r
 each subject ALONE, at the sets of tests/hadamard_cohort_cases.py; tests/test_hadamard_cohort_models_cpu.py checks the subjects'
 preconditions and the padded formulations.  The file mirrors tests/test_gpu_hadamard_cohort.py.
 
-Bars: eval_errors(model, ...) of tests/test_gpu_hadamard_sweep.py, the standing bars of the two models.  Padding inert, a subject
+Bars: eval_errors(model, ...) of tests/test_gpu_hadamard_sweep.py, the standing bars of the two models and the gradient block by block
+(hadamard_cases.block_bar of the subject in its set; sep with the priors: the prior part at 1e-5).  Sets F - H (M = 4, 6, 7) run
+everything sets A - E run; set I (Nmax = 1030) with one chain per subject, here and in "padding is inert".  Padding inert, a subject
 alone against its rows of the set, value-only against value + gradient, chunked against unchunked, and a subject without padding
 against the resident path (sta: everything; sep: the likelihood, and without priors NegLog and the gradient): bit for bit.  Drivers:
 1e-6 relative on the log-posterior history, the standing bar between two evaluation paths."""
@@ -50,28 +52,29 @@ def no_sign_bit_zeros(a):
     return np.all(a == 0.0) and not np.any(np.signbit(a))
 
 
-def meets_the_restatement(model, out, grad, status, cases, k, prior, tag, Nmax):
-    """every chain's tuple and the real slots of its gradient against the restatement on the subject alone; padded slots +0.0"""
+def meets_the_restatement(model, out, grad, status, cases, k, prior, tag, Nmax, plain):
+    """every chain's tuple and the real slots of its gradient against the restatement on the subject alone, the gradient block by
+    block too (`plain`: the entry's gradient without the priors, which the prior part is taken against); padded slots +0.0"""
     S, M = len(cases), cases[0][1]
     assert status.tolist() == [0] * (S * k) and out.shape == (S * k, mc.WIDTH[model]) and grad.shape == (S * k, mc.plen(model, Nmax, M))
     pads = mc.padded_slots(model, cc.nobs(cases), M, Nmax, k)
     assert no_sign_bit_zeros(grad[pads])
-    real = mc.unpack(model, grad, cc.nobs(cases), M, k)
+    real, real_plain = mc.unpack(model, grad, cc.nobs(cases), M, k), mc.unpack(model, plain, cc.nobs(cases), M, k)
     for s, case in enumerate(cases):
         for j in range(k):
             ref_out, ref_grad = mc.reference(model, case, j, prior)
             check("hcohort_models/%s/%s/k%d/prior%d/%s/chain%d" % (model, tag, k, prior, hc.case_id(case), j),
-                  **eval_errors(model, out[s * k + j], real[s][j], ref_out, ref_grad, prior, case[0]))
+                  **eval_errors(model, out[s * k + j], real[s][j], ref_out, ref_grad, prior, case[0], M, hc.block_bar(model, case, Nmax),
+                                without=(real_plain[s][j], mc.reference(model, case, j, False)[1])))
 
 
 def evaluate_set(ctx, model, cases, k, tag, Nmax=None):
     set_subjects(ctx, cases, Nmax)
     P = packed(model, cases, k, Nmax)
+    res = {prior: entry(ctx, model)(P, mc.hyper_of(model, cases), prior=prior, want_grad=True, chains_per_subject=k) for prior in (True, False)}
+    assert np.array_equal(res[False][0][:, 0], -res[False][0][:, 1])
     for prior in (True, False):
-        out, grad, status = entry(ctx, model)(P, mc.hyper_of(model, cases), prior=prior, want_grad=True, chains_per_subject=k)
-        if not prior:
-            assert np.array_equal(out[:, 0], -out[:, 1])
-        meets_the_restatement(model, out, grad, status, cases, k, prior, tag, max(cc.nobs(cases)) if Nmax is None else Nmax)
+        meets_the_restatement(model, *res[prior], cases, k, prior, tag, max(cc.nobs(cases)) if Nmax is None else Nmax, res[False][1])
 
 
 # ---- 1. against the restatement -----------------------------------------------------------------------------------------------------------
@@ -82,12 +85,28 @@ def test_every_chain_of_the_set_meets_the_restatement_on_its_subject_alone(ctx, 
     evaluate_set(ctx, model, cc.SETS[name], k, name)
 
 
+@pytest.mark.parametrize("model", MODELS)
+def test_set_I_meets_the_restatement_beyond_one_panel_and_one_trace_pass(ctx, model):
+    """Nmax = 1030, one chain per subject (tests/hadamard_cohort_cases.py): the trace kernel's second pass for N_s = 1030 and 1025, two
+    512-column panels, 2 Nmax + 2 = 2062 riding rows."""
+    evaluate_set(ctx, model, cc.SET_I, 1, "I")
+
+
 # ---- 2. padding is inert ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model", MODELS)
 def test_padding_is_inert(ctx, model):
+    padding_is_inert(ctx, model, cc.SET_A, 2)
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_padding_is_inert_in_set_I(ctx, model):
+    padding_is_inert(ctx, model, cc.SET_I, 1)
+
+
+def padding_is_inert(ctx, model, cases, k):
     from nonstationary_multivariate_gaussian_process_amd import _lib
-    cases, k, M = cc.SET_A, 2, 2
-    sizes, Nmax = cc.nobs(cases), 128
+    M, B = cases[0][1], len(cases) * k
+    sizes, Nmax = cc.nobs(cases), max(cc.nobs(cases))
     subs = cc.subjects(cases)
     ev = entry(ctx, model)
     x, y, indx = np.zeros((len(cases), Nmax)), np.zeros((len(cases), Nmax)), np.zeros((len(cases), Nmax), dtype=np.int32)
@@ -107,16 +126,18 @@ def test_padding_is_inert(ctx, model):
         assert np.all(P[pads] == fill) if np.isfinite(fill) else np.all(np.isnan(P[pads]))
         for prior in (True, False):
             got = ev(P, hyper, prior=prior, want_grad=True, chains_per_subject=k)
-            assert got[2].tolist() == [0] * (len(cases) * k) and same_bits(got, clean[prior]), (fill, prior)
+            assert got[2].tolist() == [0] * B and same_bits(got, clean[prior]), (fill, prior)
             assert no_sign_bit_zeros(got[1][pads])
             val = ev(P, hyper, prior=prior, want_grad=False, chains_per_subject=k)
             assert val[1] is None and np.array_equal(val[0], clean[prior][0]) and val[2].tolist() == got[2].tolist()
     # a NaN in a REAL slot is reported for that chain alone
     P = packed(model, cases, k, fill=np.nan)
-    P[3, 1] = np.nan                                    # chain 1 of subject 1 (63 observations): tilde_l[1] / tilde_sigma
+    bad = 2 * k - 1                                     # the last chain of subject 1 (set A: 63 observations): tilde_l[1] / tilde_sigma
+    assert sizes[1] < Nmax and (k, bad) in ((2, 3), (1, 1))
+    P[bad, 1] = np.nan
     out, grad, status = ev(P, hyper, prior=True, want_grad=True, chains_per_subject=k)
-    assert status.tolist() == [0, 0, 0, _lib.NUM_NAN] + [0] * 8 and np.all(np.isnan(out[3])) and not np.any(grad[3])
-    keep = np.arange(12) != 3
+    assert status.tolist() == [_lib.NUM_NAN if b == bad else 0 for b in range(B)] and np.all(np.isnan(out[bad])) and not np.any(grad[bad])
+    keep = np.arange(B) != bad
     assert same_bits([out[keep], grad[keep]], [clean[True][0][keep], clean[True][1][keep]])
 
 
@@ -334,7 +355,7 @@ import test_gpu_hadamard_cohort_models as t
 from nonstationary_multivariate_gaussian_process_amd import _lib
 ctx = _lib.Context(0)
 for model in t.MODELS:
-    for name in ("A", "D"):
+    for name in ("A", "D", "F", "G", "H"):
         t.evaluate_set(ctx, model, cc.SETS[name], 2, "poison_" + name)      # a fresh (or grown) workspace: poisoned
         t.evaluate_set(ctx, model, cc.SETS[name], 2, "poison_" + name)      # the kept workspace: poisoned again
 ctx.close()

@@ -9,7 +9,9 @@ Bars.  Covariance: rtol 1e-13, atol 1e-15, exactly symmetric (the bar of the fix
 the stationary model (which has no GP prior) with them too: likelihood 1e-10 relative and gradient 1e-8 in ||dg|| / ||g||, the bars at
 which test_numpy_restatement_meets_the_reference holds the restatements to the reference itself (cond(S) N eps ~ 1e-11 here).  With the
 GP priors (factors of condition number up to 1e11): the project's standing bars -- log posterior 1e-6, likelihood 1e-9, gradient 1e-5,
-the prior components 1e-6 on prior_component_err_on_the_logdet_scale, the inverse-gamma entry 1e-12.  nmgp_predict_hadst (no prior
+the prior components 1e-6 on prior_component_err_on_the_logdet_scale, the inverse-gamma entry 1e-12.  The gradients also block by
+block (tests/hadamard_cases.py, block_bar): every block at min(1e-8, max(100 d_cpu, N cond(S) eps)) where the whole vector is held to
+1e-8, every block of the prior part g(prior) - g(no prior) at 1e-5 where it is held to 1e-5.  nmgp_predict_hadst (no prior
 regression): mean and variance 1e-9 relative; the other predictors the standing 1e-5.  Value-only against value + gradient, a chain
 alone against its row of the batch, H draws against H calls, and a batch split into chunks by NMGP_HAD_BATCH_SLAB_GB against the same
 batch in one chunk: bit for bit."""
@@ -71,8 +73,22 @@ def dm(a):
 
 
 # ---- a. objective, gradient, covariance --------------------------------------------------------------------------------------------
-def eval_errors(model, out, grad, ref_out, ref_grad, prior, N):
-    """{quantity: (achieved, bar)} of one chain's verbose tuple and gradient against the restatement's"""
+def eval_errors(model, out, grad, ref_out, ref_grad, prior, N, M, block_bar=GRAD_TIGHT, without=None):
+    """{quantity: (achieved, bar)} of one chain's verbose tuple and gradient against the restatement's.  Next to the whole-vector
+    gradient error, block by block (tests/hadamard_cases.py): without the priors, and for the stationary model with them, every block
+    "grad[block]" at `block_bar` = hc.block_bar(model, case, Nmax); with the GP priors every block "prior_grad[block]" of
+    g(prior) - g(no prior) at GRAD_TOL, `without` = (the entry's gradient, the restatement's) of the same chain without the priors."""
+    tight = model == "sta" or not prior
+    if tight:
+        blocks = hc.block_entries("grad", grad, ref_grad, model, N, M, min(block_bar, GRAD_TIGHT), hc.BLOCK_BARS)
+    else:
+        blocks = hc.block_entries("prior_grad", grad - without[0], ref_grad - without[1], model, N, M, GRAD_TOL)
+    errs = eval_errors_whole(model, out, grad, ref_out, ref_grad, prior, N)
+    errs.update(blocks)
+    return errs
+
+
+def eval_errors_whole(model, out, grad, ref_out, ref_grad, prior, N):
     tight = model == "sta" or not prior
     errs = dict(logpos=(relerr(out[0], ref_out[0]), LIK_TIGHT if not prior else VAL_TOL),
                 loglik=(relerr(out[1], ref_out[1]), LIK_TIGHT if tight else LIK_TOL),
@@ -101,6 +117,7 @@ def test_objective_gradient_and_covariance_meet_the_restatement(ctx, case, model
         np.testing.assert_allclose(S, ref, rtol=1e-13, atol=1e-15)
     ev = getattr(ctx, EVAL[model])
     hyper = c["hyper"][model]
+    plain = ev(P, hyper, prior=False, want_grad=True)[1]                 # (the prior part of a gradient is taken against it)
     for prior in (True, False):
         out, grad, status = ev(P, hyper, prior=prior, want_grad=True)
         assert status.tolist() == [0, 0] and out.shape == (2, WIDTH[model]) and grad.shape == P.shape
@@ -108,8 +125,10 @@ def test_objective_gradient_and_covariance_meet_the_restatement(ctx, case, model
         if not prior:
             assert np.array_equal(out[:, 0], -out[:, 1])                 # NegLog is the negated likelihood
         for k in (0, 1):
-            ref_out, ref_grad = hc.ref_logpos(model, P[k], c, prior, grad=True)
-            check(name(model, case, "eval_prior%d/chain%d" % (prior, k)), **eval_errors(model, out[k], grad[k], ref_out, ref_grad, prior, N))
+            ref_out, ref_grad = hc.reference(model, case, k, prior)
+            check(name(model, case, "eval_prior%d/chain%d" % (prior, k)),
+                  **eval_errors(model, out[k], grad[k], ref_out, ref_grad, prior, N, c["M"], hc.block_bar(model, case),
+                                without=(plain[k], hc.reference(model, case, k, False)[1])))
         # exactness: the value-only call, and each chain alone, return the bits of the batch
         vout, vgrad, vst = ev(P, hyper, prior=prior, want_grad=False)
         assert vgrad is None and vst.tolist() == [0, 0] and np.array_equal(vout, out)

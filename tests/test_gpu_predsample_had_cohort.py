@@ -85,7 +85,8 @@ def predict(ctx, cases, form="full", S=None, draws=None, z="fixed", star=None):
 
 
 # ---- 1. parity with the restatement on each subject alone ------------------------------------------------------------------------------
-PARITY_SETS = {"A": cc.SET_A, "B": cc.SET_B, "C": [c for c in cc.SET_C if c != hc.MINOR], "D": cc.SET_D, "E": cc.SET_E}
+PARITY_SETS = {"A": cc.SET_A, "B": cc.SET_B, "C": [c for c in cc.SET_C if c != hc.MINOR], "D": cc.SET_D, "E": cc.SET_E,
+               "F": cc.SET_F, "G": cc.SET_G, "H": cc.SET_H, "I": cc.SET_I}      # F - H: k_hadc_cross_rows<4, 6, 7>; I: Nmax = 1030
 
 
 @pytest.mark.parametrize("name", sorted(PARITY_SETS))
@@ -400,7 +401,7 @@ from nonstationary_multivariate_gaussian_process_amd import _lib, hadamard
 ctx = _lib.Context(0)
 hyper = hc.hypers()["had"]
 n = 0
-for cases in (cc.SET_D, cc.SET_A, cc.SET_E):
+for cases in (cc.SET_D, cc.SET_A, cc.SET_E, cc.SET_F, cc.SET_G, cc.SET_H):
     subs = cc.subjects(cases)
     ctx.had_set_subjects([c["x"] for c in subs], [c["indx"] for c in subs], [c["y"] for c in subs], M=cases[0][1])
     draws = [pc.subject(c)["draws"] for c in cases]
@@ -428,7 +429,7 @@ def test_repeated_calls_under_poison_give_the_same_bits():
     env.pop("NMGP_PREDSAMPLE_CHUNK", None)
     out = subprocess.run([sys.executable, "-c", POISON_SNIPPET % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}],
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
-    assert out.returncode == 0 and "POISON_OK 6" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+    assert out.returncode == 0 and "POISON_OK 12" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
 
 
 # ---- 8. the drivers ------------------------------------------------------------------------------------------------------------------------------------

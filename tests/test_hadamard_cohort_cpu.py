@@ -1,7 +1,12 @@
 """CPU half of the Hadamard cohort tests (tests/hadamard_cohort_cases.py).
 
 1. The subjects the cohort sets add to the sweep's table meet what tests/test_hadamard_sweep_cpu.py asserts for its own: every label
-   occurs, cond(S) < 1e4 for both chains, the restated gradient within 1e-5 of central differences with and without the priors.
+   occurs, cond(S) < 1e4 for both chains, the restated gradient within 1e-5 of central differences with and without the priors; for
+   the subjects of sets F - I no predictive variance meets the clip.  The two terms of the GPU half's per-block gradient bar
+   (tests/hadamard_cases.py: d_cpu between the restatement and the padded formulation at the set's Nmax, N_s cond(S) eps) are
+   computed, printed and d_cpu held below 1e-9; the prior part g(prior) - g(no prior) of the two LAPACK blockings agrees per block
+   below 1e-7.  Measured: d_cpu <= 8.8e-14 over sets A - I and the three models (2.7e-14 on sets F - H), prior part <= 3.5e-9 (set
+   I; 7.9e-10 on set H); the bars come to 2.2e-16 (N_s = M = 1) ... 4e-11 at (257, 7) ... 8.6e-10 at (1030, 2).
 2. The padded formulation nmgp_had_subjects_eval runs on the device, restated in NumPy: S, y and both GP-prior covariances padded to Nmax
    with identity / zero, the trace over the real observations.  It equals the per-subject restatement on set A: value and likelihood
    1e-12 relative, gradient 1e-10 in ||dg|| / ||g||, the GP-prior entries included (the chain of comparisons is in the test's
@@ -26,12 +31,19 @@ VAL_TOL, GRAD_TOL = 1e-12, 1e-10
 # ---- 1. preconditions of the new subjects ---------------------------------------------------------------------------------------------
 def test_the_sets_are_the_sweeps_subjects_plus_the_new_ones():
     known = set(hc.CASES + [hc.WIDE, hc.MINOR])
-    used = {case for cases in cc.SETS.values() for case in cases}
-    assert used - known == set(cc.NEW_SUBJECTS) and len(cc.NEW_SUBJECTS) == 9
+    used = {case for cases in cc.ALL_SETS.values() for case in cases}
+    assert used - known == set(cc.NEW_SUBJECTS) and len(cc.NEW_SUBJECTS) == len(set(cc.NEW_SUBJECTS)) == 9 + 17
+    assert cc.NEW_SUBJECTS[9:] == cc.SWEEP_SUBJECTS and len(cc.SWEEP_SUBJECTS) == 17
     assert cc.nobs(cc.SET_A) == [128, 63, 2, 64, 65, 127] and cc.nobs(cc.SET_B) == [193, 8, 130] and cc.nobs(cc.SET_D) == [1, 2, 70]
     assert cc.nobs(cc.SET_C) == [321, 65, 256, 3] and cc.nobs(cc.SET_E) == [64, 64]
-    for cases, M in zip((cc.SET_A, cc.SET_B, cc.SET_C, cc.SET_D, cc.SET_E), (2, 8, 3, 1, 5)):
+    assert cc.nobs(cc.SET_F) == [4, 64, 65, 129, 100] and cc.nobs(cc.SET_G) == [65, 6, 128, 127, 192]
+    assert cc.nobs(cc.SET_H) == [129, 7, 63, 257, 130] and cc.nobs(cc.SET_I) == [1030, 1025, 513, 640]
+    for cases, M in zip((cc.SET_A, cc.SET_B, cc.SET_C, cc.SET_D, cc.SET_E, cc.SET_F, cc.SET_G, cc.SET_H, cc.SET_I), (2, 8, 3, 1, 5, 4, 6, 7, 2)):
         assert {case[1] for case in cases} == {M}
+    # sets G and H keep a subject of the resident sweep each; set I stays out of the parametrisations over SETS
+    assert cc.SET_G[0] in hc.CASES and cc.SET_H[0] in hc.CASES and sorted(cc.SETS) == list("ABCDEFGH") and sorted(cc.LARGE_SETS) == ["I"]
+    # set I: the trace kernel's second pass (N_s > 1024) for two subjects and not for two, every subject beyond one 512-column panel
+    assert sum(n > 1024 for n in cc.nobs(cc.SET_I)) == 2 and min(cc.nobs(cc.SET_I)) > 512
 
 
 @pytest.mark.parametrize("case", cc.NEW_SUBJECTS, ids=hc.case_id)
@@ -53,6 +65,86 @@ def test_new_subject_meets_the_preconditions(case):
         err = abs(fd - g @ v) / abs(fd)
         print(hc.case_id(case), "prior", prior, "directional derivative", fd, "relative error", err)
         assert err < FD_TOL, (prior, err)
+
+
+@pytest.mark.parametrize("case", cc.SWEEP_SUBJECTS, ids=hc.case_id)
+def test_no_predictive_variance_of_a_sweep_subject_meets_the_clip(case):
+    """sets F - I: every variance before the clip exceeds its chain's sigma2_err, for the restatements of the separable and stationary
+    predictors (hc.predictions) and of the nonseparable one (predsample_had_cases.expected)."""
+    import predsample_had_cases as pc
+    floors = hc.raw_variance_floor(hc.predictions(case), hc.build(case)), pc.raw_variance_floor(pc.expected(case), case)
+    print(hc.case_id(case), "min variance / sigma2_err", floors)
+    assert min(floors) > 1.0, floors
+
+
+def set_nmax(name):
+    return max(cc.nobs(cc.ALL_SETS[name]))
+
+
+@pytest.mark.parametrize("name", sorted(cc.ALL_SETS))
+def test_block_bars_rest_on_two_cpu_references(name):
+    """The per-block bar of the GPU half, min(GRAD_TIGHT, max(100 d_cpu, N_s cond(S) eps)) (tests/hadamard_cases.py): both terms come
+    from the CPU alone.  d_cpu, the worst block between the per-subject restatement and the padded formulation at the set's Nmax, stays
+    below GRAD_TIGHT / 10, so the two references determine every block an order below the loosest bar."""
+    for case in cc.ALL_SETS[name]:
+        d, stable = hc.block_bar_terms("had", case, set_nmax(name))
+        print("set", name, hc.case_id(case), "had d_cpu", d, "N cond(S) eps", stable, "bar", hc.block_bar("had", case, set_nmax(name)))
+        assert d < hc.GRAD_TIGHT / 10, (case, d)
+        assert 0.0 < hc.block_bar("had", case, set_nmax(name)) <= hc.GRAD_TIGHT
+
+
+def single_observation_gradient_longdouble(model, chain):
+    """d NegLog / d pars without the priors at the subject (1, 1, interleaved) in closed form, in np.longdouble:
+    S = (K0 + jitter) L^2 + sigma2 with K0 = exp(tilde_sigma)^2 ("sep") or 1 ("had"), G = 1/2 (y^2 / S^2 - 1 / S); the lengthscale
+    has no likelihood gradient at one observation."""
+    LD = np.longdouble
+    c = hc.build((1, 1, "interleaved"))
+    p, y = [LD(v) for v in c["pars"][model][chain]], LD(c["y"][0])
+    tl, ts, L, tse = p if model == "sep" else (p[0], LD(0), p[1], p[2])
+    k0, s2, jitter = np.exp(ts) ** 2, np.exp(tse), LD(1e-6)
+    S = (k0 + jitter) * L * L + s2
+    G = LD(0.5) * ((y / S) ** 2 - 1 / S)
+    g = [LD(0)] + ([2 * G * k0 * L * L] if model == "sep" else []) + [2 * G * (k0 + jitter) * L, s2 * G]
+    return -np.array(g, dtype=LD)
+
+
+@pytest.mark.parametrize("model", ["had", "sep"])
+def test_the_single_observation_subject_has_bars_from_a_longdouble_reference(model):
+    """At N_s = M = 1 the restatement and the padded formulation run the same scalar operations: d_cpu = 0 and the rule's bar is one
+    eps, below the restatement's own distance from the closed form in np.longdouble.  hadamard_cases.BLOCK_BARS holds ten times that
+    distance for the blocks where it is not 0; every other block of the subject keeps the rule's bar."""
+    case = (1, 1, "interleaved")
+    assert hc.block_bar_terms(model, case, 70) == (0.0, hc.MACHINE_EPS) == hc.block_bar_terms(model, case)
+    tabs = []
+    for k in (0, 1):
+        ld = single_observation_gradient_longdouble(model, k)
+        ref = hc.reference(model, case, k, False)[1]
+        assert np.allclose(ref, ld.astype(np.float64), rtol=1e-14, atol=0.0)              # the closed form IS the restatement's objective
+        floor = 1e-3 * np.sqrt(np.sum(ld * ld))
+        tabs.append({name: float(np.sqrt(np.sum((ref[sl] - ld[sl]) ** 2)) / max(np.sqrt(np.sum(ld[sl] ** 2)), floor))
+                     for name, sl in __import__("objective_cases").blocks(*hc.layout(model, 1, 1))})
+    for name in tabs[0]:
+        measured = max(t[name] for t in tabs)
+        entry = hc.BLOCK_BARS.get(hc.layout(model, 1, 1) + (name,))
+        print(model, name, "restatement against np.longdouble", measured, "bar", entry)
+        if entry is None:
+            assert 10.0 * measured <= hc.MACHINE_EPS, (name, measured)
+        else:
+            assert 10.0 * measured <= entry <= 5e-15, (name, measured, entry)
+    assert [k for k in hc.BLOCK_BARS if k[1:3] != (1, 1)] == []
+
+
+@pytest.mark.parametrize("name", sorted(cc.ALL_SETS))
+def test_prior_part_is_determined_block_by_block(name):
+    """g(prior) - g(no prior), what the GPU half compares block by block at 1e-5 with the priors on: the two LAPACK blockings of the
+    reference (the subject alone, and padded to the set's Nmax) agree per block below PRIOR_PART_REFERENCE = 1e-7."""
+    worst = 0.0
+    for case in cc.ALL_SETS[name]:
+        for k in (0, 1):
+            tab = hc.block_table(hc.prior_part("had", case, k, set_nmax(name)), hc.prior_part("had", case, k), "had", case[0], case[1])
+            worst = max(worst, max(tab.values()))
+            assert max(tab.values()) < hc.PRIOR_PART_REFERENCE, (case, k, tab)
+    print("set", name, "had prior part, alone against padded: worst block", worst)
 
 
 # ---- 2. the padded formulation ---------------------------------------------------------------------------------------------------------

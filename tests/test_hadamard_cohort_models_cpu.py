@@ -3,7 +3,7 @@ tests/hadamard_cohort_model_cases.py).
 
 1. The subjects the cohort sets add to the sweep's table meet, for both models, what tests/test_hadamard_cohort_cpu.py asserts for the
    nonseparable one: cond(S) below COND_MAX for both chains, the restated gradient within FD_TOL of central differences with and
-   without the priors.
+   without the priors; the two terms of the GPU half's per-block gradient bar and the prior part of the separable gradient, as there.
 2. The padded formulations nmgp_hads_subjects_eval / nmgp_hadst_subjects_eval run on the device, restated in NumPy: S, y and (sep) both
    GP-prior covariances padded to Nmax with identity / zero, the trace over the real observations, the label reduction and the adjoint
    sums over the real observations, N_s log 2 pi.  They equal the per-subject restatements on set A: value and likelihood 1e-12
@@ -47,6 +47,33 @@ def test_new_subject_meets_the_preconditions(case, model):
         err = abs(fd - g @ v) / abs(fd)
         print(model, hc.case_id(case), "prior", prior, "directional derivative", fd, "relative error", err)
         assert err < FD_TOL, (prior, err)
+
+
+@pytest.mark.parametrize("model", mc.MODELS)
+@pytest.mark.parametrize("name", sorted(cc.ALL_SETS))
+def test_block_bars_rest_on_two_cpu_references(name, model):
+    """tests/test_hadamard_cohort_cpu.py's test of the same name for the two models: d_cpu (sta: with the priors too) below
+    GRAD_TIGHT / 10, both terms of the GPU half's per-block bar printed."""
+    Nmax = max(cc.nobs(cc.ALL_SETS[name]))
+    for case in cc.ALL_SETS[name]:
+        d, stable = hc.block_bar_terms(model, case, Nmax)
+        print("set", name, hc.case_id(case), model, "d_cpu", d, "N cond(S) eps", stable, "bar", hc.block_bar(model, case, Nmax))
+        assert d < hc.GRAD_TIGHT / 10, (case, d)
+        assert 0.0 < hc.block_bar(model, case, Nmax) <= hc.GRAD_TIGHT
+
+
+@pytest.mark.parametrize("name", sorted(cc.ALL_SETS))
+def test_prior_part_is_determined_block_by_block(name):
+    """sep: g(prior) - g(no prior) of the restatement alone against the padded formulation at the set's Nmax, two LAPACK blockings of
+    the prior factors: per block below PRIOR_PART_REFERENCE = 1e-7 (sta has no GP prior: its gradient with the priors is held to the
+    tight bar whole)."""
+    Nmax, worst = max(cc.nobs(cc.ALL_SETS[name])), 0.0
+    for case in cc.ALL_SETS[name]:
+        for k in (0, 1):
+            tab = hc.block_table(hc.prior_part("sep", case, k, Nmax), hc.prior_part("sep", case, k), "sep", case[0], case[1])
+            worst = max(worst, max(tab.values()))
+            assert max(tab.values()) < hc.PRIOR_PART_REFERENCE, (case, k, tab)
+    print("set", name, "sep prior part, alone against padded: worst block", worst)
 
 
 # ---- 2. the padded formulations --------------------------------------------------------------------------------------------------------
