@@ -206,7 +206,10 @@ int nmgp_hadst_subjects_eval(nmgp_ctx* ctx, const double* pars /*[B,T+3]*/, int 
  *            *_subjects_eval's, bit for bit, failing rows included.  Positions, gradients and a per-chain `bad` flag stay on the
  *            device; model, hyper, prior and chains_per_subject are fixed until end.  A second begin replaces the first.
  *   set_mass kind 0: identity (the default after begin); kind 1: minv [B, Pmax] = diag(M^-1) per chain row in the padded layout, of
- *            which only the real slots are read; NMGP_E_SHAPE unless they are finite and > 0 (the mass then stays what it was).
+ *            which only the real slots are read; NMGP_E_SHAPE unless they are finite and > 0; kind 2 (minv NULL): the PRIOR-FACTOR
+ *            METRIC M^-1 = L_blk,s L_blk,s^T of the begun model and hyper-parameters, with the set's cached per-subject factors
+ *            (below); NMGP_E_UNSUPPORTED for the stationary model, which has no GP prior; any other kind: NMGP_E_SHAPE.  After a
+ *            refusal the mass stays what it was.
  *   traj     nsteps leapfrog steps with step size eps[s] for every chain of subject s, momenta p0 [B, Pmax], one value + gradient
  *            evaluation per step (the chunks of the evaluation entries under NMGP_HAD_BATCH_SLAB_GB) and ONE synchronisation at the
  *            end.  Returns the end point q1, p1 (or NULL), the kinetic energy there kin1 [B] = 1/2 sum over the real slots of
@@ -219,7 +222,24 @@ int nmgp_hadst_subjects_eval(nmgp_ctx* ctx, const double* pars /*[B,T+3]*/, int 
  * own: every other entry of the context may be called between begin and traj.  NMGP_E_STATE without a set or without begin (a
  * replaced or cleared set included); NMGP_E_SHAPE for a bad model, B != S * chains_per_subject, chains_per_subject < 1, nsteps < 1 or
  * an eps[s] that is not finite and positive; NMGP_E_UNSUPPORTED under NMGP_CHOL=rocsolver.  An API-level failure inside traj puts the
- * start state back and demands a new begin. */
+ * start state back and demands a new begin.
+ *
+ * Under kind 2 the trajectory runs in the whitened coordinates of drivers.PriorMetric at rank 0 (csrc/nmgp_metric.hip):
+ *   L_blk,s = blockdiag(chol Sigma_l,s, chol Sigma_L,s per stride-T column of L_vecs, 1)    nonseparable
+ *           = blockdiag(chol Sigma_l,s, chol Sigma_sigma,s, c I_T, 1)                        separable (c: float32-rounded hyper[8])
+ * on the real slots of subject s (factors of RBF(x_s; hyper[1], hyper[2]) + 1e-6 I and of hyper[4], hyper[5]).  p0 is the WHITENED
+ * start momentum (standard normals in the real slots; padded slots are not read), a step is
+ *   kick   u -= (kick eps_s) L_blk,s^T g   (skipped for bad chains)        drift   q += eps_s L_blk,s u
+ * -- two masked triangular mat-vecs, no solve, no [P, P] matrix, nothing stored per chain -- p1 is the whitened end momentum (+0.0 in
+ * padded slots) and kin1 = 1/2 sum over the real slots of p1^2.  commit, end, the chunking, the single synchronisation, the failure
+ * semantics and the independence of a chain's bits are unchanged.
+ *
+ * nmgp_had_subjects_prior_apply: out [B, Pmax] = L_blk,s in (trans 0: whitened -> parameter coordinates, without the prior mean) or
+ * L_blk,s^T in (trans 1: a gradient -> whitened coordinates) for the B = S * chains_per_subject padded host rows of the set, model
+ * NMGP_HAD_MODEL_NONSEP (hyper[8]) or _SEP (hyper[9]) -- the cohort counterpart of nmgp_svc_batch_prior_apply / nmgp_sep_prior_apply.
+ * It needs a set but no begun trajectory.  Padded slots of `in` are never read; padded slots of `out` are +0.0.  NMGP_E_STATE without
+ * a set; NMGP_E_SHAPE for B != S * chains_per_subject, chains_per_subject < 1 or a bad model; NMGP_E_UNSUPPORTED for the stationary
+ * model and under NMGP_CHOL=rocsolver. */
 #define NMGP_HAD_MODEL_NONSEP 0
 #define NMGP_HAD_MODEL_SEP    1
 #define NMGP_HAD_MODEL_STA    2
@@ -231,6 +251,8 @@ int nmgp_had_subjects_traj(nmgp_ctx* ctx, const double* eps /*[S]*/, int nsteps,
                            double* U1 /*[B]*/, int* failed /*[B]*/);
 int nmgp_had_subjects_traj_commit(nmgp_ctx* ctx, const int* accept /*[B]*/);
 int nmgp_had_subjects_traj_end(nmgp_ctx* ctx);
+int nmgp_had_subjects_prior_apply(nmgp_ctx* ctx, int model, const double* hyper, int trans, const double* in /*[B,Pmax]*/, int B,
+                                  int chains_per_subject, double* out /*[B,Pmax]*/);
 
 /* MAP and posterior-draw prediction for the set under the two models.  Both entries follow nmgp_predsample_had_subjects in every
  * convention not named here: B = S * draws_per_subject rows, row s * draws_per_subject + h is draw h of subject s; xs [S, Smax] with

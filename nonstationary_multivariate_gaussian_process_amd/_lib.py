@@ -96,6 +96,7 @@ SIGNATURES = {
     "nmgp_had_subjects_traj": (I, [V, P, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_had_subjects_traj_commit": (I, [V, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_had_subjects_traj_end": (I, [V]),
+    "nmgp_had_subjects_prior_apply": (I, [V, I, P, I, P, I, I, P]),
     "nmgp_predsample_had_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
                                          ctypes.POINTER(ctypes.c_int)]),
     "nmgp_predsample_hads_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
@@ -971,8 +972,15 @@ class Context:
         self._cohort_traj = pars.shape
         return out, status
 
-    def had_subjects_traj_set_mass(self, minv=None):
-        """None: identity; else diag(M^-1) per chain row [B, Pmax] in the padded layout (only the real slots are read; > 0 there)."""
+    def had_subjects_traj_set_mass(self, minv=None, prior=False):
+        """None: identity; else diag(M^-1) per chain row [B, Pmax] in the padded layout (only the real slots are read; > 0 there).
+        ``prior=True``: the prior-factor metric of the begun model and hyper-parameters (kind 2; not for the stationary model) --
+        ``had_subjects_traj`` then takes and returns WHITENED momenta."""
+        if prior:
+            if minv is not None:
+                raise NmgpError("prior=True takes no minv")
+            self.check(self.lib.nmgp_had_subjects_traj_set_mass(self.h, 2, None))
+            return
         if minv is None:
             self.check(self.lib.nmgp_had_subjects_traj_set_mass(self.h, 0, None))
             return
@@ -995,6 +1003,28 @@ class Context:
         self.check(self.lib.nmgp_had_subjects_traj(self.h, ptr(eps), int(nsteps), ptr(p0), ptr(q1), ptr(p1), ptr(kin1), ptr(U1),
                                                    failed.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return q1, p1, kin1, U1, failed.astype(bool)
+
+    def had_subjects_prior_apply(self, model, hyper, v, trans=False, chains_per_subject=1):
+        """``L_blk,s v`` (or ``L_blk,s^T v``) for the padded rows v [B = S * chains_per_subject, Pmax] of the set under ``model`` "non"
+        or "sep": the block-diagonal of the set's cached GP-prior Cholesky factors of subject s (``nmgp_had_subjects_prior_apply``).
+        Padded slots of v are never read; those of the result are +0.0."""
+        if model not in self._COHORT_TRAJ_MODELS:
+            raise NmgpError("model must be one of 'non', 'sep', 'sta'; got %r" % (model,))
+        code, nhyper, _, plen, what = self._COHORT_TRAJ_MODELS[model]
+        v = as_f64(v)
+        if v.ndim == 1:
+            v = v[None]
+        cohort = getattr(self, "_cohort", None)
+        if v.ndim != 2 or (cohort is not None and v.shape[1] != plen(cohort[1], cohort[2] * (cohort[2] + 1) // 2)):
+            raise NmgpError("vectors must be [B, %s%s], got %s"
+                            % (what, "" if cohort is None else " = %d" % plen(cohort[1], cohort[2] * (cohort[2] + 1) // 2), v.shape))
+        hyper = as_f64(hyper).reshape(-1)
+        if hyper.shape[0] != nhyper:
+            raise NmgpError("hyper must hold %d entries for model %r, got %d" % (nhyper, model, hyper.shape[0]))
+        out = np.empty_like(v)
+        self.check(self.lib.nmgp_had_subjects_prior_apply(self.h, code, ptr(hyper), int(bool(trans)), ptr(v), int(v.shape[0]),
+                                                          int(chains_per_subject), ptr(out)))
+        return out
 
     def had_subjects_traj_commit(self, accept):
         acc = np.ascontiguousarray(np.asarray(accept).astype(np.int32))

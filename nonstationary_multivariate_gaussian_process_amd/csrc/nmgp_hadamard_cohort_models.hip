@@ -431,6 +431,7 @@ struct CohNon {
     static constexpr int WIDTH = 5;
     static constexpr bool GP_PRIORS = true;
     static constexpr const char* NOUN = "Hadamard cohort";
+    static constexpr int METRIC_LAYOUT = 0;       // the layout of prior_trmm_cohort (nmgp_metric.hip)
     static size_t P(int N, int T) { return (size_t)N * (1 + T) + 1; }
     static size_t part_width(int M) { return M + 1; }
     template <class Take>
@@ -482,6 +483,7 @@ struct CohSep {
     static constexpr int WIDTH = 6;
     static constexpr bool GP_PRIORS = true;
     static constexpr const char* NOUN = "separable Hadamard cohort";
+    static constexpr int METRIC_LAYOUT = 1;
     static size_t P(int N, int T) { return (size_t)2 * N + T + 1; }
     static size_t part_width(int M) { return M + 2; }
     template <class Take>
@@ -534,6 +536,7 @@ struct CohSta {
     static constexpr int WIDTH = 5;
     static constexpr bool GP_PRIORS = false;
     static constexpr const char* NOUN = "stationary Hadamard cohort";
+    static constexpr int METRIC_LAYOUT = -1;      // no GP prior: no prior-factor metric
     static size_t P(int, int T) { return (size_t)T + 3; }
     static size_t part_width(int M) { return M + 2; }
     template <class Take>
@@ -818,6 +821,38 @@ void cohm_kick_drift(nmgp_ctx* c, double kick, int drift, int first) {
     }
 }
 
+// The two products of a leapfrog step under the PRIOR-FACTOR METRIC (mass kind 2; k_prior_trmm_coh, nmgp_metric.hip), over all B rows,
+// with the set's cached per-subject factors of the trajectory's hyper-parameters -- the trajectory holds no copy of a factor:
+//   kick   u -= (kick eps_s) L_blk,s^T g   skipped for bad chains; the first one writes +0.0 to the padded slots of u
+//   drift  q += eps_s L_blk,s u            sets qbad where a real slot of q becomes non-finite
+// ht_p carries the whitened momentum u; the kinetic energy is k_hadc_hmc_kinetic's without minv.
+template <class Model>
+void cohm_metric_product(nmgp_ctx* c, const PriorFactor* p0, const PriorFactor* p1, bool kick_not_drift, double kick, int first) {
+    if constexpr (Model::GP_PRIORS) {
+        const int N = c->hc_Nmax;
+        const double cscale = Model::METRIC_LAYOUT == 1 ? (double)(float)c->ht_hyper[8] : 1.0;
+        if (kick_not_drift)
+            prior_trmm_cohort(c->stream, Model::METRIC_LAYOUT, true, p0->L, p0->ld, (long long)p0->ld * N, p1->L, p1->ld,
+                              (long long)p1->ld * N, c->ht_g, c->ht_p, c->hc_nobs, c->ht_eps, c->ht_cps, N, c->hc_T, (long long)c->ht_P,
+                              c->ht_B, kick, 2, ht_bad(c), nullptr, first, cscale);
+        else
+            prior_trmm_cohort(c->stream, Model::METRIC_LAYOUT, false, p0->L, p0->ld, (long long)p0->ld * N, p1->L, p1->ld,
+                              (long long)p1->ld * N, c->ht_p, c->ht_q, c->hc_nobs, c->ht_eps, c->ht_cps, N, c->hc_T, (long long)c->ht_P,
+                              c->ht_B, 1.0, 1, nullptr, ht_qbad(c), 0, cscale);
+    }
+}
+
+// a kick (and, if drift, the drift after it) under the trajectory's mass
+template <class Model>
+void cohm_step(nmgp_ctx* c, const PriorFactor* p0, const PriorFactor* p1, double kick, int drift, int first) {
+    if (c->ht_mass != 2) {
+        cohm_kick_drift<Model>(c, kick, drift, first);
+        return;
+    }
+    cohm_metric_product<Model>(c, p0, p1, true, kick, first);
+    if (drift) cohm_metric_product<Model>(c, p0, p1, false, 1.0, 0);
+}
+
 // One value+gradient evaluation of the resident positions, chunk by chunk (the chunks of cohm_subjects_eval): positions into the slab,
 // the enqueue half, gradient rows out, status and potential out.  No host synchronisation: the slab's reuse by the next chunk is
 // ordered by the stream.
@@ -903,6 +938,14 @@ template <class Model>
 int cohm_subjects_traj_set_mass(nmgp_ctx* c, int kind, const double* minv) {
     const int N = c->hc_Nmax, T = c->hc_T, B = c->ht_B;
     const size_t P = c->ht_P;
+    if (kind == 2) {
+        if constexpr (!Model::GP_PRIORS)
+            return nmgp_fail(c, NMGP_E_UNSUPPORTED, "the stationary model has no GP prior: no prior-factor metric (kind 2)");
+        else {
+            PriorFactor *p0 = nullptr, *p1 = nullptr;      // (cached by begin; a failure here leaves the mass as it was)
+            NMGP_TRY(nmgp_hadc_priors(c, c->ht_hyper, &p0, &p1));
+        }
+    }
     if (kind == 1)
         for (int z = 0; z < B; ++z) {
             const int Ns = c->hc_nobs_h[z / c->ht_cps];
@@ -930,6 +973,9 @@ int cohm_subjects_traj(nmgp_ctx* c, const double* eps, int nsteps, const double*
     const int B = c->ht_B;
     const size_t P = c->ht_P, bytes = (size_t)B * P * sizeof(double);
     hipStream_t s = c->stream;
+    PriorFactor *f0 = nullptr, *f1 = nullptr;                 // kind 2: the set's factors, resolved before anything of the state is touched
+    if constexpr (Model::GP_PRIORS)                           // (no look-up inside the trajectory grows the cache)
+        if (c->ht_mass == 2) NMGP_TRY(nmgp_hadc_priors(c, c->ht_hyper, &f0, &f1));
     HIP_TRY(c, hipMemcpyAsync(c->ht_eps, eps, (size_t)c->hc_S * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(c->ht_p, p0, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(c->ht_q0, c->ht_q, bytes, hipMemcpyDeviceToDevice, s));
@@ -937,11 +983,11 @@ int cohm_subjects_traj(nmgp_ctx* c, const double* eps, int nsteps, const double*
     HIP_TRY(c, hipMemcpyAsync(ht_bad0(c), ht_bad(c), (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(ht_failed(c), ht_bad(c), (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));   // bad at the start: failed
     HIP_TRY(c, hipMemsetAsync(ht_qbad(c), 0, (size_t)B * sizeof(int), s));
-    cohm_kick_drift<Model>(c, 0.5, 1, 1);
+    cohm_step<Model>(c, f0, f1, 0.5, 1, 1);
     for (int step = 0; step < nsteps; ++step) {
         if (int rc = cohm_traj_eval<Model>(c)) return cohm_traj_abort(c, rc);
         const bool last = step == nsteps - 1;
-        cohm_kick_drift<Model>(c, last ? 0.5 : 1.0, last ? 0 : 1, 0);
+        cohm_step<Model>(c, f0, f1, last ? 0.5 : 1.0, last ? 0 : 1, 0);
     }
     if (kin1)
         NMGP_LAUNCH((k_hadc_hmc_kinetic<Model>), dim3(B), dim3(256), 0, s, c->ht_p, c->ht_mass == 1 ? c->ht_minv : nullptr, c->hc_nobs,
@@ -1044,10 +1090,40 @@ extern "C" int nmgp_had_subjects_traj_begin(nmgp_ctx* c, int model, const double
 extern "C" int nmgp_had_subjects_traj_set_mass(nmgp_ctx* c, int kind, const double* minv) {
     if (!c) return NMGP_E_NULL;
     NMGP_TRY(cohm_traj_require(c));
-    if (kind < 0 || kind > 1) return nmgp_fail(c, NMGP_E_SHAPE, "mass matrix kind must be 0 (identity) or 1 (diagonal per chain row)");
+    if (kind < 0 || kind > 2)
+        return nmgp_fail(c, NMGP_E_SHAPE, "mass matrix kind must be 0 (identity), 1 (diagonal per chain row) or 2 (prior-factor metric)");
     if (kind == 1 && !minv) return nmgp_fail(c, NMGP_E_NULL, "minv must not be NULL");
     HIP_TRY(c, hipSetDevice(c->device));
     COHM_MODEL_SWITCH(c->ht_model, cohm_subjects_traj_set_mass<MODEL>(c, kind, minv));
+}
+
+// out = op(L_blk,s) in for the B padded rows of the set (mode 0 of k_prior_trmm_coh): see include/nmgp.h
+extern "C" int nmgp_had_subjects_prior_apply(nmgp_ctx* c, int model, const double* hyper, int trans, const double* in, int B,
+                                             int chains_per_subject, double* out) {
+    if (!c) return NMGP_E_NULL;
+    if (!hyper || !in || !out) return nmgp_fail(c, NMGP_E_NULL, "hyper/in/out must not be NULL");
+    if (c->hc_S <= 0) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_subjects must be called first");
+    if (model < 0 || model > 2) return nmgp_fail(c, NMGP_E_SHAPE, "model = %d must be 0 (nonseparable), 1 (separable) or 2 (stationary)", model);
+    if (model == NMGP_HAD_MODEL_STA) return nmgp_fail(c, NMGP_E_UNSUPPORTED, "the stationary model has no GP prior: no prior factors to apply");
+    if (c->chol_algo != 1)
+        return nmgp_fail(c, NMGP_E_UNSUPPORTED, "the Hadamard entries run on the custom factorisation only (riding rows)");
+    if (chains_per_subject < 1 || (long long)B != (long long)c->hc_S * chains_per_subject)
+        return nmgp_fail(c, NMGP_E_SHAPE, "B = %d must be %d subjects x chains_per_subject = %d", B, c->hc_S, chains_per_subject);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->hc_Nmax, T = c->hc_T;
+    const size_t P = model == 0 ? CohNon::P(N, T) : CohSep::P(N, T), n = (size_t)B * P;
+    PriorFactor *p0 = nullptr, *p1 = nullptr;
+    NMGP_TRY(nmgp_hadc_priors(c, hyper, &p0, &p1));
+    double *din = nullptr, *dout = nullptr;
+    NMGP_TRY(nmgp_scratch_get(c, 3, n, &din));
+    NMGP_TRY(nmgp_scratch_get(c, 4, n, &dout));
+    HIP_TRY(c, hipMemcpyAsync(din, in, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    prior_trmm_cohort(c->stream, model, trans != 0, p0->L, p0->ld, (long long)p0->ld * N, p1->L, p1->ld, (long long)p1->ld * N, din, dout,
+                      c->hc_nobs, nullptr, chains_per_subject, N, T, (long long)P, B, 1.0, 0, nullptr, nullptr, 1,
+                      model == 1 ? (double)(float)hyper[8] : 1.0);
+    HIP_TRY(c, hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return nmgp_take_launch_error(c);
 }
 
 extern "C" int nmgp_had_subjects_traj(nmgp_ctx* c, const double* eps, int nsteps, const double* p0, double* q1, double* p1,

@@ -464,6 +464,12 @@ void prior_trmm(hipStream_t s, bool trans, const double* L0, int ld0, long long 
                 const double* in, double* out, int N, int T, long long P, int B, int cps, double coef, int mode, const int* bad);
 void prior_trmm_sep(hipStream_t s, bool trans, const double* L0, int ld0, const double* L1, int ld1, const double* in, double* out, int N,
                     int T, long long P, int B, double cscale);
+// the same on the padded layouts of a Hadamard subject set (layout 0 nonseparable, 1 separable), rows [0, B) of subject row / cps:
+// every mask from nobs, coef = kick * eps[subject] (eps may be NULL in mode 0), zero_pad: +0.0 into the padded slots of out,
+// qbad (mode 1): set where a real slot of out becomes non-finite
+void prior_trmm_cohort(hipStream_t s, int layout, bool trans, const double* L0, int ld0, long long s0, const double* L1, int ld1,
+                       long long s1, const double* in, double* out, const int* nobs, const double* eps, int cps, int N, int T,
+                       long long P, int B, double kick, int mode, const int* bad, int* qbad, int zero_pad, double cscale);
 void lowrank_proj(hipStream_t s, const double* U, const double* u, double* c, long long P, int r, int B, int cps);
 void lowrank_apply(hipStream_t s, const double* U, const double* wgt, const double* c, const double* in, double* out, long long P,
                    int r, int B, int cps);

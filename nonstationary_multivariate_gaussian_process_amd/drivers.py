@@ -1393,8 +1393,8 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
     """Lock-step HMC for a cohort of ragged Hadamard subjects, shared by the three models: the buckets, sets, contexts and pack /
     unpack hooks of :class:`_HadamardCohortLoop`, :class:`LockStepHMC`'s arithmetic on the rows of the entry's padded layout with a
     step size per subject.  ``init_positions[s]`` ``[k, P_s]`` (the same k for every subject); ``step_size`` a scalar or ``[S]``;
-    ``mass`` None or a list of ``diag(M)`` ``[P_s]`` per subject; ``step_jitter`` as :class:`BatchedHMC` (one factor per iteration
-    for all subjects, from a generator of its own).  Chain k of subject s draws from ``default_rng(seed + s k_total + k)`` in
+    ``mass`` None, a list of ``diag(M)`` ``[P_s]`` per subject, or ``"prior"`` (below); ``step_jitter`` as :class:`BatchedHMC` (one
+    factor per iteration for all subjects, from a generator of its own).  Chain k of subject s draws from ``default_rng(seed + s k_total + k)`` in
     :class:`HMCSampler`'s order -- ``P_s`` standard normals of the REAL length, then the uniform of the accept test -- so a subject's
     draws do not depend on who else is in the cohort and equal those of the per-subject sampler with ``seed + s k_total``.
 
@@ -1403,9 +1403,44 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
     ``device_resident=False``: the host loop over ``*_subjects_eval`` that DEFINES the arithmetic -- padded momentum is 0, the
     kinetic energy is ``0.5 * (p * v).sum()`` over the real slots of a row; the resident loop with ``device_kinetic=False``
     reproduces it bit for bit.  ``device_kinetic=True`` takes the end point's kinetic energy from the device and 1/2 |z|^2 for the
-    start.  ``evaluators``: one callable per bucket, padded rows -> ``(out, grad, status)``, instead of contexts (host loop only)."""
+    start.  ``evaluators``: one callable per bucket, padded rows -> ``(out, grad, status)``, instead of contexts (host loop only).
+
+    ``mass="prior"`` (nonseparable and separable model; the stationary one has no GP prior: ``ValueError``): the PRIOR-FACTOR METRIC
+    ``M^-1 = L_blk,s L_blk,s^T`` of :class:`PriorMetric` at rank 0, per subject, ``L_blk,s`` the block diagonal of the Cholesky factors
+    of the subject's GP priors (``nmgp_had_subjects_traj_set_mass`` kind 2).  The chains' streams and their order are unchanged, so the
+    ``P_s`` normals z ARE the whitened momentum: ``K0 = 1/2 |z|^2``, a step is ``u -= c eps_s L_blk,s^T g``, ``q += eps_s L_blk,s u``,
+    and ``K1 = 1/2 |u1|^2`` over the real slots.  ``step_size`` is then a step in WHITENED coordinates, where the prior is N(0, I):
+    O(0.1), not the O(1e-4) the identity mass needs.  The host loop (``device_resident=False``, also with ``evaluators=``) DEFINES
+    this arithmetic with ``L_blk,s`` built in NumPy (:meth:`_prior_factor`); the resident loop agrees with it to a tolerance, NOT bit
+    for bit -- the summation order of a triangular product differs between NumPy's GEMM and the kernel's tiles."""
 
     MODEL = "non"
+
+    @staticmethod
+    def _prior_factor(x, alpha, beta):
+        """chol(RBF(x; alpha, beta) + 1e-6 I) in NumPy, expression by expression the oracle's ``RBF_cov`` (kernels.py:24-43)"""
+        xs = (np.asarray(x, dtype=np.float64) / beta).reshape(-1, 1)
+        xn = (xs ** 2).sum(1).reshape(-1, 1)
+        d = xn + xn.reshape(1, -1) - 2.0 * (xs @ xs.T)
+        return np.linalg.cholesky(np.eye(xs.shape[0]) * 1e-6 + np.exp(-0.5 * d) * alpha ** 2)
+
+    def _metric_apply(self, st, v, trans):
+        """``L_blk,s v`` (``trans``: ``L_blk,s^T v``) on the real slots of the bucket's padded rows; +0.0 in the padded ones"""
+        res = []
+        with np.errstate(invalid="ignore"):
+            rows = self._unpack(np.where(st["mask"], v, 0.0), st["nobs"], self.M, self.k)
+        for (L0, L1), r in zip(st["factors"], rows):
+            N, o = L0.shape[0], np.empty_like(r)
+            A0, A1 = (L0.T, L1.T) if trans else (L0, L1)
+            o[:, :N] = r[:, :N] @ A0.T
+            if self.MODEL == "sep":
+                o[:, N:2 * N] = r[:, N:2 * N] @ A1.T
+                o[:, 2 * N:-1] = float(np.float32(self.hyper[8])) * r[:, 2 * N:-1]
+            else:
+                o[:, N:-1] = np.matmul(A1, r[:, N:-1].reshape(r.shape[0], N, -1)).reshape(r.shape[0], -1)
+            o[:, -1] = r[:, -1]
+            res.append(o)
+        return self._pack(res, st["nobs"], self.M)
 
     def __init__(self, subjects, hyper_pars, init_positions, step_size=1e-4, num_steps_in_leap=20, seed=None, mass=None,
                  step_jitter=0.0, device_resident=True, device_kinetic=False, max_flop_waste=0.5, ctxs=None, evaluators=None):
@@ -1430,6 +1465,11 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
         self.eps = np.full(S, float(eps)) if eps.ndim == 0 else eps.reshape(-1).copy()
         if self.eps.shape[0] != S or not np.all(np.isfinite(self.eps) & (self.eps > 0)):
             raise ValueError("step_size must be a positive scalar or one positive value per subject")
+        self.prior_metric = isinstance(mass, str)
+        if self.prior_metric:
+            if mass != "prior" or self.MODEL == "sta":
+                raise ValueError('mass="prior" is the only named mass, and the stationary model has no GP prior to take it from')
+            mass = None
         if mass is not None and (len(mass) != S or any(np.shape(m) != (v.shape[1],) or np.any(np.asarray(m) <= 0) for m, v in zip(mass, starts))):
             raise ValueError("mass must hold one positive diag(M) [P_s] per subject")
         self.step_jitter = float(step_jitter)
@@ -1458,6 +1498,9 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
                 rows = lambda f: self._pack([np.tile(f(np.asarray(mass[s], dtype=np.float64)), (k, 1)) for s in idx], nb, self.M)
                 st["mchol"] = rows(np.sqrt)
                 st["minv"] = np.where(st["mask"], rows(lambda m: 1.0 / m), 1.0)
+            if self.prior_metric and not self.device_resident:
+                st["factors"] = [(self._prior_factor(subjects[s][0], self.hyper[1], self.hyper[2]),
+                                  self._prior_factor(subjects[s][0], self.hyper[4], self.hyper[5])) for s in idx]
             if evaluators is not None:
                 st["eval"] = evaluators[b]
             else:
@@ -1494,16 +1537,18 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
         """:meth:`LockStepHMC.run`'s trajectory on the bucket's padded rows with a step size per row; padded slots stay as they are"""
         mask, q1, g, U1 = st["mask"], st["q"].copy(), st["g"], st["U"]
         e = eps[:, None]
+        # under the prior metric p is the whitened momentum u: the gradient goes through L_blk^T, the velocity through L_blk
+        white = (lambda a: self._metric_apply(st, a, True)) if self.prior_metric else (lambda a: a)
         with np.errstate(invalid="ignore", over="ignore"):      # (padded slots may hold anything; np.where drops what they give)
-            p1 = np.where(mask, p0 - (0.5 * e) * g, 0.0)
+            p1 = np.where(mask, p0 - (0.5 * e) * white(g), 0.0)
             failed = ~np.isfinite(U1)
             g1 = g
             for step in range(self.L):
-                v = p1 if st["minv"] is None else st["minv"] * p1
+                v = self._metric_apply(st, p1, False) if self.prior_metric else (p1 if st["minv"] is None else st["minv"] * p1)
                 q1 = np.where(mask, q1 + e * v, q1)
                 U1, g1 = self._potential(st["eval"](q1))
                 failed |= ~np.isfinite(U1)
-                p1 = np.where(mask, p1 - (e if step < self.L - 1 else 0.5 * e) * g1, p1)
+                p1 = np.where(mask, p1 - (e if step < self.L - 1 else 0.5 * e) * white(g1), p1)
         return q1, p1, np.where(failed, np.inf, U1), g1, failed
 
     def run(self, sample_size):
@@ -1519,7 +1564,7 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
             if self.device_resident:
                 out, status = st["ctx"].had_subjects_traj_begin(self.MODEL, st["q"], self.hyper, True, k)
                 st["U"], _ = self._potential((out, None, status))
-                st["ctx"].had_subjects_traj_set_mass(st["minv"])
+                st["ctx"].had_subjects_traj_set_mass(st["minv"], prior=self.prior_metric)
             else:
                 st["U"], st["g"] = self._potential(st["eval"](st["q"]))
             st["rows"] = self._rows(st["idx"])
