@@ -254,6 +254,43 @@ int nmgp_had_subjects_traj_end(nmgp_ctx* ctx);
 int nmgp_had_subjects_prior_apply(nmgp_ctx* ctx, int model, const double* hyper, int trans, const double* in /*[B,Pmax]*/, int B,
                                   int chains_per_subject, double* out /*[B,Pmax]*/);
 
+/* ---- device-resident Adam of the cohort (drivers.HadamardCohortMAP / SepCohortMAP / StaCohortMAP with device_resident=True) ----
+ * ONE family for the three models on the set of nmgp_had_set_subjects, next to the trajectories and with allocations of its own: a
+ * begun trajectory and a begun optimiser may coexist on one context, and every other entry may be called between two calls.  model,
+ * rows, Pmax and hyper as in nmgp_had_subjects_traj_begin.
+ *   begin     uploads the start points pars [B, Pmax], zeroes both moments, marks every chain alive, sets t = 0 and stores model,
+ *             hyper, prior and chains_per_subject for the run.  It evaluates nothing.  A second begin replaces the first.
+ *   adam      niters iterations of torch.optim.Adam's update (no weight decay, no amsgrad) back to back, ONE synchronisation at the
+ *             end however many chunks the set needs (the chunks of the evaluation entries under NMGP_HAD_BATCH_SLAB_GB).  Iteration i
+ *             is drivers.LockStepMAP.step: value + gradient at the resident parameters, alive[z] &= (status 0, every real slot of the
+ *             parameters finite, out[0] and out[1] finite), then for the alive chains, on the real slots,
+ *               m = m b1 + (1 - b1) g;  v = v b2 + ((1 - b2) g) g;  pars -= (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+ *             with bc1 = 1 - b1^t, bc2 = 1 - b2^t from the running t, which persists across calls: 5 iterations in one call equal
+ *             2 + 3, bit for bit, and equal the host loop over the model's *_subjects_eval.  out_hist [niters, B, W]: row i holds the
+ *             verbose tuples AT the parameters iteration i started from (what the reference logs as target_value_hist), NaN for a
+ *             chain that is no longer alive; alive [B] as it stands after the call.  A chain that fails is frozen at its parameters
+ *             and stays dead; no other chain notices.
+ *   get_pars  pars [B, Pmax] as they stand on the device.
+ *   end       frees the state (also done by nmgp_had_set_subjects, nmgp_had_clear_subjects and the context).
+ * Padded slots of pars, of the moments and of the set are never read or written (NaN there changes no bit; get_pars returns them as
+ * uploaded).  A chain's bits depend neither on the chunking nor on the other subjects nor on Nmax.  NMGP_E_STATE without a set or
+ * without begin (a replaced or cleared set included); NMGP_E_NULL for a NULL argument; NMGP_E_SHAPE for a bad model,
+ * B != S * chains_per_subject, chains_per_subject < 1, niters < 1, or a history of niters * B * W values above
+ * NMGP_HAD_ADAM_HIST_MAX (2^24 doubles = 128 MiB on the device and in out_hist: at 128 chains that is more than 26000 iterations per
+ * call); NMGP_E_UNSUPPORTED under NMGP_CHOL=rocsolver.  The state is checked before the pointers: adam and get_pars without a begun run
+ * are NMGP_E_STATE whatever else they are given, so a caller that knows of no run may pass NULL buffers.  A refusal leaves the run as
+ * it was, and so does NMGP_E_NOMEM from growing the device history at the start of adam, before anything of the state is touched: the
+ * same call with fewer iterations may follow.  An API-level failure INSIDE adam's iterations (the evaluation's scratch allocation, a
+ * launch or copy error) ends the run: the parameters go back to where the last completed call left them, get_pars still returns
+ * them, every further adam is NMGP_E_STATE until a fresh begin, and the first message is kept. */
+#define NMGP_HAD_ADAM_HIST_MAX (1LL << 24)
+int nmgp_had_subjects_adam_begin(nmgp_ctx* ctx, int model, const double* pars /*[B,Pmax]*/, int B, int chains_per_subject,
+                                 const double* hyper, int prior);
+int nmgp_had_subjects_adam(nmgp_ctx* ctx, int niters, double lr, double beta1, double beta2, double eps,
+                           double* out_hist /*[niters,B,W]*/, int* alive /*[B]*/);
+int nmgp_had_subjects_adam_get_pars(nmgp_ctx* ctx, double* pars /*[B,Pmax]*/);
+int nmgp_had_subjects_adam_end(nmgp_ctx* ctx);
+
 /* MAP and posterior-draw prediction for the set under the two models.  Both entries follow nmgp_predsample_had_subjects in every
  * convention not named here: B = S * draws_per_subject rows, row s * draws_per_subject + h is draw h of subject s; xs [S, Smax] with
  * the table nstar (NULL: all Smax; 0 <= nstar[s] <= Smax); indx_star == NULL: mean / var [B, Smax, M], indx_star [S, Smax]: mean / var

@@ -22,6 +22,7 @@ I, D, P, V = ctypes.c_int, ctypes.c_double, c_double_p, ctypes.c_void_p
 
 NUM_NAN = 1 << 20
 NUM_EIG = (1 << 20) + 1
+HAD_ADAM_HIST_MAX = 1 << 24          # NMGP_HAD_ADAM_HIST_MAX: values of one nmgp_had_subjects_adam call's history (tests compare the two)
 STAGES = ["cov", "chol", "solve", "reduce", "prior", "inverse", "adjoint", "eig", "kronmv", "syrk"]
 
 # name -> (restype, argtypes); must list every function declared in include/nmgp.h
@@ -96,6 +97,10 @@ SIGNATURES = {
     "nmgp_had_subjects_traj": (I, [V, P, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_had_subjects_traj_commit": (I, [V, ctypes.POINTER(ctypes.c_int)]),
     "nmgp_had_subjects_traj_end": (I, [V]),
+    "nmgp_had_subjects_adam_begin": (I, [V, I, P, I, I, P, I]),
+    "nmgp_had_subjects_adam": (I, [V, I, D, D, D, D, P, ctypes.POINTER(ctypes.c_int)]),
+    "nmgp_had_subjects_adam_get_pars": (I, [V, P]),
+    "nmgp_had_subjects_adam_end": (I, [V]),
     "nmgp_had_subjects_prior_apply": (I, [V, I, P, I, P, I, I, P]),
     "nmgp_predsample_had_subjects": (I, [V, P, I, I, P, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), I, P, P, P, P, P,
                                          ctypes.POINTER(ctypes.c_int)]),
@@ -870,12 +875,14 @@ class Context:
         self.check(self.lib.nmgp_had_set_subjects(self.h, ptr(x), indx.ctypes.data_as(ip), ptr(y), nobs.ctypes.data_as(ip),
                                                   x.shape[0], x.shape[1], int(M)))
         self._cohort = (x.shape[0], x.shape[1], int(M))
-        self._cohort_traj = None          # (a new set ends a begun trajectory)
+        self._cohort_traj = None          # (a new set ends a begun trajectory and a begun optimiser)
+        self._cohort_adam = None
 
     def had_clear_subjects(self):
         self.check(self.lib.nmgp_had_clear_subjects(self.h))
         self._cohort = None
         self._cohort_traj = None
+        self._cohort_adam = None
 
     def had_subjects_eval(self, pars, hyper, prior=True, want_grad=False, chains_per_subject=1):
         """B = S * chains_per_subject chains of the cohort in one launch sequence: pars [B, Pmax = Nmax(1+T)+1] in the padded layout
@@ -1036,6 +1043,59 @@ class Context:
     def had_subjects_traj_end(self):
         self.check(self.lib.nmgp_had_subjects_traj_end(self.h))
         self._cohort_traj = None
+
+    # -- device-resident Adam of the cohort (one family for the three models, next to the trajectories) -----------
+    def had_subjects_adam_begin(self, model, pars, hyper, prior=True, chains_per_subject=1):
+        """Starts the device-resident optimiser of the cohort at ``pars`` [B = S * chains_per_subject, Pmax] (the padded layout of the
+        model's ``*_subjects_eval``; ``model`` is "non", "sep" or "sta"): moments zero, every chain alive, t = 0; nothing is
+        evaluated.  Parameters and moments then stay on the device until ``had_subjects_adam_end``."""
+        if model not in self._COHORT_TRAJ_MODELS:
+            raise NmgpError("model must be one of 'non', 'sep', 'sta'; got %r" % (model,))
+        code, nhyper, width, plen, what = self._COHORT_TRAJ_MODELS[model]
+        pars = as_f64(pars)
+        if pars.ndim == 1:
+            pars = pars[None]
+        cohort = getattr(self, "_cohort", None)
+        if pars.ndim != 2 or (cohort is not None and pars.shape[1] != plen(cohort[1], cohort[2] * (cohort[2] + 1) // 2)):
+            raise NmgpError("parameters must be [B, %s%s], got %s"
+                            % (what, "" if cohort is None else " = %d" % plen(cohort[1], cohort[2] * (cohort[2] + 1) // 2), pars.shape))
+        hyper = as_f64(hyper).reshape(-1)
+        if hyper.shape[0] != nhyper:
+            raise NmgpError("hyper must hold %d entries for model %r, got %d" % (nhyper, model, hyper.shape[0]))
+        # The recorded shape changes only when the library's state does.  A refusal (NMGP_E_SHAPE, NMGP_E_STATE, ...) leaves an
+        # earlier run begun on the device, and its shape recorded here: the caller may go on with it.  A failure after the library
+        # has dropped the earlier run (an allocation, the upload) leaves a shape nobody uses: the next call is refused before it writes.
+        self.check(self.lib.nmgp_had_subjects_adam_begin(self.h, code, ptr(pars), pars.shape[0], int(chains_per_subject), ptr(hyper),
+                                                         int(bool(prior))))
+        self._cohort_adam = pars.shape + (width,)
+
+    def had_subjects_adam(self, niters, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+        """``niters`` Adam iterations from the resident state with ONE synchronisation -> (out_hist [niters, B, W]: the verbose
+        tuples at the parameters each iteration started from, NaN rows for chains that are no longer alive; alive [B] bool).  The
+        iteration count behind the bias corrections persists across calls."""
+        shape = getattr(self, "_cohort_adam", None)
+        niters = int(niters)
+        if shape is None:
+            # no run known here: no buffer is handed over at all.  The entry checks the state first (NMGP_E_STATE), and were a run
+            # begun behind this binding's back it would refuse the NULL pointers (NMGP_E_NULL) -- it cannot write either way
+            hist = alive = ap = None
+        else:
+            # (niters < 1 is refused with NMGP_E_SHAPE before anything is written; the buffers are of the run's size all the same)
+            hist, alive = np.empty((max(niters, 1), shape[0], shape[2])), np.zeros(shape[0], dtype=np.int32)
+            ap = alive.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        self.check(self.lib.nmgp_had_subjects_adam(self.h, niters, float(lr), float(beta1), float(beta2), float(eps), ptr(hist), ap))
+        return hist, alive.astype(bool)
+
+    def had_subjects_adam_get_pars(self):
+        """The parameters [B, Pmax] as they stand on the device (padded slots as uploaded)."""
+        shape = getattr(self, "_cohort_adam", None)
+        pars = np.empty(shape[:2]) if shape is not None else None      # (no run known here: no buffer, as in had_subjects_adam)
+        self.check(self.lib.nmgp_had_subjects_adam_get_pars(self.h, ptr(pars)))
+        return pars
+
+    def had_subjects_adam_end(self):
+        self.check(self.lib.nmgp_had_subjects_adam_end(self.h))
+        self._cohort_adam = None
 
     # the three cohort predictors as the binding sees them: C entry, entries of hyper (0: the entry takes no hyper, z or star and
     # returns no starred values), length of a parameter row and its name, starred values per draw and input and their name

@@ -342,6 +342,7 @@ void nmgp_hadc_trace(hipStream_t s, const double* alpha, const double* Sinv, int
 
 void nmgp_had_subjects_free(nmgp_ctx* c) {
     nmgp_had_traj_free(c);     // a begun trajectory belongs to the set
+    nmgp_had_adam_free(c);     // ... and so does a begun optimiser
     if (c->hc_x) hipFree(c->hc_x);
     if (c->hc_y) hipFree(c->hc_y);
     if (c->hc_indx) hipFree(c->hc_indx);

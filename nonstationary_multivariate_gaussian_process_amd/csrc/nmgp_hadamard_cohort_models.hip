@@ -853,25 +853,36 @@ void cohm_step(nmgp_ctx* c, const PriorFactor* p0, const PriorFactor* p1, double
     if (drift) cohm_metric_product<Model>(c, p0, p1, false, 1.0, 0);
 }
 
-// One value+gradient evaluation of the resident positions, chunk by chunk (the chunks of cohm_subjects_eval): positions into the slab,
-// the enqueue half, gradient rows out, status and potential out.  No host synchronisation: the slab's reuse by the next chunk is
-// ordered by the stream.
-template <class Model>
-int cohm_traj_eval(nmgp_ctx* c) {
-    const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T, B = c->ht_B;
-    const size_t P = c->ht_P;
+// One value+gradient evaluation of RESIDENT rows q [B, P], chunk by chunk (the chunks of cohm_subjects_eval): positions into the slab,
+// the enqueue half, then after(b0, nb, s0, cps of the chunk, L, slab) takes what it needs out of the slab (info, scal, the gradient
+// rows at slab + L.o_grad) with work on the stream.  No host synchronisation: the slab's reuse by the next chunk is ordered by the
+// stream.  The trajectories and the optimiser share it.
+template <class Model, class After>
+int cohm_resident_eval(nmgp_ctx* c, const double* q, int B, int cps, const double* hyper, int prior, After after) {
+    const int N = c->hc_Nmax, M = c->hc_M, T = c->hc_T;
+    const size_t P = Model::P(N, T);
     hipStream_t s = c->stream;
     PriorFactor *p0 = nullptr, *p1 = nullptr;
-    if constexpr (Model::GP_PRIORS) NMGP_TRY(nmgp_hadc_priors(c, c->ht_hyper, &p0, &p1));
+    if constexpr (Model::GP_PRIORS) NMGP_TRY(nmgp_hadc_priors(c, hyper, &p0, &p1));
     const size_t per_chain = had_layout<Model>(1, N, M, T, true).total * sizeof(double);
-    return had_for_chunks(c, B, c->ht_cps, per_chain, Model::NOUN, "at Nmax", N, [&](int b0, int nb, int s0, int ccps) {
+    return had_for_chunks(c, B, cps, per_chain, Model::NOUN, "at Nmax", N, [&](int b0, int nb, int s0, int ccps) {
         const HadLayout L = had_layout<Model>(nb, N, M, T, true);
         double* slab;
         NMGP_TRY(nmgp_scratch_get(c, HSL_SLAB, L.total, &slab));
-        const size_t bytes = (size_t)nb * P * sizeof(double);
-        HIP_TRY(c, hipMemcpyAsync(slab + L.o_P, c->ht_q + (size_t)b0 * P, bytes, hipMemcpyDeviceToDevice, s));
-        NMGP_TRY(cohm_enqueue_chunk<Model>(c, L, slab, nb, s0, ccps, c->ht_hyper, c->ht_prior, p0, p1, true));
-        HIP_TRY(c, hipMemcpyAsync(c->ht_g + (size_t)b0 * P, slab + L.o_grad, bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(slab + L.o_P, q + (size_t)b0 * P, (size_t)nb * P * sizeof(double), hipMemcpyDeviceToDevice, s));
+        NMGP_TRY(cohm_enqueue_chunk<Model>(c, L, slab, nb, s0, ccps, hyper, prior, p0, p1, true));
+        return after(b0, nb, s0, ccps, L, slab);
+    });
+}
+
+// the trajectories' evaluation: gradient rows out, status and potential out
+template <class Model>
+int cohm_traj_eval(nmgp_ctx* c) {
+    const size_t P = c->ht_P;
+    hipStream_t s = c->stream;
+    return cohm_resident_eval<Model>(c, c->ht_q, c->ht_B, c->ht_cps, c->ht_hyper, c->ht_prior,
+                                     [&](int b0, int nb, int, int, const HadLayout& L, double* slab) {
+        HIP_TRY(c, hipMemcpyAsync(c->ht_g + (size_t)b0 * P, slab + L.o_grad, (size_t)nb * P * sizeof(double), hipMemcpyDeviceToDevice, s));
         NMGP_LAUNCH(k_hadc_hmc_status, dim3(cdiv(nb, 64)), dim3(64), 0, s, reinterpret_cast<const int*>(slab + L.o_info),
                     slab + L.o_scal, ht_qbad(c) + b0, ht_bad(c) + b0, ht_failed(c) + b0, c->ht_U + b0, nb);
         return 0;
@@ -1026,6 +1037,166 @@ int cohm_traj_require(nmgp_ctx* c) {
     return 0;
 }
 
+// ---- device-resident Adam of the cohort (drivers._HadamardCohortLoop with device_resident=True) --------------------------------------
+// nmgp_svc_batch_adam_step's loop on the padded rows of a subject set, many iterations per call: parameters and moments stay in HBM,
+// an iteration is the chunked evaluation and, per chunk, a status kernel and the masked update on the chunk's own gradient rows in
+// the slab (no gradient leaves it).  The arithmetic is drivers.LockStepMAP.step's, operation for operation, so both give the same bits.
+
+// After a chunk's evaluation, for chunk row z (the pointers are the chunk's): alive[z] &= the evaluation is defined -- the
+// factorisation's status, a real slot of the parameters that went non-finite, a non-finite value: the three tests of
+// cohm_chunk_epilogue / drivers.valid_rows -- then the chain's WIDTH values, or NaN (the host's std::nan("") bits) if it is not alive,
+// into its row of the history.
+__global__ void k_hadc_adam_status(const int* __restrict__ info, const double* __restrict__ scal, const int* __restrict__ qbad,
+                                   int* __restrict__ alive, double* __restrict__ hist, int W, int B) {
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z >= B) return;
+    const double v0 = scal[(size_t)z * 16 + 8], v1 = scal[(size_t)z * 16 + 9];
+    const int a = (alive[z] != 0 && info[z] == 0 && qbad[z] == 0 && isfinite(v0) && isfinite(v1)) ? 1 : 0;
+    alive[z] = a;
+    const double nan_ = __longlong_as_double(0x7ff8000000000000LL);
+    for (int t = 0; t < W; ++t) hist[(size_t)z * W + t] = a ? scal[(size_t)z * 16 + 8 + t] : nan_;
+}
+
+// Chunk rows z0 + blockIdx.y, subject z / cps of the chunk's nobs table: k_adam_step's update, statement for statement (the build has
+// no contraction), on the real slots of the alive chains.  Padded slots of par, m and v are neither read nor written.  An updated real
+// slot that is not finite raises the chain's qbad flag (the NMGP_NUM_NAN test of the next evaluation, as the drift kernel does it).
+template <class Model>
+__global__ __launch_bounds__(256) void k_hadc_adam_step(double* __restrict__ par, const double* __restrict__ g, double* __restrict__ m,
+                                                         double* __restrict__ v, const int* __restrict__ alive, int* __restrict__ qbad,
+                                                         const int* __restrict__ nobs, int cps, int z0, double b1, double omb1,
+                                                         double b2, double omb2, double bc2s, double eps, double step, int N, int T,
+                                                         long long P) {
+    const int z = z0 + blockIdx.y;
+    if (!alive[z]) return;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= P || !Model::real_slot(i, N, nobs[z / cps], T)) return;
+    const size_t o = (size_t)z * P + i;
+    const double gv = g[o];
+    const double t1 = m[o] * b1, t2 = omb1 * gv;
+    const double mn = t1 + t2;
+    const double t3 = v[o] * b2, t4 = omb2 * gv;
+    const double t5 = t4 * gv;
+    const double vn = t3 + t5;
+    const double t6 = sqrt(vn) / bc2s;
+    const double denom = t6 + eps;
+    const double t7 = mn / denom;
+    const double t8 = step * t7;
+    const double pn = par[o] - t8;
+    par[o] = pn;
+    m[o] = mn;
+    v[o] = vn;
+    if (!isfinite(pn)) qbad[z] = 1;          // (every writer stores the same word)
+}
+
+inline int* ha_alive(nmgp_ctx* c) { return c->ha_flags; }
+inline int* ha_qbad(nmgp_ctx* c) { return c->ha_flags + c->ha_B; }
+
+// An API-level failure inside an optimiser call ends the run: the parameters go back to where the call found them (the last completed
+// call's), get_pars still answers, and the next adam demands a fresh begin.  The first failure's message is kept.
+int cohm_adam_abort(nmgp_ctx* c, int rc) {
+    const std::string msg = c->err;
+    hipMemcpyAsync(c->ha_q, c->ha_q0, (size_t)c->ha_B * c->ha_P * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+    hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    c->ha_ended = true;
+    c->err = msg;
+    return rc;
+}
+
+template <class Model>
+int cohm_subjects_adam_begin(nmgp_ctx* c, int model, const double* pars, int B, int cps, const double* hyper, int prior) {
+    const int N = c->hc_Nmax, T = c->hc_T;
+    const size_t P = Model::P(N, T), n = (size_t)B * P;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    nmgp_had_adam_free(c);
+    auto fail = [c](int r) {
+        const std::string msg = c->err;
+        nmgp_had_adam_free(c);
+        c->err = msg;
+        return r;
+    };
+    double** bufs[] = {&c->ha_q, &c->ha_q0, &c->ha_m, &c->ha_v};
+    for (double** b : bufs)
+        if (int r = nmgp_dev_alloc(c, b, n)) return fail(r);
+    if (hipMalloc((void**)&c->ha_flags, 2 * (size_t)B * sizeof(int)) != hipSuccess)
+        return fail(nmgp_fail(c, NMGP_E_NOMEM, "hipMalloc of the optimiser's flags failed"));
+    // [alive = 1 | qbad = a real slot of the start point is not finite]
+    std::vector<int> flags(2 * (size_t)B, 1);
+    for (int z = 0; z < B; ++z)
+        flags[(size_t)B + z] = Model::finite_in(pars + (size_t)z * P, (size_t)N, (size_t)c->hc_nobs_h[z / cps], T) ? 0 : 1;
+    hipStream_t s = c->stream;
+    bool ok = hipMemcpyAsync(c->ha_q, pars, n * sizeof(double), hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemsetAsync(c->ha_m, 0, n * sizeof(double), s) == hipSuccess &&
+              hipMemsetAsync(c->ha_v, 0, n * sizeof(double), s) == hipSuccess &&
+              hipMemcpyAsync(c->ha_flags, flags.data(), flags.size() * sizeof(int), hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipStreamSynchronize(s) == hipSuccess;          // the sources are the caller's and this frame's
+    if (!ok) return fail(nmgp_fail(c, NMGP_E_HIP, "upload of the optimiser's start state failed (%s)", hipGetErrorString(hipGetLastError())));
+    c->ha_model = model;
+    c->ha_B = B;
+    c->ha_cps = cps;
+    c->ha_prior = prior;
+    c->ha_P = P;
+    c->ha_t = 0;
+    c->ha_ended = false;
+    std::copy(hyper, hyper + (model == 0 ? 8 : model == 1 ? 9 : 5), c->ha_hyper);
+    return 0;
+}
+
+// niters iterations from the resident state: per iteration one chunked evaluation with the status kernel and the masked update behind
+// every chunk, ONE synchronisation at the end however many chunks the set needs.  The bias corrections are the host's, from the
+// running t, exactly as nmgp_svc_batch_adam_step computes them.
+template <class Model>
+int cohm_subjects_adam(nmgp_ctx* c, int niters, double lr, double beta1, double beta2, double eps, double* out_hist, int* alive) {
+    constexpr int W = Model::WIDTH;
+    const int B = c->ha_B, N = c->hc_Nmax, T = c->hc_T;
+    const long long P = (long long)c->ha_P;
+    const size_t nh = (size_t)niters * B * W;
+    hipStream_t s = c->stream;
+    if (c->ha_hist_cap < nh) {               // before anything of the state is touched: a refusal here leaves the run as it is
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (c->ha_hist) hipFree(c->ha_hist);
+        c->ha_hist = nullptr;
+        c->ha_hist_cap = 0;
+        NMGP_TRY(nmgp_dev_alloc(c, &c->ha_hist, nh));
+        c->ha_hist_cap = nh;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->ha_q0, c->ha_q, (size_t)B * P * sizeof(double), hipMemcpyDeviceToDevice, s));
+    for (int it = 0; it < niters; ++it) {
+        const long long t = ++c->ha_t;
+        const double bc1 = 1.0 - std::pow(beta1, (double)t);
+        const double bc2s = std::sqrt(1.0 - std::pow(beta2, (double)t));
+        const double step = lr / bc1;
+        double* hist = c->ha_hist + (size_t)it * B * W;
+        const int rc = cohm_resident_eval<Model>(c, c->ha_q, B, c->ha_cps, c->ha_hyper, c->ha_prior,
+                                                 [&](int b0, int nb, int s0, int ccps, const HadLayout& L, double* slab) {
+            NMGP_LAUNCH(k_hadc_adam_status, dim3(cdiv(nb, 64)), dim3(64), 0, s, reinterpret_cast<const int*>(slab + L.o_info),
+                        slab + L.o_scal, ha_qbad(c) + b0, ha_alive(c) + b0, hist + (size_t)b0 * W, W, nb);
+            for (int z0 = 0; z0 < nb; z0 += 65535) {          // the row is a grid dimension
+                const int nz = std::min(65535, nb - z0);
+                NMGP_LAUNCH((k_hadc_adam_step<Model>), dim3((unsigned)((P + 255) / 256), nz), dim3(256), 0, s, c->ha_q + (size_t)b0 * P,
+                            slab + L.o_grad, c->ha_m + (size_t)b0 * P, c->ha_v + (size_t)b0 * P, ha_alive(c) + b0, ha_qbad(c) + b0,
+                            c->hc_nobs + s0, ccps, z0, beta1, 1.0 - beta1, beta2, 1.0 - beta2, bc2s, eps, step, N, T, P);
+            }
+            return 0;
+        });
+        if (rc) return cohm_adam_abort(c, rc);
+    }
+    hipError_t e = hipMemcpyAsync(out_hist, c->ha_hist, nh * sizeof(double), hipMemcpyDeviceToHost, s);       // the history, in one copy
+    if (e == hipSuccess) e = hipMemcpyAsync(alive, ha_alive(c), (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);          // the one synchronisation of the call
+    if (e != hipSuccess)
+        return cohm_adam_abort(c, nmgp_fail(c, NMGP_E_HIP, "the end of the optimiser call failed: %s", hipGetErrorString(e)));
+    if (int rc = nmgp_take_launch_error(c)) return cohm_adam_abort(c, rc);
+    return 0;
+}
+
+// the begun optimiser, or the refusal
+int cohm_adam_require(nmgp_ctx* c) {
+    if (c->hc_S <= 0) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_subjects must be called first");
+    if (c->ha_model < 0) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_subjects_adam_begin must be called first (on the current set)");
+    return 0;
+}
+
 #define COHM_MODEL_SWITCH(model, CALL)                \
     do {                                              \
         switch (model) {                              \
@@ -1034,6 +1205,9 @@ int cohm_traj_require(nmgp_ctx* c) {
             default: { using MODEL = CohSta; return CALL; } \
         }                                             \
     } while (0)
+
+// the width of a model's verbose tuple
+int cohm_width(int model) { COHM_MODEL_SWITCH(model, MODEL::WIDTH); }
 
 }  // namespace
 
@@ -1153,5 +1327,70 @@ extern "C" int nmgp_had_subjects_traj_end(nmgp_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     nmgp_had_traj_free(c);
+    return 0;
+}
+
+// ---- the optimiser family (see include/nmgp.h) ----------------------------------------------------------------------------------------
+void nmgp_had_adam_free(nmgp_ctx* c) {
+    double** bufs[] = {&c->ha_q, &c->ha_q0, &c->ha_m, &c->ha_v, &c->ha_hist};
+    for (double** b : bufs) {
+        if (*b) hipFree(*b);
+        *b = nullptr;
+    }
+    if (c->ha_flags) hipFree(c->ha_flags);
+    c->ha_flags = nullptr;
+    c->ha_model = -1;
+    c->ha_B = c->ha_cps = c->ha_prior = 0;
+    c->ha_P = c->ha_hist_cap = 0;
+    c->ha_t = 0;
+    c->ha_ended = false;
+}
+
+extern "C" int nmgp_had_subjects_adam_begin(nmgp_ctx* c, int model, const double* pars, int B, int chains_per_subject,
+                                            const double* hyper, int prior) {
+    if (!c) return NMGP_E_NULL;
+    if (!pars || !hyper) return nmgp_fail(c, NMGP_E_NULL, "pars/hyper must not be NULL");
+    if (model < 0 || model > 2) return nmgp_fail(c, NMGP_E_SHAPE, "model = %d must be 0 (nonseparable), 1 (separable) or 2 (stationary)", model);
+    if (c->hc_S <= 0) return nmgp_fail(c, NMGP_E_STATE, "nmgp_had_set_subjects must be called first");
+    if (c->chol_algo != 1)
+        return nmgp_fail(c, NMGP_E_UNSUPPORTED, "the Hadamard entries run on the custom factorisation only (riding rows)");
+    if (chains_per_subject < 1 || (long long)B != (long long)c->hc_S * chains_per_subject)
+        return nmgp_fail(c, NMGP_E_SHAPE, "B = %d must be %d subjects x chains_per_subject = %d", B, c->hc_S, chains_per_subject);
+    HIP_TRY(c, hipSetDevice(c->device));
+    COHM_MODEL_SWITCH(model, cohm_subjects_adam_begin<MODEL>(c, model, pars, B, chains_per_subject, hyper, prior));
+}
+
+extern "C" int nmgp_had_subjects_adam(nmgp_ctx* c, int niters, double lr, double beta1, double beta2, double eps, double* out_hist,
+                                      int* alive) {
+    if (!c) return NMGP_E_NULL;
+    NMGP_TRY(cohm_adam_require(c));          // the state first: a caller that knows of no run hands over no buffers
+    if (!out_hist || !alive) return nmgp_fail(c, NMGP_E_NULL, "out_hist/alive must not be NULL");
+    if (c->ha_ended)
+        return nmgp_fail(c, NMGP_E_STATE, "an earlier nmgp_had_subjects_adam failed and ended the run: nmgp_had_subjects_adam_begin must be called again");
+    if (niters < 1) return nmgp_fail(c, NMGP_E_SHAPE, "niters = %d must be positive", niters);
+    const int W = cohm_width(c->ha_model);
+    if ((long long)niters * c->ha_B * W > (long long)NMGP_HAD_ADAM_HIST_MAX)
+        return nmgp_fail(c, NMGP_E_SHAPE, "a history of niters = %d x B = %d x %d values is above NMGP_HAD_ADAM_HIST_MAX = %lld: ask for fewer "
+                         "iterations per call", niters, c->ha_B, W, (long long)NMGP_HAD_ADAM_HIST_MAX);
+    HIP_TRY(c, hipSetDevice(c->device));
+    COHM_MODEL_SWITCH(c->ha_model, cohm_subjects_adam<MODEL>(c, niters, lr, beta1, beta2, eps, out_hist, alive));
+}
+
+extern "C" int nmgp_had_subjects_adam_get_pars(nmgp_ctx* c, double* pars) {
+    if (!c) return NMGP_E_NULL;
+    NMGP_TRY(cohm_adam_require(c));          // (the state first, as in nmgp_had_subjects_adam)
+    if (!pars) return nmgp_fail(c, NMGP_E_NULL, "pars must not be NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(pars, c->ha_q, (size_t)c->ha_B * c->ha_P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int nmgp_had_subjects_adam_end(nmgp_ctx* c) {
+    if (!c) return NMGP_E_NULL;
+    if (c->ha_model < 0) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    nmgp_had_adam_free(c);
     return 0;
 }

@@ -202,6 +202,20 @@ struct nmgp_ctx {
     double* ht_eps = nullptr;   // [S]
     int* ht_flags = nullptr;    // [5, B]: bad (current position), bad0 (before the trajectory), failed, accept, qbad (a real slot of
                                 // the position went non-finite in a drift: the NMGP_NUM_NAN test of the evaluation entries)
+    // device-resident Adam of the cohort (nmgp_had_subjects_adam_*, nmgp_hadamard_cohort_models.hip): a family of its own next to the
+    // trajectories, with its own allocations, so that both may be begun on one context.  ha_model < 0: no optimiser begun.
+    int ha_model = -1, ha_B = 0, ha_cps = 0, ha_prior = 0;
+    bool ha_ended = false;      // an API-level failure ended the run: get_pars still answers, adam demands a fresh begin
+    size_t ha_P = 0;
+    long long ha_t = 0;         // iterations done since begin (Adam's bias corrections come from it)
+    double ha_hyper[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double* ha_q = nullptr;     // [B, Pmax] parameters (padded slots as uploaded)
+    double* ha_q0 = nullptr;    // [B, Pmax] the parameters at the start of the running call
+    double* ha_m = nullptr;     // [B, Pmax] first moments (real slots of the alive chains only)
+    double* ha_v = nullptr;     // [B, Pmax] second moments
+    double* ha_hist = nullptr;  // [niters, B, WIDTH] of the running call
+    size_t ha_hist_cap = 0;     // elements
+    int* ha_flags = nullptr;    // [2, B]: alive, qbad (a real slot of the parameters is non-finite: the NMGP_NUM_NAN test)
     int last_sep_attempts = 0;  // jitter retries the last separable / stationary evaluation needed (0 = the exact covariance)
     bool last_want_grad = false;
     int last_kind = 0;          // 1 svc
@@ -233,6 +247,7 @@ int nmgp_get_batch_prior(nmgp_ctx* c, const double* xs, int S, std::vector<Prior
 void nmgp_sep_subjects_free(nmgp_ctx* c);      // drops the separable subject set (no-op without one)
 void nmgp_had_subjects_free(nmgp_ctx* c);      // drops the Hadamard cohort (no-op without one; nmgp_hadamard_cohort.hip)
 void nmgp_had_traj_free(nmgp_ctx* c);          // ends a begun cohort trajectory (no-op without one; nmgp_hadamard_cohort_models.hip)
+void nmgp_had_adam_free(nmgp_ctx* c);          // ends a begun cohort optimiser (no-op without one; nmgp_hadamard_cohort_models.hip)
 int nmgp_ensure_S(nmgp_ctx* c);
 size_t nmgp_ld(size_t rows);      // leading dimension of a factorisation buffer with `rows` rows
 // Cholesky of the n x n lower triangle (custom gfx950 factorisation or rocSOLVER, per ctx->chol_algo); `extra` rows

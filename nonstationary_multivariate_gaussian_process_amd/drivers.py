@@ -1117,11 +1117,14 @@ class HadamardMAP(_HadamardSubject, LockStepMAP):
 class _HadamardCohortLoop:
     """The cohort MAP loop shared by the three Hadamard models: buckets of similar size (``hadamard.cohort_buckets``), one subject set
     (``nmgp_had_set_subjects``) per bucket on a ``Context`` of its own, held for the whole run, ONE ``*_subjects_eval`` per bucket and
-    Adam iteration, :class:`LockStepMAP`'s update on the rows of the entry's layout.  A model names its hyper-parameter keys, its
+    Adam iteration, :class:`LockStepMAP`'s update on the rows of the entry's layout -- or, with ``device_resident=True`` (the default:
+    faster at every measured point, README), the same iterations with parameters and moments on the device, ``iters_per_call`` of them
+    per call (``nmgp_had_subjects_adam``), bit for bit the host loop's results.  A model names its hyper-parameter keys, its
     ``Context`` entry, how per-subject vectors are packed into / unpacked from that layout, and its cohort predictor."""
 
     HYPER_KEYS = SVC_HYPER_KEYS
     EVAL = "had_subjects_eval"
+    MODEL = "non"               # the model's name in the resident families (nmgp_had_subjects_adam_*, nmgp_had_subjects_traj_*)
 
     @staticmethod
     def _pack(vectors, nobs, M):
@@ -1138,9 +1141,22 @@ class _HadamardCohortLoop:
         from . import hadamard
         return hadamard.cohort_predict(ctx, draws, xs, hyper, indx_star=indx_star)
 
-    def __init__(self, subjects, hyper_pars, init_pars, lr=2e-1, chains_per_subject=1, max_flop_waste=0.5, ctxs=None):
-        from . import _lib, hadamard
+    def __init__(self, subjects, hyper_pars, init_pars, lr=2e-1, chains_per_subject=1, max_flop_waste=0.5, ctxs=None,
+                 device_resident=True, iters_per_call=50, evaluators=None):
+        """``device_resident=True``: parameters, gradients and Adam's moments stay in HBM (``nmgp_had_subjects_adam``), every bucket
+        advances ``iters_per_call`` iterations per call with ONE synchronisation, and only the verbose tuples come back -- the same
+        bits as ``device_resident=False``, the host loop over ``*_subjects_eval`` that DEFINES the arithmetic (see :meth:`run`).
+        ``evaluators``: one callable per bucket, padded rows -> ``(out, grad, status)``, instead of contexts (host loop only; no
+        context is created).  ``iters_per_call`` may be changed between two calls of :meth:`run`; ``device_resident`` must NOT be
+        changed after the first one -- Adam's moments and iteration count live either on the host or on the device and are not
+        carried over (:meth:`run` raises ``RuntimeError``)."""
+        from . import hadamard
         k = int(chains_per_subject)
+        self.device_resident = bool(device_resident) and evaluators is None
+        self._first_run_resident = None          # the loop the first run() took
+        self.iters_per_call = int(iters_per_call)
+        if self.iters_per_call < 1:
+            raise ValueError("iters_per_call must be positive")
         subjects = [(np.ascontiguousarray(x, dtype=np.float64).reshape(-1), np.asarray(indx).reshape(-1).astype(np.int32),
                      np.ascontiguousarray(y, dtype=np.float64).reshape(-1)) for x, indx, y in subjects]
         if k < 1 or len(subjects) < 1 or len(init_pars) != len(subjects):
@@ -1152,17 +1168,27 @@ class _HadamardCohortLoop:
         self.M, self.k = Ms[0], k
         self.hyper = np.array([float(hyper_pars[key]) for key in self.HYPER_KEYS])
         self.buckets = hadamard.cohort_buckets(self.nobs, max_flop_waste)
-        if ctxs is not None and len(ctxs) != len(self.buckets):
-            raise ValueError("%d contexts for %d buckets" % (len(ctxs), len(self.buckets)))
-        self._own_ctxs = ctxs is None
-        self.ctxs = list(ctxs) if ctxs is not None else [_lib.Context() for _ in self.buckets]
+        for name, given in (("contexts", ctxs), ("evaluators", evaluators)):
+            if given is not None and len(given) != len(self.buckets):
+                raise ValueError("%d %s for %d buckets" % (len(given), name, len(self.buckets)))
+        self._own_ctxs = ctxs is None and evaluators is None
+        if evaluators is not None:
+            self.ctxs = []
+        else:
+            from . import _lib
+            self.ctxs = list(ctxs) if ctxs is not None else [_lib.Context() for _ in self.buckets]
         self.maps = []
-        for ctx, idx in zip(self.ctxs, self.buckets):
-            ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=self.M)
+        for b, idx in enumerate(self.buckets):
             m = LockStepMAP(self._pack([init_pars[s] for s in idx], [self.nobs[s] for s in idx], self.M), lr=lr)
             if m.P.shape[0] != len(idx) * k:
                 raise ValueError("init_pars must hold chains_per_subject = %d vectors per subject" % k)
-            m.value_and_grad = (lambda P, ctx=ctx: getattr(ctx, self.EVAL)(P, self.hyper, True, True, k))
+            if evaluators is not None:
+                m.value_and_grad = evaluators[b]
+            else:
+                ctx = self.ctxs[b]
+                ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=self.M)
+                m.value_and_grad = (lambda P, ctx=ctx: getattr(ctx, self.EVAL)(P, self.hyper, True, True, k))
+            m.begun = False            # the resident loop: nmgp_had_subjects_adam_begin has been called for this bucket
             self.maps.append(m)
 
     def close(self):
@@ -1196,9 +1222,18 @@ class _HadamardCohortLoop:
 
     def run(self, N_opt, callback=None):
         """Returns (list of per-subject pars [k, P_s], target_value_hist [N_opt, S k] = -NegLog per iteration, alive [S k]), rows and
-        columns in the caller's subject order."""
+        columns in the caller's subject order.  ``callback(i, hist[i])`` is called once per iteration, in order; under the resident
+        loop (``device_resident=True``) the callbacks ARRIVE LATE: those of a block of ``iters_per_call`` iterations are made after
+        the block, when the device is already that far."""
         B = len(self.nobs) * self.k
         hist = np.zeros((N_opt, B))
+        if self._first_run_resident is None:
+            self._first_run_resident = bool(self.device_resident)
+        elif self._first_run_resident != bool(self.device_resident):
+            raise RuntimeError("device_resident was changed after the first run(): Adam's moments and iteration count are not carried "
+                               "between the host loop and the device")
+        if self.device_resident:
+            return self._run_resident(N_opt, callback, hist)
         for i in range(N_opt):
             for m, idx in zip(self.maps, self.buckets):
                 neglog, _ = m.step()
@@ -1207,6 +1242,36 @@ class _HadamardCohortLoop:
                 callback(i, hist[i])
         pars, alive = [None] * len(self.nobs), np.zeros(B, dtype=bool)
         for m, idx in zip(self.maps, self.buckets):
+            alive[self._rows(idx)] = m.alive
+            for s, p in zip(idx, self._unpack(m.P, [self.nobs[s] for s in idx], self.M, self.k)):
+                pars[int(s)] = p
+        return pars, hist, alive
+
+    def _run_resident(self, N_opt, callback, hist):
+        """:meth:`run` with parameters and moments on the device: blocks of at most ``iters_per_call`` iterations per bucket and call
+        (``nmgp_had_subjects_adam``), ``hist`` from the returned tuples -- ``-out[:, 0]``, ``-inf`` where the row is NaN, what the
+        host loop records -- the callbacks of a block after the block, and ONE fetch of the parameters at the end.  A second
+        :meth:`run` goes on from the resident state, as the host loop goes on from its own."""
+        for m, ctx in zip(self.maps, self.ctxs):
+            if not m.begun:
+                ctx.had_subjects_adam_begin(self.MODEL, m.P, self.hyper, True, self.k)
+                m.begun = True
+        from . import _lib
+        width = _lib.Context._COHORT_TRAJ_MODELS[self.MODEL][2]           # values per chain and iteration in the history
+        step = min([self.iters_per_call] + [max(1, _lib.HAD_ADAM_HIST_MAX // (m.P.shape[0] * width)) for m in self.maps])
+        for i0 in range(0, N_opt, step):
+            n = min(step, N_opt - i0)
+            for m, ctx, idx in zip(self.maps, self.ctxs, self.buckets):
+                out, m.alive = ctx.had_subjects_adam(n, m.lr, m.b1, m.b2, m.eps)
+                m.t += n
+                v = out[:, :, 0]
+                hist[i0:i0 + n, self._rows(idx)] = np.where(np.isnan(v), -np.inf, -v)
+            if callback is not None:
+                for i in range(i0, i0 + n):
+                    callback(i, hist[i])
+        pars, alive = [None] * len(self.nobs), np.zeros(hist.shape[1], dtype=bool)
+        for m, ctx, idx in zip(self.maps, self.ctxs, self.buckets):
+            m.P = ctx.had_subjects_adam_get_pars()
             alive[self._rows(idx)] = m.alive
             for s, p in zip(idx, self._unpack(m.P, [self.nobs[s] for s in idx], self.M, self.k)):
                 pars[int(s)] = p
@@ -1276,6 +1341,7 @@ class HadamardSepCohortMAP(_HadamardCohortLoop):
 
     HYPER_KEYS = SEP_HYPER_KEYS
     EVAL = "hads_subjects_eval"
+    MODEL = "sep"
 
     @staticmethod
     def _pack(vectors, nobs, M):
@@ -1344,6 +1410,7 @@ class HadamardStaCohortMAP(_HadamardCohortLoop):
 
     HYPER_KEYS = STA_HYPER_KEYS
     EVAL = "hadst_subjects_eval"
+    MODEL = "sta"
 
     @staticmethod
     def _pack(vectors, nobs, M):
