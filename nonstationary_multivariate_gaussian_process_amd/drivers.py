@@ -15,11 +15,17 @@ Host-side orchestration only; every evaluation of the potential goes to the GPU 
 from __future__ import annotations
 
 import pickle
+import time
 
 import numpy as np
 import torch
 
 from .Utility import logpos, settings
+
+# the hyper-parameter dictionaries' keys, in the order of the C ABI's ``hyper`` vectors: nonseparable, separable, stationary model
+SVC_HYPER_KEYS = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_L", "beta_L", "a", "b")
+SEP_HYPER_KEYS = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_tilde_sigma", "alpha_tilde_sigma", "beta_tilde_sigma", "a", "b", "c")
+STA_HYPER_KEYS = ("mu_tilde_l", "sigma_tilde_l", "a", "b", "c")
 
 
 def map_nonseparable(x, Y, pars0, hyper_pars, N_opt=1000, lr=2e-1, checkpoint_path=None, checkpoint_every=100,
@@ -185,8 +191,7 @@ class BatchedMAP(LockStepMAP):
         xs = np.ascontiguousarray(xs, dtype=np.float64)
         Ys = np.ascontiguousarray(Ys, dtype=np.float64)
         self.ctx = ctx if ctx is not None else _lib.default_context()
-        keys = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_L", "beta_L", "a", "b")
-        self.hyper = np.array([float(hyper_pars[k]) for k in keys])
+        self.hyper = np.array([float(hyper_pars[k]) for k in SVC_HYPER_KEYS])
         self.ctx.set_data(xs[0], Ys[0])
         self.ctx.svc_batch_alloc(xs.shape[0])
         self.ctx.svc_batch_set_subjects(xs, Ys)
@@ -353,9 +358,6 @@ class HMCSampler:
 def sampler(**kw):
     """Alias with the reference's constructor spelling: ``HMC_Sampler.HMC_sampler.sampler(...)``."""
     return HMCSampler(**kw)
-
-
-SVC_HYPER_KEYS = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_L", "beta_L", "a", "b")
 
 
 def _randomized_eigs(hvp, P, k, rank, power_iters, lam_min, seed):
@@ -616,9 +618,6 @@ def prior_lowrank_metric(x, Y, hyper_pars, q_ref, rank=96, oversample=32, power_
     return PriorMetric(hyper_pars, U, lam, info)
 
 
-SEP_HYPER_KEYS = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_tilde_sigma", "alpha_tilde_sigma", "beta_tilde_sigma", "a", "b", "c")
-
-
 class SeparablePriorMetric:
     """The prior-factor metric of the SEPARABLE model (logpos.py:216-296; sampler call Separable_model.py:209-210), host side: its
     parameter vector [tilde_l (N) | tilde_sigma (N) | uL_vec (T) | tilde_sigma2_err] carries GP priors RBF(alpha, beta) + 1e-6 I on
@@ -760,6 +759,96 @@ def polish_map_separable(x, Y, hyper_pars, q, maxiter=300, ctx=None, history=30,
     return _preconditioned_lbfgs(f, to_pars_factory, make_metric, q_cur, maxiter, rounds, history, gtol, verbose, nev)
 
 
+# ---- what every lock-step sampler shares: the potential of a batched evaluation, the host leapfrog, the Metropolis loop ------------
+def _potential_and_grad(out, g, bad):
+    """U [B] = ``out[:, 0]`` and dU/dq = ``g`` of a batched evaluation: a chain that is ``bad`` gets U = inf and a zero gradient
+    (``g`` may be None: a value-only evaluation).  Each driver states its own ``bad``: they differ on purpose (jitter retries)."""
+    U = np.array(out[:, 0])
+    U[bad] = np.inf
+    if g is not None:
+        g[bad] = 0.0
+    return U, g
+
+
+def _leapfrog(q, p, U, g, eps, L, evaluate, kick, drift, mask=None):
+    """THE host leapfrog: ``L`` steps from ``(q, p)`` [B, P] with the potential ``U`` [B] and its gradient ``g`` at q,
+
+        p -= eps/2 kick(g);   L x { q += eps drift(p);   U, g = evaluate(q);   p -= eps kick(g) }   (eps/2 in the last step)
+
+    ``eps`` a scalar or a column [B, 1] (a step per row), ``kick`` / ``drift`` the maps the metric puts on the gradient and on the
+    momentum.  ``mask`` [B, P] marks the real slots of padded rows: a padded p is +0.0 from the first kick on, a padded q never
+    changes, and whatever the padded slots hold (NaN, inf) raises no warning; without a mask every slot is real.  Returns
+    ``(q1, p1, U1, g1, failed)``.  A chain whose potential is undefined at ANY point of the trajectory has left the leapfrog map
+    (its kick was skipped there): it is ``failed``, and its ``U1`` is inf even if the trajectory came back to a valid point,
+    exactly as ``HMCSampler.leapfrog`` returns inf at the first non-finite potential.  The START counts as a point: a chain that
+    starts at U = inf has H0 = inf, so dH is -inf or NaN whatever U1 is -- it is rejected and records NaN either way."""
+    keep = (lambda new, old: new) if mask is None else (lambda new, old: np.where(mask, new, old))
+    with np.errstate(**({} if mask is None else {"invalid": "ignore", "over": "ignore"})):
+        p = keep(p - (0.5 * eps) * kick(g), 0.0)
+        failed = ~np.isfinite(U)
+        for step in range(L):
+            q = keep(q + eps * drift(p), q)
+            U, g = evaluate(q)
+            failed |= ~np.isfinite(U)
+            p = keep(p - (eps if step < L - 1 else 0.5 * eps) * kick(g), p)
+    return q, p, np.where(failed, np.inf, U), g, failed
+
+
+def _jitter_rng(seed):
+    """the generator of the step jitter: its own stream, so the chains' streams do not depend on ``step_jitter``"""
+    return np.random.default_rng(None if seed is None else 7919 * (seed + 1))
+
+
+def _metropolis(groups, n, B, t_start, step_jitter=0.0, jitter_rng=None):
+    """THE Metropolis loop of every lock-step sampler: ``n`` iterations over one or more ``groups`` of chains, ``B`` chains in all.
+    A complete-data or per-subject sampler is one group, a cohort bucket is a group.  A group is a dictionary with its state
+
+        ``q`` [b, P] positions (updated in place), ``U`` [b] their potentials, ``rngs`` its chains' generators, ``rows`` the columns
+        of the caller's [.., B] order that its chains fill, ``samples`` a list of arrays [n, ...] and ``split(q)`` the list of what
+        iteration ``it`` writes into ``samples[j][it]``,
+
+    and with what differs between the samplers:
+
+        ``draw() -> (p0, K0)``: the momenta (or whatever ``trajectory`` takes for them) and the start's kinetic energy; every chain
+        draws its P (real) standard normals from its own generator here, the accept uniform follows below (:class:`HMCSampler`'s order);
+        ``trajectory(jit, p0) -> (q1, m1, U1, failed, g1)`` at ``jit`` times the group's step size: the end point, its momentum (or
+        its kinetic energy, where the device forms it), its potential, the chains that left the domain, and its gradient (or None);
+        ``kinetic_end(m1) -> K1``;  ``commit(acc, g1)``: keep the end point's gradient where ``acc`` -- on the host, or on the device.
+
+    ``step_jitter`` j > 0: iteration i runs at ``jit = 1 + j u_i``, u_i ~ U(-1, 1) from ``jitter_rng``, one draw per iteration for
+    all groups; otherwise ``jit = 1`` and no generator is touched.  Returns ``(accepted [B], energy_error [n, B], timing)``:
+    ``timing`` splits the wall time since ``t_start`` into the setup before the loop, the loop, and inside it the ``trajectory``
+    calls (on the device: the upload, the leapfrog launches, the end point's download) against everything the host does around
+    them (normal draws, energies, accept test, bookkeeping)."""
+    accepted, energy_err = np.zeros(B), np.zeros((n, B))
+    t_loop = time.perf_counter()
+    t_traj = 0.0
+    for it in range(n):
+        jit = 1.0 if step_jitter <= 0 else 1.0 + step_jitter * jitter_rng.uniform(-1.0, 1.0)
+        for gr in groups:
+            p0, K0 = gr["draw"]()
+            H0 = gr["U"] + K0
+            t0 = time.perf_counter()
+            q1, m1, U1, failed, g1 = gr["trajectory"](jit, p0)
+            t_traj += time.perf_counter() - t0
+            U1 = np.where(failed, np.inf, U1)
+            H1 = U1 + gr["kinetic_end"](m1)
+            with np.errstate(invalid="ignore"):       # inf - inf: start and end potential both undefined
+                dH = H1 - H0
+            u = np.array([np.log(r.random()) for r in gr["rngs"]])      # drawn every iteration: the stream does not depend on the outcome
+            acc = np.isfinite(dH) & (u < -dH)
+            gr["commit"](acc, g1)
+            gr["q"][acc] = q1[acc]
+            gr["U"] = np.where(acc, U1, gr["U"])
+            accepted[gr["rows"]] += acc
+            energy_err[it, gr["rows"]] = np.where(np.isfinite(dH), dH, np.nan)
+            for rec, v in zip(gr["samples"], gr["split"](gr["q"])):
+                rec[it] = v
+    t_end = time.perf_counter()
+    return accepted, energy_err, {"setup_seconds": t_loop - t_start, "loop_seconds": t_end - t_loop, "trajectory_call_seconds": t_traj,
+                                  "device_share": t_traj / max(t_end - t_loop, 1e-12)}
+
+
 class LockStepHMC:
     """B independent HMC chains advanced in lock-step: every leapfrog step asks ``potential_and_grad(q [B, P])`` for the
     potentials U [B] and gradients [B, P] of ALL chains at once (U = inf marks a chain whose potential is undefined at
@@ -818,7 +907,7 @@ class LockStepHMC:
 
     def draw_momenta(self):
         """[B, P]: chain b draws P standard normals from its own generator (the stream of :class:`HMCSampler`), then p = chol(M) z."""
-        z = np.stack([r.standard_normal(self.P) for r in self.rngs])
+        z = self._normals()
         if self.mass_kind == 0:
             return z
         if self.mass_kind >= 3:
@@ -838,40 +927,42 @@ class LockStepHMC:
     def potential_and_grad(self, q):
         raise NotImplementedError
 
-    def run(self, sample_size):
-        B, P = self.B, self.P
-        samples = np.zeros((sample_size, B, P))
+    def _normals(self):
+        """z [B, P]: chain b's next P standard normals, from its own generator"""
+        return np.stack([r.standard_normal(self.P) for r in self.rngs])
+
+    def _host_group(self, draw, kick, drift, kinetic):
+        """The B chains as one group of :func:`_metropolis` whose trajectory runs on the host: :func:`_leapfrog` with the metric's
+        ``kick`` and ``drift`` around ``potential_and_grad``, the gradient at the chains' positions kept on the host."""
         U, g = self.potential_and_grad(self.q)
-        accepted = np.zeros(B)
-        energy_err = np.zeros((sample_size, B))
-        for it in range(sample_size):
-            p0 = self.draw_momenta()
-            H0 = U + self.kinetic(p0)
-            q1 = self.q.copy()
-            p1 = p0 - 0.5 * self.eps * g
-            U1, g1 = U, g
-            # A chain whose potential is undefined at ANY intermediate point has left the leapfrog map (its momentum kick
-            # was skipped there): it must be rejected even if the trajectory comes back to a valid point, exactly as
-            # HMCSampler.leapfrog returns inf at the first non-finite potential.
-            failed = np.zeros(B, dtype=bool)
-            for step in range(self.L):
-                q1 = q1 + self.eps * self.velocity(p1)
-                U1, g1 = self.potential_and_grad(q1)
-                failed |= ~np.isfinite(U1)
-                p1 = p1 - (self.eps if step < self.L - 1 else 0.5 * self.eps) * g1
-            U1 = np.where(failed, np.inf, U1)
-            H1 = U1 + self.kinetic(p1)
-            with np.errstate(invalid="ignore"):       # inf - inf: start and end potential both undefined
-                dH = H1 - H0
-            u = np.array([np.log(r.random()) for r in self.rngs])
-            acc = np.isfinite(dH) & (u < -dH)
-            self.q[acc] = q1[acc]
-            U = np.where(acc, U1, U)
-            g = np.where(acc[:, None], g1, g)
-            accepted += acc
-            energy_err[it] = np.where(np.isfinite(dH), dH, np.nan)
-            samples[it] = self.q
-        return samples, {"accept_rate": accepted / sample_size, "energy_error": energy_err}
+        gr = {"q": self.q, "U": U, "g": g, "draw": draw, "kinetic_end": kinetic}
+
+        def trajectory(jit, p0):
+            q1, p1, U1, g1, failed = _leapfrog(gr["q"], p0, gr["U"], gr["g"], self.eps * jit, self.L, self.potential_and_grad, kick, drift)
+            return q1, p1, U1, failed, g1
+
+        def commit(acc, g1):
+            gr["g"] = np.where(acc[:, None], g1, gr["g"])
+        gr.update(trajectory=trajectory, commit=commit)
+        return gr
+
+    def _sample(self, group, n, t_start, jittered=False):
+        """:func:`_metropolis` over the B chains as ONE group; ``jittered``: with the driver's ``step_jitter``.  Returns
+        ``(samples [n, B, P], info)``: ``accept_rate`` [B], ``energy_error`` [n, B] (NaN where it is undefined) and ``timing``."""
+        samples = np.zeros((n, self.B, self.P))
+        group.update(rngs=self.rngs, rows=slice(None), samples=[samples], split=lambda q: [q])
+        accepted, energy_err, timing = _metropolis([group], n, self.B, t_start, *((self.step_jitter, self.jitter_rng) if jittered else ()))
+        return samples, {"accept_rate": accepted / n, "energy_error": energy_err, "timing": timing}
+
+    def _draw(self):
+        p0 = self.draw_momenta()
+        return p0, self.kinetic(p0)
+
+    def run(self, sample_size):
+        """``sample_size`` iterations of :func:`_metropolis` with the trajectories on the host (:func:`_leapfrog`) under the constant
+        mass of :meth:`set_mass`: p0 = ``draw_momenta()``, K = ``kinetic(p)``, kick p -= c g, drift q += eps ``velocity(p)``."""
+        t_start = time.perf_counter()
+        return self._sample(self._host_group(self._draw, lambda g: g, self.velocity, self.kinetic), sample_size, t_start)
 
 
 class BatchedHMC(LockStepHMC):
@@ -897,9 +988,10 @@ class BatchedHMC(LockStepHMC):
         self.device_resident = bool(device_resident)
         # step_jitter j > 0: iteration i uses eps (1 + j u_i), u_i ~ U(-1, 1) from a generator of its own (the chains' streams are
         # untouched), the same step for all chains of the iteration -- the usual guard against a trajectory length that resonates
-        # with the posterior's periods (under a PriorMetric they are all ~2 pi).  Device-resident loop only.
+        # with the posterior's periods (under a PriorMetric they are all ~2 pi).  Device-resident loop only: device_resident=False
+        # IGNORES step_jitter.
         self.step_jitter = float(step_jitter)
-        self.jitter_rng = np.random.default_rng(None if seed is None else 7919 * (seed + 1))
+        self.jitter_rng = _jitter_rng(seed)
         # device_momenta: the host only draws the standard normals z; p0 = chol(M) z and the end point's kinetic energy
         # 1/2 p1^T M^-1 p1 are formed on the device (nmgp_svc_batch_traj_z).  Default: on whenever a mass matrix is set -- the
         # host's share of a dense-mass sample was two [B, P] x [P, P] NumPy products -- off for the identity (where it would only
@@ -928,23 +1020,16 @@ class BatchedHMC(LockStepHMC):
         self.ctx.svc_batch_set_pars(q)
         self.ctx.svc_batch_eval(self.hyper, True, want_grad=True)
         out, status = self.ctx.svc_batch_fetch()
-        g = self.ctx.svc_batch_fetch_grad()
-        U = out[:, 0].copy()
-        bad = ~valid_rows(out, status)
-        U[bad] = np.inf
-        g[bad] = 0.0
-        return U, g
+        return _potential_and_grad(out, self.ctx.svc_batch_fetch_grad(), ~valid_rows(out, status))
 
     def run(self, sample_size):
         """``device_resident=True`` (default): positions, momenta and gradients stay in HBM for the whole trajectory
         (``nmgp_svc_batch_traj``: the leapfrog updates are elementwise kernels between the batched evaluations); per sample
-        the host uploads the momenta it drew, reads the end point back and decides acceptance -- the same arithmetic and
-        the same random streams as the host-side lock-step loop (``device_resident=False``), bit for bit."""
+        the host uploads the momenta it drew, reads the end point back and decides acceptance (:func:`_metropolis`) -- the same
+        arithmetic and the same random streams as the host-side trajectories of :meth:`LockStepHMC.run`
+        (``device_resident=False``, which ignores ``step_jitter``), bit for bit."""
         if not self.device_resident:
             return super().run(sample_size)
-        import time
-        B, P = self.B, self.P
-        samples = np.zeros((sample_size, B, P))
         t_start = time.perf_counter()
         U, _ = self.potential_and_grad(self.q)           # leaves q and dU/dq resident
         if self.mass_kind == 3:
@@ -954,44 +1039,22 @@ class BatchedHMC(LockStepHMC):
             if self.device_momenta and self.mass_kind != 0:
                 self.ctx.svc_batch_traj_set_mass_chol(self.Mchol)
         self.ctx.svc_batch_traj_begin()
-        accepted = np.zeros(B)
-        energy_err = np.zeros((sample_size, B))
-        t_loop = time.perf_counter()
-        t_traj = 0.0
-        for it in range(sample_size):
-            eps = self.eps if self.step_jitter <= 0 else self.eps * (1.0 + self.step_jitter * self.jitter_rng.uniform(-1.0, 1.0))
-            if self.device_momenta:
-                # the same random stream: chain b draws its P standard normals, then (below) the accept uniform
-                z = np.stack([r.standard_normal(P) for r in self.rngs])
-                H0 = U + 0.5 * (z * z).sum(1)            # p0 = chol(M) z  =>  1/2 p0^T M^-1 p0 = 1/2 |z|^2
-                t0 = time.perf_counter()
-                q1, K1, U1, failed = self.ctx.svc_batch_traj_z(self.hyper, True, eps, self.L, z)
-                t_traj += time.perf_counter() - t0
-            else:
-                p0 = self.draw_momenta()
-                H0 = U + self.kinetic(p0)
-                t0 = time.perf_counter()
-                q1, p1, U1, failed = self.ctx.svc_batch_traj(self.hyper, True, eps, self.L, p0)
-                t_traj += time.perf_counter() - t0
-                K1 = self.kinetic(p1)
-            U1 = np.where(failed, np.inf, U1)
-            H1 = U1 + K1
-            with np.errstate(invalid="ignore"):       # inf - inf: start and end potential both undefined
-                dH = H1 - H0
-            u = np.array([np.log(r.random()) for r in self.rngs])
-            acc = np.isfinite(dH) & (u < -dH)
-            self.ctx.svc_batch_traj_commit(acc)
-            self.q[acc] = q1[acc]
-            U = np.where(acc, U1, U)
-            accepted += acc
-            energy_err[it] = np.where(np.isfinite(dH), dH, np.nan)
-            samples[it] = self.q
-        t_end = time.perf_counter()
-        # where a sample's wall time goes: the synchronous trajectory calls (upload of the normals, the leapfrog launches, the end
-        # point's download) against everything the host does around them (normal draws, energies, accept test, bookkeeping)
-        timing = {"setup_seconds": t_loop - t_start, "loop_seconds": t_end - t_loop, "trajectory_call_seconds": t_traj,
-                  "device_share": t_traj / max(t_end - t_loop, 1e-12)}
-        return samples, {"accept_rate": accepted / sample_size, "energy_error": energy_err, "timing": timing}
+        gr = {"q": self.q, "U": U, "commit": lambda acc, g1: self.ctx.svc_batch_traj_commit(acc)}
+        if self.device_momenta:
+            def draw():
+                z = self._normals()
+                return z, 0.5 * (z * z).sum(1)           # p0 = chol(M) z  =>  1/2 p0^T M^-1 p0 = 1/2 |z|^2
+
+            def trajectory(jit, z):
+                q1, K1, U1, failed = self.ctx.svc_batch_traj_z(self.hyper, True, self.eps * jit, self.L, z)
+                return q1, K1, U1, failed, None
+            gr.update(draw=draw, trajectory=trajectory, kinetic_end=lambda K1: K1)
+        else:
+            def trajectory(jit, p0):
+                q1, p1, U1, failed = self.ctx.svc_batch_traj(self.hyper, True, self.eps * jit, self.L, p0)
+                return q1, p1, U1, failed, None
+            gr.update(draw=self._draw, trajectory=trajectory, kinetic_end=self.kinetic)
+        return self._sample(gr, sample_size, t_start, jittered=True)
 
 
 class BatchedHMCSeparable(LockStepHMC):
@@ -1001,7 +1064,8 @@ class BatchedHMCSeparable(LockStepHMC):
     ``Separable_model_mpiKAISER.py:281`` for B chains at once; chain b reproduces ``HMCSampler(potential_func=logpos.nlogpos_obj,
     ...)`` started from the same state with the same random stream.  The leapfrog update runs on the host (P = 2N + T + 1).
     ``M=`` a :class:`SeparablePriorMetric` (from :func:`separable_prior_metric`) selects the whitened-momentum loop -- the metric
-    under which this model's chains mix; ``step_jitter`` as in :class:`BatchedHMC`.
+    under which this model's chains mix; ``step_jitter`` as in :class:`BatchedHMC`, in that loop only: without a prior metric it is
+    IGNORED.
     SEVERAL SUBJECTS: ``x`` [S, N] with ``Y`` [S, N, M] puts B / S consecutive chains on each subject (``nmgp_sep_batch_set_subjects_
     chains``: chain b belongs to subject b // (B / S)); identity, diagonal or dense mass only -- a prior metric belongs to one subject."""
 
@@ -1012,7 +1076,7 @@ class BatchedHMCSeparable(LockStepHMC):
         from . import _lib
         super().__init__(init_positions, step_size, num_steps_in_leap, seed, M, Minv)
         self.step_jitter = float(step_jitter)
-        self.jitter_rng = np.random.default_rng(None if seed is None else 7919 * (seed + 1))
+        self.jitter_rng = _jitter_rng(seed)
         self.ctx = ctx if ctx is not None else _lib.default_context()
         self.hyper = np.array([float(hyper_pars[k]) for k in self.KEYS])
         x, Y = np.asarray(x, dtype=np.float64), np.asarray(Y, dtype=np.float64)
@@ -1033,57 +1097,27 @@ class BatchedHMCSeparable(LockStepHMC):
     def potential_and_grad(self, q):
         """U [B] and dU/dq [B, P]; a chain whose covariance stays numerically singular after the jitter retries gets U = inf."""
         out, g, status = self.ctx.sep_batch_eval(q, self.hyper, True, True)
-        U = out[:, 0].copy()
-        bad = (status < 0) | ~np.isfinite(U)
-        U[bad] = np.inf
-        g[bad] = 0.0
-        return U, g
+        return _potential_and_grad(out, g, (status < 0) | ~np.isfinite(out[:, 0]))
 
     def run(self, sample_size):
         """With ``M=`` a :class:`SeparablePriorMetric` the chains carry the whitened momentum u = L_blk^T p (as the device-resident
-        nonseparable sampler does): draw u = (I + U lam U^T)^1/2 z, kick u -= c L_blk^T g, drift q += eps L_blk (I + U lam U^T)^-1 u,
-        kinetic energy 1/2 u^T (I + U lam U^T)^-1 u -- triangular PRODUCTS with the prior factors only, on the host, around one
-        batched evaluation on the GPU per leapfrog step.  Any other mass matrix: the lock-step loop of the base class."""
+        nonseparable sampler does): draw u = (I + U lam U^T)^1/2 z with K0 = 1/2 |z|^2, kick u -= c L_blk^T g, drift
+        q += eps L_blk (I + U lam U^T)^-1 u, kinetic energy 1/2 u^T (I + U lam U^T)^-1 u -- triangular PRODUCTS with the prior
+        factors only, on the host (:func:`_leapfrog`), around one batched evaluation on the GPU per leapfrog step, with
+        ``step_jitter``.  Any other mass matrix: :meth:`LockStepHMC.run`, which IGNORES ``step_jitter``."""
         if self.mass_kind != 4:
             return super().run(sample_size)
+        t_start = time.perf_counter()
         met = self.metric
-        B, P = self.B, self.P
-        samples = np.zeros((sample_size, B, P))
-        U, g = self.potential_and_grad(self.q)
-        accepted = np.zeros(B)
-        energy_err = np.zeros((sample_size, B))
-        for it in range(sample_size):
-            eps = self.eps if self.step_jitter <= 0 else self.eps * (1.0 + self.step_jitter * self.jitter_rng.uniform(-1.0, 1.0))
-            z = np.stack([r.standard_normal(P) for r in self.rngs])
-            H0 = U + 0.5 * (z * z).sum(1)
-            q1 = self.q.copy()
-            u1 = met.root(z) - 0.5 * eps * met.apply(g, True)
-            U1, g1 = U, g
-            failed = np.zeros(B, dtype=bool)
-            for step in range(self.L):
-                q1 = q1 + eps * met.apply(met.W(u1), False)
-                U1, g1 = self.potential_and_grad(q1)
-                failed |= ~np.isfinite(U1)
-                u1 = u1 - (eps if step < self.L - 1 else 0.5 * eps) * met.apply(g1, True)
-            U1 = np.where(failed, np.inf, U1)
-            H1 = U1 + met.kinetic(u1)
-            with np.errstate(invalid="ignore"):
-                dH = H1 - H0
-            lu = np.array([np.log(r.random()) for r in self.rngs])
-            acc = np.isfinite(dH) & (lu < -dH)
-            self.q[acc] = q1[acc]
-            U = np.where(acc, U1, U)
-            g = np.where(acc[:, None], g1, g)
-            accepted += acc
-            energy_err[it] = np.where(np.isfinite(dH), dH, np.nan)
-            samples[it] = self.q
-        return samples, {"accept_rate": accepted / sample_size, "energy_error": energy_err}
+
+        def draw():
+            z = self._normals()
+            return met.root(z), 0.5 * (z * z).sum(1)
+        group = self._host_group(draw, lambda g: met.apply(g, True), lambda u: met.apply(met.W(u), False), met.kinetic)
+        return self._sample(group, sample_size, t_start, jittered=True)
 
 
 # ---- Hadamard form of the nonseparable model (irregularly observed outputs) -------------------------------------------------------
-SVC_HYPER_KEYS = ("mu_tilde_l", "alpha_tilde_l", "beta_tilde_l", "mu_L", "alpha_L", "beta_L", "a", "b")
-
-
 class _HadamardSubject:
     """One Hadamard subject (x [N], indx [N], y [N]) on a context: the batched objective of ``hadamard.nlogpos_obj_hadamard_SVC``."""
 
@@ -1114,17 +1148,15 @@ class HadamardMAP(_HadamardSubject, LockStepMAP):
         return self._eval(P)
 
 
-class _HadamardCohortLoop:
-    """The cohort MAP loop shared by the three Hadamard models: buckets of similar size (``hadamard.cohort_buckets``), one subject set
-    (``nmgp_had_set_subjects``) per bucket on a ``Context`` of its own, held for the whole run, ONE ``*_subjects_eval`` per bucket and
-    Adam iteration, :class:`LockStepMAP`'s update on the rows of the entry's layout -- or, with ``device_resident=True`` (the default:
-    faster at every measured point, README), the same iterations with parameters and moments on the device, ``iters_per_call`` of them
-    per call (``nmgp_had_subjects_adam``), bit for bit the host loop's results.  A model names its hyper-parameter keys, its
-    ``Context`` entry, how per-subject vectors are packed into / unpacked from that layout, and its cohort predictor."""
+class _HadamardNonCohort:
+    """What a cohort driver (:class:`_HadamardCohort`) asks of its MODEL, here the nonseparable one: the hyper-parameter keys, the
+    ``Context`` entry of a set's evaluation, the model's name in the resident families (``nmgp_had_subjects_adam_*``,
+    ``nmgp_had_subjects_traj_*``), how per-subject vectors are packed into / unpacked from the entry's padded layout, and the cohort
+    predictor.  The MAP driver and the HMC driver of a model both take them from here."""
 
     HYPER_KEYS = SVC_HYPER_KEYS
     EVAL = "had_subjects_eval"
-    MODEL = "non"               # the model's name in the resident families (nmgp_had_subjects_adam_*, nmgp_had_subjects_traj_*)
+    MODEL = "non"
 
     @staticmethod
     def _pack(vectors, nobs, M):
@@ -1141,26 +1173,19 @@ class _HadamardCohortLoop:
         from . import hadamard
         return hadamard.cohort_predict(ctx, draws, xs, hyper, indx_star=indx_star)
 
-    def __init__(self, subjects, hyper_pars, init_pars, lr=2e-1, chains_per_subject=1, max_flop_waste=0.5, ctxs=None,
-                 device_resident=True, iters_per_call=50, evaluators=None):
-        """``device_resident=True``: parameters, gradients and Adam's moments stay in HBM (``nmgp_had_subjects_adam``), every bucket
-        advances ``iters_per_call`` iterations per call with ONE synchronisation, and only the verbose tuples come back -- the same
-        bits as ``device_resident=False``, the host loop over ``*_subjects_eval`` that DEFINES the arithmetic (see :meth:`run`).
-        ``evaluators``: one callable per bucket, padded rows -> ``(out, grad, status)``, instead of contexts (host loop only; no
-        context is created).  ``iters_per_call`` may be changed between two calls of :meth:`run`; ``device_resident`` must NOT be
-        changed after the first one -- Adam's moments and iteration count live either on the host or on the device and are not
-        carried over (:meth:`run` raises ``RuntimeError``)."""
+
+class _HadamardCohort:
+    """A cohort of ragged Hadamard subjects on the device, under the model a mixin names (:class:`_HadamardNonCohort`): buckets of
+    similar size (``hadamard.cohort_buckets``), one subject set (``nmgp_had_set_subjects``) per bucket on a ``Context`` of its own,
+    held until :meth:`close`.  What the cohort MAP loop and the cohort sampler share."""
+
+    def _bind(self, subjects, hyper_pars, k, max_flop_waste, ctxs, evaluators):
+        """Sets ``nobs``, ``M``, ``k``, ``hyper``, ``buckets`` and ``ctxs`` and puts every bucket's subjects on its context (with
+        ``evaluators`` no context is created).  Returns the subjects as arrays and, per bucket, the evaluation of the entry's
+        padded rows -> ``(out, grad, status)``: the model's ``*_subjects_eval`` on the set, or the caller's evaluator."""
         from . import hadamard
-        k = int(chains_per_subject)
-        self.device_resident = bool(device_resident) and evaluators is None
-        self._first_run_resident = None          # the loop the first run() took
-        self.iters_per_call = int(iters_per_call)
-        if self.iters_per_call < 1:
-            raise ValueError("iters_per_call must be positive")
         subjects = [(np.ascontiguousarray(x, dtype=np.float64).reshape(-1), np.asarray(indx).reshape(-1).astype(np.int32),
                      np.ascontiguousarray(y, dtype=np.float64).reshape(-1)) for x, indx, y in subjects]
-        if k < 1 or len(subjects) < 1 or len(init_pars) != len(subjects):
-            raise ValueError("subjects and init_pars must be lists of one positive length, chains_per_subject >= 1")
         self.nobs = [s[0].shape[0] for s in subjects]
         Ms = sorted({int(np.unique(s[1]).shape[0]) for s in subjects})
         if len(Ms) != 1:
@@ -1172,24 +1197,14 @@ class _HadamardCohortLoop:
             if given is not None and len(given) != len(self.buckets):
                 raise ValueError("%d %s for %d buckets" % (len(given), name, len(self.buckets)))
         self._own_ctxs = ctxs is None and evaluators is None
+        self.ctxs = []
         if evaluators is not None:
-            self.ctxs = []
-        else:
-            from . import _lib
-            self.ctxs = list(ctxs) if ctxs is not None else [_lib.Context() for _ in self.buckets]
-        self.maps = []
-        for b, idx in enumerate(self.buckets):
-            m = LockStepMAP(self._pack([init_pars[s] for s in idx], [self.nobs[s] for s in idx], self.M), lr=lr)
-            if m.P.shape[0] != len(idx) * k:
-                raise ValueError("init_pars must hold chains_per_subject = %d vectors per subject" % k)
-            if evaluators is not None:
-                m.value_and_grad = evaluators[b]
-            else:
-                ctx = self.ctxs[b]
-                ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=self.M)
-                m.value_and_grad = (lambda P, ctx=ctx: getattr(ctx, self.EVAL)(P, self.hyper, True, True, k))
-            m.begun = False            # the resident loop: nmgp_had_subjects_adam_begin has been called for this bucket
-            self.maps.append(m)
+            return subjects, list(evaluators)
+        from . import _lib
+        self.ctxs = list(ctxs) if ctxs is not None else [_lib.Context() for _ in self.buckets]
+        for ctx, idx in zip(self.ctxs, self.buckets):
+            ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=self.M)
+        return subjects, [(lambda P, ctx=ctx: getattr(ctx, self.EVAL)(P, self.hyper, True, True, k)) for ctx in self.ctxs]
 
     def close(self):
         """Drops the sets; closes the contexts this object created itself."""
@@ -1219,6 +1234,41 @@ class _HadamardCohortLoop:
     def _rows(self, idx):
         """columns of the caller's [.., S k] order that a bucket's rows fill"""
         return (np.asarray(idx)[:, None] * self.k + np.arange(self.k)[None, :]).reshape(-1)
+
+
+class _HadamardCohortLoop(_HadamardCohort):
+    """The cohort MAP loop shared by the three Hadamard models: the buckets and sets of :class:`_HadamardCohort`, ONE
+    ``*_subjects_eval`` per bucket and Adam iteration, :class:`LockStepMAP`'s update on the rows of the entry's layout -- or, with
+    ``device_resident=True`` (the default: faster at every measured point, README), the same iterations with parameters and moments
+    on the device, ``iters_per_call`` of them per call (``nmgp_had_subjects_adam``), bit for bit the host loop's results."""
+
+    def __init__(self, subjects, hyper_pars, init_pars, lr=2e-1, chains_per_subject=1, max_flop_waste=0.5, ctxs=None,
+                 device_resident=True, iters_per_call=50, evaluators=None):
+        """``device_resident=True``: parameters, gradients and Adam's moments stay in HBM (``nmgp_had_subjects_adam``), every bucket
+        advances ``iters_per_call`` iterations per call with ONE synchronisation, and only the verbose tuples come back -- the same
+        bits as ``device_resident=False``, the host loop over ``*_subjects_eval`` that DEFINES the arithmetic (see :meth:`run`).
+        ``evaluators``: one callable per bucket, padded rows -> ``(out, grad, status)``, instead of contexts (host loop only; no
+        context is created).  ``iters_per_call`` may be changed between two calls of :meth:`run`; ``device_resident`` must NOT be
+        changed after the first one -- Adam's moments and iteration count live either on the host or on the device and are not
+        carried over (:meth:`run` raises ``RuntimeError``)."""
+        k = int(chains_per_subject)
+        self.device_resident = bool(device_resident) and evaluators is None
+        self._first_run_resident = None          # the loop the first run() took
+        self.iters_per_call = int(iters_per_call)
+        if self.iters_per_call < 1:
+            raise ValueError("iters_per_call must be positive")
+        subjects = list(subjects)
+        if k < 1 or len(subjects) < 1 or len(init_pars) != len(subjects):
+            raise ValueError("subjects and init_pars must be lists of one positive length, chains_per_subject >= 1")
+        _, evals = self._bind(subjects, hyper_pars, k, max_flop_waste, ctxs, evaluators)
+        self.maps = []
+        for idx, ev in zip(self.buckets, evals):
+            m = LockStepMAP(self._pack([init_pars[s] for s in idx], [self.nobs[s] for s in idx], self.M), lr=lr)
+            if m.P.shape[0] != len(idx) * k:
+                raise ValueError("init_pars must hold chains_per_subject = %d vectors per subject" % k)
+            m.value_and_grad = ev
+            m.begun = False            # the resident loop: nmgp_had_subjects_adam_begin has been called for this bucket
+            self.maps.append(m)
 
     def run(self, N_opt, callback=None):
         """Returns (list of per-subject pars [k, P_s], target_value_hist [N_opt, S k] = -NegLog per iteration, alive [S k]), rows and
@@ -1278,7 +1328,7 @@ class _HadamardCohortLoop:
         return pars, hist, alive
 
 
-class HadamardCohortMAP(_HadamardCohortLoop):
+class HadamardCohortMAP(_HadamardNonCohort, _HadamardCohortLoop):
     """The MAP loop of :class:`HadamardMAP` for a cohort of subjects of RAGGED size: ``subjects`` is a list of ``(x, indx, y)``,
     ``init_pars`` a list of ``[k, P_s]`` (k = ``chains_per_subject`` restarts of subject s, ``P_s = N_s (1 + T) + 1``).  The subjects
     are split into buckets of similar size (``hadamard.cohort_buckets(nobs, max_flop_waste)``); every bucket is one subject set
@@ -1303,11 +1353,7 @@ class BatchedHMCHadamard(_HadamardSubject, LockStepHMC):
     def potential_and_grad(self, q):
         """U [B] and dU/dq [B, P]; a chain whose covariance is not positive definite (or not finite) gets U = inf."""
         out, g, status = self._eval(q)
-        U = out[:, 0].copy()
-        bad = (status != 0) | ~np.isfinite(U)
-        U[bad] = np.inf
-        g[bad] = 0.0
-        return U, g
+        return _potential_and_grad(out, g, (status != 0) | ~np.isfinite(out[:, 0]))
 
 
 # ---- Hadamard form of the separable model (one cross-output matrix shared by all observations) -------------------------------------
@@ -1333,11 +1379,9 @@ class HadamardSepMAP(_HadamardSepSubject, LockStepMAP):
         return self._eval(P)
 
 
-class HadamardSepCohortMAP(_HadamardCohortLoop):
-    """:class:`HadamardCohortMAP`'s loop under the separable model, against :class:`HadamardSepMAP` subject by subject:
-    ``init_pars[s]`` ``[k, 2 N_s + T + 1]``, the hyper-parameter keys of the per-subject driver, ONE ``nmgp_hads_subjects_eval`` per
-    bucket and Adam iteration on the padded layout of ``hadamard_sep.cohort_pack`` (padded slots have zero gradient and never move).
-    :meth:`predict` is ``hadamard_sep.cohort_predict`` per bucket."""
+class _HadamardSepCohort:
+    """:class:`_HadamardNonCohort`'s hooks for the separable model: the hyper-parameter keys of the per-subject driver,
+    ``nmgp_hads_subjects_eval``, the padded layout of ``hadamard_sep.cohort_pack`` and ``hadamard_sep.cohort_predict``."""
 
     HYPER_KEYS = SEP_HYPER_KEYS
     EVAL = "hads_subjects_eval"
@@ -1359,6 +1403,12 @@ class HadamardSepCohortMAP(_HadamardCohortLoop):
         return hadamard_sep.cohort_predict(ctx, draws, xs, hyper, indx_star=indx_star)
 
 
+class HadamardSepCohortMAP(_HadamardSepCohort, _HadamardCohortLoop):
+    """:class:`HadamardCohortMAP`'s loop under the separable model, against :class:`HadamardSepMAP` subject by subject:
+    ``init_pars[s]`` ``[k, 2 N_s + T + 1]``, ONE ``nmgp_hads_subjects_eval`` per bucket and Adam iteration on the padded layout
+    (padded slots have zero gradient and never move).  :meth:`predict` is ``hadamard_sep.cohort_predict`` per bucket."""
+
+
 class BatchedHMCHadamardSep(_HadamardSepSubject, LockStepHMC):
     """B independent HMC chains of the separable Hadamard model of one subject in lock-step: every leapfrog step evaluates
     ``logpos.nlogpos_obj_hadamard`` and its gradient for all chains with one ``nmgp_hads_batch_eval``.  The leapfrog update runs on
@@ -1376,9 +1426,6 @@ class BatchedHMCHadamardSep(_HadamardSepSubject, LockStepHMC):
 
 
 # ---- Hadamard form of the stationary model (the LMC baseline: T + 3 parameters, no GP prior) --------------------------------------
-STA_HYPER_KEYS = ("mu_tilde_l", "sigma_tilde_l", "a", "b", "c")
-
-
 class _HadamardStaSubject(_HadamardSubject):
     """One Hadamard subject on a context under the stationary model: the batched objective of ``hadamard_sta.nlogpos_obj_hadamard_S``."""
 
@@ -1401,12 +1448,10 @@ class HadamardStaMAP(_HadamardStaSubject, LockStepMAP):
         return self._eval(P)
 
 
-class HadamardStaCohortMAP(_HadamardCohortLoop):
-    """:class:`HadamardCohortMAP`'s loop under the stationary model, against :class:`HadamardStaMAP` subject by subject:
-    ``init_pars[s]`` ``[k, T + 3]`` (the vector has no per-observation part, so rows are stacked as they are), the hyper-parameter keys
-    and the update of the per-subject driver (every entry moves, ``tilde_sigma`` included, as there), ONE
-    ``nmgp_hadst_subjects_eval`` per bucket and Adam iteration.  :meth:`predict` is ``hadamard_sta.cohort_predict`` per bucket (no
-    starred values: ``(mean, var, status)`` per subject)."""
+class _HadamardStaCohort:
+    """:class:`_HadamardNonCohort`'s hooks for the stationary model: the hyper-parameter keys of the per-subject driver,
+    ``nmgp_hadst_subjects_eval``, rows stacked as they are (the ``T + 3`` vector has no per-observation part: every slot is real)
+    and ``hadamard_sta.cohort_predict`` (no starred values: ``(mean, var, status)`` per subject)."""
 
     HYPER_KEYS = STA_HYPER_KEYS
     EVAL = "hadst_subjects_eval"
@@ -1424,6 +1469,12 @@ class HadamardStaCohortMAP(_HadamardCohortLoop):
     def _predict(ctx, hyper, draws, xs, indx_star):
         from . import hadamard_sta
         return hadamard_sta.cohort_predict(ctx, draws, xs, indx_star=indx_star)
+
+
+class HadamardStaCohortMAP(_HadamardStaCohort, _HadamardCohortLoop):
+    """:class:`HadamardCohortMAP`'s loop under the stationary model, against :class:`HadamardStaMAP` subject by subject:
+    ``init_pars[s]`` ``[k, T + 3]``, the update of the per-subject driver (every entry moves, ``tilde_sigma`` included, as there),
+    ONE ``nmgp_hadst_subjects_eval`` per bucket and Adam iteration.  :meth:`predict` is ``hadamard_sta.cohort_predict`` per bucket."""
 
 
 class BatchedHMCHadamardSta(_HadamardStaSubject, LockStepHMC):
@@ -1456,10 +1507,10 @@ class BatchedHMCHadamardSta(_HadamardStaSubject, LockStepHMC):
 
 
 # ---- HMC for a cohort of ragged Hadamard subjects: the sampler between the cohort's MAP and its predictive bands ---------------------
-class _HadamardCohortHMC(_HadamardCohortLoop):
-    """Lock-step HMC for a cohort of ragged Hadamard subjects, shared by the three models: the buckets, sets, contexts and pack /
-    unpack hooks of :class:`_HadamardCohortLoop`, :class:`LockStepHMC`'s arithmetic on the rows of the entry's padded layout with a
-    step size per subject.  ``init_positions[s]`` ``[k, P_s]`` (the same k for every subject); ``step_size`` a scalar or ``[S]``;
+class _HadamardCohortHMC(_HadamardCohort):
+    """Lock-step HMC for a cohort of ragged Hadamard subjects, shared by the three models: the buckets, sets and contexts of
+    :class:`_HadamardCohort`, the model's pack / unpack hooks, every bucket a group of :func:`_metropolis`, :class:`LockStepHMC`'s
+    arithmetic on the rows of the entry's padded layout with a step size per subject.  ``init_positions[s]`` ``[k, P_s]`` (the same k for every subject); ``step_size`` a scalar or ``[S]``;
     ``mass`` None, a list of ``diag(M)`` ``[P_s]`` per subject, or ``"prior"`` (below); ``step_jitter`` as :class:`BatchedHMC` (one
     factor per iteration for all subjects, from a generator of its own).  Chain k of subject s draws from ``default_rng(seed + s k_total + k)`` in
     :class:`HMCSampler`'s order -- ``P_s`` standard normals of the REAL length, then the uniform of the accept test -- so a subject's
@@ -1480,8 +1531,6 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
     O(0.1), not the O(1e-4) the identity mass needs.  The host loop (``device_resident=False``, also with ``evaluators=``) DEFINES
     this arithmetic with ``L_blk,s`` built in NumPy (:meth:`_prior_factor`); the resident loop agrees with it to a tolerance, NOT bit
     for bit -- the summation order of a triangular product differs between NumPy's GEMM and the kernel's tiles."""
-
-    MODEL = "non"
 
     @staticmethod
     def _prior_factor(x, alpha, beta):
@@ -1511,9 +1560,7 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
 
     def __init__(self, subjects, hyper_pars, init_positions, step_size=1e-4, num_steps_in_leap=20, seed=None, mass=None,
                  step_jitter=0.0, device_resident=True, device_kinetic=False, max_flop_waste=0.5, ctxs=None, evaluators=None):
-        from . import hadamard
-        subjects = [(np.ascontiguousarray(x, dtype=np.float64).reshape(-1), np.asarray(indx).reshape(-1).astype(np.int32),
-                     np.ascontiguousarray(y, dtype=np.float64).reshape(-1)) for x, indx, y in subjects]
+        subjects = list(subjects)
         S = len(subjects)
         if S < 1 or len(init_positions) != S:
             raise ValueError("subjects and init_positions must be lists of one positive length")
@@ -1521,12 +1568,6 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
         k = starts[0].shape[0]
         if any(v.shape[0] != k for v in starts):
             raise ValueError("every subject must have the same number of chains")
-        self.nobs = [s[0].shape[0] for s in subjects]
-        Ms = sorted({int(np.unique(s[1]).shape[0]) for s in subjects})
-        if len(Ms) != 1:
-            raise ValueError("the subjects have different numbers of distinct labels: %s" % Ms)
-        self.M, self.k = Ms[0], k
-        self.hyper = np.array([float(hyper_pars[key]) for key in self.HYPER_KEYS])
         self.L = int(num_steps_in_leap)
         eps = np.asarray(step_size, dtype=np.float64)
         self.eps = np.full(S, float(eps)) if eps.ndim == 0 else eps.reshape(-1).copy()
@@ -1540,25 +1581,16 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
         if mass is not None and (len(mass) != S or any(np.shape(m) != (v.shape[1],) or np.any(np.asarray(m) <= 0) for m, v in zip(mass, starts))):
             raise ValueError("mass must hold one positive diag(M) [P_s] per subject")
         self.step_jitter = float(step_jitter)
-        self.jitter_rng = np.random.default_rng(None if seed is None else 7919 * (seed + 1))
+        self.jitter_rng = _jitter_rng(seed)
         self.rngs = [np.random.default_rng(None if seed is None else seed + b) for b in range(S * k)]
         self.device_resident = bool(device_resident) and evaluators is None
         self.device_kinetic = bool(device_kinetic) and self.device_resident
-        self.buckets = hadamard.cohort_buckets(self.nobs, max_flop_waste)
-        for name, given in (("contexts", ctxs), ("evaluators", evaluators)):
-            if given is not None and len(given) != len(self.buckets):
-                raise ValueError("%d %s for %d buckets" % (len(given), name, len(self.buckets)))
-        self._own_ctxs = ctxs is None and evaluators is None
-        if evaluators is not None:
-            self.ctxs = []
-        else:
-            from . import _lib
-            self.ctxs = list(ctxs) if ctxs is not None else [_lib.Context() for _ in self.buckets]
+        subjects, evals = self._bind(subjects, hyper_pars, k, max_flop_waste, ctxs, evaluators)
         # per bucket: the padded rows q, the mask of their real slots, and (with a mass) sqrt(diag M) and diag(M^-1) in that layout
         self.state = []
         for b, idx in enumerate(self.buckets):
             nb = [self.nobs[s] for s in idx]
-            st = {"idx": [int(s) for s in idx], "nobs": nb, "q": self._pack([starts[s] for s in idx], nb, self.M)}
+            st = {"idx": [int(s) for s in idx], "nobs": nb, "q": self._pack([starts[s] for s in idx], nb, self.M), "eval": evals[b]}
             st["mask"] = self._pack([np.ones_like(starts[s]) for s in idx], nb, self.M) == 1.0
             st["mchol"] = st["minv"] = None
             if mass is not None:
@@ -1568,13 +1600,8 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
             if self.prior_metric and not self.device_resident:
                 st["factors"] = [(self._prior_factor(subjects[s][0], self.hyper[1], self.hyper[2]),
                                   self._prior_factor(subjects[s][0], self.hyper[4], self.hyper[5])) for s in idx]
-            if evaluators is not None:
-                st["eval"] = evaluators[b]
-            else:
-                ctx = self.ctxs[b]
-                ctx.had_set_subjects([subjects[s][0] for s in idx], [subjects[s][1] for s in idx], [subjects[s][2] for s in idx], M=self.M)
-                st["ctx"] = ctx
-                st["eval"] = (lambda P, ctx=ctx: getattr(ctx, self.EVAL)(P, self.hyper, True, True, k))
+            if self.ctxs:
+                st["ctx"] = self.ctxs[b]
             self.state.append(st)
 
     def close(self):
@@ -1582,128 +1609,99 @@ class _HadamardCohortHMC(_HadamardCohortLoop):
         for ctx in self.ctxs:
             if ctx.h:
                 ctx.had_subjects_traj_end()
-        _HadamardCohortLoop.close(self)
+        _HadamardCohort.close(self)
 
     @staticmethod
     def _potential(res):
         """U [B] and dU/dq [B, Pmax] of an evaluation; a chain whose potential is undefined gets U = inf and a zero gradient"""
         out, g, status = res
-        U = np.array(out[:, 0])
-        bad = (np.asarray(status) != 0) | ~np.isfinite(U)
-        U[bad] = np.inf
-        if g is not None:
-            g[bad] = 0.0
-        return U, g
+        return _potential_and_grad(out, g, (np.asarray(status) != 0) | ~np.isfinite(out[:, 0]))
 
-    def _kinetic(self, st, p):
-        """0.5 * (p * v).sum() over the real slots of each row, v = diag(M^-1) p"""
-        v = p if st["minv"] is None else p * st["minv"]
+    def _kinetic(self, st, p, minv=True):
+        """0.5 * (p * v).sum() over the real slots of each row, v = diag(M^-1) p (``minv=False``: v = p)"""
+        v = p if st["minv"] is None or not minv else p * st["minv"]
         return np.array([0.5 * (p[z][m] * v[z][m]).sum() for z, m in enumerate(st["mask"])])
 
     def _host_traj(self, st, eps, p0):
-        """:meth:`LockStepHMC.run`'s trajectory on the bucket's padded rows with a step size per row; padded slots stay as they are"""
-        mask, q1, g, U1 = st["mask"], st["q"].copy(), st["g"], st["U"]
-        e = eps[:, None]
-        # under the prior metric p is the whitened momentum u: the gradient goes through L_blk^T, the velocity through L_blk
-        white = (lambda a: self._metric_apply(st, a, True)) if self.prior_metric else (lambda a: a)
-        with np.errstate(invalid="ignore", over="ignore"):      # (padded slots may hold anything; np.where drops what they give)
-            p1 = np.where(mask, p0 - (0.5 * e) * white(g), 0.0)
-            failed = ~np.isfinite(U1)
-            g1 = g
-            for step in range(self.L):
-                v = self._metric_apply(st, p1, False) if self.prior_metric else (p1 if st["minv"] is None else st["minv"] * p1)
-                q1 = np.where(mask, q1 + e * v, q1)
-                U1, g1 = self._potential(st["eval"](q1))
-                failed |= ~np.isfinite(U1)
-                p1 = np.where(mask, p1 - (e if step < self.L - 1 else 0.5 * e) * white(g1), p1)
-        return q1, p1, np.where(failed, np.inf, U1), g1, failed
+        """:func:`_leapfrog` on the bucket's padded rows from ``st["q"]``, ``st["U"]``, ``st["g"]`` with a step size per row; padded
+        slots stay as they are.  Under the prior metric p is the whitened momentum u: the gradient goes through L_blk^T, the
+        velocity through L_blk."""
+        if self.prior_metric:
+            kick, drift = (lambda g: self._metric_apply(st, g, True)), (lambda u: self._metric_apply(st, u, False))
+        else:
+            kick, drift = (lambda g: g), (lambda p: p if st["minv"] is None else st["minv"] * p)
+        return _leapfrog(st["q"], p0, st["U"], st["g"], eps[:, None], self.L, lambda q: self._potential(st["eval"](q)), kick, drift,
+                         st["mask"])
+
+    def _group(self, st, n):
+        """Makes the bucket's state ``st`` a group of :func:`_metropolis`: begins its trajectories (resident) or evaluates its start
+        (host), and names how it draws, runs a trajectory and commits."""
+        k, mask, resident, dk = self.k, st["mask"], self.device_resident, self.device_kinetic
+        if resident:
+            out, status = st["ctx"].had_subjects_traj_begin(self.MODEL, st["q"], self.hyper, True, k)
+            st["U"], _ = self._potential((out, None, status))
+            st["ctx"].had_subjects_traj_set_mass(st["minv"], prior=self.prior_metric)
+        else:
+            st["U"], st["g"] = self._potential(st["eval"](st["q"]))
+        real = [int(m.sum()) for m in mask]
+
+        def draw():
+            z = np.zeros(mask.shape)
+            for r, (rng, m) in enumerate(zip(st["rngs"], mask)):
+                z[r, m] = rng.standard_normal(real[r])
+            p0 = z if st["mchol"] is None else np.where(mask, z * st["mchol"], 0.0)
+            return p0, self._kinetic(st, z, minv=False) if dk else self._kinetic(st, p0)
+
+        def trajectory(jit, p0):
+            eps = self.eps[st["idx"]] * jit            # per subject
+            if resident:
+                q1, p1, K1, U1, failed = st["ctx"].had_subjects_traj(eps, self.L, p0, want_p1=not dk, want_kin=dk)
+                return q1, (K1 if dk else p1), U1, failed, None
+            q1, p1, U1, g1, failed = self._host_traj(st, np.repeat(eps, k), p0)
+            return q1, p1, U1, failed, g1
+
+        def commit(acc, g1):
+            if resident:
+                st["ctx"].had_subjects_traj_commit(acc)
+            else:
+                st["g"] = np.where(acc[:, None], g1, st["g"])
+        st.update(rows=self._rows(st["idx"]), draw=draw, trajectory=trajectory, commit=commit,
+                  kinetic_end=(lambda K1: K1) if dk else (lambda p1: self._kinetic(st, p1)),
+                  samples=[np.zeros((n, k, real[j * k])) for j in range(len(st["idx"]))],
+                  split=lambda q: self._unpack(q, st["nobs"], self.M, k))
+        st["rngs"] = [self.rngs[b] for b in st["rows"]]
+        return st
 
     def run(self, sample_size):
         """Returns ``(samples, info)``: ``samples[s]`` ``[n, k, P_s]`` in the caller's subject order (what the three
         ``posterior_predict_hadamard*_cohort`` functions take), ``info`` with ``accept_rate`` ``[S k]``, ``energy_error`` ``[n, S k]``
         and ``timing`` as :class:`BatchedHMC`."""
-        import time
-        n, k, S = int(sample_size), self.k, len(self.nobs)
-        samples = [None] * S
-        accepted, energy_err = np.zeros(S * k), np.zeros((n, S * k))
+        n, S = int(sample_size), len(self.nobs)
         t_start = time.perf_counter()
+        groups = [self._group(st, n) for st in self.state]
+        accepted, energy_err, timing = _metropolis(groups, n, S * self.k, t_start, self.step_jitter, self.jitter_rng)
+        samples = [None] * S
         for st in self.state:
-            if self.device_resident:
-                out, status = st["ctx"].had_subjects_traj_begin(self.MODEL, st["q"], self.hyper, True, k)
-                st["U"], _ = self._potential((out, None, status))
-                st["ctx"].had_subjects_traj_set_mass(st["minv"], prior=self.prior_metric)
-            else:
-                st["U"], st["g"] = self._potential(st["eval"](st["q"]))
-            st["rows"] = self._rows(st["idx"])
-            st["real"] = [int(m.sum()) for m in st["mask"]]
-            st["samples"] = [np.zeros((n, k, st["real"][j * k])) for j in range(len(st["idx"]))]
-        t_loop = time.perf_counter()
-        t_traj = 0.0
-        for it in range(n):
-            jit = 1.0 if self.step_jitter <= 0 else 1.0 + self.step_jitter * self.jitter_rng.uniform(-1.0, 1.0)
-            for st in self.state:
-                rows, mask = st["rows"], st["mask"]
-                eps = np.repeat(self.eps[st["idx"]] * jit, k)            # per row
-                # the chains' own streams: P_s standard normals of the real length, then (below) the accept uniform
-                z = np.zeros(mask.shape)
-                for r, (b, m) in enumerate(zip(rows, mask)):
-                    z[r, m] = self.rngs[b].standard_normal(st["real"][r])
-                p0 = z if st["mchol"] is None else np.where(mask, z * st["mchol"], 0.0)
-                K0 = np.array([0.5 * (z[r][m] * z[r][m]).sum() for r, m in enumerate(mask)]) if self.device_kinetic else self._kinetic(st, p0)
-                H0 = st["U"] + K0
-                t0 = time.perf_counter()
-                if self.device_resident:
-                    q1, p1, K1, U1, failed = st["ctx"].had_subjects_traj(eps[::k], self.L, p0, want_p1=not self.device_kinetic,
-                                                                        want_kin=self.device_kinetic)
-                    U1 = np.where(failed, np.inf, U1)
-                else:
-                    q1, p1, U1, g1, failed = self._host_traj(st, eps, p0)
-                t_traj += time.perf_counter() - t0
-                if not self.device_kinetic:
-                    K1 = self._kinetic(st, p1)
-                H1 = U1 + K1
-                with np.errstate(invalid="ignore"):       # inf - inf: start and end potential both undefined
-                    dH = H1 - H0
-                u = np.array([np.log(self.rngs[b].random()) for b in rows])
-                acc = np.isfinite(dH) & (u < -dH)
-                if self.device_resident:
-                    st["ctx"].had_subjects_traj_commit(acc)
-                else:
-                    st["g"] = np.where(acc[:, None], g1, st["g"])
-                st["q"][acc] = q1[acc]
-                st["U"] = np.where(acc, U1, st["U"])
-                accepted[rows] += acc
-                energy_err[it, rows] = np.where(np.isfinite(dH), dH, np.nan)
-                for j, v in enumerate(self._unpack(st["q"], st["nobs"], self.M, k)):
-                    st["samples"][j][it] = v
-        t_end = time.perf_counter()
-        for st in self.state:
-            for j, s in enumerate(st["idx"]):
-                samples[s] = st["samples"][j]
-        timing = {"setup_seconds": t_loop - t_start, "loop_seconds": t_end - t_loop, "trajectory_call_seconds": t_traj,
-                  "device_share": t_traj / max(t_end - t_loop, 1e-12)}
+            for s, rec in zip(st["idx"], st["samples"]):
+                samples[s] = rec
         return samples, {"accept_rate": accepted / max(n, 1), "energy_error": energy_err, "timing": timing}
 
 
-class HadamardCohortHMC(_HadamardCohortHMC):
+class HadamardCohortHMC(_HadamardNonCohort, _HadamardCohortHMC):
     """:class:`_HadamardCohortHMC` under the nonseparable model: ``init_positions[s]`` ``[k, N_s (1 + T) + 1]``, against
     :class:`BatchedHMCHadamard` subject by subject; ``samples`` go to :func:`posterior_predict_hadamard_cohort`."""
 
 
-class HadamardSepCohortHMC(_HadamardCohortHMC, HadamardSepCohortMAP):
-    """:class:`_HadamardCohortHMC` under the separable model (keys, entry and layout of :class:`HadamardSepCohortMAP`):
+class HadamardSepCohortHMC(_HadamardSepCohort, _HadamardCohortHMC):
+    """:class:`_HadamardCohortHMC` under the separable model (keys, entry and layout of :class:`_HadamardSepCohort`):
     ``init_positions[s]`` ``[k, 2 N_s + T + 1]``, against :class:`BatchedHMCHadamardSep`; ``samples`` go to
     :func:`posterior_predict_hadamard_sep_cohort`."""
 
-    MODEL = "sep"
 
-
-class HadamardStaCohortHMC(_HadamardCohortHMC, HadamardStaCohortMAP):
-    """:class:`_HadamardCohortHMC` under the stationary model (keys, entry and layout of :class:`HadamardStaCohortMAP`; every slot of
+class HadamardStaCohortHMC(_HadamardStaCohort, _HadamardCohortHMC):
+    """:class:`_HadamardCohortHMC` under the stationary model (keys, entry and layout of :class:`_HadamardStaCohort`; every slot of
     the ``T + 3`` vector is real): against :class:`BatchedHMCHadamardSta`; ``samples`` go to
     :func:`posterior_predict_hadamard_sta_cohort`."""
-
-    MODEL = "sta"
 
 
 # ---- stationary (LMC) model, complete data: the baseline ----------------------------------------------------------------------------
@@ -1788,11 +1786,7 @@ class BatchedHMCStationary(LockStepHMC):
     def potential_and_grad(self, q):
         """U [B] and dU/dq [B, P]; a chain whose covariance stays numerically singular after the jitter retries gets U = inf."""
         out, g, status = self.ctx.sta_batch_eval(q, self.hyper, True, True)
-        U = out[:, 0].copy()
-        bad = (status < 0) | ~np.isfinite(U)
-        U[bad] = np.inf
-        g[bad] = 0.0
-        return U, g
+        return _potential_and_grad(out, g, (status < 0) | ~np.isfinite(out[:, 0]))
 
     draw_momenta = BatchedHMCHadamardSta.draw_momenta
     velocity = BatchedHMCHadamardSta.velocity
@@ -1804,7 +1798,6 @@ def _sample_recipe(polish, build_metric, make_sampler, pars0, chains, iters, war
     """Mode -> metric -> thermalising iterations -> (metric rebuilt at the chains' mean) x windows -> step search -> main run.
     polish(pars0) -> (mode, NegLog, |grad|, evaluations); build_metric(point, k) -> metric; make_sampler(positions, metric, eps, seed)
     -> an object with run(n) -> (samples [n, B, P], info).  Returns (samples [iters, B, P], info)."""
-    import time
     say = progress if progress is not None else (lambda msg: None)
     info = {}
     t0 = time.time()
